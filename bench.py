@@ -103,10 +103,8 @@ def cpu_baseline(model, task, d, kt, kv, N, H, interp, sigma, budget_s=24.0):
     """Reference-shaped CPU path (oracle = our restatement; the reference cannot be built here: MuJoCo absent).
     Persistent worker pool + per-worker data (threadpool.cc:30-85, planners/planner.cc:23-33); median plan-step time."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import __graft_entry__ as g
-    g.build_oracle()
     import oracle_lib as ol
-    ol.FAST = True                           # -O3 -march=native build of the oracle, compiled on this box
+    ol.FAST = True                           # -O3 -march=native build of the oracle, compiled on this box outside the checkout
     ncpu = os.cpu_count() or 1
     phys = min(physical_cores(), ncpu)
     affinity, quota = cpu_share()
@@ -152,6 +150,37 @@ def cpu_baseline(model, task, d, kt, kv, N, H, interp, sigma, budget_s=24.0):
                      "(cgroup quota / affinity) cannot speed up")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+TRAJECTORY_KEYS = ("states", "actions", "times", "residual", "costs", "trace")
+
+
+def dump_outputs(out_dir, res, world):
+    """--dump-outputs: what the caller of the timed path received from its last plan step, one float64 .npy per array: the
+    global elite (`winner`, `winner_return`, `winner_knots`), this rank's per-candidate `returns` / `failure` and the winner's
+    trajectory rows where this process holds them (always at N=1; at N>1 only on the rank that owns the elite).  Should the
+    per-candidate arrays not fit the 64 MB budget they are cut to a fixed seeded sample of candidates, listed in
+    `candidate_index`."""
+    local = res["local"]
+    arrays = dict(winner=[res["winner"]], winner_return=[res["winner_return"]], winner_knots=res["winner_knots"],
+                  returns=local["returns"], failure=local["failure"])
+    rows = res.get("trajectory") or (local if world == 1 else None)      # shards of a sharded plan fetch summaries only
+    if rows is not None:
+        arrays.update((k, rows[k]) for k in TRAJECTORY_KEYS)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - (1 << 16)          # headroom for the .npy headers
+    if total > budget:
+        n = arrays["returns"].shape[0]
+        keep = (budget - (total - arrays["returns"].nbytes - arrays["failure"].nbytes)) // 24      # returns, failure, index
+        idx = np.sort(np.random.default_rng(0x5EED).choice(n, size=keep, replace=False))
+        for k in ("returns", "failure"):
+            arrays[k] = arrays[k][idx]
+        arrays["candidate_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 WORKLOADS = {
     # name: (generator, samples, horizon, knots, interpolation, sigma, label, BASELINE config index)
     "quadruped": ("quadruped", 256, 100, 3, 2, 0.04, "Quadruped flat (A1)", 1),
@@ -176,7 +205,11 @@ def main():
                     help="diagnostics (include/mjpc_hip_debug.h): A = full-capacity kernel only, B = always the dense tier first; default: the engine decides")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary line (strong_scaling_ref at N=1, weak at N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last plan step returned as DIR/<name>.npy (float64, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: start the N ranks ourselves as CHILD processes (the driver's command line, 127.0.0.1
@@ -271,7 +304,7 @@ def main():
             print("per-step ms:", " ".join(f"{1e3 * x:.2f}" for x in per_step), file=sys.stderr)
             print("rollout ms: ", " ".join(f"{1e-3 * x:.2f}" for x in roll_us), file=sys.stderr)
         rec = dict(n_per_rank=n_per_rank, elapsed=elapsed, steps=steps, rollout_us=rollout_us, total_us=total_us, launches=nlaunch,
-                   median_ms=1e3 * statistics.median(per_step), lds=be.lds_bytes(), winner=res["winner"], winner_return=res["winner_return"],
+                   median_ms=1e3 * statistics.median(per_step), lds=be.lds_bytes(), winner=res["winner"], winner_return=res["winner_return"], last=res,
                    phases_ms=dict(noise=1e-3 * statistics.median(noise_us), rollouts=1e-3 * statistics.median(roll_us),
                                   policy_update_and_exchange=max(0.0, 1e3 * statistics.median(per_step) - 1e-3 * (statistics.median(noise_us) + statistics.median(roll_us)))))
         be.close()
@@ -299,6 +332,8 @@ def main():
 
     n_head = (n_global // world) if mode == "strong" else n_weak
     head = measure(n_head, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["last"], world)
     second = None
     if not args.no_secondary:
         if world == 1 and mode == "weak" and args.workload == "quadruped":

@@ -9,7 +9,7 @@
 // timing fields.
 //
 // Not linked in this repository: it needs MuJoCo and abseil, neither of which exists in the build image (SURVEY.md section
-// 8c).  What IS checked here: tests/test_integration_syntax.py runs `g++ -std=c++20 -fsyntax-only` over integration/*.cc and
+// 8c).  What IS checked here: tools/check_integration_syntax.py runs `g++ -std=c++20 -fsyntax-only` over integration/*.cc and
 // over the reference's own ilqs/planner.cc with SamplingPlanner swapped for this class, against the reference's real mjpc/
 // headers and declaration-only stand-ins for <mujoco/*.h> / <absl/*> (tests/stubs/) — a syntax and type check, nothing more.
 // Everything below this class — include/mjpc_hip.h (C ABI), include/mjpc_hip_planner.h (C++ planner with the reference's

@@ -3,7 +3,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -24,7 +26,7 @@ class OPlanOutput(C.Structure):
 
 
 _lib = None
-FAST = False      # bench.py's cpu_baseline sets this before the first use: -O3 -march=native build, rebuilt locally
+FAST = False      # bench.py's cpu_baseline sets this before the first use: -O3 -march=native build, compiled at load time
 
 
 def lib():
@@ -33,10 +35,14 @@ def lib():
         return _lib
     srcs = [os.path.join(ORACLE_DIR, f) for f in os.listdir(ORACLE_DIR) if f.endswith((".c", ".h"))]
     srcs.append(os.path.join(ROOT, "include", "mjpc_hip.h"))
-    so = ORACLE_SO
     if FAST:
-        so = os.path.join(ORACLE_DIR, "_build", "liboracle_fast.so")
-        subprocess.check_call(["make", "-B", "-C", ORACLE_DIR, "fast"], stdout=subprocess.DEVNULL)   # -march=native: build where it runs
+        # -march=native: built where it runs, into a private directory (whoever times bench.py need not be able to write the checkout)
+        tmp = tempfile.mkdtemp(prefix="mjpc_oracle_fast_")
+        try:
+            subprocess.check_call(["make", "-B", "-C", ORACLE_DIR, "fast", "BUILD=" + tmp], stdout=subprocess.DEVNULL)
+            L = C.CDLL(os.path.join(tmp, "liboracle_fast.so"))
+        finally:
+            shutil.rmtree(tmp)        # a loaded library stays mapped
     else:
         # parallel test workers: one of them rebuilds, the others wait for the lock and find the library fresh (the Makefile renames
         # the finished file into place, so a reader never sees a half-written one)
@@ -46,7 +52,7 @@ def lib():
             fcntl.flock(lock, fcntl.LOCK_EX)
             if (not os.path.exists(ORACLE_SO)) or any(os.path.getmtime(s) > os.path.getmtime(ORACLE_SO) for s in srcs):
                 subprocess.check_call(["make", "-C", ORACLE_DIR], stdout=subprocess.DEVNULL)
-    L = C.CDLL(so)
+        L = C.CDLL(ORACLE_SO)
     L.oracle_create.restype = C.c_void_p
     L.oracle_create.argtypes = [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask)]
     L.oracle_destroy.argtypes = [C.c_void_p]

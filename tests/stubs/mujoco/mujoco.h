@@ -1,5 +1,5 @@
 // tests/stubs/mujoco/mujoco.h — DECLARATION-ONLY stand-in for MuJoCo's public header, for ONE purpose: letting
-// tests/test_integration_syntax.py run `g++ -fsyntax-only` over integration/*.cc (the reference-side adapter) against the
+// tools/check_integration_syntax.py run `g++ -fsyntax-only` over integration/*.cc (the reference-side adapter) against the
 // reference's real mjpc/ headers in an image that has no MuJoCo.  It declares the slice of the public API (names, types,
 // struct fields as documented for MuJoCo 3.1) that the adapter, the mjpc headers it includes and ilqs/planner.cc touch.
 // Nothing here has a body, nothing is linked, no product or oracle code includes it, and it proves nothing about numerics.

@@ -1,33 +1,45 @@
 """The hand-authored task generators (modelgen/tasks.py) against the reference's own MJCF files, through the MJCF subset loader.
 
-Runs only where /root/reference is mounted (this container); the GPU box skips it.  Nothing of the reference is copied: the XML is
-read in place, translated into ModelBuilder calls and the compiled arrays are compared with the generator's."""
-import os
+What the loader reads from the reference's task files (compiled arrays, cost terms, numerics, keyframes, bodies) is stored in
+tests/golden/mjcf/tasks.npz by tests/golden/make_mjcf_fixtures.py, which reads the XML in place: nothing of the reference is
+copied, and the checks below need no reference tree.  The loader itself is exercised on an inline document at the end."""
+import functools
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+from golden import make_mjcf_fixtures
 from mujoco_mpc_amd.modelgen import mjcf, tasks
-
-REF = "/root/reference/mjpc"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
 
 # spheres do not care about their frame: the hand geoms carry a zaxis in the XML that the generator drops
 _ORIENTATION_FREE = {"geom_quat": ("geom", ["hand_right", "hand_left"]), "body_iquat": ("body", ["hand_right", "hand_left"])}
 _SKIP = {"nconmax", "nefcmax", "names"}
 
 
-def _reader(p):
-    if os.path.basename(p) == "humanoid_modified.xml":       # exists upstream only as dm_control's file + this patch
-        return mjcf.read_patch_new_file(os.path.join(REF, "tasks/humanoid/humanoid.xml.patch"))
-    with open(p) as f:
-        return f.read()
+@functools.lru_cache(maxsize=1)
+def _fixture():
+    return make_mjcf_fixtures.load()
+
+
+class _Parsed:
+    """what the checks read of the loader's ModelBuilder for one task file: options, bodies and the compiled model"""
+
+    def __init__(self, rec):
+        self.opt = rec["opt"]
+        self.bodies = [SimpleNamespace(**bd) for bd in rec["bodies"]]
+        self._model = rec["model"]
+
+    def compile(self):
+        assert self._model is not None, "the fixture holds the compiled model only for the files in FILES marked to compile"
+        return self._model
 
 
 def _load(rel):
-    b, info = mjcf.parse_mjcf(os.path.join(REF, rel), reader=_reader)
-    b.opt["timestep"] = info["numeric"].get("agent_timestep", [b.opt["timestep"]])[0]     # mjpc/agent.cc: agent_timestep overrides
-    return b, info
+    """(builder, info) of a task file as make_mjcf_fixtures.FILES loads it: a complete task with agent_timestep applied, or
+    without the includes that exist upstream only as patches"""
+    rec = _fixture()[rel]
+    return _Parsed(rec), rec["info"]
 
 
 def _compare(m, m2, tol=1e-12):
@@ -99,6 +111,12 @@ def _terms_of(task):
 
 def _xml_terms(info):
     return [(d, n, w, list(prm[:tasks.NORM_NPARAM[n]])) for d, n, w, prm, _ in info["cost_terms"]]
+
+
+def test_fixture_holds_every_task_file():
+    assert list(_fixture()) == list(make_mjcf_fixtures.FILES)
+    for rel, (_, compiled) in make_mjcf_fixtures.FILES.items():
+        assert (_fixture()[rel]["model"] is not None) == compiled, rel
 
 
 def test_particle_xml_matches_generator():
@@ -186,7 +204,8 @@ def _residual_parameters(info):
 def test_task_tables_of_models_that_need_the_zoo(rel, missing, gen):
     """cartpole / A1 model files exist upstream only as patches against dm_control / menagerie (absent here); their task files are
     complete, so the cost table, residual parameters, planner numerics, keyframes and mocap bodies are checked"""
-    b, info = mjcf.parse_mjcf(os.path.join(REF, rel), missing_ok=(missing,))
+    assert missing in make_mjcf_fixtures.FILES[rel][0]
+    b, info = _load(rel)
     m2, task, d = gen()
     assert _xml_terms(info) == _terms_of(task)
     got, want = _residual_parameters(info), list(task["parameters"])
@@ -213,8 +232,8 @@ def test_cost_tables_and_agent_numerics_of_the_late_registry_tasks(rel, missing,
     """Swimmer / Quadrotor / Particle: the model files are patches against dm_control / menagerie (absent here), the task files are
     complete: the generators carry their cost terms, time step, spline points and (swimmer / particle) the horizon; the quadrotor's
     stage goals are the task file's keyframe mocap positions."""
-    extra = ("gates.xml",) if "quadrotor" in rel else ()
-    b, info = mjcf.parse_mjcf(os.path.join(REF, rel), missing_ok=(missing,) + extra)
+    assert missing in make_mjcf_fixtures.FILES[rel][0]
+    b, info = _load(rel)
     m2, task, d = gen()
     assert _xml_terms(info) == _terms_of(task)
     assert info["numeric"]["agent_timestep"] == [m2["timestep"]]
@@ -228,7 +247,7 @@ def test_cost_tables_and_agent_numerics_of_the_late_registry_tasks(rel, missing,
 def test_humanoid_interact_xml_matches_generator():
     """tasks/humanoid/interact/task.xml + scenes/armchair.xml (both local; the humanoid itself is the patched dm_control file the
     other humanoid tasks share): cost table, residual parameters, agent numerics, the chair's five boxes and the scene's home key"""
-    b, info = mjcf.parse_mjcf(os.path.join(REF, "tasks/humanoid/interact/task.xml"), missing_ok=("humanoid_modified.xml",))
+    b, info = _load("tasks/humanoid/interact/task.xml")
     m2, task, d = tasks.humanoid_interact()
     assert _xml_terms(info) == _terms_of(task)
     assert [info["numeric"]["residual_Head Height"][0], info["numeric"]["residual_Torso Height"][0]] == list(task["parameters"])

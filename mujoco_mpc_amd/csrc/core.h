@@ -86,6 +86,17 @@ struct Ctx {
   int role;            // 0: owns the rollout scalars (misc[0..8], time); 1: side wave, only reports warnings (misc[11])
 };
 
+// LDS block at Lay offset `off`, or (spill flavour) the candidate's slab in HBM when the offset is LAY_SLAB-tagged.  Without
+// MJPC_SPILL this is base + off: the other flavours' code does not change
+DEV double *lay_ptr(const KParams *K, double *base, int off) {
+#ifdef MJPC_SPILL
+  return off >= 0 ? base + off : K->slab + (size_t)cand_index() * (size_t)K->slab_stride + (-1 - off);
+#else
+  (void)K;
+  return base + off;
+#endif
+}
+
 DEV void ctx_init(Ctx &c, const KParams *K, double *base) {
   const Lay &L = K->L;
   c.K = K;
@@ -99,9 +110,11 @@ DEV void ctx_init(Ctx &c, const KParams *K, double *base) {
   P_(xpos); P_(xquat); P_(xmat); P_(xipos); P_(ximat); P_(xanchor); P_(xaxis); P_(geom_xpos); P_(geom_xmat); P_(site_xpos);
   P_(subtree_com); P_(cinert); P_(crb); P_(cdof); P_(cvel); P_(cdof_dot); P_(cacc); P_(cfrc); P_(cfrc_sub);
   P_(subtree_linvel); P_(bodytmp); P_(qM); P_(qL); P_(qH); P_(Linv); P_(Hinv);
-  c.efc_J = base + L.efc_J - K->M.nfric * K->M.nvp;      // rows [nfric, nefcmax) are stored: a friction-loss row is the unit vector of its dof
-  P_(efc_JA); P_(efc_D); P_(efc_R); P_(efc_aref); P_(efc_force); P_(efc_jar); P_(efc_jv); P_(efc_floss);
-  P_(efc_pos); P_(efc_margin); P_(efc_diag); P_(contact);
+  c.efc_J = lay_ptr(K, base, L.efc_J) - K->M.nfric * K->M.nvp;      // rows [nfric, nefcmax) are stored: a friction-loss row is the unit vector of its dof
+#define R_(f) c.f = lay_ptr(K, base, L.f)      // the blocks the spill flavour may keep in HBM (host.h make_layout)
+  R_(efc_JA); R_(efc_D); R_(efc_R); R_(efc_aref); R_(efc_force); R_(efc_jar); R_(efc_jv); R_(efc_floss);
+  R_(efc_pos); R_(efc_margin); R_(efc_diag); R_(contact);
+#undef R_
   P_(Ma); P_(grad); P_(Mgrad); P_(search); P_(Mv); P_(vtmp); P_(sgl);
 #ifdef MJPC_LEAN_LDS      // dense tier: the spline knots stay in HBM / L2 (the nominal's times; this candidate's values, written by ph_init)
   c.knot_times = const_cast<double *>(K->knot_times);
@@ -266,7 +279,9 @@ DEV_NOINLINE void ph_init(KP Kc) {
   PFOR(i, nv) { c.qvel[i] = K->state[nq + i]; R.states[nq + i] = K->state[nq + i]; c.qacc_ws[i] = 0; }
   if (M.na) PFOR(i, M.na) { C_ACT(c)[i] = K->state[nq + nv + i]; R.states[nq + nv + i] = K->state[nq + nv + i]; C_ACTDOT(c)[i] = 0; }
   PFOR(e, nv * M.nvp) c.qM[e] = 0;
-  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;      // (no qH in the layout of a one-column-group register solve)
+  // (no qH in the layout of a one-column-group register solve.  qH's size is the distance to Linv: both are nv-sized blocks that
+  // never spill, laid out back to back in every layout, host.h make_layout)
+  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;
 #ifndef MJPC_LEAN_LDS
   PFOR(e, M.nhpair + nv) c.hpair[e] = MI(hpair_i)[e] | (MI(hpair_j)[e] << 8);
 #endif
@@ -536,7 +551,7 @@ DEV_NOINLINE void ph_side_worker(KP Kc, int t) {
 DEV void implicit_rne_columns(Ctx &c, double *A, double h) {
   const DevModel &M = *c.M;
   const int nv = M.nv, nvp = M.nvp, nb = M.nbody;
-  double *S = lds_base() + c.K->L.efc_J;
+  double *S = lay_ptr(c.K, lds_base(), c.K->L.efc_J);
   int B = M.int_scratch / (18 * nb);                            // lanes (= columns) per batch
   B = B > NLANE ? NLANE : B;
 #define S_(b, k) S[((b) * 18 + (k)) * B + LANE]
@@ -615,7 +630,7 @@ DEV void implicit_dense_solve(Ctx &c) {
   SYNC();
   if (M.fluid) {
     // per body: the diagonal of -d lfrc / d lvel in the inertial frame (scratch: 6 per body, from efc_J on)
-    double *DL = lds_base() + c.K->L.efc_J;
+    double *DL = lay_ptr(c.K, lds_base(), c.K->L.efc_J);
     PFOR(b, nb) {
       double dl[6] = {0, 0, 0, 0, 0, 0};
       double mass = MDH(body_mass)[b];

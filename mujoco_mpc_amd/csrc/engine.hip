@@ -28,6 +28,7 @@ extern "C" RolloutFn mjpc_pick_rollout_cached(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_direct(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_dense2(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_dense2h(int nv, int *exact);
+extern "C" RolloutFn mjpc_pick_rollout_spill(int nv, int *exact);
 extern "C" int mjpc_rollout_threads_cached(void);
 
 // Capacity tiers.  One candidate per CU leaves every SIMD with a single, mostly stalled wave; two resident workgroups per CU
@@ -139,6 +140,7 @@ struct MjpcHipEngine {
   double acc_rollout_us = 0, acc_total_us = 0; int acc_n = 0;
   size_t lds_bytes = 0;
   RolloutFn kernel = nullptr; bool cached = true;
+  bool spill = false; double *d_slab = nullptr; int slab_bytes = 0;   // spill flavour: per-candidate HBM slab (bytes per candidate, whole 256-B blocks)
   int fault = 0;               // diagnostics knob fault_inject (mjpc_hip_debug.h; test-suite only)
   int summary_only = 0, last_summary = 0;      // mjpc_hip_set_fetch_mode
   int last_dense = 0;
@@ -153,6 +155,44 @@ static int upload_model(MjpcHipEngine *e) {
   e->K.L = e->pm.L;
   e->K.ibase = e->d_ib; e->K.dbase = e->d_db; e->K.cache_i = (int)e->pm.cache_i; e->K.cache_d = (int)e->pm.cache_d;
   return 0;
+}
+
+// Kernel flavour of the full-capacity launch: tables cached in LDS when that fits next to the candidate's state and a
+// compile-time-nv kernel exists there; otherwise the flavour that reads them from HBM / L2; and when even that one's state exceeds
+// 160 KiB, the spill flavour, which keeps the row- / contact-sized blocks in a per-candidate HBM slab (rollout_spill.hip).
+// Host-only (no HIP call): mjpc_hip_create and mjpc_hip_debug_spill_layout share it.
+static bool pick_flavour(const MjpcHipModel *model, const MjpcHipTask *task, int P_max, PackedModel &pm, RolloutFn *kernel, bool *cached, bool *spill, const char *who) {
+  int exact_c = 0, exact_d = 0, exact_s = 0;
+  RolloutFn kc = mjpc_pick_rollout_cached(model->nv, &exact_c), kd = mjpc_pick_rollout_direct(model->nv, &exact_d);
+  RolloutFn ks = mjpc_pick_rollout_spill(model->nv, &exact_s);
+  bool use_cache = !(exact_d && !exact_c);
+  if (mjpc_host::debug_knob("no_model_cache")) use_cache = false;     // diagnostics knob (mjpc_hip_debug.h)
+  std::string sp;
+  const bool spill_all = mjpc_host::debug_knob("spill", &sp) && sp == "all";      // diagnostics knob: every eligible block in HBM
+  *spill = false;
+  // (the flavour without the whole copy still keeps the hot prefix - kinematic / tree tables - in LDS: hot_only)
+  // (a compile-time-nv kernel solves with the Hessian in registers: its layout has no scaled-row table, host.h)
+  if (spill_all) {
+    use_cache = false; *spill = true;
+    if (!mjpc_host::build(pm, model, task, P_max, false, false, true, exact_s != 0, SPILL_ALL)) { set_error(std::string(who) + ": " + pm.error); return false; }
+  } else {
+    if (!mjpc_host::build(pm, model, task, P_max, use_cache, false, !use_cache, use_cache ? exact_c != 0 : exact_d != 0)) { set_error(std::string(who) + ": " + pm.error); return false; }
+    if (use_cache && (size_t)pm.L.total_doubles * sizeof(double) > 160 * 1024) {
+      use_cache = false;
+      if (!mjpc_host::build(pm, model, task, P_max, false, false, true, exact_d != 0)) { set_error(std::string(who) + ": " + pm.error); return false; }
+    }
+    if ((size_t)pm.L.total_doubles * sizeof(double) > 160 * 1024) {
+      *spill = true;
+      if (!mjpc_host::build(pm, model, task, P_max, false, false, true, exact_s != 0, SPILL_AUTO)) { set_error(std::string(who) + ": " + pm.error); return false; }
+    }
+  }
+  if ((size_t)pm.L.total_doubles * sizeof(double) > 160 * 1024) {
+    set_error(std::string(who) + ": per-candidate state exceeds 160 KiB of LDS even with the constraint-row and contact buffers in HBM; lower nconmax/nefcmax");
+    return false;
+  }
+  *kernel = *spill ? ks : use_cache ? kc : kd;
+  *cached = use_cache;
+  return true;
 }
 
 extern "C" {
@@ -181,21 +221,12 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   e = new MjpcHipEngine();
   e->device = device;
   e->P_max = 36;     // MaxSamplingSplinePoints (mjpc/planners/sampling/planner.h:35-36)
-  // kernel flavour: tables cached in LDS when that fits next to the candidate's state and a compile-time-nv kernel exists
-  // there; otherwise the flavour that reads them from HBM / L2
   {
-    int exact_c = 0, exact_d = 0;
-    RolloutFn kc = mjpc_pick_rollout_cached(model->nv, &exact_c), kd = mjpc_pick_rollout_direct(model->nv, &exact_d);
-    bool use_cache = !(exact_d && !exact_c);
-    if (mjpc_host::debug_knob("no_model_cache")) use_cache = false;     // diagnostics knob (mjpc_hip_debug.h)
-    // (the flavour without the whole copy still keeps the hot prefix - kinematic / tree tables - in LDS: hot_only)
-    // (a compile-time-nv kernel solves with the Hessian in registers: its layout has no scaled-row table, host.h)
-    if (!mjpc_host::build(e->pm, model, task, e->P_max, use_cache, false, !use_cache, use_cache ? exact_c != 0 : exact_d != 0)) { set_error("mjpc_hip_create: " + e->pm.error); delete e; return nullptr; }
-    if (use_cache && (size_t)e->pm.L.total_doubles * sizeof(double) > 160 * 1024) {
-      use_cache = false;
-      if (!mjpc_host::build(e->pm, model, task, e->P_max, false, false, true, exact_d != 0)) { set_error("mjpc_hip_create: " + e->pm.error); delete e; return nullptr; }
-    }
-    e->kernel = use_cache ? kc : kd;
+    bool use_cache = true, spill = false;
+    if (!pick_flavour(model, task, e->P_max, e->pm, &e->kernel, &use_cache, &spill, "mjpc_hip_create")) { delete e; return nullptr; }
+    e->spill = spill;
+    // (the compile-time-nv spill kernels' register-solver layout can fit without a slab where the generic direct one did not)
+    if (spill) e->slab_bytes = (int)(((size_t)e->pm.slab_doubles * sizeof(double) + 255) / 256 * 256);
     // dense tier: needs a compile-time-nv kernel of that flavour, a model that asks for more capacity than the tier's and a
     // layout of <= 80 KiB
     int exact_b = 0;
@@ -249,6 +280,10 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   HIPCHKP(hipMalloc(&e->d_ib, e->pm.ib.size() * sizeof(int)));
   HIPCHKP(hipMalloc(&e->d_db, e->pm.db.size() * sizeof(double)));
   if (upload_model(e) != 0) { mjpc_hip_destroy(e); return nullptr; }
+  if (e->slab_bytes) {          // spill flavour: one slab per local candidate; holds no state across launches (like LDS)
+    HIPCHKP(hipMalloc(&e->d_slab, (size_t)max_local * e->slab_bytes));
+    e->K.slab = e->d_slab; e->K.slab_stride = e->slab_bytes / (long long)sizeof(double);
+  }
   HIPCHKP(hipStreamCreate(&e->stream));
   for (int i = 0; i < 4; i++) HIPCHKP(hipEventCreate(&e->ev[i]));
   size_t NL = (size_t)max_local, H = (size_t)max_horizon;
@@ -293,7 +328,7 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   void *bufs[] = {e->d_userdata, e->d_cand, e->d_std, e->d_ib, e->d_db, e->d_state, e->d_mocap, e->d_kt, e->d_kv, e->d_eps, e->d_sel, e->d_states, e->d_actions,
                   e->d_times, e->d_residual, e->d_costs, e->d_trace, e->d_knots, e->d_returns, e->d_failure, e->d_diag,
-                  e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt};
+                  e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt, e->d_slab};
   for (void *b : bufs) if (b) hipFree(b);
   if (e->h_small) hipHostFree(e->h_small);
   for (int i = 0; i < 2; i++) { if (e->h_task[i]) hipHostFree(e->h_task[i]); if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]); }
@@ -577,6 +612,24 @@ int mjpc_hip_get_all_candidates(MjpcHipEngine *e, double *states, double *action
 }
 
 int mjpc_hip_lds_bytes(MjpcHipEngine *e) { return e ? (int)e->lds_bytes : 0; }
+// 1 when the engine runs the spill flavour; *slab_bytes = its HBM slab per candidate (0 without one)
+int mjpc_hip_debug_spill(MjpcHipEngine *e, int *slab_bytes) {
+  if (slab_bytes) *slab_bytes = e ? e->slab_bytes : 0;
+  return (e && e->spill) ? 1 : 0;
+}
+// host-only (no HIP call): the (LDS bytes, slab bytes per candidate) of the full-capacity flavour mjpc_hip_create would choose for
+// this model under the current knobs; returns 1 when that is the spill flavour, 0 otherwise, < 0: refused (mjpc_hip_last_error)
+int mjpc_hip_debug_spill_layout(const MjpcHipModel *model, const MjpcHipTask *task, int *lds_bytes, int *slab_bytes) {
+  if (!model || !task) { set_error("mjpc_hip_debug_spill_layout: invalid argument"); return -1; }
+  if (model->struct_size != (int)sizeof(MjpcHipModel) || task->struct_size != (int)sizeof(MjpcHipTask)) {
+    set_error("mjpc_hip_debug_spill_layout: MjpcHipModel / MjpcHipTask struct_size does not match this library"); return -1; }
+  PackedModel pm;
+  RolloutFn k = nullptr; bool cached = true, spill = false;
+  if (!pick_flavour(model, task, 36, pm, &k, &cached, &spill, "mjpc_hip_debug_spill_layout")) return -1;
+  if (lds_bytes) *lds_bytes = (int)((size_t)pm.L.total_doubles * sizeof(double));
+  if (slab_bytes) *slab_bytes = spill ? (int)(((size_t)pm.slab_doubles * sizeof(double) + 255) / 256 * 256) : 0;
+  return spill ? 1 : 0;
+}
 void mjpc_hip_debug_dense_capacity(MjpcHipEngine *e, int *nefc, int *ncon, int *hot) {
   if (nefc) *nefc = (e && e->kernelB) ? e->nefcB : 0;
   if (ncon) *ncon = (e && e->kernelB) ? e->nconB : 0;

@@ -23,6 +23,7 @@ struct PackedModel {
   size_t task_i0, task_d0, task_i_cap, task_d_cap;   // task region inside ib/db
   size_t cache_i, cache_d;                           // prefix of ib/db copied into LDS by every workgroup
   size_t hot_i = 0, hot_d = 0;                       // the shorter prefix the hot-tables-only flavour copies
+  int slab_doubles = 0;                              // per-candidate HBM slab of the spill flavour (make_layout), 0 without one
   std::string error;
 };
 
@@ -79,12 +80,16 @@ static inline void pack_task(PackedModel &p, const MjpcHipTask *t) {
 }
 
 // lean: the dense tier's layout (rollout_dense2.hip, MJPC_LEAN_LDS): spline knots and the Hessian entry table are read from HBM / L2
-static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel *m, const MjpcHipTask *t, int P_max, size_t cache_d, size_t cache_i, bool lean = false, bool reg_solver = false) {
+// spill: a mask of SPILL_* blocks laid out in the per-candidate HBM slab instead of LDS (rollout_spill.hip; never with lean).  A
+// spilled block's offset is LAY_SLAB(offset in the slab); the slab keeps the blocks in the LDS order (efc_J, efc_JA, vectors,
+// contact, noslip), so efc_J and efc_JA stay adjacent when both move.  *slab_doubles = the slab's extent (0 without spill).
+static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel *m, const MjpcHipTask *t, int P_max, size_t cache_d, size_t cache_i, bool lean = false, bool reg_solver = false, unsigned spill = 0, int *slab_doubles = nullptr, int *scratch = nullptr) {
   const DevModel &M = p.M;
   int nb = m->nbody, nj = m->njnt, nv = m->nv, ng = m->ngeom, ns = m->nsite, nu = m->nu;
-  int o = 0;
+  int o = 0, so = 0;
   int nvp = M.nvp, ne = M.nefcmax, nc = M.nconmax, nr = t->num_residual;
 #define A_(f, n) L.f = o; o += (int)(n)
+#define S_(bit, f, n) if (spill & (bit)) { L.f = LAY_SLAB(so); so += (int)(n); } else { A_(f, n); }
   A_(qpos, m->nq); A_(qvel, nv); A_(ctrl, nu + 1 + 2 * m->na);      // activations and their derivatives sit behind ctrl (C_ACT / C_ACTDOT)
   A_(qacc, nv); A_(qacc_ws, nv); A_(qacc_smooth, nv); A_(qfrc_smooth, nv);
   A_(qfrc_bias, nv); A_(qfrc_constraint, nv); A_(actuator_force, nu + 1); A_(mocap_pos, 3 * m->nmocap + 3); A_(mocap_quat, 4 * m->nmocap + 4);
@@ -103,7 +108,7 @@ static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel 
   // contact (padded to 4)
   int ja_rows = ((ne - M.nfric + 7) & ~7) + (m->cone == MJPC_CONE_ELLIPTIC ? ((nc + 3) & ~3) : 0) + 4 + ((M.ntfric + 3) & ~3);
   
-  A_(efc_J, (ne - M.nfric) * nvp + 1);
+  S_(SPILL_EFC_J, efc_J, (ne - M.nfric) * nvp + 1);
   // the register Newton path (solver_reg.h) uses the same block for its gradient scratch (64), the line search's row / contact
   // records (7 per row, 17 per contact) and, on elliptic models, the contacts' dof lists (a byte per dof), their (contact, row) pairs (two bytes each) and one partial Hessian
   // per worker wave (nv x nvp each)
@@ -112,26 +117,32 @@ static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel 
   // builds the scaled-row table: the block only has to hold the records / partials above (hand: 12 KB instead of 35 KB)
   int ja_size = reg_solver ? ja_need + 1 : ja_rows * nvp + 1;
   if (ja_size < ja_need) ja_size = ja_need;
-  A_(efc_JA, ja_size);
+  S_(SPILL_EFC_JA, efc_JA, ja_size);
+  // the implicit integrators' scratch (DevModel::int_scratch): efc_J, and efc_JA behind it when both live in the same memory
+  if (scratch) *scratch = ((spill & SPILL_EFC_J) != 0) == ((spill & SPILL_EFC_JA) != 0) ? (ne - M.nfric) * nvp + 1 + ja_size : (ne - M.nfric) * nvp + 1;
   if (lean) {
     int q = L.efc_JA;
     L.cinert = q; q += 10 * nb; L.crb = q; q += 10 * nb; L.cdof_dot = q; q += 6 * nv + 18;
     L.cacc = q; q += 6 * nb; L.cfrc = q; q += 6 * nb; L.cfrc_sub = q; q += 6 * nb;
     if (q > o) o = q;
   }
-  A_(efc_D, ne); A_(efc_R, ne); A_(efc_aref, ne); A_(efc_force, ne); A_(efc_jar, ne); A_(efc_jv, ne);
-  A_(efc_floss, ne); A_(efc_pos, ne);
+  S_(SPILL_EFC_VEC, efc_D, ne); S_(SPILL_EFC_VEC, efc_R, ne); S_(SPILL_EFC_VEC, efc_aref, ne); S_(SPILL_EFC_VEC, efc_force, ne);
+  S_(SPILL_EFC_VEC, efc_jar, ne); S_(SPILL_EFC_VEC, efc_jv, ne); S_(SPILL_EFC_VEC, efc_floss, ne); S_(SPILL_EFC_VEC, efc_pos, ne);
   L.efc_margin = L.efc_jv; L.efc_diag = L.efc_force;
-  A_(contact, nc * M.con_stride + 1);
+  S_(SPILL_CONTACT, contact, nc * M.con_stride + 1);
   A_(Ma, nv + 1); A_(grad, nv + 1); A_(Mgrad, nv + 1); A_(search, nv + 1); A_(Mv, nv + 1); A_(vtmp, nv + 1); A_(sgl, 4 * nv + 1);
   if (lean) { L.knot_times = 0; L.knot_values = 0; } else { A_(knot_times, P_max); A_(knot_values, P_max * nu + 1); }
   A_(residual, nr + 1); A_(terms, t->num_term + 1); A_(red, 8); A_(prof, 26);
   A_(scr_a, nv + 1); A_(scr_b, nv + 1);                       // solve-phase scratch of the side wave / of the helper's cost at qacc_smooth
   if (lean) L.xfrc = 0; else { A_(xfrc, 6 * nb); }             // no force noise on the dense tier (engine.hip)
-  if (m->noslip_iterations > 0) { A_(noslip, ne * nvp + nc * 36 + 2 * ne + 1); } else L.noslip = 0;
+  if (m->noslip_iterations > 0) { S_(SPILL_NOSLIP, noslip, ne * nvp + nc * 36 + 2 * ne + 1); } else L.noslip = 0;
   A_(mc_d, cache_d + 1); A_(mc_i, (cache_i + 2) / 2);
   L.ints = o;
+#undef S_
 #undef A_
+  // a spilled block is read past its end the way LDS is (a friction-loss-only step reads the nvp doubles of "row nfric" of a
+  // one-double efc_J block): the slab's tail pad keeps every such read inside the allocation
+  if (slab_doubles) *slab_doubles = so ? so + nvp + 64 : 0;
   int io = 0;
   L.i_efc_type = io; io += ne; L.i_efc_id = io; io += ne; L.i_efc_state = io; io += ne; L.i_efc_dof = io; io += ne;
   L.i_con = io; io += nc * CONI_STRIDE; L.i_active = io; io += (ne + nc + M.ntfric > MAX_ACTIVE_PAIRS ? ne + nc + M.ntfric : MAX_ACTIVE_PAIRS); L.i_misc = io; io += MISC_INTS;
@@ -141,8 +152,10 @@ static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel 
 
 // use_cache: lay out an LDS copy of the model tables (rollout_cached.hip) or none (rollout_direct.hip)
 // use_cache: whole LDS copy of the tables; hot_only (with use_cache == false): only the hot prefix
-static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTask *t, int P_max, bool use_cache = true, bool lean = false, bool hot_only = false, bool reg_solver = false) {
-  p.ib.clear(); p.db.clear(); p.error.clear();
+// spill_mode (the spill flavour, rollout_spill.hip; not with lean): SPILL_AUTO moves the eligible blocks to the HBM slab one after
+// the other in SPILL_ORDER until the LDS part fits 160 KiB, SPILL_ALL moves every eligible block (diagnostics knob "spill")
+static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTask *t, int P_max, bool use_cache = true, bool lean = false, bool hot_only = false, bool reg_solver = false, int spill_mode = SPILL_NONE) {
+  p.ib.clear(); p.db.clear(); p.error.clear(); p.slab_doubles = 0;
   DevModel &M = p.M;
   memset(&M, 0, sizeof(M));
   int nb = m->nbody, nj = m->njnt, nv = m->nv, ng = m->ngeom, ns = m->nsite, nu = m->nu;
@@ -592,6 +605,22 @@ static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTas
   if (!use_cache) { p.cache_i = hot_only ? p.hot_i : 0; p.cache_d = hot_only ? p.hot_d : 0; }      // the kernel reads (the rest of) the tables from HBM / L2
   make_layout(p, p.L, m, t, P_max, p.cache_d, p.cache_i, lean, reg_solver);
   M.int_scratch = p.L.efc_D - p.L.efc_J;            // efc_J and efc_JA are adjacent and dead after the solve
+  if (spill_mode != SPILL_NONE && !lean) {
+    // eligible: the blocks sized by nefcmax / nconmax.  In a compile-time-nv layout efc_JA holds the cone partial Hessians that
+    // solver_reg.h accumulates with LDS atomics: it stays in LDS there
+    static const unsigned order[] = {SPILL_NOSLIP, SPILL_EFC_JA, SPILL_EFC_J, SPILL_CONTACT, SPILL_EFC_VEC};
+    const unsigned eligible = SPILL_EVERY & ~(reg_solver ? SPILL_EFC_JA : 0u) & ~(m->noslip_iterations > 0 ? 0u : SPILL_NOSLIP);
+    unsigned mask = 0;
+    for (unsigned bit : order) {
+      if (!(eligible & bit)) continue;
+      if (spill_mode == SPILL_AUTO && (size_t)p.L.total_doubles * sizeof(double) <= 160 * 1024) break;
+      mask |= bit;
+      if (M.int_dense && bit == SPILL_EFC_JA) mask |= SPILL_EFC_J;      // the dense integrator path's scratch runs from efc_J into efc_JA
+      int scratch = 0;
+      make_layout(p, p.L, m, t, P_max, p.cache_d, p.cache_i, lean, reg_solver, mask, &p.slab_doubles, &scratch);
+      M.int_scratch = scratch;
+    }
+  }
   if (M.int_dense == 2 && M.int_scratch < 18 * nb) { p.error = "implicit integrator: no room for the bias-derivative scratch in LDS (raise nefcmax)"; return false; }
   if (M.int_dense && lean) { p.error = "the implicit integrators' dense path has no dense-tier layout"; return false; }
   return true;

@@ -159,6 +159,16 @@ struct DevModel {
 };
 
 // LDS carve-up, offsets in doubles (ints live behind `ints`, offsets in ints)
+// The spill flavour (rollout_spill.hip) keeps the blocks sized by nefcmax / nconmax in a per-candidate slab in HBM instead: such a
+// block's offset is LAY_SLAB(offset in the slab), negative, and core.h lay_ptr() resolves it (host.h make_layout, SPILL_*)
+#define LAY_SLAB(off) (-1 - (off))
+#define SPILL_NOSLIP 1u        // noslip table
+#define SPILL_EFC_JA 2u        // scaled rows of the Newton Hessian (never in a compile-time-nv layout: LDS atomics, solver_reg.h)
+#define SPILL_EFC_J 4u         // constraint Jacobian rows
+#define SPILL_CONTACT 8u       // contact records
+#define SPILL_EFC_VEC 16u      // the eight efc_* vectors (with their aliases efc_margin / efc_diag)
+#define SPILL_EVERY 31u
+enum { SPILL_NONE = 0, SPILL_AUTO = 1, SPILL_ALL = 2 };
 #define MISC_INTS 48     // per-candidate scalars and hand-shake flags in LDS (core.h / solver.h: misc[])
 struct Lay {
   int qpos, qvel, ctrl, qacc, qacc_ws, qacc_smooth, qfrc_smooth, qfrc_bias, qfrc_constraint, actuator_force;
@@ -201,4 +211,7 @@ struct KParams {
   int *failure, *diag;
   double *frame;       // kinematic frame of local candidate 0 at step 0: xpos | xmat | site_xpos | subtree_com | subtree_linvel
   long long *prof;     // optional per-candidate phase cycle counters (MJPC_PROFILE builds)
+  // spill flavour (MJPC_SPILL): candidate r's slab is slab + r * slab_stride (doubles, whole 256-B blocks).  Last in the struct:
+  // the other flavours' kernarg offsets stay what they were
+  double *slab; long long slab_stride;
 };

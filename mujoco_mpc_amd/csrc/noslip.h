@@ -8,7 +8,7 @@
 // w += sum_k d_k B_k, the small diagonal blocks J_blk B_blk^T are formed once per step.  Same sweeps, same block updates and
 // the same stopping rule as the CPU restatement the tests check it against.
 #pragma once
-#define NS_BT(c) (lds_base() + (c).K->L.noslip)
+#define NS_BT(c) lay_ptr((c).K, lds_base(), (c).K->L.noslip)      // LDS, or the HBM slab in the spill flavour
 
 // entry i of constraint row r (a friction-loss row is the unit vector of its dof and has no stored row)
 DEV double ns_jent(Ctx &c, int r, int i) { return r < c.M->nfric ? (c.efc_dof[r] == i ? 1.0 : 0.0) : c.efc_J[r * c.M->nvp + i]; }

@@ -48,6 +48,16 @@ DEV int wave_any(int flag) { return flag != 0; }
 //   helpers (waves 1 .. MJPC_WAVES-2): share the data-parallel parts of every Newton iteration with role 0 (solver.h).
 // SYNC() orders LDS traffic inside ONE wave (DS operations of a wave execute in order; only the compiler must not
 // reorder them), XBAR() is the workgroup barrier between the roles.
+// The spill flavour (rollout_spill.hip) keeps some of the same state in a per-candidate HBM slab, accessed with global / flat
+// instructions, and relies on the same fences to order it (LLVM AMDGPU memory model, GFX942 family, which gfx950 follows):
+//  - one wave: vector memory operations of a wave complete in issue order and a load sees the wave's earlier store to the
+//    same address, so a wavefront-scope fence needs no wait instruction; the fence in SYNC() has no address space attached, so
+//    it also stops the compiler from moving a global access across it.
+//  - waves of the workgroup: without threadgroup-split mode (never enabled here) all waves of a workgroup run on one CU and
+//    share its vector L1, so workgroup scope needs no cache invalidation; a workgroup-scope release (XBAR(), flag_set) waits
+//    for the wave's earlier vector memory operations (s_waitcnt vmcnt) before the barrier / flag store, the acquire after it
+//    keeps the later loads behind it.  Checked in the flavour's ISA: every s_barrier follows a vmcnt wait or the return of a
+//    call (which drains all counters).
 #ifndef MJPC_WAVES
 #define MJPC_WAVES 4
 #endif

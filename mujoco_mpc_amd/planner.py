@@ -120,6 +120,12 @@ class HipBackend:
     def lds_bytes(self):
         return self.lib.mjpc_hip_lds_bytes(self.h)
 
+    def spill_bytes(self):
+        """Bytes of HBM slab per candidate of the spill flavour (state too large for LDS, rollout_spill.hip); 0 when it runs in LDS."""
+        n = C.c_int(0)
+        self.lib.mjpc_hip_debug_spill(self.h, C.byref(n))
+        return n.value
+
     def dense_tier(self):
         """(LDS bytes of the two-candidates-per-CU tier or 0, whether the last plan ran on it)."""
         used = C.c_int(0)

@@ -116,7 +116,8 @@ DEV void subtree_sums(Ctx &c, int part) {
     } else {
       int kk = k - 3;
       double s = 0;
-      for (int q = MIH(subtree_adr)[b]; q < MIH(subtree_adr)[b + 1]; q++) s += c.bodytmp[3 * MIH(subtree_list)[q] + kk];
+      // (a list starts with the body itself; the world's own entry is skipped: it has no momentum, and bodytmp[0] is residual scratch)
+      for (int q = MIH(subtree_adr)[b] + (b == 0); q < MIH(subtree_adr)[b + 1]; q++) s += c.bodytmp[3 * MIH(subtree_list)[q] + kk];
       c.subtree_linvel[3 * b + kk] = s / fmax(D_MINVAL, MDH(body_subtreemass)[b]);
     }
   }

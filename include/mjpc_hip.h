@@ -79,8 +79,12 @@ enum {
                                   * x, y, (local_pos1[3], local_pos2[3]) x 5]; parameters = [head height goal, torso height goal] */
   MJPC_TASK_FINGERS = 16,        /* mjpc/tasks/fingers/fingers.cc:31-62: finger_a - object, finger_b - object (framepos of the bodies), distance of the three
                                   * object sites to their targets, control; int_data = [body finger_a, finger_b, object, sites 0 1 2, sites 0t 1t 2t] */
-  MJPC_TASK_QUADROTOR = 13       /* mjpc/tasks/quadrotor/quadrotor.cc:37-60: position - goal, linear / angular velocity, control - hover thrust (13 of
+  MJPC_TASK_QUADROTOR = 13,      /* mjpc/tasks/quadrotor/quadrotor.cc:37-60: position - goal, linear / angular velocity, control - hover thrust (13 of
                                  * the 15 declared residuals are written); int_data = [body, stage]; dbl_data = stage goals [nstage][7] */
+  MJPC_TASK_ALLEGRO = 17,        /* mjpc/tasks/allegro/allegro.cc:36-77: the Shadow residual with 16-wide slices (57 residuals); int_data = [grasp site,
+                                  * cube body, goal body, key] */
+  MJPC_TASK_OP3 = 18             /* mjpc/tasks/op3/stand.cc:34-152 (53 residuals, rows by mode): int_data = [mode (0 Stand, 1 Handstand), sites head,
+                                  * left_foot, right_foot, left_hand, right_hand, torso, body body_link]; parameters = [height goal] */
 };
 enum { MJPC_TRN_JOINT = 0, MJPC_TRN_TENDON = 3, MJPC_TRN_SITE = 4 };   /* mjtTrn values of the supported actuator transmissions */
 enum { MJPC_OBJ_BODY = 1, MJPC_OBJ_XBODY = 2, MJPC_OBJ_GEOM = 5, MJPC_OBJ_SITE = 6 };

@@ -5,10 +5,11 @@
 // flat arrays, refreshed at the top of every plan step (HipSamplingPlanner::RefreshTask).  Layouts: DESIGN.md section 2 and
 // mujoco_mpc_amd/csrc/residuals.h (QI_* / QD_*).  This file is compiled inside an MJPC tree only (needs <mujoco/mujoco.h>).
 //
-// Two ResidualFn classes keep that state private.  No edit of the reference is needed: compile THIS file with
+// Four ResidualFn classes keep that state private.  No edit of the reference is needed: compile THIS file with
 // `-fno-access-control` (GCC and Clang; CMake: set_source_files_properties(frozen_state.cc PROPERTIES COMPILE_OPTIONS
 // -fno-access-control)) — or, for a compiler without that switch, add `friend struct mjpc::HipFrozenState;` to
-// QuadrupedFlat::ResidualFn (quadruped.h:169) and humanoid::Tracking::ResidualFn (tracking.h:33).
+// QuadrupedFlat::ResidualFn (quadruped.h:169), humanoid::Tracking::ResidualFn (tracking.h:33), humanoid::Interact::ResidualFn
+// and OP3::ResidualFn (stand.h:27).
 #include <string>
 #include <vector>
 
@@ -16,6 +17,7 @@
 #include "mjpc/task.h"
 #include "mjpc/tasks/humanoid/interact/interact.h"
 #include "mjpc/tasks/humanoid/tracking/tracking.h"
+#include "mjpc/tasks/op3/stand.h"
 #include "mjpc/tasks/quadruped/quadruped.h"
 #include "mjpc/utilities.h"
 
@@ -96,6 +98,17 @@ struct HipFrozenState {
     I = {SensorObject(m, "palm_position"), SensorObject(m, "cube_position"), SensorObject(m, "cube_goal_orientation"),
          0};                                   // hand.cc:75 reads key 0 (model->key_qpos)
   }
+  static void Allegro(const mjModel* m, std::vector<int>& I) {         // allegro.cc:36-77
+    I = {SensorObject(m, "cube_goal_position"), SensorObject(m, "cube_position"), SensorObject(m, "cube_goal_orientation"),
+         0};                                   // allegro.cc:64 reads key 0 (model->key_qpos)
+  }
+  // stand.cc:34-152: the mode the residual sees (current_mode_, copied from Task::mode by OP3::TransitionLocked; private), then
+  // the sites behind the task's sensors and the body of its subtree sensors
+  static void OP3(const mjpc::OP3::ResidualFn& r, const mjModel* m, std::vector<int>& I) {
+    I = {r.current_mode_, SensorObject(m, "head_position"), SensorObject(m, "left_foot_position"), SensorObject(m, "right_foot_position"),
+         SensorObject(m, "left_hand_position"), SensorObject(m, "right_hand_position"), SensorObject(m, "torso_up"),
+         SensorObject(m, "body_subtreecom")};
+  }
   // quadruped.cc:726-768 (the stage counter current_mode_ of QuadrupedHill::ResidualFn is public state of the task: Task::mode)
   static void Hill(const mjModel* m, int stage, std::vector<int>& I, std::vector<double>& D) {
     I = {SensorObject(m, "position"), SensorObject(m, "FR"), SensorObject(m, "FL"), SensorObject(m, "RR"), SensorObject(m, "RL"), stage};
@@ -149,6 +162,12 @@ void FillFrozenState(const Task& task, const ResidualFn* residual, const mjModel
       HipFrozenState::Interact(*r, m, ints, dbls);
     } break;
     case MJPC_TASK_SHADOW_REORIENT: HipFrozenState::Hand(m, ints); break;
+    case MJPC_TASK_ALLEGRO: HipFrozenState::Allegro(m, ints); break;
+    case MJPC_TASK_OP3: {
+      auto* r = dynamic_cast<const mjpc::OP3::ResidualFn*>(residual);
+      if (!r) mju_error("HipSamplingPlanner: task 'OP3' without an OP3::ResidualFn");
+      HipFrozenState::OP3(*r, m, ints);
+    } break;
     case MJPC_TASK_QUADRUPED_HILL: HipFrozenState::Hill(m, task.mode > 0 ? task.mode - 1 : 0, ints, dbls); break;
     case MJPC_TASK_QUADROTOR: HipFrozenState::Quadrotor(m, task.mode > 0 ? task.mode - 1 : 0, ints, dbls); break;
     case MJPC_TASK_SWIMMER: HipFrozenState::Swimmer(m, ints); break;

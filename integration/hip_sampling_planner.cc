@@ -41,6 +41,8 @@ int DeviceResidual(const Task& task) {
   if (name == "Swimmer") return MJPC_TASK_SWIMMER;
   if (name == "Acrobot") return MJPC_TASK_ACROBOT;
   if (name == "FreeFingers") return MJPC_TASK_FINGERS;
+  if (name == "Allegro") return MJPC_TASK_ALLEGRO;
+  if (name == "OP3") return MJPC_TASK_OP3;
   return -1;
 }
 

@@ -405,9 +405,10 @@ DEV void residual_humanoid_walk(Ctx &c, double *residual) {
   PFOR(i, nu) residual[12 + nq - 7 + 3 + i] = c.ctrl[i];
 }
 
-// mjpc/tasks/shadow_reorient/hand.cc:37-84.  int_data = [palm site, cube body, goal body, keyframe]; framepos / framequat /
-// framelinvel sensors with objtype="body" read the body's inertial frame
-DEV void residual_shadow(Ctx &c, double *residual) {
+// mjpc/tasks/shadow_reorient/hand.cc:37-84 (width 26) and mjpc/tasks/allegro/allegro.cc:36-77 (width 16).  int_data = [palm /
+// grasp site, cube body, goal body, keyframe]; framepos / framequat / framelinvel sensors with objtype="body" read the body's
+// inertial frame
+DEV void residual_hand(Ctx &c, double *residual, const int width) {
   const DevModel &M = *c.M;
   const int *I = MI(task.int_data);
   int palm = I[0], cube = I[1], goal = I[2], key = I[3], nu = M.nu;
@@ -423,11 +424,67 @@ DEV void residual_shadow(Ctx &c, double *residual) {
     residual[6] = lin[0]; residual[7] = lin[1]; residual[8] = lin[2];
   }
   PFOR(i, nu) residual[9 + i] = c.actuator_force[i];
-  // the 26-wide slices start at 7 / 6 and straddle the cube's free joint (hand.cc:75-80)
-  PFOR(i, 26) {
+  // the slices start at 7 / 6 although the goal's ball joint comes first: they straddle the cube's free joint (hand.cc:75-80,
+  // allegro.cc:64-70)
+  PFOR(i, width) {
     residual[9 + nu + i] = c.qpos[7 + i] - M.key_qpos[key * M.nq + 7 + i];
-    residual[9 + nu + 26 + i] = c.qvel[6 + i];
+    residual[9 + nu + width + i] = c.qvel[6 + i];
   }
+}
+DEV void residual_shadow(Ctx &c, double *residual) { residual_hand(c, residual, 26); }
+
+// z (axis 2) or y (axis 1) axis of a site's frame, as MuJoCo's framezaxis / frameyaxis read it: site_xmat = mat(xquat[body] *
+// site_quat), column `axis`
+DEV void site_axis(Ctx &c, int s, int axis, double *out) {
+  double q[4], sq[4], R[9];
+  d_copy4(sq, MD(site_quat) + 4 * s);
+  d_mulquat(q, c.xquat + 4 * MI(site_bodyid)[s], sq);
+  d_quat2mat(R, q);
+  out[0] = R[axis]; out[1] = R[3 + axis]; out[2] = R[6 + axis];
+}
+// mjpc/tasks/op3/stand.cc:34-152.  int_data = [mode, sites head, left_foot, right_foot, left_hand, right_hand, torso, body body_link];
+// parameters = [height goal]; 53 residuals: height, balance, CoM xy velocity, ctrl - key_qpos[mode][7:7+nu], 13 upright rows,
+// qvel[6:]
+DEV void residual_op3(Ctx &c, double *residual) {
+  const DevModel &M = *c.M;
+  const int *I = MI(task.int_data);
+  const int mode = I[0], head = I[1], lf = I[2], rf = I[3], lh = I[4], rh = I[5], torso = I[6], body = I[7];
+  const int nu = M.nu, nv = M.nv;
+  if (LANE == 0) {
+    const double *hp = c.site_xpos + 3 * head, *lfp = c.site_xpos + 3 * lf, *rfp = c.site_xpos + 3 * rf;
+    const double *lhp = c.site_xpos + 3 * lh, *rhp = c.site_xpos + 3 * rh;
+    const double *com = c.subtree_com + 3 * body, *comvel = c.subtree_linvel + 3 * body;
+    // height: the Handstand row keeps the reference's minus between the hands (stand.cc:64-67)
+    if (mode == 0) residual[0] = (hp[2] - 0.5 * (lfp[2] + rfp[2])) - MD(task.parameters)[0];
+    else residual[0] = (0.5 * (lfp[2] + rfp[2]) - 0.5 * (lhp[2] - rhp[2])) - MD(task.parameters)[0];
+    // balance: capture point (kFallTime 0.05) against the mean of the supporting sites in xy
+    double cp[3] = {com[0], com[1], com[2]};
+    for (int k = 0; k < 3; k++) cp[k] += comvel[k] * 0.05;
+    const double *a = mode == 0 ? lfp : lhp, *b = mode == 0 ? rfp : rhp;
+    double fx = 0.0, fy = 0.0;
+    fx += a[0]; fy += a[1]; fx += b[0]; fy += b[1];
+    fx *= 0.5; fy *= 0.5;
+    fx -= cp[0]; fy -= cp[1];
+    residual[1] = sqrt(fx * fx + fy * fy);
+    residual[2] = comvel[0]; residual[3] = comvel[1];
+    // upright (stand.cc:98-140): 13 rows from 4 + nu
+    double *u = residual + 4 + nu, ax[3];
+    const double z[3] = {0.0, 0.0, 1.0};
+    if (mode == 0) {
+      site_axis(c, rf, 2, ax); for (int k = 0; k < 3; k++) u[k] = (ax[k] - z[k]) * 0.1;
+      site_axis(c, lf, 2, ax); for (int k = 0; k < 3; k++) u[3 + k] = (ax[k] - z[k]) * 0.1;
+      site_axis(c, torso, 2, ax); u[6] = ax[2] - 1.0;
+      for (int k = 7; k < 13; k++) u[k] = 0.0;
+    } else {
+      site_axis(c, rh, 1, ax); for (int k = 0; k < 3; k++) u[k] = (ax[k] - z[k]) * 0.1;
+      site_axis(c, lh, 1, ax); for (int k = 0; k < 3; k++) u[3 + k] = (ax[k] + z[k]) * 0.1;
+      site_axis(c, rf, 2, ax); for (int k = 0; k < 3; k++) u[6 + k] = (ax[k] + z[k]) * 0.1;
+      site_axis(c, lf, 2, ax); for (int k = 0; k < 3; k++) u[9 + k] = (ax[k] + z[k]) * 0.1;
+      site_axis(c, torso, 2, ax); u[12] = 1.0 * (ax[2] + 1.0);
+    }
+  }
+  PFOR(i, nu) residual[4 + i] = c.ctrl[i] - M.key_qpos[mode * M.nq + 7 + i];
+  PFOR(i, nv - 6) residual[17 + nu + i] = c.qvel[6 + i];
 }
 
 DEV void task_residual(Ctx &c, double *residual) {
@@ -459,6 +516,10 @@ DEV void task_residual(Ctx &c, double *residual) {
     residual_humanoid_interact(c, residual);
   } else if (id == 7) {
     residual_shadow(c, residual);
+  } else if (id == 17) {
+    residual_hand(c, residual, 16);
+  } else if (id == 18) {
+    residual_op3(c, residual);
   } else if (id == 8) {   // walker.cc:39-57: control, torso height - goal, torso z axis z - 1, subtree x velocity - goal
     int nu = M.nu, b = MI(task.int_data)[0];
     PFOR(i, nu) residual[i] = c.ctrl[i];

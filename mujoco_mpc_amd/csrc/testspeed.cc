@@ -393,7 +393,23 @@ static void SwimmerTransition(const MjpcHipModel& m, SimState& s, HostTask& t, c
 static const double kInteractWeights[4][13] = {{10, 10, 5, 5, 0, 20, 30, 0, 0, 0, 0.01, .1, 80.}, {10, 0, 1, 1, 80, 0, 0, 100, 0, 0, 0.01, 0.025, 0.},
                                                {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.01, .8, 80.}, {0, 0, 0, 0, 0, 0, 0, 0, 0, 50, 20, .025, 80.}};
 
+// OP3::TransitionLocked (stand.cc:154-163): a mode change (0 Stand, 1 Handstand) is copied into the residual's mode and installs
+// that mode's height goal, kModeHeight (stand.h:61).  int_data[0] plays residual_.current_mode_, parameters[0] the height goal.
+static const double kOP3ModeHeight[2] = {0.38, 0.57};
+
 TransitionFn TransitionForTask(int task_id, int mode, double mode_time) {
+  if (task_id == MJPC_TASK_OP3) {
+    return [mode, mode_time](const MjpcHipModel&, SimState& s, HostTask& t, const SimFrame&) {
+      if (t.int_data.empty()) return;
+      int want = s.time >= mode_time ? mode : t.int_data[0];
+      if (want < 0 || want > 1) want = 0;
+      if (t.int_data[0] != want) {
+        t.int_data[0] = want;
+        if (!t.parameters.empty()) t.parameters[0] = kOP3ModeHeight[want];
+      }
+    };
+  }
+  if (task_id == MJPC_TASK_ALLEGRO) return HandTransition;     // Allegro::TransitionLocked (allegro.cc:79-110) has the same criterion
   if (task_id == MJPC_TASK_HUMANOID_INTERACT) {
     auto current = std::make_shared<int>(0);                 // residual_.current_task_mode_ starts as kSitting
     return [current, mode, mode_time](const MjpcHipModel&, SimState& s, HostTask& t, const SimFrame&) {

@@ -15,7 +15,7 @@ import struct
 
 import numpy as np
 
-from .builder import (BALL, BOX, CAPSULE, CYLINDER, ELLIPSOID, FREE, HFIELD, HINGE, PLANE, SLIDE, SPHERE, ModelBuilder)
+from .builder import (BALL, BOX, CAPSULE, CYLINDER, ELLIPSOID, FREE, HFIELD, HINGE, MESH, PLANE, SLIDE, SPHERE, ModelBuilder)
 
 TASK_PARTICLE, TASK_CARTPOLE, TASK_QUADRUPED, TASK_COPYSTATE, TASK_HUMANOID_TRACK, TASK_HUMANOID_STAND, TASK_HUMANOID_WALK = 0, 1, 2, 3, 4, 5, 6
 TASK_SHADOW_REORIENT = 7
@@ -834,6 +834,205 @@ def shadow_hand(timestep=0.01, cone=0, nconmax=32, nefcmax=128):
     return m, task, defaults
 
 
+# ----------------------------------------------------------------------------------- Allegro hand + cube (registry "Allegro")
+# mjpc/tasks/allegro/task.xml is local (implicitfast, iterations 100 / ls_iterations 50, default friction 0.3, the floor at z -0.2,
+# the goal body, the cost table, planner numerics and the 27-value `home` key), so is the cube (common_assets/reorientation_cube.xml,
+# unpatched here: half size 0.03, 0.122 kg, at 0.2 0 0.075).  right_hand.xml.patch shows what the task changes in menagerie's
+# wonik_allegro/right_hand.xml: position kp 0.5, the palm at pos 0.25 0 0 / quat 0 1 0 0.7, `grasp_site` at the palm's origin and the
+# trace sensors on rf_tip, ff_tip, mf_tip and th_tip.  The hand file itself is fetched by CMake and NOT in the reference tree, so the
+# hand below is SYNTHETIC, documented as such: the published kinematic tree of the Allegro right hand (palm welded to the world; first,
+# middle and ring finger with joints j0 about the local z axis and j1..j3 about y; the thumb's j0 about -x, j1 about z, j2 and j3 about
+# y; 16 hinges in the order ff, mf, rf, th), link offsets, joint ranges and joint damping 0.1 as recalled from that file; collision
+# boxes of the links' dimensions and sphere finger tips (density 800) stand in for its meshes; the actuators' force range +-0.7 is an
+# assumption.  The hand's own geoms do not collide with each other (they touch the cube and the floor only).
+# Sizes match the reference's task: nq 27, nv 25, nu 16, 57 residuals, 6 cost terms.
+TASK_ALLEGRO = 17
+_ALLEGRO_HOME = [1, 0, 0, 0, 0.2, 0.025, 0.075, 1, 0, 0, 0, 0, 0.58058, 0.701595, 0.538675, 0, 0.60767, 0.758085, 0.741625, 0, 0.8876,
+                 0.720425, 0.5848, 0.263, 0.32612, 1.08493, 0.806715]        # task.xml:69
+_ALLEGRO_FINGER_RANGES = [(-0.47, 0.47), (-0.196, 1.61), (-0.174, 1.709), (-0.227, 1.618)]
+_ALLEGRO_THUMB_RANGES = [(0.263, 1.396), (-0.105, 1.163), (-0.189, 1.644), (-0.162, 1.719)]
+
+
+def allegro(timestep=0.01, nconmax=32, nefcmax=128):
+    """Allegro-hand cube rotation (mjpc/tasks/allegro/task.xml + allegro.cc) on the synthetic hand described above."""
+    b = ModelBuilder(timestep=timestep, cone=0, integrator=3, iterations=100, ls_iterations=50)
+    b.nconmax = nconmax; b.nefcmax = nefcmax
+    fr = (0.3, 0.005, 0.0001)                                       # task.xml:36-38 <default><geom friction=".3"/>
+    b.geom(0, "floor", PLANE, pos=(0, 0, -0.2), size=(0, 0, 0.05), friction=fr)
+    goal = b.body("goal", 0, pos=(0.325, 0.17, 0.0475))            # task.xml:44-47
+    b.joint(goal, "goal_ball", BALL, damping=0.001)
+    b.geom(goal, "goal", BOX, size=(0.03, 0.03, 0.03), mass=0.124, contype=0, conaffinity=0, friction=fr)
+    cube = b.body("cube", 0, pos=(0.2, 0.0, 0.075))                 # reorientation_cube.xml
+    b.joint(cube, "cube_free", FREE)
+    b.geom(cube, "cube", BOX, size=(0.03, 0.03, 0.03), mass=0.122, friction=fr)
+    H = dict(contype=0, conaffinity=1, friction=fr, density=800.0)  # hand geoms: touch the cube and the floor, not each other
+    palm = b.body("palm", 0, pos=(0.25, 0, 0), quat=(0, 1, 0, 0.7))   # right_hand.xml.patch: pos 0.25 0 0, quat 0 1 0 0.7
+    grasp_site = b.site(palm, "grasp_site")
+    b.geom(palm, "palm", BOX, size=(0.0204, 0.0565, 0.0475), pos=(-0.0093, 0, -0.0475), **H)
+
+    def hinge(body, name, axis, rng):
+        b.joint(body, name, HINGE, axis=axis, limited=True, range=rng, damping=0.1)
+
+    def links(prefix, base, lengths):
+        """proximal / medial / distal links of the given lengths below `base`, each a box collision, then the tip body"""
+        parent, pos = base, lengths[0]
+        for k, (link, length) in enumerate(zip(("proximal", "medial", "distal"), lengths[1:])):
+            body = b.body(f"{prefix}_{link}", parent, pos=(0, 0, pos))
+            hinge(body, f"{prefix}j{k + 1}", (0, 1, 0), (_ALLEGRO_THUMB_RANGES if prefix == "th" else _ALLEGRO_FINGER_RANGES)[k + 1])
+            b.geom(body, f"{prefix}_{link}", BOX, size=(0.0098, 0.01375, 0.5 * length), pos=(0, 0, 0.5 * length), **H)
+            parent, pos = body, length
+        tip = b.body(f"{prefix}_tip", parent, pos=(0, 0, pos))
+        b.geom(tip, f"{prefix}_tip", SPHERE, size=(0.012,), **H)
+        if prefix == "ff":
+            b.site(tip, "tip")                                      # right_hand.xml.patch: <site name="tip"/> in ff_tip
+        return tip
+
+    for prefix, pos, quat in (("ff", (0, 0.0435, -0.001542), (0.999048, -0.0436194, 0, 0)), ("mf", (0, 0, 0.0007), (1, 0, 0, 0)),
+                              ("rf", (0, -0.0435, -0.001542), (0.999048, 0.0436194, 0, 0))):
+        base = b.body(f"{prefix}_base", palm, pos=pos, quat=quat)
+        hinge(base, f"{prefix}j0", (0, 0, 1), _ALLEGRO_FINGER_RANGES[0])
+        b.geom(base, f"{prefix}_base", BOX, size=(0.0098, 0.01375, 0.0082), pos=(0, 0, 0.0082), **H)
+        links(prefix, base, [0.0164, 0.054, 0.0384, 0.0267])
+    thb = b.body("th_base", palm, pos=(-0.0182, 0.019333, -0.045987), quat=(0.477714, -0.521334, -0.521334, -0.477714))
+    hinge(thb, "thj0", (-1, 0, 0), _ALLEGRO_THUMB_RANGES[0])
+    b.geom(thb, "th_base", BOX, size=(0.0179, 0.017, 0.02275), pos=(-0.0179, 0.009, 0.0145), **H)
+    thp = b.body("th_proximal", thb, pos=(-0.027, 0.005, 0.0399))
+    hinge(thp, "thj1", (0, 0, 1), _ALLEGRO_THUMB_RANGES[1])
+    b.geom(thp, "th_proximal", BOX, size=(0.0098, 0.01375, 0.00885), pos=(0, 0, 0.00885), **H)
+    thm = b.body("th_medial", thp, pos=(0, 0, 0.0177))
+    hinge(thm, "thj2", (0, 1, 0), _ALLEGRO_THUMB_RANGES[2])
+    b.geom(thm, "th_medial", BOX, size=(0.0098, 0.01375, 0.0257), pos=(0, 0, 0.0257), **H)
+    thd = b.body("th_distal", thm, pos=(0, 0, 0.0514))
+    hinge(thd, "thj3", (0, 1, 0), _ALLEGRO_THUMB_RANGES[3])
+    b.geom(thd, "th_distal", BOX, size=(0.0098, 0.01375, 0.02115), pos=(0, 0, 0.02115), **H)
+    tht = b.body("th_tip", thd, pos=(0, 0, 0.0423))
+    b.geom(tht, "th_tip", SPHERE, size=(0.012,), **H)
+    # position servos, kp 0.5 (right_hand.xml.patch), control range = joint range, in the order of the original's <actuator> block
+    for prefix in ("ff", "mf", "rf", "th"):
+        for k in range(4):
+            rng = (_ALLEGRO_THUMB_RANGES if prefix == "th" else _ALLEGRO_FINGER_RANGES)[k]
+            b.position(f"{prefix}a{k}", f"{prefix}j{k}", kp=0.5, ctrlrange=rng, forcerange=(-0.7, 0.7))
+    b.key("home", _ALLEGRO_HOME)
+    m = b.compile()
+    assert (m["nq"], m["nv"], m["nu"]) == (27, 25, 16)
+    bid = m["names"]["body"]
+    # cost table: task.xml:51-56 (user = norm, weight, lo, hi, params...)
+    terms = [(3, 1, 75.0, [0.02, 2.0]), (3, 0, 7.5), (3, 0, 10.0), (16, 0, 1.0), (16, 0, 0.1), (16, 0, 1.0e-3)]
+    traces = [(OBJ_BODY, bid[n]) for n in ("cube", "rf_tip", "ff_tip", "mf_tip", "th_tip")]     # trace0 (task.xml), trace1..4 (the patch)
+    task = make_task(TASK_ALLEGRO, terms, traces=traces, int_data=[grasp_site, bid["cube"], bid["goal"], 0])
+    key = np.array(_ALLEGRO_HOME, float)
+    state = np.concatenate([key, np.zeros(m["nv"])])
+    # sampling numerics of task.xml:9-22: horizon 0.5 s at 0.01 s (H = 51), 6 cubic spline points, 10 trajectories, exploration 0.1
+    defaults = dict(N=10, P=6, sigma=(0.1, 0.0), interp=2, horizon=51, state=state, mocap=np.zeros(0), ctrl0=key[11:27].copy())
+    return m, task, defaults
+
+
+# ----------------------------------------------------------------------------------- Robotis OP3 (registry "OP3": Stand | Handstand)
+# mjpc/tasks/op3/task.xml is local (planner numerics with agent_timestep 0.015 as the model time step, the cost table, the height goal
+# 0.38, the keys `home` and `handstand`), op3.xml.patch shows what the task changes in menagerie's robotis_op3/op3.xml: the floor, the
+# head joints and their actuators removed (nq 25, nv 24, nu 18), the sites head / left_hand / right_hand / left_foot / right_foot and
+# the two foot boxes per foot with their sizes and positions.  The robot file itself is fetched by CMake and NOT in the reference tree,
+# so the robot below is SYNTHETIC, documented as such:
+#   * kinematic tree, joint order and axes as recalled from op3.xml: the free root body_link; per arm sho_pitch (y), sho_roll (-x),
+#     el (x); per leg hip_yaw (-z), hip_roll (-x), hip_pitch, knee, ank_pitch, ank_roll (x), the right side mirrored (pitch axes of
+#     the right arm and leg flipped).  The link offsets put the soles 1 mm above the floor at the `home` key (body_link at 0.246).
+#   * body_link's and the head links' inertials are the patch's context lines; the other links' masses are recalled, their
+#     inertias those of boxes of the links' size.
+#   * joints unlimited, damping 1.084, armature 0.045, frictionloss 0.03; position servos kp 21.1, ctrlrange +-pi, forcerange +-5;
+#     implicitfast integrator.  All recalled.
+#   * collision: the foot boxes of the patch; boxes / capsules for the torso, head, upper arms and legs; the forearms are convex
+#     meshes (the real robot's la3c / ra3c), since the handstand puts them on the floor.  The robot's geoms touch the floor only: the
+#     real model's <contact> excludes switch off the self-contacts between neighbouring links, here none are generated at all.
+#   * a `torso` site at body_link's origin (the task's framezaxis sensor names one; the patch does not show where it is).
+# int_data[0] / parameters[0] hold the mode and its height goal (stand.h:61: 0.38 Stand, 0.57 Handstand); OP3::Transition sets them.
+TASK_OP3 = 18
+OP3_MODE_HEIGHT = (0.38, 0.57)
+_OP3_KEYS = [("home", [-0.00363268, -6.3448e-07, 0.246, 1, 0, 0, 0, -0.534072, 0.879648, -0.62832, 0.534072, -0.879648, 0.62832, 1.93442e-05,
+                       -6.23496e-05, -0.596904, 1.13098, 0.534072, 0, -1.80695e-05, 6.15245e-05, 0.596904, -1.13098, -0.534072, 4.91532e-06]),
+             ("handstand", [-0.00363268, -6.3448e-07, 0.338, 0, 1, 0, 0, 3.1416, 0.879648, -0.62832, -3.1416, -0.879648, 0.62832, 1.93442e-05,
+                            -6.23496e-05, -0.596904, 1.13098, 0.534072, 0, -1.80695e-05, 6.15245e-05, 0.596904, -1.13098, -0.534072, 4.91532e-06])]
+
+
+def _box_inertia(mass, half):
+    x, y, z = half
+    return (mass / 3.0 * (y * y + z * z), mass / 3.0 * (x * x + z * z), mass / 3.0 * (x * x + y * y))
+
+
+def op3(mode=0, timestep=0.015, nconmax=32, nefcmax=160):
+    """OP3 Stand (mode 0) / Handstand (mode 1) (mjpc/tasks/op3/task.xml + stand.cc) on the synthetic robot described above."""
+    b = ModelBuilder(timestep=timestep, cone=0, integrator=3)
+    b.nconmax = nconmax; b.nefcmax = nefcmax
+    b.geom(0, "floor", PLANE, size=(0, 0, 0.05))                   # op3.xml.patch:8
+    R = dict(contype=0, conaffinity=1)                             # robot geoms: touch the floor only
+    body = b.body("body_link", 0, pos=(0, 0, 0.3),
+                  inertial=dict(mass=1.34928, pos=(-0.01501, 0.00013, 0.06582), quat=(0.704708, 0.704003, 0.0667707, -0.0575246),
+                                diaginertia=(0.00340344, 0.00296563, 0.00317513)))
+    b.joint(body, "root", FREE)
+    b.geom(body, "body", BOX, size=(0.045, 0.06, 0.06), pos=(-0.01, 0, 0.065), mass=0.0, **R)
+    torso = b.site(body, "torso")
+    pan = b.body("head_pan_link", body, pos=(-0.001, 0, 0.1365),
+                 inertial=dict(mass=0.01176, pos=(0.00233, 0, 0.00823), quat=(0.663575, 0.663575, 0.244272, -0.244272),
+                               diaginertia=(4.23401e-06, 3.60599e-06, 1.65e-06)))
+    head = b.site(pan, "head")
+    tilt = b.body("head_tilt_link", pan, pos=(0.01, 0.019, 0.0285),
+                  inertial=dict(mass=0.13631, pos=(0.0023, -0.01863, 0.0277), quat=(0.997312, 0.00973825, 0.0726131, -0.00102702),
+                                diaginertia=(0.000107452, 8.72266e-05, 4.39413e-05)))
+    b.geom(tilt, "head", BOX, size=(0.04, 0.05, 0.045), pos=(0.0, -0.019, 0.03), mass=0.0, **R)
+
+    def link(name, parent, pos, jname, axis, mass, half, com=(0, 0, 0)):
+        bd = b.body(name, parent, pos=pos, inertial=dict(mass=mass, pos=com, diaginertia=_box_inertia(mass, half)))
+        b.joint(bd, jname, HINGE, axis=axis, damping=1.084, armature=0.045, frictionloss=0.03)
+        return bd
+
+    # forearm stand-in mesh (la3c / ra3c): a tapered block from the elbow to 2 cm past the hand site
+    def forearm(s):
+        return [(x, s * y, z) for x in (-0.04, 0.005) for y in (0.0, 0.16) for z in ((-0.018, 0.018) if y == 0.0 else (-0.012, 0.012))]
+
+    hands = {}
+    for side, s in (("l", 1.0), ("r", -1.0)):
+        sp = link(f"{side}_sho_pitch_link", body, (-0.001, s * 0.06, 0.111), f"{side}_sho_pitch", (0, s, 0), 0.01176, (0.01, 0.01, 0.01))
+        sr = link(f"{side}_sho_roll_link", sp, (0, s * 0.016, 0), f"{side}_sho_roll", (-1, 0, 0), 0.17758, (0.02, 0.03, 0.02), com=(-0.0182, s * 0.0437, 0))
+        b.geom(sr, f"{side}_upper_arm", CAPSULE, size=(0.018, 0), fromto=(-0.015, s * 0.01, 0, -0.015, s * 0.05, 0), mass=0.0, **R)
+        el = link(f"{side}_el_link", sr, (0, s * 0.06, 0), f"{side}_el", (1, 0, 0), 0.04127, (0.02, 0.06, 0.015), com=(-0.019, s * 0.073, 0))
+        b.geom(el, f"{side}_forearm", MESH, mesh=forearm(s), mass=0.0, **R)
+        hands[side] = b.site(el, "left_hand" if side == "l" else "right_hand", pos=(-0.02, s * 0.14, 0))      # op3.xml.patch:33, :41
+    feet = {}
+    for side, s in (("l", 1.0), ("r", -1.0)):
+        hy = link(f"{side}_hip_yaw_link", body, (0, s * 0.035, 0), f"{side}_hip_yaw", (0, 0, -1), 0.01181, (0.01, 0.01, 0.01))
+        hr = link(f"{side}_hip_roll_link", hy, (-0.024, 0, -0.0285), f"{side}_hip_roll", (-1, 0, 0), 0.17886, (0.03, 0.02, 0.02), com=(0.0192, 0, -0.014))
+        hp = link(f"{side}_hip_pitch_link", hr, (0.0241, s * 0.019, 0), f"{side}_hip_pitch", (0, s, 0), 0.11543, (0.02, 0.02, 0.055), com=(0, -s * 0.019, -0.055))
+        b.geom(hp, f"{side}_thigh", CAPSULE, size=(0.022, 0), fromto=(0, -s * 0.019, -0.015, 0, -s * 0.019, -0.095), mass=0.0, **R)
+        kn = link(f"{side}_knee_link", hp, (0, 0, -0.11015), f"{side}_knee", (0, s, 0), 0.04015, (0.02, 0.02, 0.055), com=(0, -s * 0.019, -0.055))
+        b.geom(kn, f"{side}_shin", CAPSULE, size=(0.022, 0), fromto=(0, -s * 0.019, -0.015, 0, -s * 0.019, -0.095), mass=0.0, **R)
+        ap = link(f"{side}_ank_pitch_link", kn, (0, 0, -0.11), f"{side}_ank_pitch", (0, -s, 0), 0.17886, (0.03, 0.02, 0.02), com=(-0.0192, -s * 0.019, 0.014))
+        ar = link(f"{side}_ank_roll_link", ap, (-0.0241, -s * 0.019, 0), f"{side}_ank_roll", (1, 0, 0), 0.06934, (0.0635, 0.039, 0.005), com=(0.024, 0, -0.0265))
+        # op3.xml.patch:49-50 / :58-59: the two foot boxes and the foot site
+        b.geom(ar, f"{side}_foot_a", BOX, pos=(0.024, s * 0.013, -0.0265), size=(0.0635, 0.028, 0.004), mass=0.0, **R)
+        b.geom(ar, f"{side}_foot_b", BOX, pos=(0.024, s * 0.0125, -0.0265), size=(0.057, 0.039, 0.004), mass=0.0, **R)
+        feet[side] = b.site(ar, "left_foot" if side == "l" else "right_foot", pos=(0.025, 0, -0.025))
+    for side in ("l", "r"):
+        for j in ("sho_pitch", "sho_roll", "el"):
+            b.position(f"{side}_{j}_act", f"{side}_{j}", kp=21.1, ctrlrange=(-math.pi, math.pi), forcerange=(-5, 5))
+    for side in ("l", "r"):
+        for j in ("hip_yaw", "hip_roll", "hip_pitch", "knee", "ank_pitch", "ank_roll"):
+            b.position(f"{side}_{j}_act", f"{side}_{j}", kp=21.1, ctrlrange=(-math.pi, math.pi), forcerange=(-5, 5))
+    for name, q in _OP3_KEYS:
+        b.key(name, q)
+    m = b.compile()
+    assert (m["nq"], m["nv"], m["nu"]) == (25, 24, 18)
+    # cost table: task.xml:20-25 (user = norm, weight, lo, hi, params...)
+    terms = [(1, 6, 100.0, [0.1]), (1, 6, 50.0, [0.1]), (2, 0, 10.0), (18, 0, 0.25), (13, 2, 5.0, [0.01]), (18, 0, 1.0e-5)]
+    task = make_task(TASK_OP3, terms, parameters=[OP3_MODE_HEIGHT[mode]],
+                     int_data=[int(mode), head, feet["l"], feet["r"], hands["l"], hands["r"], torso, body])
+    key = np.array(_OP3_KEYS[0][1], float)
+    state = np.concatenate([key, np.zeros(m["nv"])])
+    # sampling numerics of task.xml:7-17: horizon 0.35 s at 0.015 s (H = 24), 3 spline points (cubic: the planner's default
+    # representation), 32 trajectories, exploration 0.1; nominal controls = the mode's key row
+    defaults = dict(N=32, P=3, sigma=(0.1, 0.0), interp=2, horizon=24, state=state, mocap=np.zeros(0),
+                    ctrl0=np.array(_OP3_KEYS[mode][1][7:25], float))
+    return m, task, defaults
+
+
 # ----------------------------------------------------------------------------------- quadruped on the fractal terrain
 TASK_QUADRUPED_HILL = 10
 
@@ -1027,4 +1226,4 @@ def terrain_balls(timestep=0.004):
     return m, task, defaults
 
 
-REGISTRY = {"humanoid_interact": humanoid_interact, "fingers": fingers, "site_servo": site_servo, "noslip_elliptic3": lambda: noslip_mix(1, 3), "noslip_elliptic4": lambda: noslip_mix(1, 4), "noslip_elliptic6": lambda: noslip_mix(1, 6), "noslip_pyramidal3": lambda: noslip_mix(0, 3), "noslip_pyramidal6": lambda: noslip_mix(0, 6), "fingers_grasp": lambda: fingers(grasp=True), "welded": welded, "swimmer": swimmer, "quadrotor": quadrotor, "linkage": linkage, "servo_arm": servo_arm, "particle_timevarying": particle_task, "particle_fixed": lambda: particle_task(fixed=True), "filter_arm": filter_arm, "ball_chain_friction": lambda: ball_chain(tendon_frictionloss=0.3), "quadruped_hill": quadruped_hill, "terrain_balls": terrain_balls, "walker": walker, "acrobot": acrobot, "ball_chain": ball_chain, "cylinder_pile": cylinder_pile, "humanoid_stand": humanoid_stand, "humanoid_walk": humanoid_walk, "particle": particle, "cartpole": cartpole, "quadruped": quadruped, "humanoid_track": humanoid_track, "shadow_hand": shadow_hand}
+REGISTRY = {"humanoid_interact": humanoid_interact, "fingers": fingers, "site_servo": site_servo, "noslip_elliptic3": lambda: noslip_mix(1, 3), "noslip_elliptic4": lambda: noslip_mix(1, 4), "noslip_elliptic6": lambda: noslip_mix(1, 6), "noslip_pyramidal3": lambda: noslip_mix(0, 3), "noslip_pyramidal6": lambda: noslip_mix(0, 6), "fingers_grasp": lambda: fingers(grasp=True), "welded": welded, "swimmer": swimmer, "quadrotor": quadrotor, "linkage": linkage, "servo_arm": servo_arm, "particle_timevarying": particle_task, "particle_fixed": lambda: particle_task(fixed=True), "filter_arm": filter_arm, "ball_chain_friction": lambda: ball_chain(tendon_frictionloss=0.3), "quadruped_hill": quadruped_hill, "terrain_balls": terrain_balls, "walker": walker, "acrobot": acrobot, "ball_chain": ball_chain, "cylinder_pile": cylinder_pile, "humanoid_stand": humanoid_stand, "humanoid_walk": humanoid_walk, "particle": particle, "cartpole": cartpole, "quadruped": quadruped, "humanoid_track": humanoid_track, "shadow_hand": shadow_hand, "allegro": allegro, "op3": op3}

@@ -83,9 +83,56 @@ enum {
                                  * the 15 declared residuals are written); int_data = [body, stage]; dbl_data = stage goals [nstage][7] */
   MJPC_TASK_ALLEGRO = 17,        /* mjpc/tasks/allegro/allegro.cc:36-77: the Shadow residual with 16-wide slices (57 residuals); int_data = [grasp site,
                                   * cube body, goal body, key] */
-  MJPC_TASK_OP3 = 18             /* mjpc/tasks/op3/stand.cc:34-152 (53 residuals, rows by mode): int_data = [mode (0 Stand, 1 Handstand), sites head,
+  MJPC_TASK_OP3 = 18,            /* mjpc/tasks/op3/stand.cc:34-152 (53 residuals, rows by mode): int_data = [mode (0 Stand, 1 Handstand), sites head,
                                   * left_foot, right_foot, left_hand, right_hand, torso, body body_link]; parameters = [height goal] */
+  MJPC_TASK_TABLE = 19           /* the caller's own residual, described by a table in int_data / dbl_data (below): no device code per task */
 };
+/* ---- MJPC_TASK_TABLE: a residual as a table --------------------------------------------------------------------------------
+ * The residual is a list of BLOCKS.  Block b writes `dim` consecutive rows starting at `row`; the blocks cover [0, num_residual)
+ * exactly once, in ascending order.  A block is a sum of TERMS,  v[k] = sum_j coef_j * src_j[off_j + k],  added in table order,
+ * followed by one operation:
+ *   MJPC_TBL_OP_SUM      rows = v[0 .. dim)  (ncomp = dim; a block without terms writes zeros)
+ *   MJPC_TBL_OP_NORM     one row (dim = 1): sqrt(sum_{k < ncomp} v[k]^2), 1 <= ncomp <= MJPC_TBL_MAX_NORM, at least one term
+ *   MJPC_TBL_OP_SUBQUAT  three rows (dim = 3, ncomp = 4), exactly two terms, both quaternions (MJPC_TBL_QUAT or MJPC_TBL_MOCAP_QUAT,
+ *                        off = 0): coef_0 * mju_subQuat(src_0, src_1); coef_1 is not read
+ * A SOURCE is a vector; a term reads `ncomp` components of it from its offset `off` on (xy of a position: off 0 of a 2-row block;
+ * its z: off 2 of a 1-row block; a slice of qpos: off = first index):
+ *   kind                          components  id             reads
+ *   MJPC_TBL_CONST                objtype     first index    dbl_data[id .. id + objtype)  (the record's objtype field holds the count)
+ *   MJPC_TBL_PARAM                num_parameter  -           MjpcHipTask.parameters (mjpc_hip_set_task moves a goal without a new table)
+ *   MJPC_TBL_QPOS / QVEL / ACT    nq / nv / na   -           the candidate's state at this step (ACT: refused when na = 0; qpos as the
+ *                                                            position stage leaves it: free / ball joint quaternions normalised)
+ *   MJPC_TBL_CTRL / ACTUATOR_FORCE  nu           -           the step's control / actuator forces
+ *   MJPC_TBL_KEY_QPOS             nq          key            key_qpos[key]
+ *   MJPC_TBL_MOCAP_POS / QUAT / MAT  3 / 4 / 9  mocap body   the plan input's mocap pose as handed in (MAT: the quaternion's matrix, row-major)
+ *   MJPC_TBL_SUBTREE_COM / LINVEL 3           body           centre of mass of the body's subtree / its linear velocity
+ *   MJPC_TBL_POS / QUAT / MAT     3 / 4 / 9   object         frame of the object `objtype` = MJPC_OBJ_BODY (the body's INERTIAL frame, as
+ *   MJPC_TBL_XAXIS / YAXIS / ZAXIS  3         object         MuJoCo's objtype="body" sensors read it), MJPC_OBJ_XBODY (the body's own frame),
+ *   MJPC_TBL_LINVEL / ANGVEL      3           object         MJPC_OBJ_GEOM or MJPC_OBJ_SITE, in the world frame: what the framepos / framequat /
+ *                                                            frame?axis / framelinvel / frameangvel sensors give (MAT row-major; a quaternion
+ *                                                            of a site / geom / inertial frame is xquat[body] * the local quaternion)
+ * Only position- and velocity-stage quantities exist when the residual runs (beside the constraint solve): accelerations, constraint
+ * forces and the time are not sources.
+ * Encoding.  int_data = [MJPC_TBL_VERSION, nblock, nterm,  nblock x {op, row, dim, ncomp, first term, number of terms},
+ *                        nterm x {kind, objtype (CONST: count; 0 where the kind has none), id (0 where the kind has none), off}];
+ * a block's terms are consecutive and the blocks use the terms in order.  dbl_data = [coef_0 .. coef_{nterm-1}, constants ...].
+ * Caps: nblock <= MJPC_TBL_MAX_BLOCKS, nterm <= MJPC_TBL_MAX_TERMS.  mjpc_hip_create / mjpc_hip_layout_bytes / mjpc_hip_set_task
+ * refuse a table that breaks any rule above or names an object, key, mocap body, parameter or dbl_data index out of range;
+ * mjpc_hip_last_error names the block and term.  mjpc_hip_set_task may install another table of at most the created size.
+ * Example, the Walker task (control, torso height - goal, torso z axis z - 1, forward speed - goal; torso = body 1, nu = 6):
+ *   int_data = {1, 4, 7,   SUM,0,6,6,0,1,  SUM,6,1,1,1,2,  SUM,7,1,1,3,2,  SUM,8,1,1,5,2,
+ *               CTRL,0,0,0,   POS,MJPC_OBJ_XBODY,1,2,  PARAM,0,0,0,   ZAXIS,MJPC_OBJ_XBODY,1,2,  CONST,1,7,0,
+ *               SUBTREE_LINVEL,0,1,0,  PARAM,0,0,1}
+ *   dbl_data = {1, 1, -1, 1, -1, 1, -1,   1.0}            parameters = {height goal, speed goal} */
+enum { MJPC_TBL_OP_SUM = 0, MJPC_TBL_OP_NORM = 1, MJPC_TBL_OP_SUBQUAT = 2 };
+enum { MJPC_TBL_CONST = 0, MJPC_TBL_PARAM = 1, MJPC_TBL_QPOS = 2, MJPC_TBL_QVEL = 3, MJPC_TBL_ACT = 4, MJPC_TBL_CTRL = 5,
+       MJPC_TBL_ACTUATOR_FORCE = 6, MJPC_TBL_KEY_QPOS = 7, MJPC_TBL_MOCAP_POS = 8, MJPC_TBL_MOCAP_QUAT = 9, MJPC_TBL_MOCAP_MAT = 10,
+       MJPC_TBL_SUBTREE_COM = 11, MJPC_TBL_SUBTREE_LINVEL = 12, MJPC_TBL_POS = 13, MJPC_TBL_QUAT = 14, MJPC_TBL_MAT = 15,
+       MJPC_TBL_XAXIS = 16, MJPC_TBL_YAXIS = 17, MJPC_TBL_ZAXIS = 18, MJPC_TBL_LINVEL = 19, MJPC_TBL_ANGVEL = 20 };
+#define MJPC_TBL_VERSION 1
+#define MJPC_TBL_MAX_BLOCKS 64
+#define MJPC_TBL_MAX_TERMS 256
+#define MJPC_TBL_MAX_NORM 16
 enum { MJPC_TRN_JOINT = 0, MJPC_TRN_TENDON = 3, MJPC_TRN_SITE = 4 };   /* mjtTrn values of the supported actuator transmissions */
 enum { MJPC_OBJ_BODY = 1, MJPC_OBJ_XBODY = 2, MJPC_OBJ_GEOM = 5, MJPC_OBJ_SITE = 6 };
 

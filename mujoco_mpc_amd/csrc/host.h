@@ -79,6 +79,79 @@ static inline void pack_task(PackedModel &p, const MjpcHipTask *t) {
   T.dbl_data = as_off<double>(put_d(p, t->dbl_data, t->num_dbl));
 }
 
+// MJPC_TASK_TABLE: the table is input from outside the program and the kernel trusts every index in it, so everything is checked
+// here (include/mjpc_hip.h states the rules).  M: the sizes of the model the table will run on.
+static_assert(TBL_OP_SUM == MJPC_TBL_OP_SUM && TBL_OP_NORM == MJPC_TBL_OP_NORM && TBL_OP_SUBQUAT == MJPC_TBL_OP_SUBQUAT, "table operations");
+static_assert(TBL_CONST == MJPC_TBL_CONST && TBL_PARAM == MJPC_TBL_PARAM && TBL_QPOS == MJPC_TBL_QPOS && TBL_QVEL == MJPC_TBL_QVEL && TBL_ACT == MJPC_TBL_ACT &&
+              TBL_CTRL == MJPC_TBL_CTRL && TBL_ACTUATOR_FORCE == MJPC_TBL_ACTUATOR_FORCE && TBL_KEY_QPOS == MJPC_TBL_KEY_QPOS && TBL_MOCAP_POS == MJPC_TBL_MOCAP_POS &&
+              TBL_MOCAP_QUAT == MJPC_TBL_MOCAP_QUAT && TBL_MOCAP_MAT == MJPC_TBL_MOCAP_MAT && TBL_SUBTREE_COM == MJPC_TBL_SUBTREE_COM &&
+              TBL_SUBTREE_LINVEL == MJPC_TBL_SUBTREE_LINVEL && TBL_POS == MJPC_TBL_POS && TBL_QUAT == MJPC_TBL_QUAT && TBL_MAT == MJPC_TBL_MAT &&
+              TBL_XAXIS == MJPC_TBL_XAXIS && TBL_YAXIS == MJPC_TBL_YAXIS && TBL_ZAXIS == MJPC_TBL_ZAXIS && TBL_LINVEL == MJPC_TBL_LINVEL && TBL_ANGVEL == MJPC_TBL_ANGVEL,
+              "table source kinds");
+static_assert(TBL_VERSION == MJPC_TBL_VERSION && TBL_MAX_BLOCKS == MJPC_TBL_MAX_BLOCKS && TBL_MAX_TERMS == MJPC_TBL_MAX_TERMS && TBL_MAX_NORM == MJPC_TBL_MAX_NORM, "table caps");
+static inline bool table_check(const DevModel &M, const MjpcHipTask *t, std::string &err) {
+  if (t->task_id != MJPC_TASK_TABLE) return true;
+  auto fail = [&](const std::string &s) { err = "residual table: " + s; return false; };
+  const int *I = t->int_data;
+  if (t->num_int < TBL_HEADER || !I) return fail("num_int = " + std::to_string(t->num_int) + " is shorter than the header (version, blocks, terms)");
+  if (I[0] != TBL_VERSION) return fail("encoding version " + std::to_string(I[0]) + " (this library reads version " + std::to_string(TBL_VERSION) + ")");
+  const int nb = I[1], nt = I[2];
+  if (nb < 1 || nb > TBL_MAX_BLOCKS) return fail(std::to_string(nb) + " blocks (1 .. " + std::to_string(TBL_MAX_BLOCKS) + ")");
+  if (nt < 0 || nt > TBL_MAX_TERMS) return fail(std::to_string(nt) + " terms (0 .. " + std::to_string(TBL_MAX_TERMS) + ")");
+  const int need_int = TBL_HEADER + TBL_BLOCK_INTS * nb + TBL_TERM_INTS * nt;
+  if (t->num_int < need_int) return fail("num_int = " + std::to_string(t->num_int) + " is shorter than the " + std::to_string(need_int) + " ints the header claims");
+  if (t->num_dbl < nt || (nt > 0 && !t->dbl_data)) return fail("num_dbl = " + std::to_string(t->num_dbl) + " is shorter than the " + std::to_string(nt) + " coefficients the header claims");
+  if (t->num_parameter > 0 && !t->parameters) return fail("num_parameter > 0 without parameters");
+  const int *B = I + TBL_HEADER, *T = B + TBL_BLOCK_INTS * nb;
+  int row = 0, term = 0;
+  for (int b = 0; b < nb; b++, B += TBL_BLOCK_INTS) {
+    const std::string blk = "block " + std::to_string(b);
+    const int op = B[0], brow = B[1], dim = B[2], ncomp = B[3], t0 = B[4], n = B[5];
+    if (op != TBL_OP_SUM && op != TBL_OP_NORM && op != TBL_OP_SUBQUAT) return fail(blk + ": unknown operation " + std::to_string(op));
+    if (brow < row) return fail(blk + ": starts at row " + std::to_string(brow) + " and overlaps the block before it (which ends at " + std::to_string(row) + ")");
+    if (brow > row) return fail(blk + ": starts at row " + std::to_string(brow) + " and leaves a gap behind row " + std::to_string(row));
+    if (dim < 1 || dim > t->num_residual - brow) return fail(blk + ": " + std::to_string(dim) + " rows from row " + std::to_string(brow) + " do not fit num_residual = " + std::to_string(t->num_residual));
+    if (n < 0 || t0 != term || n > nt - t0) return fail(blk + ": terms [" + std::to_string(t0) + ", " + std::to_string(t0) + " + " + std::to_string(n) + ") are not the next of the " + std::to_string(nt) + " terms (next is " + std::to_string(term) + ")");
+    if (op == TBL_OP_SUM && ncomp != dim) return fail(blk + ": SUM needs ncomp = dim");
+    if (op == TBL_OP_NORM && (dim != 1 || ncomp < 1 || ncomp > TBL_MAX_NORM || n < 1)) return fail(blk + ": NORM needs dim = 1, 1 <= ncomp <= " + std::to_string(TBL_MAX_NORM) + " and at least one term");
+    if (op == TBL_OP_SUBQUAT && (dim != 3 || ncomp != 4 || n != 2)) return fail(blk + ": SUBQUAT needs dim = 3, ncomp = 4 and exactly two terms");
+    for (int j = t0; j < t0 + n; j++) {
+      const std::string trm = blk + " term " + std::to_string(j);
+      const int *R = T + TBL_TERM_INTS * j, kind = R[0], ty = R[1], id = R[2], off = R[3];
+      int len = 0;
+      auto obj = [&](int count, const char *what) { if (id < 0 || id >= count) { fail(trm + ": " + what + " " + std::to_string(id) + " out of range (" + std::to_string(count) + ")"); return false; } return true; };
+      switch (kind) {
+        case TBL_CONST:
+          if (ty < 1 || id < 0 || id > t->num_dbl - ty) return fail(trm + ": constants dbl_data[" + std::to_string(id) + " .. +" + std::to_string(ty) + ") out of range (num_dbl = " + std::to_string(t->num_dbl) + ")");
+          len = ty; break;
+        case TBL_PARAM: len = t->num_parameter; break;
+        case TBL_QPOS: len = M.nq; break;
+        case TBL_QVEL: len = M.nv; break;
+        case TBL_ACT: if (M.na == 0) return fail(trm + ": ACT on a model without activation states (na = 0)"); len = M.na; break;
+        case TBL_CTRL: case TBL_ACTUATOR_FORCE: len = M.nu; break;
+        case TBL_KEY_QPOS: if (!obj(M.nkey, "key")) return false; len = M.nq; break;
+        case TBL_MOCAP_POS: case TBL_MOCAP_QUAT: case TBL_MOCAP_MAT:
+          if (!obj(M.nmocap, "mocap body")) return false;
+          len = kind == TBL_MOCAP_POS ? 3 : (kind == TBL_MOCAP_QUAT ? 4 : 9); break;
+        case TBL_SUBTREE_COM: case TBL_SUBTREE_LINVEL: if (!obj(M.nbody, "body")) return false; len = 3; break;
+        case TBL_POS: case TBL_QUAT: case TBL_MAT: case TBL_XAXIS: case TBL_YAXIS: case TBL_ZAXIS: case TBL_LINVEL: case TBL_ANGVEL:
+          if (ty == MJPC_OBJ_BODY || ty == MJPC_OBJ_XBODY) { if (!obj(M.nbody, "body")) return false; }
+          else if (ty == MJPC_OBJ_GEOM) { if (!obj(M.ngeom, "geom")) return false; }
+          else if (ty == MJPC_OBJ_SITE) { if (!obj(M.nsite, "site")) return false; }
+          else return fail(trm + ": unknown object type " + std::to_string(ty));
+          len = kind == TBL_QUAT ? 4 : (kind == TBL_MAT ? 9 : 3); break;
+        default: return fail(trm + ": unknown source kind " + std::to_string(kind));
+      }
+      if (op == TBL_OP_SUBQUAT && ((kind != TBL_QUAT && kind != TBL_MOCAP_QUAT) || off != 0)) return fail(trm + ": SUBQUAT takes two quaternion sources (QUAT / MOCAP_QUAT) at offset 0");
+      if (off < 0 || off > len - ncomp) return fail(trm + ": components [" + std::to_string(off) + ", " + std::to_string(off) + " + " + std::to_string(ncomp) + ") beyond the source's length " + std::to_string(len));
+    }
+    row += dim; term += n;
+  }
+  if (row != t->num_residual) return fail("the blocks end at row " + std::to_string(row) + ", num_residual is " + std::to_string(t->num_residual));
+  if (term != nt) return fail("the blocks use " + std::to_string(term) + " of the " + std::to_string(nt) + " terms");
+  return true;
+}
+
 // lean: the dense tier's layout (rollout_dense2.hip, MJPC_LEAN_LDS): spline knots and the Hessian entry table are read from HBM / L2
 // spill: a mask of SPILL_* blocks laid out in the per-candidate HBM slab instead of LDS (rollout_spill.hip; never with lean).  A
 // spilled block's offset is LAY_SLAB(offset in the slab); the slab keeps the blocks in the LDS order (efc_J, efc_JA, vectors,
@@ -583,6 +656,7 @@ static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTas
     M.idrv_e = as_off<int>(put_i(p, ei.data(), ei.size())); M.idrv_c = as_off<double>(put_d(p, ec.data(), ec.size())); }
   if (M.nefcmax < M.nfric + M.ntfric + M.neqrow + 2) M.nefcmax = M.nfric + M.ntfric + M.neqrow + 2;
   // task region (re-packable by set_task)
+  if (!table_check(M, t, p.error)) return false;
   p.task_i0 = p.ib.size(); p.task_d0 = p.db.size();
   pack_task(p, t);
   p.task_i_cap = p.ib.size() - p.task_i0; p.task_d_cap = p.db.size() - p.task_d0;
@@ -661,12 +735,21 @@ static inline DevModel relocate(const PackedModel &p, const int *ibase, const do
 
 // re-pack the task into the reserved region (sizes must not exceed the initial ones)
 static inline bool repack_task(PackedModel &p, const MjpcHipTask *t) {
+  if (!table_check(p.M, t, p.error)) return false;      // before anything is touched: the engine keeps its task
   std::vector<int> ib_tail(p.ib.begin() + p.task_i0 + p.task_i_cap, p.ib.end());       // keyframe tables behind the task region
   std::vector<double> db_tail(p.db.begin() + p.task_d0 + p.task_d_cap, p.db.end());
+  const std::vector<int> ib_old(p.ib.begin() + p.task_i0, p.ib.begin() + p.task_i0 + p.task_i_cap);      // a refused task leaves the old one in place
+  const std::vector<double> db_old(p.db.begin() + p.task_d0, p.db.begin() + p.task_d0 + p.task_d_cap);
+  const DevTask task_old = p.M.task;
   p.ib.resize(p.task_i0); p.db.resize(p.task_d0);
   pack_task(p, t);
   bool ok = !(p.ib.size() - p.task_i0 > p.task_i_cap || p.db.size() - p.task_d0 > p.task_d_cap);
-  if (!ok) p.error = "task grew beyond the size given at create()";
+  if (!ok) {
+    p.error = "task grew beyond the size given at create()";
+    p.ib.resize(p.task_i0); p.db.resize(p.task_d0);
+    p.ib.insert(p.ib.end(), ib_old.begin(), ib_old.end()); p.db.insert(p.db.end(), db_old.begin(), db_old.end());
+    p.M.task = task_old;
+  }
   p.ib.resize(p.task_i0 + p.task_i_cap, 0); p.db.resize(p.task_d0 + p.task_d_cap, 0.0);
   p.ib.insert(p.ib.end(), ib_tail.begin(), ib_tail.end()); p.db.insert(p.db.end(), db_tail.begin(), db_tail.end());
   return ok;

@@ -80,6 +80,13 @@ enum { CNSTR_EQUALITY = 0, CNSTR_FRICTION_DOF = 1, CNSTR_FRICTION_TENDON = 2, CN
 enum { STATE_SATISFIED = 0, STATE_QUADRATIC = 1, STATE_LINEARNEG = 2, STATE_LINEARPOS = 3, STATE_CONE = 4 };
 enum { WARN_BADQPOS = 1, WARN_BADQVEL = 2, WARN_BADQACC = 4, WARN_CONTACTFULL = 8, WARN_CNSTRFULL = 16, WARN_RAY = 32, WARN_SYNC = 64, WARN_UNSUPPORTED = 128 };
 
+// table-driven residual (MJPC_TASK_TABLE): the int_data encoding of include/mjpc_hip.h (MJPC_TBL_* there, same values: host.h asserts it)
+enum { TBL_CONST = 0, TBL_PARAM = 1, TBL_QPOS = 2, TBL_QVEL = 3, TBL_ACT = 4, TBL_CTRL = 5, TBL_ACTUATOR_FORCE = 6, TBL_KEY_QPOS = 7,
+       TBL_MOCAP_POS = 8, TBL_MOCAP_QUAT = 9, TBL_MOCAP_MAT = 10, TBL_SUBTREE_COM = 11, TBL_SUBTREE_LINVEL = 12, TBL_POS = 13,
+       TBL_QUAT = 14, TBL_MAT = 15, TBL_XAXIS = 16, TBL_YAXIS = 17, TBL_ZAXIS = 18, TBL_LINVEL = 19, TBL_ANGVEL = 20, TBL_NKIND = 21 };
+enum { TBL_OP_SUM = 0, TBL_OP_NORM = 1, TBL_OP_SUBQUAT = 2 };
+enum { TBL_VERSION = 1, TBL_HEADER = 3, TBL_BLOCK_INTS = 6, TBL_TERM_INTS = 4, TBL_MAX_BLOCKS = 64, TBL_MAX_TERMS = 256, TBL_MAX_NORM = 16 };
+
 struct DevTask {
   int task_id, num_residual, num_term, num_trace, num_parameter, num_int, num_dbl;
   double risk;

@@ -487,6 +487,99 @@ DEV void residual_op3(Ctx &c, double *residual) {
   PFOR(i, nv - 6) residual[17 + nu + i] = c.qvel[6 + i];
 }
 
+// ---- table-driven residual (MJPC_TASK_TABLE; encoding and semantics: include/mjpc_hip.h, validated by host.h table_check) ----
+// frame quantities of an object (MJPC_OBJ_BODY = the inertial frame, XBODY, GEOM, SITE), world frame
+DEV const double *tbl_pos(Ctx &c, int ty, int id) {
+  return ty == 6 ? c.site_xpos + 3 * id : (ty == 5 ? c.geom_xpos + 3 * id : (ty == 1 ? c.xipos + 3 * id : c.xpos + 3 * id));
+}
+DEV int tbl_body(Ctx &c, int ty, int id) { return ty == 6 ? MI(site_bodyid)[id] : (ty == 5 ? MI(geom_bodyid)[id] : id); }
+// body quaternion times the local one, as site_axis composes a site's frame (a body's own frame: xquat as it is)
+DEV void tbl_quat(Ctx &c, int ty, int id, double *q) {
+  const double *bq = c.xquat + 4 * tbl_body(c, ty, id);
+  if (ty == 2) { d_copy4(q, bq); return; }
+  double lq[4];
+  d_copy4(lq, ty == 6 ? MD(site_quat) + 4 * id : (ty == 5 ? MD(geom_quat) + 4 * id : MDH(body_iquat) + 4 * id));
+  d_mulquat(q, bq, lq);
+}
+DEV void tbl_quat_src(Ctx &c, const int *T, double *q) {      // a SUBQUAT operand: a frame's quaternion or a mocap body's
+  if (T[0] == TBL_MOCAP_QUAT) d_copy4(q, c.mocap_quat + 4 * T[2]); else tbl_quat(c, T[1], T[2], q);
+}
+DEV double tbl_pick9(const double *R, int e) {      // R lives in registers: no dynamic index
+  return e == 0 ? R[0] : (e == 1 ? R[1] : (e == 2 ? R[2] : (e == 3 ? R[3] : (e == 4 ? R[4] : (e == 5 ? R[5] : (e == 6 ? R[6] : (e == 7 ? R[7] : R[8])))))));
+}
+// element e (row-major) of an object's rotation matrix: bodies and geoms from the matrices the kinematics keeps, sites from the quaternions
+DEV double tbl_mat(Ctx &c, int ty, int id, int e) {
+  if (ty == 2) return c.xmat[9 * id + e];
+  if (ty == 1) return c.ximat[9 * id + e];
+  if (ty == 5) return c.geom_xmat[9 * id + e];
+  double q[4], R[9];
+  tbl_quat(c, ty, id, q);
+  d_quat2mat(R, q);
+  return tbl_pick9(R, e);
+}
+// component e of the source a term record T = [kind, object type / length, id, offset] names
+DEV double tbl_src(Ctx &c, const int *T, const double *D, int e) {
+  const DevModel &M = *c.M;
+  const int kind = T[0], ty = T[1], id = T[2];
+  switch (kind) {
+    case TBL_CONST: return D[id + e];
+    case TBL_PARAM: return MD(task.parameters)[e];
+    case TBL_QPOS: return c.qpos[e];
+    case TBL_QVEL: return c.qvel[e];
+    case TBL_ACT: return C_ACT(c)[e];
+    case TBL_CTRL: return c.ctrl[e];
+    case TBL_ACTUATOR_FORCE: return c.actuator_force[e];
+    case TBL_KEY_QPOS: return M.key_qpos[id * M.nq + e];
+    case TBL_MOCAP_POS: return c.mocap_pos[3 * id + e];
+    case TBL_MOCAP_QUAT: return c.mocap_quat[4 * id + e];
+    case TBL_MOCAP_MAT: { double R[9]; d_quat2mat(R, c.mocap_quat + 4 * id); return tbl_pick9(R, e); }
+    case TBL_SUBTREE_COM: return c.subtree_com[3 * id + e];
+    case TBL_SUBTREE_LINVEL: return c.subtree_linvel[3 * id + e];
+    case TBL_POS: return tbl_pos(c, ty, id)[e];
+    case TBL_QUAT: { double q[4]; tbl_quat(c, ty, id, q); return e == 0 ? q[0] : (e == 1 ? q[1] : (e == 2 ? q[2] : q[3])); }
+    case TBL_MAT: return tbl_mat(c, ty, id, e);
+    case TBL_XAXIS: case TBL_YAXIS: case TBL_ZAXIS: return tbl_mat(c, ty, id, 3 * e + (kind - TBL_XAXIS));
+    case TBL_ANGVEL: return c.cvel[6 * tbl_body(c, ty, id) + e];
+    case TBL_LINVEL: {      // velocity of the frame's origin, as body_linvel: angular x (origin - com of the tree) + linear, component e
+      const int body = tbl_body(c, ty, id), e1 = e == 2 ? 0 : e + 1, e2 = e == 0 ? 2 : e - 1;
+      const double *p = tbl_pos(c, ty, id), *com = c.subtree_com + 3 * MIH(body_rootid)[body], *w = c.cvel + 6 * body;
+      return (w[e1] * (p[e2] - com[e2]) - w[e2] * (p[e1] - com[e1])) + w[3 + e];
+    }
+    default: return 0.0;
+  }
+}
+// One lane per residual row: the lane finds its block (rows ascend, a bisection over the block records), then adds the block's
+// terms for its own component; a NORM row's lane walks the block's components, the first lane of a SUBQUAT block writes its three rows
+DEV void residual_table(Ctx &c, double *residual) {
+  const int *I = MI(task.int_data);
+  const double *D = MD(task.dbl_data);
+  const int nblock = I[1];
+  const int *B = I + TBL_HEADER, *T = I + TBL_HEADER + TBL_BLOCK_INTS * nblock;
+  PFOR(r, c.M->task.num_residual) {
+    int lo = 0, hi = nblock;
+    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (B[TBL_BLOCK_INTS * mid + 1] <= r) lo = mid; else hi = mid; }
+    const int *b = B + TBL_BLOCK_INTS * lo;
+    const int op = b[0], row = b[1], ncomp = b[3], t0 = b[4], nt = b[5];
+    if (op == TBL_OP_SUBQUAT) {
+      if (r != row) continue;
+      double qa[4], qb[4], r3[3];
+      tbl_quat_src(c, T + TBL_TERM_INTS * t0, qa);
+      tbl_quat_src(c, T + TBL_TERM_INTS * (t0 + 1), qb);
+      d_subquat(r3, qa, qb);
+      residual[row] = D[t0] * r3[0]; residual[row + 1] = D[t0] * r3[1]; residual[row + 2] = D[t0] * r3[2];
+      continue;
+    }
+    const int k0 = op == TBL_OP_NORM ? 0 : r - row, n = op == TBL_OP_NORM ? ncomp : 1;
+    double v = 0, s = 0;
+    for (int k = 0; k < n; k++) {
+      v = 0;
+      for (int j = t0; j < t0 + nt; j++) { const int *Tj = T + TBL_TERM_INTS * j; v += D[j] * tbl_src(c, Tj, D, Tj[3] + k0 + k); }
+      s += v * v;
+    }
+    residual[r] = op == TBL_OP_NORM ? sqrt(s) : v;
+  }
+}
+
 DEV void task_residual(Ctx &c, double *residual) {
   const DevModel &M = *c.M;
   int id = M.task.task_id;
@@ -590,6 +683,8 @@ DEV void task_residual(Ctx &c, double *residual) {
       residual[3] = c.qvel[1];
       residual[4] = c.ctrl[0];
     }
+  } else if (id == 19) {  // MJPC_TASK_TABLE: the caller's own residual, described by a table
+    residual_table(c, residual);
   }
   c.warning = wave_or_i(c.warning);      // a ray miss is raised by the lane that cast it
   SYNC();

@@ -1,4 +1,5 @@
-"""Diagnostic: kernel time of one plan step of a registry model (tools/time_task.py name N [key=value ...] for the generator)."""
+"""Diagnostic: kernel time of one plan step of a registry model (tools/time_task.py name N [key=value ...] for the generator);
+name `table:<task>` takes the task with its residual restated as a table (modelgen.TABLE_TASKS)."""
 import sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -10,7 +11,11 @@ from mujoco_mpc_amd.planner import HipBackend
 name, N = sys.argv[1], int(sys.argv[2])
 kw = {k: (int(v) if v.lstrip("-").isdigit() else v == "True" if v in ("True", "False") else float(v)) for k, v in (a.split("=") for a in sys.argv[3:])}
 import mujoco_mpc_amd.modelgen.tasks as T
-gen = (lambda: getattr(T, name)(**kw)) if (kw or name not in REGISTRY) else REGISTRY[name]
+if name.startswith("table:"):          # a registry task with its residual restated as a table (modelgen/residual_table.py: TABLE_TASKS)
+    from mujoco_mpc_amd.modelgen import TABLE_TASKS
+    gen = lambda: TABLE_TASKS[name[6:]](**kw)
+else:
+    gen = (lambda: getattr(T, name)(**kw)) if (kw or name not in REGISTRY) else REGISTRY[name]
 m, task, d = gen()
 H, P = d["horizon"], d["P"]
 kt = np.linspace(0, (H - 1) * m["timestep"], P); kv = np.tile(d["ctrl0"], (P, 1)) if "ctrl0" in d else np.zeros((P, m["nu"]))

@@ -393,6 +393,30 @@ int mjpc_hip_get_traces(MjpcHipEngine *e, double *traces);
  * iterations summed over the steps, max contacts, max constraint rows, MJPC_WARN_* bits. */
 int mjpc_hip_get_all_candidates(MjpcHipEngine *e, double *states, double *actions, double *times, double *residual,
                                 double *costs, double *trace, double *knots, int *diag);
+/* ---- Sample-Gradient planner (mjpc/planners/sample_gradient/planner.cc) -------------------------------------------------
+ * Its batch is mixed: one un-noised nominal (in->nominal_index), noisy candidates, then explicit policies; and its update needs
+ * the standard normals themselves, which exist on the device only.  Three calls, one engine: there is no multi-device variant
+ * (the planner drives one engine, like the Cross-Entropy planner).
+ *
+ * mjpc_hip_plan_mixed[_async]: a plan step whose candidates with global index < first_explicit are sampled as with
+ * in->noise_std (required: nominal + noise_std * eps, clamped; bit for bit the rows a plain mjpc_hip_plan with noise_std gives)
+ * and whose candidates >= first_explicit use in->candidate_knots[i] verbatim ([num_trajectory][P][nu], global indexing; rows
+ * below first_explicit are not read; may be NULL when first_explicit == num_trajectory).  The table is assembled on the device
+ * behind the noise kernel.  Fetch with mjpc_hip_plan_fetch; tiers, candidate_offset / num_local and mjpc_hip_get_* work as for
+ * any plan.
+ * Noise history: a device buffer [max_local][36 * nu], zero after create.  A mixed plan copies eps into slot r (local row) for
+ * noisy rows only - nominal_index < global index < first_explicit - and only the first P * nu elements: slot 0, the explicit
+ * slots and the tail of every slot keep what an earlier plan left (the reference's persistent `noise` vector, planner.cc:94,
+ * 339-344).  mjpc_hip_noise_history_reset zeroes it (Planner::Reset, planner.cc:138).
+ *
+ * mjpc_hip_sample_gradient: gradient_out[k] = sum_{i<n} history[slot[i]][k] * scale[i] for k < P * nu, P of the last plan;
+ * starts from 0.0, every product rounded and then added in ascending i (mju_addToScl, planner.cc:452-459): the result is the
+ * reference loop's bit for bit, whatever the launch shape.  Blocking.  Errors: a plan in flight, no mixed plan yet, n outside
+ * 1..max_local, a slot outside 0..max_local-1. */
+int mjpc_hip_plan_mixed_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit);
+int mjpc_hip_plan_mixed(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit, MjpcHipPlanOutput *out);
+int mjpc_hip_noise_history_reset(MjpcHipEngine *e);
+int mjpc_hip_sample_gradient(MjpcHipEngine *e, int n, const int *slot, const double *scale, double *gradient_out);
 /* Bytes of LDS one candidate's workgroup occupies (its whole mjData-equivalent). */
 int mjpc_hip_lds_bytes(MjpcHipEngine *e);
 /* Capacity tiers: when a shard holds more candidates than the GPU has CUs and the model allows it, the engine first runs a

@@ -8,6 +8,7 @@
 //   mjpc/planners/sampling/planner.h:51-162  SamplingPlanner (+ RankedPlanner virtuals, planners/planner.h:84-101)
 //   mjpc/planners/cross_entropy/planner.h:32-147  CrossEntropyPlanner (same rollout engine, elite mean/variance update)
 //   mjpc/planners/robust/robust_planner.h:31-80   RobustPlanner (top-k candidates x R noisy rollouts on a second engine)
+//   mjpc/planners/sample_gradient/planner.h:35-175 SampleGradientPlanner (mixed batch; gradient reduced on the device)
 // Differences forced by the boundary: `mjModel*` / `const Task&` become the ABI's MjpcHipModel / MjpcHipTask views
 // plus the planner's <custom><numeric> settings (Numerics); `ThreadPool&` arguments are gone (the GPU is the pool);
 // `State` is passed as its raw arrays (State::CopyTo, mjpc/states/state.cc:128-135).
@@ -95,6 +96,8 @@ struct Numerics {                       // the planner's <custom><numeric> entri
   int device = 0;                      // first HIP device ordinal
   int n_devices = 1;                   // SamplingPlanner: GPUs the candidate batch is sharded over (one engine each)
   std::vector<int> devices;            // optional explicit ordinals (repeats allowed); default device, device+1, ...
+  int sample_gradient_trajectories = 0;    // sample gradient: gradient candidates among sampling_trajectories (sample_gradient/planner.cc:66)
+  double sample_gradient_filter = 1.0;     // weight of the new gradient against the previous one (planner.cc:69)
 };
 
 class SamplingPlanner {
@@ -257,6 +260,96 @@ class RobustPlanner {
   int nu_ = 0, ns_ = 0, nmocap_ = 0, nuserdata_ = 0;
   std::vector<double> state_, mocap_, userdata_, cand_knots_;
   double time_ = 0;
+};
+
+// mjpc/planners/sample_gradient/planner.{h,cc}: of the num_trajectory_ candidates of a plan step, candidate 0 is the (resampled)
+// nominal, candidates 1 .. n_noisy-1 are nominal + noise_exploration * N(0, 1) (clamped), and the last num_gradient_ are policies
+// the PREVIOUS plan step built along its gradient estimate; the best of all becomes the policy.  Then the noise of this step's
+// noisy candidates, weighted by a fitness shaping of their returns, is summed into `gradient`, and num_gradient_ new candidates
+// are laid along it at log-spaced step sizes for the next plan step.  One engine: the batch is one mjpc_hip_plan_mixed launch
+// and the sum runs on the device over the engine's noise history (mjpc_hip_sample_gradient); no multi-GPU sharding.
+// Restated formula by formula; the reference's quirks are kept:
+//  - the noise is absolute: noise_exploration for every parameter, no ctrlrange scaling (planner.cc:346-351);
+//  - num_gradient_ is clamped to num_trajectory - 1 on every call, and stays clamped (planner.cc:176);
+//  - gradient candidates are host-side splines that persist between plans and are resampled to the current time by
+//    ResamplePolicy before every plan, like the nominal (planner.cc:199-202); after Reset they are empty (all-zero actions);
+//  - winner = order[0] only when its return is STRICTLY below the nominal's, else the nominal (planner.cc:232-237);
+//  - previous_policy is never refreshed by OptimizePolicy;
+//  - the return weights are computed once, when return_weight_.size() != n_noisy, and then cached for good: later plans reuse
+//    the first plan's weights whatever the returns are (planner.cc:419-450);
+//  - at that moment, and only then, the noisy candidates are re-sorted among themselves;
+//  - the weights use log(trajectory_order[i] + 1): the candidate's INDEX, not its rank;
+//  - on every other call the sum reads the first n_noisy entries of the order left by the full sort, which can name gradient
+//    slots, whose noise history is zero or stale (planner.cc:454-459);
+//  - the history keeps stale values in slot 0, the explicit slots and behind P * nu when the sliders move (include/mjpc_hip.h);
+//  - the step sizes are cached on their count (utilities.cc:802-808 LogScale(2.0, 1e-3)); their first value is pinned to 1e-3
+//    exactly (the reference's exp(log(1e-3)) is one ulp above it with glibc), the others are the reference's expression;
+//  - gradient_previous enters un-resampled (planner.cc:486).
+// Deliberate difference: std::partial_sort is not stable; candidates are ordered by (return, index), lowest index first, as
+// everywhere in this repository (failed candidates all tie at 1e6).  All candidates of a plan share one interpolation.
+class SampleGradientPlanner {
+ public:
+  enum WinnerType : int { kNominal = 0, kPerturb, kGradient };
+  SampleGradientPlanner() = default;
+  ~SampleGradientPlanner();
+  SampleGradientPlanner(const SampleGradientPlanner&) = delete;
+  SampleGradientPlanner& operator=(const SampleGradientPlanner&) = delete;
+
+  void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
+  void Allocate();
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void OptimizePolicy(int horizon);
+  void NominalTrajectory(int horizon);                 // rolls resampled_policy out into trajectory[0] (planner.cc:276-287)
+  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
+  void ResamplePolicy(SamplingPolicy& policy, int horizon, int num_spline_points);
+  const Trajectory* BestTrajectory();                  // trajectory[winner]
+  int NumParameters() { return policy.num_spline_points * nu_; }
+  void SetTask(const MjpcHipTask* task);
+  // candidate_policy[index] as the reference holds it after OptimizePolicy: the rolled-out knots for index < n_noisy, the
+  // freshly built gradient candidate otherwise; returns P, fills times[P] / values[P * nu] when non-null
+  int CandidatePolicy(int index, double* times, double* values);
+  // host closed forms (static: the tests call them without an engine)
+  static void ReturnWeights(const int* order, int num_noisy, double* weights);      // planner.cc:437-449
+  static void LogScale(double* values, double max_value, double min_value, int steps);   // utilities.cc:802-808
+
+  SamplingPolicy policy, resampled_policy, previous_policy;
+  std::vector<double> state, mocap, userdata;
+  double time = 0;
+  Trajectory trajectory_winner;                        // trajectory[winner]; the other candidates stay on the device
+  std::vector<int> trajectory_order;
+  std::vector<double> returns;                         // trajectory[i].total_return
+  std::vector<int> failures;
+  double noise_exploration = 0.1;
+  int interpolation_ = kZeroSpline;
+  int num_trajectory_ = 10;
+  int num_gradient_ = 0;
+  double gradient_filter_ = 1.0;
+  std::vector<double> gradient, gradient_previous;     // [max spline points * nu]
+  std::vector<double> step_size_;
+  double gradient_max_step_size = 2.0, gradient_min_step_size = 1.0e-3;
+  std::vector<double> return_weight_;
+  int winner = 0;
+  int winner_type_ = kNominal;
+  double improvement = 0;
+  double noise_compute_time = 0, rollouts_compute_time = 0, gradient_candidates_compute_time = 0, policy_update_compute_time = 0;   // microseconds
+  unsigned long long seed = 0x5EED;
+  unsigned long long plan_iter = 0;
+  const double* injected_noise_eps = nullptr;          // [num_trajectory * P * nu], standard normal (tests)
+
+ private:
+  void GradientCandidates(int num_trajectory, int num_gradient, int horizon);
+  SamplingPolicy& Candidate(int index);                // candidate_policy[index], materialised from the last plan's knots on demand
+  MjpcHipEngine* engine_ = nullptr;
+  Numerics numerics_;
+  int nq_ = 0, nv_ = 0, na_ = 0, ns_ = 0, nu_ = 0, nmocap_ = 0, nuserdata_ = 0, nr_ = 0, ntrace_ = 0;
+  double timestep_ = 0;
+  std::vector<double> ctrlrange_, knot_times_, knot_values_, noise_std_, cand_table_, all_knots_, scale_;
+  std::vector<SamplingPolicy> candidate_policy_;       // explicit (gradient) candidates; noisy ones live in all_knots_
+  std::vector<char> candidate_valid_;                  // candidate_policy_[i] is current (else: row i of all_knots_ / empty)
+  int last_horizon_ = 0, last_N_ = 0, last_P_ = 0, last_interp_ = kZeroSpline;
+  TimeSpline plan_scratch_;
+  mutable std::shared_mutex mtx_;
 };
 
 }  // namespace mjpc_hip

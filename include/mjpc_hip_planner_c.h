@@ -4,6 +4,7 @@
  *   mjpc_spline_*   -> mjpc::spline::TimeSpline              (mjpc/spline/spline.h:41-276)
  *   mjpc_planner_*  -> mjpc::SamplingPlanner / RankedPlanner (mjpc/planners/sampling/planner.h:51-162,
  *                                                             mjpc/planners/planner.h:38-101)
+ *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
  */
 #ifndef MJPC_HIP_PLANNER_C_H_
@@ -87,8 +88,40 @@ void mjpc_robust_action_from_policy(void *planner, double *action, double time);
 void mjpc_robust_last(void *planner, int *out /* [3] best, ncand, rep */, double *scores, double *noisy_returns);
 void *mjpc_robust_delegate(void *planner);     /* the SamplingPlanner handle (mjpc_planner_* calls), owned by the robust planner */
 
+/* SampleGradientPlanner (mjpc/planners/sample_gradient/planner.h:35-175): create = Initialize + Allocate */
+void *mjpc_sg_create(const MjpcHipModel *model, const MjpcHipTask *task, double exploration, int trajectories, int gradient_trajectories,
+                     double gradient_filter, int representation, int spline_points, int max_samples, int max_horizon, int device);
+void mjpc_sg_destroy(void *planner);
+void mjpc_sg_reset(void *planner, int horizon, const double *initial_repeated_action);
+void mjpc_sg_set_state(void *planner, const double *state, const double *mocap, const double *userdata, double time);
+void mjpc_sg_set_task(void *planner, const MjpcHipTask *task);
+void mjpc_sg_set_seed(void *planner, unsigned long long seed, unsigned long long plan_iter);
+void mjpc_sg_set_noise(void *planner, const double *eps);      /* [num_trajectory * P * nu] standard normals, borrowed until the next call */
+void mjpc_sg_set_counts(void *planner, int trajectories, int gradient_trajectories);   /* the GUI sliders num_trajectory_ / num_gradient_ */
+void mjpc_sg_optimize_policy(void *planner, int horizon);
+void mjpc_sg_nominal_trajectory(void *planner, int horizon);
+void mjpc_sg_action_from_policy(void *planner, double *action, double time, int use_previous);
+double mjpc_sg_improvement(void *planner);
+int mjpc_sg_winner(void *planner);
+int mjpc_sg_winner_type(void *planner);                        /* 0 nominal, 1 perturbed, 2 gradient */
+int mjpc_sg_num_gradient(void *planner);                       /* num_gradient_ after its clamp */
+int mjpc_sg_num_parameters(void *planner);
+void mjpc_sg_returns(void *planner, double *out, int n);
+void mjpc_sg_trajectory_order(void *planner, int *out, int n);
+void mjpc_sg_gradient(void *planner, double *out, int n);
+int mjpc_sg_return_weight(void *planner, double *out /* NULL: size only */);   /* return_weight_; returns its size */
+int mjpc_sg_step_size(void *planner, double *out /* NULL: size only */);       /* step_size_; returns its size */
+int mjpc_sg_policy(void *planner, double *times, double *values);                                  /* returns P */
+int mjpc_sg_candidate_policy(void *planner, int index, double *times, double *values);             /* candidate_policy[index]; returns P */
+int mjpc_sg_best_trajectory(void *planner, double *states, double *actions, double *costs, double *total_return);   /* returns H */
+void mjpc_sg_timings(void *planner, double *noise_us, double *rollouts_us, double *policy_update_us, double *gradient_candidates_us);
+/* the planner's host closed forms without a planner (no GPU needed): fitness-shaping weights over an order of candidate indices
+ * (planner.cc:437-449) and LogScale (utilities.cc:802-808) */
+void mjpc_sg_return_weights(const int *order, int num_noisy, double *weights);
+void mjpc_sg_log_scale(double *values, double max_value, double min_value, int steps);
+
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
- * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create.  state / mocap are in-out;
+ * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create.  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,
  * plan_steps, failure}.  Returns the total cost. */
 double mjpc_testspeed_run(const MjpcHipModel *model, const MjpcHipTask *task, void *planner, int planner_kind, double *state,

@@ -93,6 +93,7 @@ struct PlannerOps {                               // the four Planner calls the 
 };
 PlannerOps Ops(SamplingPlanner& p);
 PlannerOps Ops(CrossEntropyPlanner& p);
+PlannerOps Ops(SampleGradientPlanner& p);
 
 struct TestspeedResult {
   int total_steps = 0, plan_steps = 0;

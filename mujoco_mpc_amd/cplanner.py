@@ -33,6 +33,14 @@ PLANNER_C_SYMBOLS = [
     "mjpc_robust_create", "mjpc_robust_destroy", "mjpc_robust_reset", "mjpc_robust_set_state", "mjpc_robust_set_seed",
     "mjpc_robust_optimize_policy", "mjpc_robust_action_from_policy", "mjpc_robust_last", "mjpc_robust_delegate",
 ]
+# the flat C view of the SampleGradientPlanner (same header)
+SAMPLE_GRADIENT_C_SYMBOLS = [
+    "mjpc_sg_create", "mjpc_sg_destroy", "mjpc_sg_reset", "mjpc_sg_set_state", "mjpc_sg_set_task", "mjpc_sg_set_seed", "mjpc_sg_set_noise",
+    "mjpc_sg_set_counts", "mjpc_sg_optimize_policy", "mjpc_sg_nominal_trajectory", "mjpc_sg_action_from_policy", "mjpc_sg_improvement",
+    "mjpc_sg_winner", "mjpc_sg_winner_type", "mjpc_sg_num_gradient", "mjpc_sg_num_parameters", "mjpc_sg_returns", "mjpc_sg_trajectory_order",
+    "mjpc_sg_gradient", "mjpc_sg_return_weight", "mjpc_sg_step_size", "mjpc_sg_policy", "mjpc_sg_candidate_policy", "mjpc_sg_best_trajectory",
+    "mjpc_sg_timings", "mjpc_sg_return_weights", "mjpc_sg_log_scale",
+]
 
 
 class PlannerError(RuntimeError):
@@ -102,6 +110,21 @@ def lib():
         "mjpc_robust_set_seed": (None, [vp, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]),
         "mjpc_robust_optimize_policy": (None, [vp, i]), "mjpc_robust_action_from_policy": (None, [vp, c_double_p, d]),
         "mjpc_robust_last": (None, [vp, c_int_p, c_double_p, c_double_p]), "mjpc_robust_delegate": (vp, [vp]),
+        "mjpc_sg_create": (vp, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), d, i, i, d, i, i, i, i, i]),
+        "mjpc_sg_destroy": (None, [vp]), "mjpc_sg_reset": (None, [vp, i, c_double_p]),
+        "mjpc_sg_set_state": (None, [vp, c_double_p, c_double_p, c_double_p, d]),
+        "mjpc_sg_set_task": (None, [vp, C.POINTER(capi.MjpcHipTask)]),
+        "mjpc_sg_set_seed": (None, [vp, C.c_ulonglong, C.c_ulonglong]), "mjpc_sg_set_noise": (None, [vp, c_double_p]),
+        "mjpc_sg_set_counts": (None, [vp, i, i]),
+        "mjpc_sg_optimize_policy": (None, [vp, i]), "mjpc_sg_nominal_trajectory": (None, [vp, i]),
+        "mjpc_sg_action_from_policy": (None, [vp, c_double_p, d, i]), "mjpc_sg_improvement": (d, [vp]),
+        "mjpc_sg_winner": (i, [vp]), "mjpc_sg_winner_type": (i, [vp]), "mjpc_sg_num_gradient": (i, [vp]), "mjpc_sg_num_parameters": (i, [vp]),
+        "mjpc_sg_returns": (None, [vp, c_double_p, i]), "mjpc_sg_trajectory_order": (None, [vp, c_int_p, i]),
+        "mjpc_sg_gradient": (None, [vp, c_double_p, i]), "mjpc_sg_return_weight": (i, [vp, c_double_p]), "mjpc_sg_step_size": (i, [vp, c_double_p]),
+        "mjpc_sg_policy": (i, [vp, c_double_p, c_double_p]), "mjpc_sg_candidate_policy": (i, [vp, i, c_double_p, c_double_p]),
+        "mjpc_sg_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_sg_timings": (None, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_sg_return_weights": (None, [c_int_p, i, c_double_p]), "mjpc_sg_log_scale": (None, [c_double_p, d, d, i]),
         "mjpc_testspeed_run": (d, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), vp, i, c_double_p, c_double_p, d, i, i, d, i,
                                    c_double_p, c_double_p, i, d, c_double_p]),
     }
@@ -357,9 +380,140 @@ class CrossEntropyPlanner:
         return t
 
 
+class SampleGradientPlanner:
+    """mjpc_hip::SampleGradientPlanner (C++) driven from Python; names follow planners/sample_gradient/planner.h:35-175."""
+    kNominal, kPerturb, kGradient = 0, 1, 2
+
+    def __init__(self):
+        self._L = lib()
+        self._h = None
+        self._noise = None
+
+    def Initialize(self, model: dict, task: dict, numerics: dict | None = None, max_samples=128, max_horizon=512, device=0):
+        numerics = numerics or {}
+        self.cm = capi.CModel(model, task)
+        self.nu = int(model["nu"]); self.ns = int(model["nq"] + model["nv"] + model["na"])
+        self.max_samples, self.max_horizon = int(max_samples), int(max_horizon)
+        self.P = int(numerics.get("sampling_spline_points", 512))
+        self.close()
+        h = self._L.mjpc_sg_create(C.byref(self.cm.c_model), C.byref(self.cm.c_task), float(numerics.get("sampling_exploration", 0.1)),
+                                   int(numerics.get("sampling_trajectories", 10)), int(numerics.get("sample_gradient_trajectories", 0)),
+                                   float(numerics.get("sample_gradient_filter", 1.0)), int(numerics.get("sampling_representation", 0)), self.P,
+                                   self.max_samples, self.max_horizon, int(device))
+        self._h = C.c_void_p(h)
+        _check()
+
+    def Allocate(self):
+        pass
+
+    def close(self):
+        if self._h:
+            self._L.mjpc_sg_destroy(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def Reset(self, horizon=0, initial_repeated_action=None):
+        a = None if initial_repeated_action is None else np.ascontiguousarray(initial_repeated_action, dtype=np.float64)
+        self._L.mjpc_sg_reset(self._h, int(horizon or 0), _dp(a)); _check()
+
+    def SetState(self, state, mocap=None, userdata=None, time=0.0):
+        s = np.ascontiguousarray(state, dtype=np.float64)
+        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
+        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
+        self._L.mjpc_sg_set_state(self._h, _dp(s), _dp(m), _dp(u), float(time))
+
+    def SetTask(self, task: dict):
+        t = self.cm.make_task(task)
+        self._L.mjpc_sg_set_task(self._h, C.byref(t)); _check()
+
+    def set_seed(self, seed, plan_iter=0): self._L.mjpc_sg_set_seed(self._h, int(seed), int(plan_iter))
+    def set_counts(self, trajectories, gradient_trajectories): self._L.mjpc_sg_set_counts(self._h, int(trajectories), int(gradient_trajectories))
+
+    def set_noise(self, eps):
+        self._noise = None if eps is None else np.ascontiguousarray(eps, dtype=np.float64)
+        self._L.mjpc_sg_set_noise(self._h, _dp(self._noise))
+
+    def OptimizePolicy(self, horizon): self._L.mjpc_sg_optimize_policy(self._h, int(horizon)); _check()
+    def NominalTrajectory(self, horizon): self._L.mjpc_sg_nominal_trajectory(self._h, int(horizon)); _check()
+
+    def ActionFromPolicy(self, time, use_previous=False):
+        a = np.zeros(self.nu)
+        self._L.mjpc_sg_action_from_policy(self._h, _dp(a), float(time), int(bool(use_previous))); _check()
+        return a
+
+    @property
+    def improvement(self): return self._L.mjpc_sg_improvement(self._h)
+    @property
+    def winner(self): return self._L.mjpc_sg_winner(self._h)
+    @property
+    def winner_type_(self): return self._L.mjpc_sg_winner_type(self._h)
+    @property
+    def num_gradient_(self): return self._L.mjpc_sg_num_gradient(self._h)
+    def NumParameters(self): return self._L.mjpc_sg_num_parameters(self._h)
+
+    def returns(self, n):
+        out = np.zeros(int(n)); self._L.mjpc_sg_returns(self._h, _dp(out), int(n)); return out
+
+    def trajectory_order(self, n):
+        out = np.zeros(int(n), np.int32); self._L.mjpc_sg_trajectory_order(self._h, out.ctypes.data_as(c_int_p), int(n)); return out
+
+    def gradient(self):
+        out = np.zeros(self.NumParameters()); self._L.mjpc_sg_gradient(self._h, _dp(out), out.size); return out
+
+    def return_weight(self):
+        out = np.zeros(max(self._L.mjpc_sg_return_weight(self._h, None), 1)); n = self._L.mjpc_sg_return_weight(self._h, _dp(out)); return out[:n]
+
+    def step_size(self):
+        out = np.zeros(max(self._L.mjpc_sg_step_size(self._h, None), 1)); n = self._L.mjpc_sg_step_size(self._h, _dp(out)); return out[:n]
+
+    def policy_knots(self):
+        P = self._L.mjpc_sg_policy(self._h, None, None)
+        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
+        self._L.mjpc_sg_policy(self._h, _dp(t), _dp(v))
+        return t[:P], v[:P]
+
+    def candidate_policy(self, index):
+        P = self._L.mjpc_sg_candidate_policy(self._h, int(index), None, None)
+        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
+        self._L.mjpc_sg_candidate_policy(self._h, int(index), _dp(t), _dp(v))
+        return t[:P], v[:P]
+
+    def timings(self):
+        a, b, c, g = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        self._L.mjpc_sg_timings(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(g))
+        return dict(noise_us=a.value, rollouts_us=b.value, policy_update_us=c.value, gradient_candidates_us=g.value)
+
+    def BestTrajectory(self):
+        Hm = self.max_horizon
+        st = np.zeros((Hm, self.ns)); ac = np.zeros((Hm, self.nu)); co = np.zeros(Hm); tot = C.c_double()
+        H = self._L.mjpc_sg_best_trajectory(self._h, _dp(st), _dp(ac), _dp(co), C.byref(tot))
+        t = Trajectory()
+        t.horizon = H; t.states = st.ravel()[:H * self.ns].reshape(H, self.ns); t.actions = ac.ravel()[:H * self.nu].reshape(H, self.nu)
+        t.costs = co[:H]; t.total_return = tot.value
+        return t
+
+
+def sample_gradient_return_weights(order):
+    """the planner's fitness-shaping weights over an order of candidate indices (host closed form, no GPU needed)"""
+    o = np.ascontiguousarray(order, dtype=np.int32); w = np.zeros(o.size)
+    lib().mjpc_sg_return_weights(o.ctypes.data_as(c_int_p), int(o.size), _dp(w))
+    return w
+
+
+def sample_gradient_step_sizes(steps, max_value=2.0, min_value=1.0e-3):
+    """LogScale(max, min, steps) as the planner spaces its gradient candidates (host closed form, no GPU needed)"""
+    v = np.zeros(max(int(steps), 1))
+    lib().mjpc_sg_log_scale(_dp(v), float(max_value), float(min_value), int(steps))
+    return v[:int(steps)]
+
+
 def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_planning_iteration=1, total_time=1.0, device=0, mode=0, mode_time=0.0):
     """mjpc/testspeed.cc:44-129 (`SynchronousPlanningCost`) through the C++ harness: `planner` is a cplanner.SamplingPlanner or
-    cplanner.CrossEntropyPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
+    cplanner.CrossEntropyPlanner / cplanner.SampleGradientPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
     L = lib()
     cm = planner.cm
     m = cm.model
@@ -367,7 +521,7 @@ def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_pla
     st = np.ascontiguousarray(state, dtype=np.float64).copy()
     mc = None if (mocap is None or m["nmocap"] == 0) else np.ascontiguousarray(mocap, dtype=np.float64).copy()
     costs = np.zeros(nsteps); out = np.zeros(6); params = np.zeros(max(int(cm.task["num_parameter"]), 1))
-    kind = 1 if isinstance(planner, CrossEntropyPlanner) else 0
+    kind = 1 if isinstance(planner, CrossEntropyPlanner) else 2 if isinstance(planner, SampleGradientPlanner) else 0
     total = L.mjpc_testspeed_run(C.byref(cm.c_model), C.byref(cm.c_task), planner._h, kind, _dp(st), _dp(mc), float(time0), int(horizon),
                                  int(steps_per_planning_iteration), float(total_time), int(device), _dp(costs), _dp(out), int(mode), float(mode_time), _dp(params))
     _check()

@@ -7,6 +7,8 @@
 //                   whole mjData-equivalent lives in dynamic LDS for all H steps; HBM traffic is only
 //                   the Trajectory record (coalesced row writes by the owning wave) + model reads
 //                   that hit L2 / the scalar cache.  Replaces planner.cc:342-380 + trajectory.cc:100-210.
+//   sg_assemble_kernel / sg_gradient_kernel  (gradient.h)  Sample-Gradient planner: the mixed candidate table + noise history of a
+//                   mjpc_hip_plan_mixed step, and the weighted sum of history rows that is the planner's gradient
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
 #include <hip/hip_runtime.h>
@@ -18,6 +20,7 @@
 #include "model.h"
 #include "spmd.h"
 #include "philox.h"
+#include "gradient.h"
 #include "host.h"
 #include "../../include/mjpc_hip_debug.h"
 
@@ -59,6 +62,29 @@ extern "C" __global__ void noise_kernel(double *eps, int *sel, unsigned long lon
     sel[idx] = (sigma1 > 0 && u < 0.2) ? 1 : 0;
   }
 }
+
+// mjpc_hip_plan_mixed: candidate table rows below first_explicit + noise history (gradient.h), one thread per table element
+extern "C" __global__ void __launch_bounds__(256) sg_assemble_kernel(const SgAssembleArgs a) {
+  size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < (size_t)a.nlocal * a.PN) sg_assemble(a, idx);
+}
+
+// mjpc_hip_sample_gradient: block b owns parameters [b * SG_KT, (b + 1) * SG_KT); wave 0 (lanes < SG_KT) runs the add chains,
+// waves 1 .. 3 are the SG_PROD producer groups; two tiles, one barrier per tile: the producers fill tile t while the consumer
+// adds tile t - 1, and a tile is written again only after the barrier that follows its consumption
+extern "C" __global__ void __launch_bounds__(256) sg_gradient_kernel(const SgGradArgs a) {
+  __shared__ double buf[2][SG_T * SG_KT];
+  const int kb = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ntile = (a.n + SG_T - 1) / SG_T;
+  double acc = 0.0;
+  for (int t = 0; t <= ntile; t++) {
+    if (w > 0 && t < ntile) sg_produce(a, kb, t, (w - 1) * (64 / SG_KT) + lane / SG_KT, lane % SG_KT, buf[t & 1]);
+    if (w == 0 && t > 0 && lane < SG_KT) acc = sg_consume(a, t - 1, lane, buf[(t - 1) & 1], acc);
+    __syncthreads();
+  }
+  if (w == 0 && lane < SG_KT && kb * SG_KT + lane < a.PN) a.gradient[kb * SG_KT + lane] = acc;
+}
+static_assert(SG_PROD == 3 * (64 / SG_KT), "sg_gradient_kernel: three producer waves");
 
 // winner[0] = local index of the first minimum of returns[0..n), winner_val[0] = its value
 extern "C" __global__ void __launch_bounds__(64) argmin_kernel(const double *returns, int n, int *winner, double *winner_val) {
@@ -144,6 +170,8 @@ struct MjpcHipEngine {
   int fault = 0;               // diagnostics knob fault_inject (mjpc_hip_debug.h; test-suite only)
   int summary_only = 0, last_summary = 0;      // mjpc_hip_set_fetch_mode
   int last_dense = 0;
+  // Sample-Gradient planner (mjpc_hip_plan_mixed / mjpc_hip_sample_gradient): noise history [max_local][P_max * nu], gradient inputs / output
+  double *d_hist = nullptr, *d_scale = nullptr, *d_grad = nullptr; int *d_slot = nullptr; int have_mixed = 0;
   // dense tier (two workgroups per CU), see "Capacity tiers" above
   RolloutFn kernelB = nullptr; Lay layB; int nefcB = 0, nconB = 0, cacheB_i = 0, cacheB_d = 0; size_t ldsB = 0; int num_cu = 256, force_tier = 0;
 };
@@ -310,6 +338,11 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   HIPCHKP(hipMalloc(&e->d_prof, sizeof(long long) * NL * 24));
   HIPCHKP(hipMemset(e->d_prof, 0, sizeof(long long) * NL * 24));
   HIPCHKP(hipMalloc(&e->d_winner_val, sizeof(double) * 2));
+  HIPCHKP(hipMalloc(&e->d_hist, sizeof(double) * NL * e->P_max * (e->nu + 1)));
+  HIPCHKP(hipMemset(e->d_hist, 0, sizeof(double) * NL * e->P_max * (e->nu + 1)));
+  HIPCHKP(hipMalloc(&e->d_slot, sizeof(int) * NL));
+  HIPCHKP(hipMalloc(&e->d_scale, sizeof(double) * NL));
+  HIPCHKP(hipMalloc(&e->d_grad, sizeof(double) * (e->P_max * e->nu + 1)));
   HIPCHKP(hipHostMalloc(&e->h_small, sizeof(double) * (e->ds + 7 * e->nmocap + e->P_max * (2 * e->nu + 1) + model->nuserdata + 16)));
   HIPCHKP(hipFuncSetAttribute((const void *)e->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
   if (e->kernelB) {
@@ -328,7 +361,8 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   void *bufs[] = {e->d_userdata, e->d_cand, e->d_std, e->d_ib, e->d_db, e->d_state, e->d_mocap, e->d_kt, e->d_kv, e->d_eps, e->d_sel, e->d_states, e->d_actions,
                   e->d_times, e->d_residual, e->d_costs, e->d_trace, e->d_knots, e->d_returns, e->d_failure, e->d_diag,
-                  e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt, e->d_slab};
+                  e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt, e->d_slab,
+                  e->d_hist, e->d_slot, e->d_scale, e->d_grad};
   for (void *b : bufs) if (b) hipFree(b);
   if (e->h_small) hipHostFree(e->h_small);
   for (int i = 0; i < 2; i++) { if (e->h_task[i]) hipHostFree(e->h_task[i]); if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]); }
@@ -365,7 +399,8 @@ int mjpc_hip_set_task(MjpcHipEngine *e, const MjpcHipTask *task) {
   return 0;
 }
 
-int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) {
+// first_explicit < 0: mjpc_hip_plan_async; >= 0: mjpc_hip_plan_mixed_async (the candidate table is assembled on the device)
+static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit) {
   if (!e || !in) { set_error("mjpc_hip_plan: invalid argument"); return -1; }
   if (e->pending) { set_error("mjpc_hip_plan_async: the previous plan step has not been fetched (one plan in flight per engine)"); return -1; }
   int P = in->num_spline_points, H = in->horizon, nl = in->num_local, nu = e->nu;
@@ -374,6 +409,12 @@ int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) {
   if (nl < 1 || nl > e->max_local || in->candidate_offset < 0 || in->candidate_offset + nl > in->num_trajectory) { set_error("mjpc_hip_plan: candidate range out of bounds"); return -1; }
   if (in->interpolation < 0 || in->interpolation > 2) { set_error("mjpc_hip_plan: unknown interpolation"); return -1; }
   if (!in->state || !in->knot_times || !in->knot_values || (e->nmocap > 0 && !in->mocap)) { set_error("mjpc_hip_plan: null input"); return -1; }
+  const bool mixed = first_explicit >= 0;
+  if (mixed) {
+    if (first_explicit > in->num_trajectory) { set_error("mjpc_hip_plan_mixed: first_explicit out of range (0..num_trajectory)"); return -1; }
+    if (!in->noise_std) { set_error("mjpc_hip_plan_mixed: noise_std is required"); return -1; }
+    if (first_explicit < in->num_trajectory && !in->candidate_knots) { set_error("mjpc_hip_plan_mixed: candidate_knots is required for the rows from first_explicit on"); return -1; }
+  }
   HIPCHK(hipSetDevice(e->device));
   size_t need = (size_t)nl * P * nu;
   if (need > e->eps_cap) {
@@ -427,13 +468,26 @@ int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) {
   K.noise_std = in->noise_std ? e->d_std : nullptr; K.nominal_index = in->nominal_index;
   K.cand_knots = nullptr; K.xfrc_std = in->xfrc_std; K.xfrc_rate = in->xfrc_rate;
   if (in->xfrc_std > 0 && !(in->xfrc_rate > 0)) { set_error("mjpc_hip_plan: xfrc_rate must be positive when xfrc_std > 0"); return -1; }
-  if (in->candidate_knots) {
+  if (in->candidate_knots || mixed) {
     if (need > e->cand_cap) {
       if (e->d_cand) HIPCHK(hipFree(e->d_cand));
       HIPCHK(hipMalloc(&e->d_cand, sizeof(double) * (need + 1)));
       e->cand_cap = need;
     }
-    HIPCHK(hipMemcpyAsync(e->d_cand, in->candidate_knots + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+    if (!mixed) HIPCHK(hipMemcpyAsync(e->d_cand, in->candidate_knots + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+    else {
+      // the caller's rows [first_explicit, offset + nl) verbatim, straight into the table; the kernel builds the rows below them
+      const size_t row = (size_t)P * nu;
+      const int r0 = first_explicit > in->candidate_offset ? first_explicit - in->candidate_offset : 0;      // first explicit local row
+      if (r0 < nl) HIPCHK(hipMemcpyAsync(e->d_cand + r0 * row, in->candidate_knots + ((size_t)in->candidate_offset + r0) * row, sizeof(double) * (nl - r0) * row,
+                                         hipMemcpyHostToDevice, e->stream));
+      if (r0 > 0) {
+        SgAssembleArgs sa{e->d_kv, e->d_std, e->d_eps, e->K.M.actuator_ctrlrange, e->d_cand, e->d_hist, (long long)e->P_max * nu,
+                          in->candidate_offset, nl, P * nu, nu, in->nominal_index, first_explicit};
+        hipLaunchKernelGGL(sg_assemble_kernel, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, e->stream, sa);
+      }
+      e->have_mixed = 1;
+    }
     K.cand_knots = e->d_cand;
   }
   K.states = e->d_states; K.actions = e->d_actions; K.times = e->d_times; K.residual = e->d_residual; K.costs = e->d_costs;
@@ -473,6 +527,8 @@ int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) {
   e->last_H = H; e->last_P = P; e->last_nlocal = nl; e->last_offset = in->candidate_offset; e->pending = 1;
   return 0;
 }
+
+int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) { return plan_async_impl(e, in, -1); }
 
 static int fetch_rows(MjpcHipEngine *e, int local, MjpcHipPlanOutput *out) {
   size_t H = (size_t)e->last_H, P = (size_t)e->last_P, r = (size_t)local;
@@ -533,6 +589,43 @@ int mjpc_hip_plan(MjpcHipEngine *e, const MjpcHipPlanInput *in, MjpcHipPlanOutpu
   int rc = mjpc_hip_plan_async(e, in);
   if (rc != 0) return rc;
   return mjpc_hip_plan_fetch(e, out);
+}
+
+int mjpc_hip_plan_mixed_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit) {
+  if (first_explicit < 0) { set_error("mjpc_hip_plan_mixed: first_explicit out of range (0..num_trajectory)"); return -1; }
+  return plan_async_impl(e, in, first_explicit);
+}
+
+int mjpc_hip_plan_mixed(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit, MjpcHipPlanOutput *out) {
+  int rc = mjpc_hip_plan_mixed_async(e, in, first_explicit);
+  if (rc != 0) return rc;
+  return mjpc_hip_plan_fetch(e, out);
+}
+
+int mjpc_hip_noise_history_reset(MjpcHipEngine *e) {
+  if (!e) { set_error("mjpc_hip_noise_history_reset: invalid argument"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(double) * (size_t)e->max_local * e->P_max * e->nu, e->stream));     // stream-ordered: behind a plan in flight
+  return 0;
+}
+
+int mjpc_hip_sample_gradient(MjpcHipEngine *e, int n, const int *slot, const double *scale, double *gradient_out) {
+  if (!e || !slot || !scale || !gradient_out) { set_error("mjpc_hip_sample_gradient: invalid argument"); return -1; }
+  if (e->pending) { set_error("mjpc_hip_sample_gradient: a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
+  if (!e->have_mixed || e->last_P < 1) { set_error("mjpc_hip_sample_gradient: no mixed plan yet (mjpc_hip_plan_mixed fills the noise history)"); return -1; }
+  if (n < 1 || n > e->max_local) { set_error("mjpc_hip_sample_gradient: n out of range (1..max_local)"); return -1; }
+  for (int i = 0; i < n; i++)
+    if (slot[i] < 0 || slot[i] >= e->max_local) { set_error("mjpc_hip_sample_gradient: slot[" + std::to_string(i) + "] = " + std::to_string(slot[i]) + " out of range (0..max_local-1)"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  const int PN = e->last_P * e->nu;
+  HIPCHK(hipMemcpyAsync(e->d_slot, slot, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(e->d_scale, scale, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
+  SgGradArgs ga{e->d_hist, (long long)e->P_max * e->nu, e->d_slot, e->d_scale, n, PN, e->d_grad};
+  hipLaunchKernelGGL(sg_gradient_kernel, dim3((PN + SG_KT - 1) / SG_KT), dim3(256), 0, e->stream, ga);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(gradient_out, e->d_grad, sizeof(double) * PN, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
 }
 
 int mjpc_hip_get_frame(MjpcHipEngine *e, double *xpos, double *xmat, double *site_xpos, double *subtree_com, double *subtree_linvel) {

@@ -3,6 +3,7 @@
 //   mjpc/spline/spline.cc:103-277            TimeSpline::Sample / DiscardBefore / AddNode / Slope
 //   mjpc/planners/sampling/policy.cc:30-78   SamplingPolicy
 //   mjpc/planners/sampling/planner.cc:40-310,525-534   SamplingPlanner host logic
+//   mjpc/planners/sample_gradient/planner.cc:43-493    SampleGradientPlanner host logic (batch + gradient sum on the engine)
 #include "../../include/mjpc_hip_planner.h"
 #include "../../include/mjpc_hip_planner_c.h"
 
@@ -683,6 +684,285 @@ void RobustPlanner::OptimizePolicy(int horizon) {   // robust_planner.cc:91-157
   delegate.CopyCandidateToPolicy(best_candidate);
 }
 
+
+// ------------------------------------------------------------------ SampleGradientPlanner
+SampleGradientPlanner::~SampleGradientPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
+
+void SampleGradientPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {   // planner.cc:43-75
+  numerics_ = numerics;
+  nq_ = model->nq; nv_ = model->nv; na_ = model->na; ns_ = nq_ + nv_ + na_; nu_ = model->nu; nmocap_ = model->nmocap;
+  nuserdata_ = model->nuserdata; nr_ = task->num_residual; ntrace_ = task->num_trace; timestep_ = model->timestep;
+  ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
+  noise_exploration = numerics.sampling_exploration[0];
+  num_trajectory_ = numerics.sampling_trajectories;
+  interpolation_ = numerics.sampling_representation;
+  num_gradient_ = numerics.sample_gradient_trajectories;
+  gradient_filter_ = numerics.sample_gradient_filter;
+  if (num_trajectory_ > numerics.max_samples) {
+    char msg[128]; std::snprintf(msg, sizeof(msg), "Too many trajectories, %d is the maximum allowed.", numerics.max_samples);
+    Fatal(msg);
+    return;
+  }
+  if (engine_) { mjpc_hip_destroy(engine_); engine_ = nullptr; }
+  engine_ = mjpc_hip_create(model, task, numerics.max_samples, numerics.max_horizon, numerics.device);
+  if (!engine_) { Fatal(mjpc_hip_last_error()); return; }
+  policy.Allocate(model, numerics.sampling_spline_points);
+  resampled_policy.Allocate(model, numerics.sampling_spline_points);
+  previous_policy.Allocate(model, numerics.sampling_spline_points);
+}
+
+void SampleGradientPlanner::Allocate() {   // planner.cc:78-118
+  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  plan_scratch_ = TimeSpline(nu_);
+  trajectory_order.resize(numerics_.max_samples);
+  std::iota(trajectory_order.begin(), trajectory_order.end(), 0);
+  returns.assign(numerics_.max_samples, 0.0); failures.assign(numerics_.max_samples, 0);
+  candidate_policy_.resize(numerics_.max_samples);
+  for (auto& c : candidate_policy_) { c.nu = nu_; c.ctrlrange = ctrlrange_; c.num_spline_points = policy.num_spline_points; c.plan = TimeSpline(nu_); }
+  candidate_valid_.assign(numerics_.max_samples, 1);
+  size_t Hm = (size_t)numerics_.max_horizon;
+  trajectory_winner.dim_state = ns_; trajectory_winner.dim_action = nu_; trajectory_winner.dim_residual = nr_;
+  trajectory_winner.dim_trace = 3 * ntrace_;
+  trajectory_winner.states.assign(Hm * ns_, 0.0); trajectory_winner.actions.assign(Hm * nu_, 0.0);
+  trajectory_winner.times.assign(Hm, 0.0); trajectory_winner.residual.assign(Hm * nr_, 0.0);
+  trajectory_winner.costs.assign(Hm, 0.0); trajectory_winner.trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+  int num_max_parameter = nu_ * MaxSamplingSplinePoints;       // the engine's spline capacity
+  gradient.assign(num_max_parameter, 0.0); gradient_previous.assign(num_max_parameter, 0.0);
+}
+
+void SampleGradientPlanner::Reset(int horizon, const double* initial_repeated_action) {   // planner.cc:121-160
+  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0);
+  std::fill(userdata.begin(), userdata.end(), 0.0);
+  time = 0.0;
+  policy.Reset(horizon, initial_repeated_action);
+  resampled_policy.Reset(horizon, initial_repeated_action);
+  previous_policy.Reset(horizon, initial_repeated_action);
+  plan_scratch_.Clear();
+  if (engine_ && mjpc_hip_noise_history_reset(engine_) != 0) Fatal(mjpc_hip_last_error());      // std::fill(noise, 0)
+  for (size_t i = 0; i < candidate_policy_.size(); i++) { candidate_policy_[i].Reset(horizon); candidate_valid_[i] = 1; }
+  improvement = 0.0;
+  winner = 0;
+  std::fill(gradient.begin(), gradient.end(), 0.0);
+  std::fill(gradient_previous.begin(), gradient_previous.end(), 0.0);
+}
+
+void SampleGradientPlanner::SetState(const double* s, const double* m, const double* u, double t) {
+  std::copy(s, s + ns_, state.begin());
+  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
+  if (u) std::copy(u, u + nuserdata_, userdata.begin());
+  time = t;
+}
+
+void SampleGradientPlanner::SetTask(const MjpcHipTask* task) {
+  if (mjpc_hip_set_task(engine_, task) != 0) Fatal(mjpc_hip_last_error());
+}
+
+void SampleGradientPlanner::ResamplePolicy(SamplingPolicy& p, int horizon, int num_spline_points) {   // planner.cc:302-326
+  double nominal_time = time;
+  double time_shift = std::max((horizon - 1) * timestep_ / (num_spline_points - 1), 1.0e-5);
+  plan_scratch_.Clear();
+  plan_scratch_.SetInterpolation(p.plan.Interpolation());
+  for (int t = 0; t < num_spline_points; t++) {
+    double* node = plan_scratch_.AddNode(nominal_time);
+    p.Action(node, nullptr, nominal_time);
+    nominal_time += time_shift;
+  }
+  p.plan = plan_scratch_;
+  p.num_spline_points = num_spline_points;
+}
+
+// candidate_policy[index] of the reference.  Only explicit candidates are kept as splines; a noisy candidate of the last plan is
+// rebuilt from its rolled-out knots when somebody asks for it (the sliders moved and its slot became a gradient slot).
+SamplingPolicy& SampleGradientPlanner::Candidate(int index) {
+  SamplingPolicy& c = candidate_policy_[index];
+  if (!candidate_valid_[index]) {
+    c.plan = TimeSpline(nu_, (SplineInterpolation)last_interp_);
+    if (index < last_N_)
+      for (int t = 0; t < last_P_; t++) c.plan.AddNode(knot_times_[t], all_knots_.data() + ((size_t)index * last_P_ + t) * nu_);
+    c.num_spline_points = last_P_;
+    candidate_valid_[index] = 1;
+  }
+  return c;
+}
+
+int SampleGradientPlanner::CandidatePolicy(int index, double* times, double* values) {
+  const SamplingPolicy& c = Candidate(index);
+  int P = (int)c.plan.Size();
+  for (int t = 0; t < P; t++) {
+    if (times) times[t] = c.plan.NodeTime(t);
+    if (values) std::copy(c.plan.NodeValues(t), c.plan.NodeValues(t) + nu_, values + (size_t)t * nu_);
+  }
+  return P;
+}
+
+void SampleGradientPlanner::OptimizePolicy(int horizon) {   // planner.cc:169-273
+  int num_trajectory = num_trajectory_;
+  num_gradient_ = std::min(num_gradient_, num_trajectory - 1);
+  int num_gradient = num_gradient_;
+  int num_noisy = num_trajectory - num_gradient;
+  int num_spline_points = policy.num_spline_points;
+  if (num_spline_points < 1 || num_spline_points > MaxSamplingSplinePoints) { Fatal("SampleGradientPlanner: spline points out of range (1..36)"); return; }
+  policy.plan.SetInterpolation((SplineInterpolation)interpolation_);
+  {
+    const std::shared_lock<std::shared_mutex> lock(mtx_);
+    resampled_policy.CopyFrom(policy, num_spline_points);
+  }
+  resampled_policy.num_spline_points = num_spline_points;
+  ResamplePolicy(resampled_policy, horizon, num_spline_points);
+  for (int i = 0; i < num_gradient; i++) ResamplePolicy(Candidate(num_noisy + i), horizon, num_spline_points);
+
+  // ----- rollouts (planner.cc:358-398): nominal, noisy and gradient candidates in one launch
+  auto rollouts_start = std::chrono::steady_clock::now();
+  int P = num_spline_points;
+  size_t row = (size_t)P * nu_;
+  knot_times_.resize(P); knot_values_.resize(row); noise_std_.assign(row, noise_exploration);
+  for (int t = 0; t < P; t++) {
+    knot_times_[t] = resampled_policy.plan.NodeTime(t);
+    std::copy(resampled_policy.plan.NodeValues(t), resampled_policy.plan.NodeValues(t) + nu_, knot_values_.begin() + (size_t)t * nu_);
+  }
+  cand_table_.resize((size_t)num_trajectory * row);             // rows below num_noisy are not read by the engine
+  for (int i = num_noisy; i < num_trajectory; i++) {
+    const SamplingPolicy& c = candidate_policy_[i];
+    for (int t = 0; t < P; t++) std::copy(c.plan.NodeValues(t), c.plan.NodeValues(t) + nu_, cand_table_.begin() + (size_t)i * row + (size_t)t * nu_);
+  }
+  MjpcHipPlanInput in;
+  std::memset(&in, 0, sizeof(in));
+  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
+  in.knot_times = knot_times_.data(); in.knot_values = knot_values_.data(); in.num_spline_points = P;
+  in.interpolation = (int)resampled_policy.plan.Interpolation();
+  in.num_trajectory = num_trajectory; in.horizon = horizon; in.candidate_offset = 0; in.num_local = num_trajectory;
+  in.noise_eps = injected_noise_eps; in.seed = seed; in.stream = plan_iter++;
+  in.noise_std = noise_std_.data(); in.nominal_index = 0;
+  in.candidate_knots = cand_table_.data();
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.returns = returns.data(); out.failure = failures.data();
+  if (mjpc_hip_plan_mixed(engine_, &in, num_noisy, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
+  noise_compute_time = out.noise_compute_time_us;
+  all_knots_.resize((size_t)num_trajectory * row);
+  if (mjpc_hip_get_knots(engine_, all_knots_.data()) != 0) { Fatal(mjpc_hip_last_error()); return; }
+  last_horizon_ = horizon; last_N_ = num_trajectory; last_P_ = P; last_interp_ = in.interpolation;
+  for (int i = 0; i < num_noisy; i++) candidate_valid_[i] = 0;        // candidate_policy[i] = row i of all_knots_ now
+  rollouts_compute_time = Micros(rollouts_start);
+
+  // ----- update policy (planner.cc:216-262)
+  auto policy_update_start = std::chrono::steady_clock::now();
+  trajectory_order.resize(std::max((int)trajectory_order.size(), num_trajectory));
+  for (int i = 0; i < num_trajectory; i++) trajectory_order[i] = i;
+  std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + num_trajectory,
+                   [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+  const int idx_nominal = 0;
+  if (returns[trajectory_order[0]] < returns[idx_nominal]) winner = trajectory_order[0];
+  else winner = idx_nominal;
+  if (winner > idx_nominal) winner_type_ = winner < num_trajectory - num_gradient ? kPerturb : kGradient;
+  else winner_type_ = kNominal;
+  {
+    const SamplingPolicy& w = Candidate(winner);
+    const std::unique_lock<std::shared_mutex> lock(mtx_);
+    policy.plan = w.plan;
+  }
+  improvement = std::max(returns[idx_nominal] - returns[winner], 0.0);
+  {
+    MjpcHipPlanOutput best;
+    std::memset(&best, 0, sizeof(best));
+    best.states = trajectory_winner.states.data(); best.actions = trajectory_winner.actions.data(); best.times = trajectory_winner.times.data();
+    best.residual = trajectory_winner.residual.data(); best.costs = trajectory_winner.costs.data(); best.trace = trajectory_winner.trace.data();
+    if (mjpc_hip_get_candidate(engine_, winner, &best) != 0) { Fatal(mjpc_hip_last_error()); return; }
+    trajectory_winner.horizon = horizon; trajectory_winner.total_return = returns[winner]; trajectory_winner.failure = failures[winner] != 0;
+  }
+  policy_update_compute_time = Micros(policy_update_start);
+
+  // ----- gradient candidates for the next plan step (planner.cc:264-272)
+  auto gradient_start = std::chrono::steady_clock::now();
+  GradientCandidates(num_trajectory, num_gradient, horizon);
+  gradient_candidates_compute_time = Micros(gradient_start);
+}
+
+void SampleGradientPlanner::ReturnWeights(const int* order, int num_noisy, double* weights) {   // planner.cc:437-449
+  double f0 = std::log(0.5 * num_noisy + 1.0);
+  double den = 0.0;
+  for (int i = 0; i < num_noisy; i++) den += std::max(0.0, f0 - std::log(order[i] + 1));
+  for (int i = 0; i < num_noisy; i++) weights[i] = std::max(0.0, f0 - std::log(order[i] + 1)) / den - 1.0 / num_noisy;
+}
+
+void SampleGradientPlanner::LogScale(double* values, double max_value, double min_value, int steps) {   // utilities.cc:802-808
+  double step = (std::log(max_value) - std::log(min_value)) / std::max((steps - 1), 1);
+  for (int i = 0; i < steps; i++) values[i] = std::exp(std::log(min_value) + i * step);
+  // the scale starts at min_value itself: exp(log(1e-3)) comes out one ulp above 1e-3 with glibc, and the smallest step is a
+  // documented constant of the planner (gradient_min_step_size), not a libm artefact
+  if (steps > 0) values[0] = min_value;
+}
+
+void SampleGradientPlanner::GradientCandidates(int num_trajectory, int num_gradient, int) {   // planner.cc:401-493
+  if (num_gradient < 1) return;
+  int num_spline_points = resampled_policy.num_spline_points;
+  int num_parameters = num_spline_points * nu_;
+  std::copy(gradient.begin(), gradient.begin() + num_parameters, gradient_previous.begin());
+  int num_noisy = num_trajectory - num_gradient;
+  // fitness shaping, computed when the count of noisy candidates changes and only then (planner.cc:419-450)
+  if ((int)return_weight_.size() != num_noisy) {
+    return_weight_.resize(num_noisy);
+    for (int i = 0; i < num_noisy; i++) trajectory_order[i] = i;
+    std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + num_noisy,
+                     [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+    ReturnWeights(trajectory_order.data(), num_noisy, return_weight_.data());
+  }
+  // gradient = sum_i noise[trajectory_order[i]] * return_weight_[i] / num_noisy, on the device over the noise history
+  scale_.resize(num_noisy);
+  for (int i = 0; i < num_noisy; i++) scale_[i] = return_weight_[i] / num_noisy;
+  std::fill(gradient.begin(), gradient.end(), 0.0);
+  if (mjpc_hip_sample_gradient(engine_, num_noisy, trajectory_order.data(), scale_.data(), gradient.data()) != 0) { Fatal(mjpc_hip_last_error()); return; }
+  if ((int)step_size_.size() != num_gradient) {
+    step_size_.resize(num_gradient);
+    LogScale(step_size_.data(), gradient_max_step_size, gradient_min_step_size, num_gradient);
+  }
+  double gradient_filter = gradient_filter_;
+  for (int i = num_noisy; i < num_trajectory; i++) {
+    SamplingPolicy& c = candidate_policy_[i];
+    c.CopyFrom(resampled_policy, num_spline_points);
+    candidate_valid_[i] = 1;
+    double scaling = step_size_[i - num_noisy] / noise_exploration;
+    for (int t = 0; t < (int)c.plan.Size(); t++) {
+      double* n = c.plan.NodeValues(t);
+      for (int k = 0; k < nu_; k++) n[k] += gradient[(size_t)t * nu_ + k] * (-scaling * gradient_filter);                     // mju_addToScl
+      for (int k = 0; k < nu_; k++) n[k] += gradient_previous[(size_t)t * nu_ + k] * (-scaling * (1.0 - gradient_filter));
+      for (int k = 0; k < nu_; k++) n[k] = std::max(ctrlrange_[2 * k], std::min(ctrlrange_[2 * k + 1], n[k]));                  // Clamp
+    }
+  }
+}
+
+void SampleGradientPlanner::NominalTrajectory(int horizon) {   // planner.cc:276-287: rollout of resampled_policy into trajectory[0]
+  int P = (int)resampled_policy.plan.Size();
+  std::vector<double> kt(std::max(P, 1), time), kv((size_t)std::max(P, 1) * nu_, 0.0);
+  for (int p = 0; p < P; p++) {
+    kt[p] = resampled_policy.plan.NodeTime(p);
+    std::copy(resampled_policy.plan.NodeValues(p), resampled_policy.plan.NodeValues(p) + nu_, kv.begin() + (size_t)p * nu_);
+  }
+  MjpcHipPlanInput in;
+  std::memset(&in, 0, sizeof(in));
+  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
+  in.knot_times = kt.data(); in.knot_values = kv.data(); in.num_spline_points = std::max(P, 1);
+  in.interpolation = (int)resampled_policy.plan.Interpolation(); in.num_trajectory = 1; in.horizon = horizon; in.num_local = 1;
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  double ret = 0; int fail = 0;
+  out.returns = &ret; out.failure = &fail;
+  out.states = trajectory_winner.states.data(); out.actions = trajectory_winner.actions.data(); out.times = trajectory_winner.times.data();
+  out.residual = trajectory_winner.residual.data(); out.costs = trajectory_winner.costs.data(); out.trace = trajectory_winner.trace.data();
+  if (mjpc_hip_plan(engine_, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
+  trajectory_winner.horizon = horizon; trajectory_winner.total_return = ret; trajectory_winner.failure = fail != 0;
+  returns[0] = ret; failures[0] = fail;
+  winner = 0;                                          // BestTrajectory() shows trajectory[0] until the next OptimizePolicy
+}
+
+void SampleGradientPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {   // planner.cc:290-299
+  const std::shared_lock<std::shared_mutex> lock(mtx_);
+  if (use_previous) previous_policy.Action(action, s, t);
+  else policy.Action(action, s, t);
+}
+
+const Trajectory* SampleGradientPlanner::BestTrajectory() { return &trajectory_winner; }
+
 }  // namespace mjpc_hip
 
 // ====================================================================== flat C wrapper (tests / ctypes)
@@ -817,6 +1097,67 @@ int mjpc_cem_best_trajectory(void* p, double* states, double* actions, double* c
   if (total_return) *total_return = t->total_return;
   return t->horizon;
 }
+
+// ---- SampleGradientPlanner
+#define SGP(p) ((mjpc_hip::SampleGradientPlanner*)(p))
+void* mjpc_sg_create(const MjpcHipModel* model, const MjpcHipTask* task, double exploration, int trajectories, int gradient_trajectories,
+                     double gradient_filter, int representation, int spline_points, int max_samples, int max_horizon, int device) {
+  auto* p = new mjpc_hip::SampleGradientPlanner();
+  mjpc_hip::Numerics n;
+  n.sampling_exploration[0] = exploration; n.sampling_trajectories = trajectories; n.sample_gradient_trajectories = gradient_trajectories;
+  n.sample_gradient_filter = gradient_filter; n.sampling_representation = representation; n.sampling_spline_points = spline_points;
+  n.max_samples = max_samples; n.max_horizon = max_horizon; n.device = device;
+  p->Initialize(model, task, n);
+  p->Allocate();
+  return p;
+}
+void mjpc_sg_destroy(void* p) { delete SGP(p); }
+void mjpc_sg_reset(void* p, int horizon, const double* a) { SGP(p)->Reset(horizon, a); }
+void mjpc_sg_set_state(void* p, const double* s, const double* m, const double* u, double t) { SGP(p)->SetState(s, m, u, t); }
+void mjpc_sg_set_task(void* p, const MjpcHipTask* task) { SGP(p)->SetTask(task); }
+void mjpc_sg_set_seed(void* p, unsigned long long seed, unsigned long long it) { SGP(p)->seed = seed; SGP(p)->plan_iter = it; }
+void mjpc_sg_set_noise(void* p, const double* eps) { SGP(p)->injected_noise_eps = eps; }
+void mjpc_sg_set_counts(void* p, int trajectories, int gradient_trajectories) { SGP(p)->num_trajectory_ = trajectories; SGP(p)->num_gradient_ = gradient_trajectories; }
+void mjpc_sg_optimize_policy(void* p, int horizon) { SGP(p)->OptimizePolicy(horizon); }
+void mjpc_sg_nominal_trajectory(void* p, int horizon) { SGP(p)->NominalTrajectory(horizon); }
+void mjpc_sg_action_from_policy(void* p, double* a, double t, int prev) { SGP(p)->ActionFromPolicy(a, nullptr, t, prev != 0); }
+double mjpc_sg_improvement(void* p) { return SGP(p)->improvement; }
+int mjpc_sg_winner(void* p) { return SGP(p)->winner; }
+int mjpc_sg_winner_type(void* p) { return SGP(p)->winner_type_; }
+int mjpc_sg_num_gradient(void* p) { return SGP(p)->num_gradient_; }
+int mjpc_sg_num_parameters(void* p) { return SGP(p)->NumParameters(); }
+void mjpc_sg_returns(void* p, double* out, int n) { std::copy(SGP(p)->returns.begin(), SGP(p)->returns.begin() + n, out); }
+void mjpc_sg_trajectory_order(void* p, int* out, int n) { std::copy(SGP(p)->trajectory_order.begin(), SGP(p)->trajectory_order.begin() + n, out); }
+void mjpc_sg_gradient(void* p, double* out, int n) { std::copy(SGP(p)->gradient.begin(), SGP(p)->gradient.begin() + n, out); }
+int mjpc_sg_return_weight(void* p, double* out) { auto& w = SGP(p)->return_weight_; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
+int mjpc_sg_step_size(void* p, double* out) { auto& w = SGP(p)->step_size_; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
+int mjpc_sg_policy(void* p, double* times, double* values) {
+  auto& pol = SGP(p)->policy;
+  int P = (int)pol.plan.Size();
+  for (int i = 0; i < P; i++) {
+    if (times) times[i] = pol.plan.NodeTime(i);
+    if (values) std::copy(pol.plan.NodeValues(i), pol.plan.NodeValues(i) + pol.nu, values + (size_t)i * pol.nu);
+  }
+  return P;
+}
+int mjpc_sg_candidate_policy(void* p, int index, double* times, double* values) { return SGP(p)->CandidatePolicy(index, times, values); }
+int mjpc_sg_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
+  const mjpc_hip::Trajectory* t = SGP(p)->BestTrajectory();
+  size_t H = (size_t)t->horizon;
+  if (states) std::copy(t->states.begin(), t->states.begin() + H * t->dim_state, states);
+  if (actions) std::copy(t->actions.begin(), t->actions.begin() + H * t->dim_action, actions);
+  if (costs) std::copy(t->costs.begin(), t->costs.begin() + H, costs);
+  if (total_return) *total_return = t->total_return;
+  return t->horizon;
+}
+void mjpc_sg_timings(void* p, double* noise, double* rollouts, double* update, double* gradient) {
+  *noise = SGP(p)->noise_compute_time; *rollouts = SGP(p)->rollouts_compute_time; *update = SGP(p)->policy_update_compute_time;
+  *gradient = SGP(p)->gradient_candidates_compute_time;
+}
+// host closed forms, no engine needed
+void mjpc_sg_return_weights(const int* order, int num_noisy, double* weights) { mjpc_hip::SampleGradientPlanner::ReturnWeights(order, num_noisy, weights); }
+void mjpc_sg_log_scale(double* values, double max_value, double min_value, int steps) { mjpc_hip::SampleGradientPlanner::LogScale(values, max_value, min_value, steps); }
+#undef SGP
 
 // ---- RobustPlanner
 void* mjpc_robust_create(const MjpcHipModel* model, const MjpcHipTask* task, const double* exploration, int trajectories, int representation,

@@ -95,6 +95,36 @@ class HipBackend:
         o["trace"] = o["trace"][:, :ntr]
         return o
 
+    def plan_mixed(self, first_explicit, **kw):
+        """Sample-Gradient batch (mjpc_hip_plan_mixed): candidates with global index < first_explicit are sampled with the
+        required noise_std (the nominal_index one un-noised), the others use candidate_knots[i] verbatim; noisy rows leave
+        their standard normals in the engine's noise history."""
+        inp = self.make_input(**kw)
+        o, c, ntr = self._alloc_out(inp.num_local, inp.horizon, inp.num_spline_points)
+        if self.lib.mjpc_hip_plan_mixed(self.h, C.byref(inp), int(first_explicit), C.byref(c)) != 0:
+            raise RuntimeError("mjpc_hip_plan_mixed failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["winner"] = c.winner; o["winner_return"] = c.winner_return
+        o["noise_compute_time_us"] = c.noise_compute_time_us; o["rollouts_compute_time_us"] = c.rollouts_compute_time_us
+        o["trace"] = o["trace"][:, :ntr]
+        self._last_PN = inp.num_spline_points * self.model["nu"]
+        return o
+
+    def sample_gradient(self, slot, scale):
+        """gradient[k] = sum_i history[slot[i]][k] * scale[i] over the noise history, k < P * nu of the last plan
+        (mjpc_hip_sample_gradient): products rounded, added in ascending i."""
+        sl = np.ascontiguousarray(slot, dtype=np.int32); sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sl.shape != sc.shape or sl.ndim != 1:
+            raise ValueError("sample_gradient: slot and scale must be 1-d and of equal length")
+        g = np.zeros(36 * self.model["nu"])
+        if self.lib.mjpc_hip_sample_gradient(self.h, int(sl.size), sl.ctypes.data_as(capi.c_int_p), sc.ctypes.data_as(capi.c_double_p),
+                                             g.ctypes.data_as(capi.c_double_p)) != 0:
+            raise RuntimeError("mjpc_hip_sample_gradient failed: " + self.lib.mjpc_hip_last_error().decode())
+        return g[:getattr(self, "_last_PN", g.size)]
+
+    def noise_history_reset(self):
+        if self.lib.mjpc_hip_noise_history_reset(self.h) != 0:
+            raise RuntimeError(self.lib.mjpc_hip_last_error().decode())
+
     def candidate(self, local_index, H, P):
         o, c, ntr = self._alloc_out(1, H, P)
         if self.lib.mjpc_hip_get_candidate(self.h, int(local_index), C.byref(c)) != 0:

@@ -100,23 +100,72 @@ struct Numerics {                       // the planner's <custom><numeric> entri
   double sample_gradient_filter = 1.0;     // weight of the new gradient against the previous one (planner.cc:69)
 };
 
-class SamplingPlanner {
+// What the three planners on the rollout engine share: the planner's state, its policies, the bookkeeping of a plan step and the
+// engine I/O around them.  Not polymorphic: nothing dispatches on a planner pointer, a planner is used as its own type.
+class PlannerBase {
  public:
-  SamplingPlanner() = default;
+  PlannerBase() = default;
+  PlannerBase(const PlannerBase&) = delete;
+  PlannerBase& operator=(const PlannerBase&) = delete;
+
+  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
+  int NumParameters() { return policy.num_spline_points * nu_; }
+
+  // ---- public members other code reads/writes in the reference (sampling/planner.h:115-162)
+  SamplingPolicy policy, previous_policy;
+  std::vector<double> state, mocap, userdata;
+  double time = 0;
+  std::vector<double> returns;                         // trajectory[i].total_return
+  std::vector<int> failures;
+  std::vector<int> trajectory_order;
+  double improvement = 0;
+  double noise_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;   // microseconds
+  int interpolation_ = kZeroSpline;
+  int num_trajectory_ = 10;
+  unsigned long long seed = 0x5EED;
+  unsigned long long plan_iter = 0;
+  // reproducible-noise hook (the reference's absl::BitGen is unseedable): optional injected standard normals, one row of
+  // P * nu per candidate of the batch
+  const double* injected_noise_eps = nullptr;
+
+ protected:
+  ~PlannerBase() = default;
+  // dimensions, ctrlrange_, num_trajectory_, interpolation_; false after the "Too many trajectories" refusal
+  bool InitializeCommon(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
+  void AllocateState();                                // state / mocap / userdata, zeroed
+  void ResetState(int horizon, const double* initial_repeated_action);   // state, time, policy, previous_policy
+  void SizeTrajectory(Trajectory& trajectory) const;   // rows for numerics_.max_horizon steps
+  // the spline's nodes as the ABI's knot arrays; returns their count.  An empty plan samples zeros: one knot at `time`.
+  int KnotArrays(const TimeSpline& plan, std::vector<double>& times, std::vector<double>& values) const;
+  // a plan of num_trajectory candidates at the current state / time; noise, explicit candidates, seed and stream are the caller's
+  MjpcHipPlanInput PlanInput(const double* knot_times, const double* knot_values, int num_spline_points, int interpolation,
+                             int num_trajectory, int horizon) const;
+  static MjpcHipPlanOutput TrajectoryOutput(Trajectory& trajectory);   // the row pointers are the trajectory's buffers
+  void OrderCandidates(int n);                         // trajectory_order[0 .. n) by (return, index)
+  // `plan` alone, un-noised, on `engine` into `trajectory` (horizon, return and failure included; the engine's failure flags
+  // into *failure); false after an engine error
+  bool RolloutNominal(MjpcHipEngine* engine, const TimeSpline& plan, int horizon, Trajectory& trajectory, int* failure = nullptr);
+
+  Numerics numerics_;
+  int nq_ = 0, nv_ = 0, na_ = 0, ns_ = 0, nu_ = 0, nmocap_ = 0, nuserdata_ = 0, nr_ = 0, ntrace_ = 0;
+  double timestep_ = 0;
+  std::vector<double> ctrlrange_;
+  mutable std::shared_mutex mtx_;
+};
+
+class SamplingPlanner : public PlannerBase {
+ public:
+  SamplingPlanner() { interpolation_ = kCubicSpline; }
   ~SamplingPlanner();
-  SamplingPlanner(const SamplingPlanner&) = delete;
-  SamplingPlanner& operator=(const SamplingPlanner&) = delete;
 
   // ---- Planner virtuals (planners/planner.h:38-80); errors abort like mju_error unless a handler is installed
   void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
   void Allocate();
   void Reset(int horizon, const double* initial_repeated_action = nullptr);
-  void SetState(const double* state, const double* mocap, const double* userdata, double time);
   void OptimizePolicy(int horizon);
   void NominalTrajectory(int horizon);
-  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
   const Trajectory* BestTrajectory();
-  int NumParameters() { return policy.num_spline_points * nu_; }
   // ---- RankedPlanner virtuals (planners/planner.h:84-101)
   int OptimizePolicyCandidates(int ncandidates, int horizon);
   double CandidateScore(int candidate) const;
@@ -135,97 +184,57 @@ class SamplingPlanner {
   // every candidate's trace rows of the last plan step [num_trajectory][horizon][3*num_trace] in one copy (Traces, planner.cc:388-434)
   void AllTraces(double* out);
   const std::vector<double>& KnotTimes() const { return knot_times_; }
-  // ---- public members other code reads/writes in the reference (planner.h:115-162)
-  SamplingPolicy policy, previous_policy;
-  std::vector<double> state, mocap, userdata;
-  double time = 0;
   Trajectory trajectory_winner;                        // trajectory[winner]; other candidates stay on the device
-  std::vector<double> returns;                         // trajectory[i].total_return
-  std::vector<int> failures;
-  std::vector<int> trajectory_order;
   int winner = 0;
   double noise_exploration[2] = {0.1, 0.0};
-  int num_trajectory_ = 10;
-  int interpolation_ = kCubicSpline;
   int sliding_plan_ = 0;
-  double improvement = 0;
-  double noise_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;   // microseconds
-  unsigned long long seed = 0x5EED;
-  unsigned long long plan_iter = 0;
-  // reproducible-noise hook (the reference's absl::BitGen is unseedable): optional injected tensors
-  const double* injected_noise_eps = nullptr;   // [num_trajectory * P * nu]
-  const int* injected_noise_sel = nullptr;      // [num_trajectory]
+  const int* injected_noise_sel = nullptr;             // [num_trajectory], with injected_noise_eps [num_trajectory * P * nu]
 
  private:
   void FetchCandidate(int global_index);
   MjpcHipMulti* engine_ = nullptr;             // one rollout engine per GPU
-  Numerics numerics_;
-  int nq_ = 0, nv_ = 0, na_ = 0, ns_ = 0, nu_ = 0, nmocap_ = 0, nuserdata_ = 0, nr_ = 0, ntrace_ = 0;
-  double timestep_ = 0;
-  std::vector<double> ctrlrange_;
   SamplingPolicy winner_policy_;               // candidate_policy[winner]
   TimeSpline plan_scratch_;
   std::vector<double> knot_times_, knot_values_, winner_knots_;
   int last_horizon_ = 0, fetched_ = -1, nominal_horizon_ = 0;
   MjpcHipEngine* nominal_engine_ = nullptr;            // one-candidate engine of NominalTrajectory()
-  mutable std::shared_mutex mtx_;
 };
 
 // mjpc/planners/cross_entropy/planner.{h,cc}: all N candidates are perturbed with a per-parameter std (elite variance,
 // floored at std_min), the nominal (resampled) policy is rolled out as one extra candidate, the new policy is the mean
 // of the n_elite best candidates.  Quirks kept: the variance loop reads the best elite's parameters for every elite
 // (planner.cc:240-253); previous_policy is never refreshed by OptimizePolicy.
-class CrossEntropyPlanner {
+class CrossEntropyPlanner : public PlannerBase {
  public:
   CrossEntropyPlanner() = default;
   ~CrossEntropyPlanner();
-  CrossEntropyPlanner(const CrossEntropyPlanner&) = delete;
-  CrossEntropyPlanner& operator=(const CrossEntropyPlanner&) = delete;
 
   void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
   void Allocate();
   void Reset(int horizon, const double* initial_repeated_action = nullptr);
-  void SetState(const double* state, const double* mocap, const double* userdata, double time);
   void OptimizePolicy(int horizon);
   void NominalTrajectory(int horizon);
-  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
   void ResamplePolicy(int horizon);
   const Trajectory* BestTrajectory();                  // the nominal trajectory (planner.cc:418-420)
-  int NumParameters() { return policy.num_spline_points * nu_; }
   void SetTask(const MjpcHipTask* task);
 
-  SamplingPolicy policy, resampled_policy, previous_policy;
-  std::vector<double> state, mocap, userdata;
-  double time = 0;
+  SamplingPolicy resampled_policy;
   Trajectory nominal_trajectory;
-  std::vector<double> returns;                         // trajectory[i].total_return, i < num_trajectory
-  std::vector<int> failures;
-  std::vector<int> trajectory_order;
   std::vector<double> parameters_scratch, times_scratch, variance;
   double std_initial_ = 0.1, std_min_ = 0.1;
   int n_elite_ = 2;
-  double improvement = 0;
-  double noise_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;   // microseconds
-  int interpolation_ = kZeroSpline;
-  int num_trajectory_ = 10;
-  unsigned long long seed = 0x5EED;
-  unsigned long long plan_iter = 0;
-  const double* injected_noise_eps = nullptr;          // [(num_trajectory + 1) * P * nu], standard normal (tests)
+  // returns / failures: the candidates i < num_trajectory, then the nominal; injected_noise_eps: [(num_trajectory + 1) * P * nu]
 
  private:
   MjpcHipEngine* engine_ = nullptr;
-  Numerics numerics_;
-  int nq_ = 0, nv_ = 0, na_ = 0, ns_ = 0, nu_ = 0, nmocap_ = 0, nuserdata_ = 0, nr_ = 0, ntrace_ = 0;
-  double timestep_ = 0;
-  std::vector<double> ctrlrange_, knot_values_, noise_std_, all_knots_;
+  std::vector<double> knot_values_, noise_std_, all_knots_;
   int last_horizon_ = 0;
-  mutable std::shared_mutex mtx_;
 };
 
 // mjpc/planners/robust/robust_planner.{h,cc}: the delegate ranks its candidates; the best `ncandidates_` are rolled out
 // `nrepetitions_` times each with Ornstein-Uhlenbeck force noise on every body (Trajectory::NoisyRollout) in ONE launch of a
 // second engine (explicit candidate policies); the candidate with the best mean return over the delegate's own score and
-// its valid noisy rollouts is adopted.
+// its valid noisy rollouts is adopted.  The planner's state is the delegate's.
 class RobustPlanner {
  public:
   RobustPlanner() = default;
@@ -234,9 +243,9 @@ class RobustPlanner {
   RobustPlanner& operator=(const RobustPlanner&) = delete;
 
   void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
-  void Allocate();
-  void Reset(int horizon, const double* initial_repeated_action = nullptr);
-  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void Allocate() { delegate.Allocate(); }
+  void Reset(int horizon, const double* initial_repeated_action = nullptr) { delegate.Reset(horizon, initial_repeated_action); }
+  void SetState(const double* state, const double* mocap, const double* userdata, double time) { delegate.SetState(state, mocap, userdata, time); }
   void OptimizePolicy(int horizon);
   void NominalTrajectory(int horizon) { delegate.NominalTrajectory(horizon); }
   void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false) { delegate.ActionFromPolicy(action, state, time, use_previous); }
@@ -257,9 +266,8 @@ class RobustPlanner {
  private:
   MjpcHipEngine* engine_ = nullptr;                    // noisy rollouts (the delegate's engine keeps its plan for CopyCandidateToPolicy)
   Numerics numerics_;
-  int nu_ = 0, ns_ = 0, nmocap_ = 0, nuserdata_ = 0;
-  std::vector<double> state_, mocap_, userdata_, cand_knots_;
-  double time_ = 0;
+  int nu_ = 0;
+  std::vector<double> cand_knots_;
 };
 
 // mjpc/planners/sample_gradient/planner.{h,cc}: of the num_trajectory_ candidates of a plan step, candidate 0 is the (resampled)
@@ -287,24 +295,19 @@ class RobustPlanner {
 //  - gradient_previous enters un-resampled (planner.cc:486).
 // Deliberate difference: std::partial_sort is not stable; candidates are ordered by (return, index), lowest index first, as
 // everywhere in this repository (failed candidates all tie at 1e6).  All candidates of a plan share one interpolation.
-class SampleGradientPlanner {
+class SampleGradientPlanner : public PlannerBase {
  public:
   enum WinnerType : int { kNominal = 0, kPerturb, kGradient };
   SampleGradientPlanner() = default;
   ~SampleGradientPlanner();
-  SampleGradientPlanner(const SampleGradientPlanner&) = delete;
-  SampleGradientPlanner& operator=(const SampleGradientPlanner&) = delete;
 
   void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
   void Allocate();
   void Reset(int horizon, const double* initial_repeated_action = nullptr);
-  void SetState(const double* state, const double* mocap, const double* userdata, double time);
   void OptimizePolicy(int horizon);
   void NominalTrajectory(int horizon);                 // rolls resampled_policy out into trajectory[0] (planner.cc:276-287)
-  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
   void ResamplePolicy(SamplingPolicy& policy, int horizon, int num_spline_points);
   const Trajectory* BestTrajectory();                  // trajectory[winner]
-  int NumParameters() { return policy.num_spline_points * nu_; }
   void SetTask(const MjpcHipTask* task);
   // candidate_policy[index] as the reference holds it after OptimizePolicy: the rolled-out knots for index < n_noisy, the
   // freshly built gradient candidate otherwise; returns P, fills times[P] / values[P * nu] when non-null
@@ -313,16 +316,9 @@ class SampleGradientPlanner {
   static void ReturnWeights(const int* order, int num_noisy, double* weights);      // planner.cc:437-449
   static void LogScale(double* values, double max_value, double min_value, int steps);   // utilities.cc:802-808
 
-  SamplingPolicy policy, resampled_policy, previous_policy;
-  std::vector<double> state, mocap, userdata;
-  double time = 0;
+  SamplingPolicy resampled_policy;
   Trajectory trajectory_winner;                        // trajectory[winner]; the other candidates stay on the device
-  std::vector<int> trajectory_order;
-  std::vector<double> returns;                         // trajectory[i].total_return
-  std::vector<int> failures;
   double noise_exploration = 0.1;
-  int interpolation_ = kZeroSpline;
-  int num_trajectory_ = 10;
   int num_gradient_ = 0;
   double gradient_filter_ = 1.0;
   std::vector<double> gradient, gradient_previous;     // [max spline points * nu]
@@ -331,25 +327,17 @@ class SampleGradientPlanner {
   std::vector<double> return_weight_;
   int winner = 0;
   int winner_type_ = kNominal;
-  double improvement = 0;
-  double noise_compute_time = 0, rollouts_compute_time = 0, gradient_candidates_compute_time = 0, policy_update_compute_time = 0;   // microseconds
-  unsigned long long seed = 0x5EED;
-  unsigned long long plan_iter = 0;
-  const double* injected_noise_eps = nullptr;          // [num_trajectory * P * nu], standard normal (tests)
+  double gradient_candidates_compute_time = 0;         // microseconds
 
  private:
   void GradientCandidates(int num_trajectory, int num_gradient, int horizon);
   SamplingPolicy& Candidate(int index);                // candidate_policy[index], materialised from the last plan's knots on demand
   MjpcHipEngine* engine_ = nullptr;
-  Numerics numerics_;
-  int nq_ = 0, nv_ = 0, na_ = 0, ns_ = 0, nu_ = 0, nmocap_ = 0, nuserdata_ = 0, nr_ = 0, ntrace_ = 0;
-  double timestep_ = 0;
-  std::vector<double> ctrlrange_, knot_times_, knot_values_, noise_std_, cand_table_, all_knots_, scale_;
+  std::vector<double> knot_times_, knot_values_, noise_std_, cand_table_, all_knots_, scale_;
   std::vector<SamplingPolicy> candidate_policy_;       // explicit (gradient) candidates; noisy ones live in all_knots_
   std::vector<char> candidate_valid_;                  // candidate_policy_[i] is current (else: row i of all_knots_ / empty)
   int last_horizon_ = 0, last_N_ = 0, last_P_ = 0, last_interp_ = kZeroSpline;
   TimeSpline plan_scratch_;
-  mutable std::shared_mutex mtx_;
 };
 
 }  // namespace mjpc_hip

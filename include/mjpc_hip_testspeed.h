@@ -91,9 +91,14 @@ struct PlannerOps {                               // the four Planner calls the 
   std::function<void(double* action, double time)> ActionFromPolicy;
   std::function<void(const MjpcHipTask*)> SetTask;
 };
-PlannerOps Ops(SamplingPlanner& p);
-PlannerOps Ops(CrossEntropyPlanner& p);
-PlannerOps Ops(SampleGradientPlanner& p);
+template <class P> PlannerOps Ops(P& p) {         // any planner of include/mjpc_hip_planner.h
+  PlannerOps o;
+  o.SetState = [&p](const SimState& s) { p.SetState(s.state.data(), s.mocap.data(), s.userdata.data(), s.time); };
+  o.OptimizePolicy = [&p](int h) { p.OptimizePolicy(h); };
+  o.ActionFromPolicy = [&p](double* a, double t) { p.ActionFromPolicy(a, nullptr, t, false); };
+  o.SetTask = [&p](const MjpcHipTask* t) { p.SetTask(t); };
+  return o;
+}
 
 struct TestspeedResult {
   int total_steps = 0, plan_steps = 0;

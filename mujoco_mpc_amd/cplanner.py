@@ -171,13 +171,83 @@ class Trajectory:
     pass
 
 
-class SamplingPlanner:
-    """mjpc_hip::SamplingPlanner (C++) driven from Python; method names follow planners/sampling/planner.h:51-112."""
+class _Planner:
+    """What the four ctypes views share: the handle and the calls that differ only in the C symbol prefix."""
+    _prefix = ""
 
     def __init__(self):
         self._L = lib()
         self._h = None
         self._noise = None
+
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
+
+    def Allocate(self):        # done inside the C create call (Initialize + Allocate)
+        pass
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def Reset(self, horizon=0, initial_repeated_action=None):
+        a = None if initial_repeated_action is None else np.ascontiguousarray(initial_repeated_action, dtype=np.float64)
+        self._fn("reset")(self._h, int(horizon or 0), _dp(a)); _check()
+
+    def SetState(self, state, mocap=None, userdata=None, time=0.0):
+        s = np.ascontiguousarray(state, dtype=np.float64)
+        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
+        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
+        self._fn("set_state")(self._h, _dp(s), _dp(m), _dp(u), float(time))
+
+    def SetTask(self, task: dict):
+        t = self.cm.make_task(task)
+        self._fn("set_task")(self._h, C.byref(t)); _check()
+
+    def set_seed(self, seed, plan_iter=0): self._fn("set_seed")(self._h, int(seed), int(plan_iter))
+    def OptimizePolicy(self, horizon): self._fn("optimize_policy")(self._h, int(horizon)); _check()
+    def NominalTrajectory(self, horizon): self._fn("nominal_trajectory")(self._h, int(horizon)); _check()
+
+    def ActionFromPolicy(self, time, use_previous=False):
+        a = np.zeros(self.nu)
+        self._fn("action_from_policy")(self._h, _dp(a), float(time), int(bool(use_previous))); _check()
+        return a
+
+    @property
+    def improvement(self): return self._fn("improvement")(self._h)
+
+    def returns(self, n):
+        out = np.zeros(int(n)); self._fn("returns")(self._h, _dp(out), int(n)); return out
+
+    def _knots(self, name, *lead):
+        """a `<prefix><name>(handle, *lead, times, values)` call that returns P: asked once for P, once for the arrays"""
+        f = self._fn(name)
+        P = f(self._h, *lead, None, None)
+        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
+        f(self._h, *lead, _dp(t), _dp(v))
+        return t[:P], v[:P]
+
+    def policy_knots(self): return self._knots("policy")
+
+    def BestTrajectory(self):
+        Hm = self.max_horizon
+        st = np.zeros((Hm, self.ns)); ac = np.zeros((Hm, self.nu)); co = np.zeros(Hm); tot = C.c_double()
+        H = self._fn("best_trajectory")(self._h, _dp(st), _dp(ac), _dp(co), C.byref(tot))
+        t = Trajectory()
+        t.horizon = H; t.states = st.ravel()[:H * self.ns].reshape(H, self.ns); t.actions = ac.ravel()[:H * self.nu].reshape(H, self.nu)
+        t.costs = co[:H]; t.total_return = tot.value
+        return t
+
+
+class SamplingPlanner(_Planner):
+    """mjpc_hip::SamplingPlanner (C++) driven from Python; method names follow planners/sampling/planner.h:51-112."""
+    _prefix = "mjpc_planner_"
 
     def Initialize(self, model: dict, task: dict, numerics: dict | None = None, max_samples=128, max_horizon=512, device=0, devices=None):
         """devices: list of HIP ordinals to shard every plan step's candidate batch over (one engine each); None = `device` only."""
@@ -202,34 +272,6 @@ class SamplingPlanner:
         self._h = C.c_void_p(h)
         _check()
 
-    def Allocate(self):        # done inside mjpc_planner_create (Initialize + Allocate)
-        pass
-
-    def close(self):
-        if self._h:
-            self._L.mjpc_planner_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def Reset(self, horizon=0, initial_repeated_action=None):
-        a = None if initial_repeated_action is None else np.ascontiguousarray(initial_repeated_action, dtype=np.float64)
-        self._L.mjpc_planner_reset(self._h, int(horizon or 0), _dp(a))
-
-    def SetState(self, state, mocap=None, userdata=None, time=0.0):
-        s = np.ascontiguousarray(state, dtype=np.float64)
-        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
-        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
-        self._L.mjpc_planner_set_state(self._h, _dp(s), _dp(m), _dp(u), float(time))
-
-    def SetTask(self, task: dict):
-        t = self.cm.make_task(task)
-        self._L.mjpc_planner_set_task(self._h, C.byref(t)); _check()
-
-    def set_seed(self, seed, plan_iter=0): self._L.mjpc_planner_set_seed(self._h, int(seed), int(plan_iter))
     def set_num_trajectory(self, n): self._L.mjpc_planner_set_num_trajectory(self._h, int(n))
 
     def set_noise(self, eps, sel):
@@ -240,9 +282,6 @@ class SamplingPlanner:
         e = np.ascontiguousarray(eps, dtype=np.float64); s = np.ascontiguousarray(sel, dtype=np.int32)
         self._noise = (e, s)
         self._L.mjpc_planner_set_noise(self._h, _dp(e), s.ctypes.data_as(c_int_p))
-
-    def OptimizePolicy(self, horizon): self._L.mjpc_planner_optimize_policy(self._h, int(horizon)); _check()
-    def NominalTrajectory(self, horizon): self._L.mjpc_planner_nominal_trajectory(self._h, int(horizon)); _check()
 
     def OptimizePolicyCandidates(self, ncandidates, horizon):
         n = self._L.mjpc_planner_optimize_policy_candidates(self._h, int(ncandidates), int(horizon)); _check()
@@ -256,32 +295,17 @@ class SamplingPlanner:
         self._L.mjpc_planner_action_from_candidate_policy(self._h, _dp(a), int(candidate), float(time)); _check()
         return a
 
-    def ActionFromPolicy(self, time, use_previous=False):
-        a = np.zeros(self.nu)
-        self._L.mjpc_planner_action_from_policy(self._h, _dp(a), float(time), int(bool(use_previous))); _check()
-        return a
-
     @property
     def winner(self): return self._L.mjpc_planner_winner(self._h)
-    @property
-    def improvement(self): return self._L.mjpc_planner_improvement(self._h)
     def NumParameters(self): return self._L.mjpc_planner_num_parameters(self._h)
-
-    def returns(self, n):
-        out = np.zeros(int(n)); self._L.mjpc_planner_returns(self._h, _dp(out), int(n)); return out
-
-    def policy_knots(self, previous=False):
-        P = self._L.mjpc_planner_policy(self._h, int(previous), None, None)
-        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
-        self._L.mjpc_planner_policy(self._h, int(previous), _dp(t), _dp(v))
-        return t[:P], v[:P]
+    def policy_knots(self, previous=False): return self._knots("policy", int(previous))
 
     def timings(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self._L.mjpc_planner_timings(self._h, C.byref(a), C.byref(b), C.byref(c))
         return dict(noise_us=a.value, rollouts_us=b.value, policy_update_us=c.value)
 
-    def BestTrajectory(self):
+    def BestTrajectory(self):      # the long form: times, residual, trace and the failure flag as well; None before the first rollout
         Hm = self.max_horizon
         st = np.zeros((Hm, self.ns)); ac = np.zeros((Hm, self.nu)); ti = np.zeros(Hm); re = np.zeros((Hm, max(self.nr, 1)))
         co = np.zeros(Hm); tr = np.zeros((Hm, 3 * max(self.ntrace, 1))); tot = C.c_double(); fail = C.c_int()
@@ -296,13 +320,9 @@ class SamplingPlanner:
         return t
 
 
-class CrossEntropyPlanner:
+class CrossEntropyPlanner(_Planner):
     """mjpc_hip::CrossEntropyPlanner (C++) driven from Python; names follow planners/cross_entropy/planner.h:32-147."""
-
-    def __init__(self):
-        self._L = lib()
-        self._h = None
-        self._noise = None
+    _prefix = "mjpc_cem_"
 
     def Initialize(self, model: dict, task: dict, numerics: dict | None = None, max_samples=128, max_horizon=512, device=0):
         numerics = numerics or {}
@@ -318,76 +338,18 @@ class CrossEntropyPlanner:
         self._h = C.c_void_p(h)
         _check()
 
-    def Allocate(self):
-        pass
-
-    def close(self):
-        if self._h:
-            self._L.mjpc_cem_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def Reset(self, horizon=0, initial_repeated_action=None):
-        a = None if initial_repeated_action is None else np.ascontiguousarray(initial_repeated_action, dtype=np.float64)
-        self._L.mjpc_cem_reset(self._h, int(horizon or 0), _dp(a))
-
-    def SetState(self, state, mocap=None, userdata=None, time=0.0):
-        s = np.ascontiguousarray(state, dtype=np.float64)
-        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
-        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
-        self._L.mjpc_cem_set_state(self._h, _dp(s), _dp(m), _dp(u), float(time))
-
-    def set_seed(self, seed, plan_iter=0): self._L.mjpc_cem_set_seed(self._h, int(seed), int(plan_iter))
-
     def set_noise(self, eps):
         self._noise = None if eps is None else np.ascontiguousarray(eps, dtype=np.float64)
         self._L.mjpc_cem_set_noise(self._h, _dp(self._noise))
 
-    def OptimizePolicy(self, horizon): self._L.mjpc_cem_optimize_policy(self._h, int(horizon)); _check()
-    def NominalTrajectory(self, horizon): self._L.mjpc_cem_nominal_trajectory(self._h, int(horizon)); _check()
-
-    def ActionFromPolicy(self, time, use_previous=False):
-        a = np.zeros(self.nu)
-        self._L.mjpc_cem_action_from_policy(self._h, _dp(a), float(time), int(bool(use_previous))); _check()
-        return a
-
-    @property
-    def improvement(self): return self._L.mjpc_cem_improvement(self._h)
-
-    def returns(self, n):
-        out = np.zeros(int(n)); self._L.mjpc_cem_returns(self._h, _dp(out), int(n)); return out
-
     def variance(self):
         out = np.zeros(self.P * self.nu); self._L.mjpc_cem_variance(self._h, _dp(out), out.size); return out
 
-    def policy_knots(self):
-        P = self._L.mjpc_cem_policy(self._h, None, None)
-        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
-        self._L.mjpc_cem_policy(self._h, _dp(t), _dp(v))
-        return t[:P], v[:P]
 
-    def BestTrajectory(self):
-        Hm = self.max_horizon
-        st = np.zeros((Hm, self.ns)); ac = np.zeros((Hm, self.nu)); co = np.zeros(Hm); tot = C.c_double()
-        H = self._L.mjpc_cem_best_trajectory(self._h, _dp(st), _dp(ac), _dp(co), C.byref(tot))
-        t = Trajectory()
-        t.horizon = H; t.states = st.ravel()[:H * self.ns].reshape(H, self.ns); t.actions = ac.ravel()[:H * self.nu].reshape(H, self.nu)
-        t.costs = co[:H]; t.total_return = tot.value
-        return t
-
-
-class SampleGradientPlanner:
+class SampleGradientPlanner(_Planner):
     """mjpc_hip::SampleGradientPlanner (C++) driven from Python; names follow planners/sample_gradient/planner.h:35-175."""
+    _prefix = "mjpc_sg_"
     kNominal, kPerturb, kGradient = 0, 1, 2
-
-    def __init__(self):
-        self._L = lib()
-        self._h = None
-        self._noise = None
 
     def Initialize(self, model: dict, task: dict, numerics: dict | None = None, max_samples=128, max_horizon=512, device=0):
         numerics = numerics or {}
@@ -403,50 +365,12 @@ class SampleGradientPlanner:
         self._h = C.c_void_p(h)
         _check()
 
-    def Allocate(self):
-        pass
-
-    def close(self):
-        if self._h:
-            self._L.mjpc_sg_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def Reset(self, horizon=0, initial_repeated_action=None):
-        a = None if initial_repeated_action is None else np.ascontiguousarray(initial_repeated_action, dtype=np.float64)
-        self._L.mjpc_sg_reset(self._h, int(horizon or 0), _dp(a)); _check()
-
-    def SetState(self, state, mocap=None, userdata=None, time=0.0):
-        s = np.ascontiguousarray(state, dtype=np.float64)
-        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
-        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
-        self._L.mjpc_sg_set_state(self._h, _dp(s), _dp(m), _dp(u), float(time))
-
-    def SetTask(self, task: dict):
-        t = self.cm.make_task(task)
-        self._L.mjpc_sg_set_task(self._h, C.byref(t)); _check()
-
-    def set_seed(self, seed, plan_iter=0): self._L.mjpc_sg_set_seed(self._h, int(seed), int(plan_iter))
     def set_counts(self, trajectories, gradient_trajectories): self._L.mjpc_sg_set_counts(self._h, int(trajectories), int(gradient_trajectories))
 
     def set_noise(self, eps):
         self._noise = None if eps is None else np.ascontiguousarray(eps, dtype=np.float64)
         self._L.mjpc_sg_set_noise(self._h, _dp(self._noise))
 
-    def OptimizePolicy(self, horizon): self._L.mjpc_sg_optimize_policy(self._h, int(horizon)); _check()
-    def NominalTrajectory(self, horizon): self._L.mjpc_sg_nominal_trajectory(self._h, int(horizon)); _check()
-
-    def ActionFromPolicy(self, time, use_previous=False):
-        a = np.zeros(self.nu)
-        self._L.mjpc_sg_action_from_policy(self._h, _dp(a), float(time), int(bool(use_previous))); _check()
-        return a
-
-    @property
-    def improvement(self): return self._L.mjpc_sg_improvement(self._h)
     @property
     def winner(self): return self._L.mjpc_sg_winner(self._h)
     @property
@@ -454,9 +378,6 @@ class SampleGradientPlanner:
     @property
     def num_gradient_(self): return self._L.mjpc_sg_num_gradient(self._h)
     def NumParameters(self): return self._L.mjpc_sg_num_parameters(self._h)
-
-    def returns(self, n):
-        out = np.zeros(int(n)); self._L.mjpc_sg_returns(self._h, _dp(out), int(n)); return out
 
     def trajectory_order(self, n):
         out = np.zeros(int(n), np.int32); self._L.mjpc_sg_trajectory_order(self._h, out.ctypes.data_as(c_int_p), int(n)); return out
@@ -470,31 +391,12 @@ class SampleGradientPlanner:
     def step_size(self):
         out = np.zeros(max(self._L.mjpc_sg_step_size(self._h, None), 1)); n = self._L.mjpc_sg_step_size(self._h, _dp(out)); return out[:n]
 
-    def policy_knots(self):
-        P = self._L.mjpc_sg_policy(self._h, None, None)
-        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
-        self._L.mjpc_sg_policy(self._h, _dp(t), _dp(v))
-        return t[:P], v[:P]
-
-    def candidate_policy(self, index):
-        P = self._L.mjpc_sg_candidate_policy(self._h, int(index), None, None)
-        t = np.zeros(max(P, 1)); v = np.zeros((max(P, 1), self.nu))
-        self._L.mjpc_sg_candidate_policy(self._h, int(index), _dp(t), _dp(v))
-        return t[:P], v[:P]
+    def candidate_policy(self, index): return self._knots("candidate_policy", int(index))
 
     def timings(self):
         a, b, c, g = C.c_double(), C.c_double(), C.c_double(), C.c_double()
         self._L.mjpc_sg_timings(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(g))
         return dict(noise_us=a.value, rollouts_us=b.value, policy_update_us=c.value, gradient_candidates_us=g.value)
-
-    def BestTrajectory(self):
-        Hm = self.max_horizon
-        st = np.zeros((Hm, self.ns)); ac = np.zeros((Hm, self.nu)); co = np.zeros(Hm); tot = C.c_double()
-        H = self._L.mjpc_sg_best_trajectory(self._h, _dp(st), _dp(ac), _dp(co), C.byref(tot))
-        t = Trajectory()
-        t.horizon = H; t.states = st.ravel()[:H * self.ns].reshape(H, self.ns); t.actions = ac.ravel()[:H * self.nu].reshape(H, self.nu)
-        t.costs = co[:H]; t.total_return = tot.value
-        return t
 
 
 def sample_gradient_return_weights(order):
@@ -529,12 +431,9 @@ def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_pla
                 plan_steps=int(out[4]), failure=bool(out[5]), cost_per_step=costs, state=st, mocap=mc, parameters=params)
 
 
-class RobustPlanner:
+class RobustPlanner(_Planner):
     """mjpc_hip::RobustPlanner (C++) driven from Python; mirrors planners/robust/robust_planner.h:31-80 over a SamplingPlanner."""
-
-    def __init__(self):
-        self._L = lib()
-        self._h = None
+    _prefix = "mjpc_robust_"
 
     def Initialize(self, model: dict, task: dict, numerics: dict | None = None, max_samples=128, max_horizon=512, device=0):
         numerics = numerics or {}
@@ -559,28 +458,10 @@ class RobustPlanner:
         self.delegate.max_samples = int(max_samples); self.delegate.max_horizon = int(max_horizon)
         self.delegate.close = lambda: None
 
-    def close(self):
-        if self._h:
-            self._L.mjpc_robust_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def Reset(self, horizon=0): self._L.mjpc_robust_reset(self._h, int(horizon or 0))
-
-    def SetState(self, state, mocap=None, userdata=None, time=0.0):
-        s = np.ascontiguousarray(state, dtype=np.float64)
-        m = None if mocap is None else np.ascontiguousarray(mocap, dtype=np.float64)
-        u = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64)
-        self._L.mjpc_robust_set_state(self._h, _dp(s), _dp(m), _dp(u), float(time))
 
     def set_seed(self, delegate_seed, robust_seed, plan_iter=0):
         self._L.mjpc_robust_set_seed(self._h, int(delegate_seed), int(robust_seed), int(plan_iter))
-
-    def OptimizePolicy(self, horizon): self._L.mjpc_robust_optimize_policy(self._h, int(horizon)); _check()
 
     def ActionFromPolicy(self, time):
         a = np.zeros(self.nu)

@@ -128,15 +128,19 @@ void SamplingPolicy::Action(double* action, const double*, double time) const {
 void SamplingPolicy::CopyFrom(const SamplingPolicy& p, int) {
   plan = p.plan; num_spline_points = p.num_spline_points; nu = p.nu; ctrlrange = p.ctrlrange;
 }
-
-// ------------------------------------------------------------------ SamplingPlanner
-static double Micros(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+// the policy's knots for the flat C view: returns P; fills times[P] and values[P * nu] when non-null
+static int CopyKnots(const SamplingPolicy& policy, double* times, double* values) {
+  int P = (int)policy.plan.Size();
+  for (int i = 0; i < P; i++) {
+    if (times) times[i] = policy.plan.NodeTime(i);
+    if (values) std::copy(policy.plan.NodeValues(i), policy.plan.NodeValues(i) + policy.nu, values + (size_t)i * policy.nu);
+  }
+  return P;
 }
 
-SamplingPlanner::~SamplingPlanner() {
-  if (engine_) mjpc_hip_multi_destroy(engine_);
-  if (nominal_engine_) mjpc_hip_destroy(nominal_engine_);
+// ------------------------------------------------------------------ PlannerBase
+static double Micros(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // returns sorted ascending with every non-finite value treated as +inf: a strict weak order even when a rollout produced NaN
@@ -148,21 +152,120 @@ static inline bool ReturnLess(double a, double b) {
   return a < b;
 }
 
-void SamplingPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
+// candidates 0 .. num_trajectory-1 of one plan on one engine; everything else (noise, explicit candidates, seed, stream) is zero
+static MjpcHipPlanInput MakePlanInput(const double* state, const double* mocap, const double* userdata, double time,
+                                      const double* knot_times, const double* knot_values, int num_spline_points, int interpolation,
+                                      int num_trajectory, int horizon) {
+  MjpcHipPlanInput in;
+  std::memset(&in, 0, sizeof(in));
+  in.state = state; in.mocap = mocap; in.userdata = userdata; in.time = time;
+  in.knot_times = knot_times; in.knot_values = knot_values; in.num_spline_points = num_spline_points;
+  in.interpolation = interpolation; in.num_trajectory = num_trajectory; in.horizon = horizon;
+  in.candidate_offset = 0; in.num_local = num_trajectory;
+  return in;
+}
+
+bool PlannerBase::InitializeCommon(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
   numerics_ = numerics;
   nq_ = model->nq; nv_ = model->nv; na_ = model->na; ns_ = nq_ + nv_ + na_; nu_ = model->nu; nmocap_ = model->nmocap; nuserdata_ = model->nuserdata;
   nr_ = task->num_residual; ntrace_ = task->num_trace; timestep_ = model->timestep;
   ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
-  noise_exploration[0] = numerics.sampling_exploration[0];
-  noise_exploration[1] = numerics.sampling_exploration[1];
   num_trajectory_ = numerics.sampling_trajectories;
   interpolation_ = numerics.sampling_representation;
-  sliding_plan_ = numerics.sampling_sliding_plan;
   if (num_trajectory_ > numerics.max_samples) {
     char msg[128]; std::snprintf(msg, sizeof(msg), "Too many trajectories, %d is the maximum allowed.", numerics.max_samples);
     Fatal(msg);
-    return;
+    return false;
   }
+  return true;
+}
+
+void PlannerBase::AllocateState() { state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0); }
+
+void PlannerBase::ResetState(int horizon, const double* initial_repeated_action) {
+  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0);
+  std::fill(userdata.begin(), userdata.end(), 0.0);
+  time = 0.0;
+  policy.Reset(horizon, initial_repeated_action);
+  previous_policy.Reset(horizon, initial_repeated_action);
+}
+
+void PlannerBase::SetState(const double* s, const double* m, const double* u, double t) {
+  std::copy(s, s + ns_, state.begin());
+  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
+  if (u) std::copy(u, u + nuserdata_, userdata.begin());
+  time = t;
+}
+
+void PlannerBase::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {   // planner.cc:225-233
+  const std::shared_lock<std::shared_mutex> lock(mtx_);
+  if (use_previous) previous_policy.Action(action, s, t);
+  else policy.Action(action, s, t);
+}
+
+void PlannerBase::SizeTrajectory(Trajectory& tr) const {
+  size_t Hm = (size_t)numerics_.max_horizon;
+  tr.dim_state = ns_; tr.dim_action = nu_; tr.dim_residual = nr_; tr.dim_trace = 3 * ntrace_;
+  tr.states.assign(Hm * ns_, 0.0); tr.actions.assign(Hm * nu_, 0.0);
+  tr.times.assign(Hm, 0.0); tr.residual.assign(Hm * nr_, 0.0);
+  tr.costs.assign(Hm, 0.0); tr.trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+}
+
+int PlannerBase::KnotArrays(const TimeSpline& plan, std::vector<double>& times, std::vector<double>& values) const {
+  int P = (int)plan.Size();
+  times.resize(std::max(P, 1)); values.resize((size_t)std::max(P, 1) * nu_);
+  for (int p = 0; p < P; p++) {
+    times[p] = plan.NodeTime(p);
+    std::copy(plan.NodeValues(p), plan.NodeValues(p) + nu_, values.begin() + (size_t)p * nu_);
+  }
+  if (P == 0) { P = 1; times[0] = time; std::fill(values.begin(), values.end(), 0.0); }   // empty plan samples zeros
+  return P;
+}
+
+MjpcHipPlanInput PlannerBase::PlanInput(const double* knot_times, const double* knot_values, int num_spline_points, int interpolation,
+                                        int num_trajectory, int horizon) const {
+  return MakePlanInput(state.data(), mocap.data(), userdata.data(), time, knot_times, knot_values, num_spline_points, interpolation,
+                       num_trajectory, horizon);
+}
+
+MjpcHipPlanOutput PlannerBase::TrajectoryOutput(Trajectory& tr) {
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.states = tr.states.data(); out.actions = tr.actions.data(); out.times = tr.times.data();
+  out.residual = tr.residual.data(); out.costs = tr.costs.data(); out.trace = tr.trace.data();
+  return out;
+}
+
+void PlannerBase::OrderCandidates(int n) {   // ties: lowest index, like the engine's argmin
+  if ((int)trajectory_order.size() < n) trajectory_order.resize(n);
+  std::iota(trajectory_order.begin(), trajectory_order.begin() + n, 0);
+  std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + n, [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+}
+
+bool PlannerBase::RolloutNominal(MjpcHipEngine* engine, const TimeSpline& plan, int horizon, Trajectory& tr, int* failure) {
+  std::vector<double> kt, kv;
+  int P = KnotArrays(plan, kt, kv);
+  MjpcHipPlanInput in = PlanInput(kt.data(), kv.data(), P, (int)plan.Interpolation(), 1, horizon);
+  double ret = 0; int fail = 0;
+  MjpcHipPlanOutput out = TrajectoryOutput(tr);
+  out.returns = &ret; out.failure = &fail;
+  if (mjpc_hip_plan(engine, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return false; }
+  tr.horizon = horizon; tr.total_return = ret; tr.failure = fail != 0;
+  if (failure) *failure = fail;
+  return true;
+}
+
+// ------------------------------------------------------------------ SamplingPlanner
+SamplingPlanner::~SamplingPlanner() {
+  if (engine_) mjpc_hip_multi_destroy(engine_);
+  if (nominal_engine_) mjpc_hip_destroy(nominal_engine_);
+}
+
+void SamplingPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
+  noise_exploration[0] = numerics.sampling_exploration[0];
+  noise_exploration[1] = numerics.sampling_exploration[1];
+  sliding_plan_ = numerics.sampling_sliding_plan;
+  if (!InitializeCommon(model, task, numerics)) return;
   if (engine_) { mjpc_hip_multi_destroy(engine_); engine_ = nullptr; }     // the model might have changed
   // one engine per GPU (Numerics::n_devices, ordinals in Numerics::devices or device, device+1, ...): the candidate batch of a
   // plan step is block-partitioned over them (include/mjpc_hip.h, mjpc_hip_multi_plan)
@@ -185,38 +288,20 @@ void SamplingPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* t
 }
 
 void SamplingPlanner::Allocate() {
-  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  AllocateState();
   plan_scratch_ = TimeSpline(nu_);
-  trajectory_winner.dim_state = ns_; trajectory_winner.dim_action = nu_;
-  trajectory_winner.dim_residual = nr_; trajectory_winner.dim_trace = 3 * ntrace_;
-  trajectory_winner.states.assign((size_t)numerics_.max_horizon * ns_, 0.0);
-  trajectory_winner.actions.assign((size_t)numerics_.max_horizon * nu_, 0.0);
-  trajectory_winner.times.assign(numerics_.max_horizon, 0.0);
-  trajectory_winner.residual.assign((size_t)numerics_.max_horizon * nr_, 0.0);
-  trajectory_winner.costs.assign(numerics_.max_horizon, 0.0);
-  trajectory_winner.trace.assign((size_t)numerics_.max_horizon * 3 * std::max(ntrace_, 1), 0.0);
+  SizeTrajectory(trajectory_winner);
   returns.assign(numerics_.max_samples, 0.0); failures.assign(numerics_.max_samples, 0);
   winner = -1;
 }
 
 void SamplingPlanner::Reset(int horizon, const double* initial_repeated_action) {
-  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0);
-  std::fill(userdata.begin(), userdata.end(), 0.0);
-  time = 0.0;
-  policy.Reset(horizon, initial_repeated_action);
-  previous_policy.Reset(horizon, initial_repeated_action);
+  ResetState(horizon, initial_repeated_action);
   winner_policy_.Reset(horizon, initial_repeated_action);
   plan_scratch_.Clear();
   improvement = 0.0;
   winner = 0;
   fetched_ = -1;
-}
-
-void SamplingPlanner::SetState(const double* s, const double* m, const double* u, double t) {
-  std::copy(s, s + ns_, state.begin());
-  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
-  if (u) std::copy(u, u + nuserdata_, userdata.begin());
-  time = t;
 }
 
 void SamplingPlanner::SetTask(const MjpcHipTask* task) {
@@ -263,46 +348,27 @@ int SamplingPlanner::OptimizePolicyCandidates(int ncandidates, int horizon) {   
   ncandidates = std::min(ncandidates, num_trajectory);
   auto rollouts_start = std::chrono::steady_clock::now();
   policy.plan.SetInterpolation((SplineInterpolation)interpolation_);
-  int P = (int)policy.plan.Size();
-  knot_times_.resize(std::max(P, 1)); knot_values_.resize((size_t)std::max(P, 1) * nu_);
-  for (int p = 0; p < P; p++) {
-    knot_times_[p] = policy.plan.NodeTime(p);
-    std::copy(policy.plan.NodeValues(p), policy.plan.NodeValues(p) + nu_, knot_values_.begin() + (size_t)p * nu_);
-  }
-  if (P == 0) { P = 1; knot_times_[0] = time; std::fill(knot_values_.begin(), knot_values_.end(), 0.0); }   // empty plan samples zeros
+  int P = KnotArrays(policy.plan, knot_times_, knot_values_);
   winner_knots_.assign((size_t)P * nu_, 0.0);
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = knot_times_.data(); in.knot_values = knot_values_.data(); in.num_spline_points = P;
-  in.interpolation = interpolation_; in.num_trajectory = num_trajectory; in.horizon = horizon;
-  in.candidate_offset = 0; in.num_local = num_trajectory;
+  MjpcHipPlanInput in = PlanInput(knot_times_.data(), knot_values_.data(), P, interpolation_, num_trajectory, horizon);
   in.noise_exploration[0] = noise_exploration[0]; in.noise_exploration[1] = noise_exploration[1];
   in.noise_eps = injected_noise_eps; in.noise_sel = injected_noise_sel; in.seed = seed; in.stream = plan_iter++;
-  MjpcHipPlanOutput out;
-  std::memset(&out, 0, sizeof(out));
-  out.returns = returns.data(); out.failure = failures.data();
-  out.states = trajectory_winner.states.data(); out.actions = trajectory_winner.actions.data();
-  out.times = trajectory_winner.times.data(); out.residual = trajectory_winner.residual.data();
-  out.costs = trajectory_winner.costs.data(); out.trace = trajectory_winner.trace.data(); out.winner_knots = winner_knots_.data();
+  MjpcHipPlanOutput out = TrajectoryOutput(trajectory_winner);
+  out.returns = returns.data(); out.failure = failures.data(); out.winner_knots = winner_knots_.data();
   if (mjpc_hip_multi_plan(engine_, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return 0; }
   last_horizon_ = horizon; fetched_ = out.winner;
   noise_compute_time = out.noise_compute_time_us;
-  // order so that the first ncandidates are the best (ties: lowest index, like the engine's argmin)
+  // order so that the first ncandidates are the best
   trajectory_order.resize(num_trajectory);
-  std::iota(trajectory_order.begin(), trajectory_order.end(), 0);
-  std::stable_sort(trajectory_order.begin(), trajectory_order.end(), [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+  OrderCandidates(num_trajectory);
   rollouts_compute_time = Micros(rollouts_start);
   return ncandidates;
 }
 
 void SamplingPlanner::FetchCandidate(int global_index) {
   if (fetched_ == global_index) return;
-  MjpcHipPlanOutput out;
-  std::memset(&out, 0, sizeof(out));
-  out.states = trajectory_winner.states.data(); out.actions = trajectory_winner.actions.data();
-  out.times = trajectory_winner.times.data(); out.residual = trajectory_winner.residual.data();
-  out.costs = trajectory_winner.costs.data(); out.trace = trajectory_winner.trace.data(); out.winner_knots = winner_knots_.data();
+  MjpcHipPlanOutput out = TrajectoryOutput(trajectory_winner);
+  out.winner_knots = winner_knots_.data();
   if (mjpc_hip_multi_get_candidate(engine_, global_index, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
   fetched_ = global_index;
 }
@@ -336,38 +402,10 @@ void SamplingPlanner::NominalTrajectory(int horizon) {   // planner.cc:211-222: 
   // one un-noised candidate on the dedicated engine: returns / failures / trajectory_order / candidate knots of the last
   // OptimizePolicyCandidates() are not touched (the reference writes nothing but trajectory[0] here either)
   policy.plan.SetInterpolation((SplineInterpolation)interpolation_);
-  int P = (int)policy.plan.Size();
-  std::vector<double> kt(std::max(P, 1)), kv((size_t)std::max(P, 1) * nu_, 0.0);
-  for (int p = 0; p < P; p++) {
-    kt[p] = policy.plan.NodeTime(p);
-    std::copy(policy.plan.NodeValues(p), policy.plan.NodeValues(p) + nu_, kv.begin() + (size_t)p * nu_);
-  }
-  if (P == 0) { P = 1; kt[0] = time; }
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = kt.data(); in.knot_values = kv.data(); in.num_spline_points = P;
-  in.interpolation = interpolation_; in.num_trajectory = 1; in.horizon = horizon; in.candidate_offset = 0; in.num_local = 1;
-  in.noise_exploration[0] = noise_exploration[0]; in.noise_exploration[1] = noise_exploration[1];
-  in.seed = seed; in.stream = plan_iter;
-  double ret = 0; int fail = 0;
-  MjpcHipPlanOutput out;
-  std::memset(&out, 0, sizeof(out));
-  out.returns = &ret; out.failure = &fail;
-  out.states = trajectory_winner.states.data(); out.actions = trajectory_winner.actions.data();
-  out.times = trajectory_winner.times.data(); out.residual = trajectory_winner.residual.data();
-  out.costs = trajectory_winner.costs.data(); out.trace = trajectory_winner.trace.data();
-  if (mjpc_hip_plan(nominal_engine_, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
+  if (!RolloutNominal(nominal_engine_, policy.plan, horizon, trajectory_winner)) return;
   fetched_ = -1;                 // trajectory_winner no longer mirrors a candidate of the last plan: re-fetch on demand
   nominal_horizon_ = horizon;
-  trajectory_winner.horizon = horizon; trajectory_winner.total_return = ret; trajectory_winner.failure = fail != 0;
   if (winner < 0) winner = 0;
-}
-
-void SamplingPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {   // planner.cc:225-233
-  const std::shared_lock<std::shared_mutex> lock(mtx_);
-  if (use_previous) previous_policy.Action(action, s, t);
-  else policy.Action(action, s, t);
 }
 
 const Trajectory* SamplingPlanner::BestTrajectory() { return winner >= 0 ? &trajectory_winner : nullptr; }
@@ -387,20 +425,10 @@ void SamplingPlanner::ActionFromCandidatePolicy(double* action, int candidate, c
 CrossEntropyPlanner::~CrossEntropyPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
 
 void CrossEntropyPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {   // planner.cc:41-72
-  numerics_ = numerics;
-  nq_ = model->nq; nv_ = model->nv; na_ = model->na; ns_ = nq_ + nv_ + na_; nu_ = model->nu; nmocap_ = model->nmocap;
-  nuserdata_ = model->nuserdata; nr_ = task->num_residual; ntrace_ = task->num_trace; timestep_ = model->timestep;
-  ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
   std_initial_ = numerics.sampling_exploration[0];
   std_min_ = numerics.std_min;
-  num_trajectory_ = numerics.sampling_trajectories;
-  n_elite_ = numerics.n_elite > 0 ? numerics.n_elite : std::max(num_trajectory_ / 10, 2);
-  interpolation_ = numerics.sampling_representation;
-  if (num_trajectory_ > numerics.max_samples) {
-    char msg[128]; std::snprintf(msg, sizeof(msg), "Too many trajectories, %d is the maximum allowed.", numerics.max_samples);
-    Fatal(msg);
-    return;
-  }
+  n_elite_ = numerics.n_elite > 0 ? numerics.n_elite : std::max(numerics.sampling_trajectories / 10, 2);
+  if (!InitializeCommon(model, task, numerics)) return;
   if (engine_) { mjpc_hip_destroy(engine_); engine_ = nullptr; }
   engine_ = mjpc_hip_create(model, task, numerics.max_samples + 1, numerics.max_horizon, numerics.device);   // + the nominal rollout
   if (!engine_) { Fatal(mjpc_hip_last_error()); return; }
@@ -410,40 +438,24 @@ void CrossEntropyPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTas
 }
 
 void CrossEntropyPlanner::Allocate() {   // planner.cc:75-117
-  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  AllocateState();
   int P = policy.num_spline_points;
   parameters_scratch.assign((size_t)P * nu_, 0.0); times_scratch.assign(P, 0.0);
   variance.assign((size_t)P * nu_, 0.0); noise_std_.assign((size_t)P * nu_, 0.0); knot_values_.assign((size_t)P * nu_, 0.0);
   trajectory_order.resize(numerics_.max_samples);
   std::iota(trajectory_order.begin(), trajectory_order.end(), 0);
   returns.assign(numerics_.max_samples + 1, 0.0); failures.assign(numerics_.max_samples + 1, 0);
-  size_t Hm = (size_t)numerics_.max_horizon;
-  nominal_trajectory.dim_state = ns_; nominal_trajectory.dim_action = nu_; nominal_trajectory.dim_residual = nr_;
-  nominal_trajectory.dim_trace = 3 * ntrace_;
-  nominal_trajectory.states.assign(Hm * ns_, 0.0); nominal_trajectory.actions.assign(Hm * nu_, 0.0);
-  nominal_trajectory.times.assign(Hm, 0.0); nominal_trajectory.residual.assign(Hm * nr_, 0.0);
-  nominal_trajectory.costs.assign(Hm, 0.0); nominal_trajectory.trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+  SizeTrajectory(nominal_trajectory);
 }
 
 void CrossEntropyPlanner::Reset(int horizon, const double* initial_repeated_action) {   // planner.cc:120-155
-  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0);
-  std::fill(userdata.begin(), userdata.end(), 0.0);
-  time = 0.0;
-  policy.Reset(horizon, initial_repeated_action);
+  ResetState(horizon, initial_repeated_action);
   resampled_policy.Reset(horizon, initial_repeated_action);
-  previous_policy.Reset(horizon, initial_repeated_action);
   std::fill(parameters_scratch.begin(), parameters_scratch.end(), 0.0);
   std::fill(times_scratch.begin(), times_scratch.end(), 0.0);
   double var = std_initial_ * std_initial_;
   std::fill(variance.begin(), variance.end(), var);
   improvement = 0.0;
-}
-
-void CrossEntropyPlanner::SetState(const double* s, const double* m, const double* u, double t) {
-  std::copy(s, s + ns_, state.begin());
-  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
-  if (u) std::copy(u, u + nuserdata_, userdata.begin());
-  time = t;
 }
 
 void CrossEntropyPlanner::SetTask(const MjpcHipTask* task) {
@@ -481,12 +493,8 @@ void CrossEntropyPlanner::OptimizePolicy(int horizon) {   // planner.cc:164-283
   int P = resampled_policy.num_spline_points;
   for (int t = 0; t < P; t++) std::copy(resampled_policy.plan.NodeValues(t), resampled_policy.plan.NodeValues(t) + nu_, knot_values_.begin() + (size_t)t * nu_);
   for (int k = 0; k < P * nu_; k++) noise_std_[k] = std::max(std::sqrt(variance[k]), std_min_);   // AddNoiseToPolicy, planner.cc:359-362
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = times_scratch.data(); in.knot_values = knot_values_.data(); in.num_spline_points = P;
-  in.interpolation = (int)resampled_policy.plan.Interpolation();
-  in.num_trajectory = num_trajectory + 1; in.horizon = horizon; in.candidate_offset = 0; in.num_local = num_trajectory + 1;
+  MjpcHipPlanInput in = PlanInput(times_scratch.data(), knot_values_.data(), P, (int)resampled_policy.plan.Interpolation(),
+                                  num_trajectory + 1, horizon);
   in.noise_eps = injected_noise_eps; in.seed = seed; in.stream = plan_iter++;
   in.noise_std = noise_std_.data(); in.nominal_index = num_trajectory;
   MjpcHipPlanOutput out;
@@ -496,19 +504,13 @@ void CrossEntropyPlanner::OptimizePolicy(int horizon) {   // planner.cc:164-283
   noise_compute_time = out.noise_compute_time_us;
   last_horizon_ = horizon;
   // nominal trajectory = candidate N
-  MjpcHipPlanOutput nom;
-  std::memset(&nom, 0, sizeof(nom));
-  nom.states = nominal_trajectory.states.data(); nom.actions = nominal_trajectory.actions.data(); nom.times = nominal_trajectory.times.data();
-  nom.residual = nominal_trajectory.residual.data(); nom.costs = nominal_trajectory.costs.data(); nom.trace = nominal_trajectory.trace.data();
+  MjpcHipPlanOutput nom = TrajectoryOutput(nominal_trajectory);
   if (mjpc_hip_get_candidate(engine_, num_trajectory, &nom) != 0) { Fatal(mjpc_hip_last_error()); return; }
   nominal_trajectory.horizon = horizon; nominal_trajectory.total_return = returns[num_trajectory];
   nominal_trajectory.failure = failures[num_trajectory] != 0;
   all_knots_.resize((size_t)(num_trajectory + 1) * P * nu_);
   if (mjpc_hip_get_knots(engine_, all_knots_.data()) != 0) { Fatal(mjpc_hip_last_error()); return; }
-  trajectory_order.resize(std::max((int)trajectory_order.size(), num_trajectory));
-  for (int i = 0; i < num_trajectory; i++) trajectory_order[i] = i;
-  std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + num_trajectory,
-                   [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+  OrderCandidates(num_trajectory);
   rollouts_compute_time = Micros(rollouts_start);
 
   // ----- update policy (planner.cc:205-283)
@@ -546,31 +548,7 @@ void CrossEntropyPlanner::OptimizePolicy(int horizon) {   // planner.cc:164-283
 }
 
 void CrossEntropyPlanner::NominalTrajectory(int horizon) {   // planner.cc:286-297: rollout of resampled_policy
-  int P = (int)resampled_policy.plan.Size();
-  std::vector<double> kt(std::max(P, 1), time), kv((size_t)std::max(P, 1) * nu_, 0.0);
-  for (int p = 0; p < P; p++) {
-    kt[p] = resampled_policy.plan.NodeTime(p);
-    std::copy(resampled_policy.plan.NodeValues(p), resampled_policy.plan.NodeValues(p) + nu_, kv.begin() + (size_t)p * nu_);
-  }
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = kt.data(); in.knot_values = kv.data(); in.num_spline_points = std::max(P, 1);
-  in.interpolation = (int)resampled_policy.plan.Interpolation(); in.num_trajectory = 1; in.horizon = horizon; in.num_local = 1;
-  MjpcHipPlanOutput out;
-  std::memset(&out, 0, sizeof(out));
-  double ret = 0; int fail = 0;
-  out.returns = &ret; out.failure = &fail;
-  out.states = nominal_trajectory.states.data(); out.actions = nominal_trajectory.actions.data(); out.times = nominal_trajectory.times.data();
-  out.residual = nominal_trajectory.residual.data(); out.costs = nominal_trajectory.costs.data(); out.trace = nominal_trajectory.trace.data();
-  if (mjpc_hip_plan(engine_, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
-  nominal_trajectory.horizon = horizon; nominal_trajectory.total_return = ret; nominal_trajectory.failure = fail != 0;
-}
-
-void CrossEntropyPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {   // planner.cc:302-310
-  const std::shared_lock<std::shared_mutex> lock(mtx_);
-  if (use_previous) previous_policy.Action(action, s, t);
-  else policy.Action(action, s, t);
+  RolloutNominal(engine_, resampled_policy.plan, horizon, nominal_trajectory);
 }
 
 const Trajectory* CrossEntropyPlanner::BestTrajectory() { return &nominal_trajectory; }
@@ -600,7 +578,7 @@ RobustPlanner::~RobustPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
 void RobustPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {   // robust_planner.cc:30-58
   numerics_ = numerics;
   delegate.Initialize(model, task, numerics);
-  nu_ = model->nu; ns_ = model->nq + model->nv + model->na; nmocap_ = model->nmocap; nuserdata_ = model->nuserdata;
+  nu_ = model->nu;
   nrepetitions_ = numerics.robust_repetitions;
   ncandidates_ = numerics.robust_candidates;
   if (ncandidates_ == -1) ncandidates_ = numerics.sampling_trajectories / nrepetitions_;
@@ -609,23 +587,6 @@ void RobustPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* tas
   int cap = std::max(1, std::max(ncandidates_, 1) * std::max(nrepetitions_, 1));
   engine_ = mjpc_hip_create(model, task, cap, numerics.max_horizon, numerics.device);
   if (!engine_) Fatal(mjpc_hip_last_error());
-}
-void RobustPlanner::Allocate() {
-  delegate.Allocate();
-  state_.assign(ns_, 0.0); mocap_.assign(7 * nmocap_, 0.0); userdata_.assign(std::max(nuserdata_, 1), 0.0);
-}
-void RobustPlanner::Reset(int horizon, const double* initial_repeated_action) {
-  delegate.Reset(horizon, initial_repeated_action);
-  std::fill(state_.begin(), state_.end(), 0.0); std::fill(mocap_.begin(), mocap_.end(), 0.0);
-  std::fill(userdata_.begin(), userdata_.end(), 0.0);
-  time_ = 0.0;
-}
-void RobustPlanner::SetState(const double* s, const double* m, const double* u, double t) {
-  delegate.SetState(s, m, u, t);
-  std::copy(s, s + ns_, state_.begin());
-  if (m) std::copy(m, m + 7 * nmocap_, mocap_.begin());
-  if (u) std::copy(u, u + nuserdata_, userdata_.begin());
-  time_ = t;
 }
 void RobustPlanner::SetTask(const MjpcHipTask* task) {
   delegate.SetTask(task);
@@ -655,11 +616,8 @@ void RobustPlanner::OptimizePolicy(int horizon) {   // robust_planner.cc:91-157
   int total = ncandidates * repetitions;
   noisy_returns.assign(total, 0.0); noisy_failures.assign(total, 0);
   std::vector<double> zeros(row, 0.0);
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state_.data(); in.mocap = mocap_.data(); in.userdata = userdata_.data(); in.time = time_;
-  in.knot_times = kt.data(); in.knot_values = zeros.data(); in.num_spline_points = P;
-  in.interpolation = delegate.interpolation_; in.num_trajectory = total; in.horizon = horizon; in.num_local = total;
+  MjpcHipPlanInput in = MakePlanInput(delegate.state.data(), delegate.mocap.data(), delegate.userdata.data(), delegate.time, kt.data(),
+                                      zeros.data(), P, delegate.interpolation_, total, horizon);
   in.candidate_knots = cand_knots_.data(); in.xfrc_std = xfrc_std_; in.xfrc_rate = xfrc_rate_;
   in.seed = seed; in.stream = plan_iter++;
   MjpcHipPlanOutput out;
@@ -689,20 +647,10 @@ void RobustPlanner::OptimizePolicy(int horizon) {   // robust_planner.cc:91-157
 SampleGradientPlanner::~SampleGradientPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
 
 void SampleGradientPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {   // planner.cc:43-75
-  numerics_ = numerics;
-  nq_ = model->nq; nv_ = model->nv; na_ = model->na; ns_ = nq_ + nv_ + na_; nu_ = model->nu; nmocap_ = model->nmocap;
-  nuserdata_ = model->nuserdata; nr_ = task->num_residual; ntrace_ = task->num_trace; timestep_ = model->timestep;
-  ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
   noise_exploration = numerics.sampling_exploration[0];
-  num_trajectory_ = numerics.sampling_trajectories;
-  interpolation_ = numerics.sampling_representation;
   num_gradient_ = numerics.sample_gradient_trajectories;
   gradient_filter_ = numerics.sample_gradient_filter;
-  if (num_trajectory_ > numerics.max_samples) {
-    char msg[128]; std::snprintf(msg, sizeof(msg), "Too many trajectories, %d is the maximum allowed.", numerics.max_samples);
-    Fatal(msg);
-    return;
-  }
+  if (!InitializeCommon(model, task, numerics)) return;
   if (engine_) { mjpc_hip_destroy(engine_); engine_ = nullptr; }
   engine_ = mjpc_hip_create(model, task, numerics.max_samples, numerics.max_horizon, numerics.device);
   if (!engine_) { Fatal(mjpc_hip_last_error()); return; }
@@ -712,7 +660,7 @@ void SampleGradientPlanner::Initialize(const MjpcHipModel* model, const MjpcHipT
 }
 
 void SampleGradientPlanner::Allocate() {   // planner.cc:78-118
-  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  AllocateState();
   plan_scratch_ = TimeSpline(nu_);
   trajectory_order.resize(numerics_.max_samples);
   std::iota(trajectory_order.begin(), trajectory_order.end(), 0);
@@ -720,23 +668,14 @@ void SampleGradientPlanner::Allocate() {   // planner.cc:78-118
   candidate_policy_.resize(numerics_.max_samples);
   for (auto& c : candidate_policy_) { c.nu = nu_; c.ctrlrange = ctrlrange_; c.num_spline_points = policy.num_spline_points; c.plan = TimeSpline(nu_); }
   candidate_valid_.assign(numerics_.max_samples, 1);
-  size_t Hm = (size_t)numerics_.max_horizon;
-  trajectory_winner.dim_state = ns_; trajectory_winner.dim_action = nu_; trajectory_winner.dim_residual = nr_;
-  trajectory_winner.dim_trace = 3 * ntrace_;
-  trajectory_winner.states.assign(Hm * ns_, 0.0); trajectory_winner.actions.assign(Hm * nu_, 0.0);
-  trajectory_winner.times.assign(Hm, 0.0); trajectory_winner.residual.assign(Hm * nr_, 0.0);
-  trajectory_winner.costs.assign(Hm, 0.0); trajectory_winner.trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+  SizeTrajectory(trajectory_winner);
   int num_max_parameter = nu_ * MaxSamplingSplinePoints;       // the engine's spline capacity
   gradient.assign(num_max_parameter, 0.0); gradient_previous.assign(num_max_parameter, 0.0);
 }
 
 void SampleGradientPlanner::Reset(int horizon, const double* initial_repeated_action) {   // planner.cc:121-160
-  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0);
-  std::fill(userdata.begin(), userdata.end(), 0.0);
-  time = 0.0;
-  policy.Reset(horizon, initial_repeated_action);
+  ResetState(horizon, initial_repeated_action);
   resampled_policy.Reset(horizon, initial_repeated_action);
-  previous_policy.Reset(horizon, initial_repeated_action);
   plan_scratch_.Clear();
   if (engine_ && mjpc_hip_noise_history_reset(engine_) != 0) Fatal(mjpc_hip_last_error());      // std::fill(noise, 0)
   for (size_t i = 0; i < candidate_policy_.size(); i++) { candidate_policy_[i].Reset(horizon); candidate_valid_[i] = 1; }
@@ -744,13 +683,6 @@ void SampleGradientPlanner::Reset(int horizon, const double* initial_repeated_ac
   winner = 0;
   std::fill(gradient.begin(), gradient.end(), 0.0);
   std::fill(gradient_previous.begin(), gradient_previous.end(), 0.0);
-}
-
-void SampleGradientPlanner::SetState(const double* s, const double* m, const double* u, double t) {
-  std::copy(s, s + ns_, state.begin());
-  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
-  if (u) std::copy(u, u + nuserdata_, userdata.begin());
-  time = t;
 }
 
 void SampleGradientPlanner::SetTask(const MjpcHipTask* task) {
@@ -786,13 +718,7 @@ SamplingPolicy& SampleGradientPlanner::Candidate(int index) {
 }
 
 int SampleGradientPlanner::CandidatePolicy(int index, double* times, double* values) {
-  const SamplingPolicy& c = Candidate(index);
-  int P = (int)c.plan.Size();
-  for (int t = 0; t < P; t++) {
-    if (times) times[t] = c.plan.NodeTime(t);
-    if (values) std::copy(c.plan.NodeValues(t), c.plan.NodeValues(t) + nu_, values + (size_t)t * nu_);
-  }
-  return P;
+  return CopyKnots(Candidate(index), times, values);
 }
 
 void SampleGradientPlanner::OptimizePolicy(int horizon) {   // planner.cc:169-273
@@ -815,22 +741,15 @@ void SampleGradientPlanner::OptimizePolicy(int horizon) {   // planner.cc:169-27
   auto rollouts_start = std::chrono::steady_clock::now();
   int P = num_spline_points;
   size_t row = (size_t)P * nu_;
-  knot_times_.resize(P); knot_values_.resize(row); noise_std_.assign(row, noise_exploration);
-  for (int t = 0; t < P; t++) {
-    knot_times_[t] = resampled_policy.plan.NodeTime(t);
-    std::copy(resampled_policy.plan.NodeValues(t), resampled_policy.plan.NodeValues(t) + nu_, knot_values_.begin() + (size_t)t * nu_);
-  }
+  KnotArrays(resampled_policy.plan, knot_times_, knot_values_);       // P nodes: ResamplePolicy has just laid them
+  noise_std_.assign(row, noise_exploration);
   cand_table_.resize((size_t)num_trajectory * row);             // rows below num_noisy are not read by the engine
   for (int i = num_noisy; i < num_trajectory; i++) {
     const SamplingPolicy& c = candidate_policy_[i];
     for (int t = 0; t < P; t++) std::copy(c.plan.NodeValues(t), c.plan.NodeValues(t) + nu_, cand_table_.begin() + (size_t)i * row + (size_t)t * nu_);
   }
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = knot_times_.data(); in.knot_values = knot_values_.data(); in.num_spline_points = P;
-  in.interpolation = (int)resampled_policy.plan.Interpolation();
-  in.num_trajectory = num_trajectory; in.horizon = horizon; in.candidate_offset = 0; in.num_local = num_trajectory;
+  MjpcHipPlanInput in = PlanInput(knot_times_.data(), knot_values_.data(), P, (int)resampled_policy.plan.Interpolation(),
+                                  num_trajectory, horizon);
   in.noise_eps = injected_noise_eps; in.seed = seed; in.stream = plan_iter++;
   in.noise_std = noise_std_.data(); in.nominal_index = 0;
   in.candidate_knots = cand_table_.data();
@@ -847,10 +766,7 @@ void SampleGradientPlanner::OptimizePolicy(int horizon) {   // planner.cc:169-27
 
   // ----- update policy (planner.cc:216-262)
   auto policy_update_start = std::chrono::steady_clock::now();
-  trajectory_order.resize(std::max((int)trajectory_order.size(), num_trajectory));
-  for (int i = 0; i < num_trajectory; i++) trajectory_order[i] = i;
-  std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + num_trajectory,
-                   [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+  OrderCandidates(num_trajectory);
   const int idx_nominal = 0;
   if (returns[trajectory_order[0]] < returns[idx_nominal]) winner = trajectory_order[0];
   else winner = idx_nominal;
@@ -863,10 +779,7 @@ void SampleGradientPlanner::OptimizePolicy(int horizon) {   // planner.cc:169-27
   }
   improvement = std::max(returns[idx_nominal] - returns[winner], 0.0);
   {
-    MjpcHipPlanOutput best;
-    std::memset(&best, 0, sizeof(best));
-    best.states = trajectory_winner.states.data(); best.actions = trajectory_winner.actions.data(); best.times = trajectory_winner.times.data();
-    best.residual = trajectory_winner.residual.data(); best.costs = trajectory_winner.costs.data(); best.trace = trajectory_winner.trace.data();
+    MjpcHipPlanOutput best = TrajectoryOutput(trajectory_winner);
     if (mjpc_hip_get_candidate(engine_, winner, &best) != 0) { Fatal(mjpc_hip_last_error()); return; }
     trajectory_winner.horizon = horizon; trajectory_winner.total_return = returns[winner]; trajectory_winner.failure = failures[winner] != 0;
   }
@@ -902,9 +815,7 @@ void SampleGradientPlanner::GradientCandidates(int num_trajectory, int num_gradi
   // fitness shaping, computed when the count of noisy candidates changes and only then (planner.cc:419-450)
   if ((int)return_weight_.size() != num_noisy) {
     return_weight_.resize(num_noisy);
-    for (int i = 0; i < num_noisy; i++) trajectory_order[i] = i;
-    std::stable_sort(trajectory_order.begin(), trajectory_order.begin() + num_noisy,
-                     [this](int a, int b) { return ReturnLess(returns[a], returns[b]); });
+    OrderCandidates(num_noisy);
     ReturnWeights(trajectory_order.data(), num_noisy, return_weight_.data());
   }
   // gradient = sum_i noise[trajectory_order[i]] * return_weight_[i] / num_noisy, on the device over the noise history
@@ -932,33 +843,9 @@ void SampleGradientPlanner::GradientCandidates(int num_trajectory, int num_gradi
 }
 
 void SampleGradientPlanner::NominalTrajectory(int horizon) {   // planner.cc:276-287: rollout of resampled_policy into trajectory[0]
-  int P = (int)resampled_policy.plan.Size();
-  std::vector<double> kt(std::max(P, 1), time), kv((size_t)std::max(P, 1) * nu_, 0.0);
-  for (int p = 0; p < P; p++) {
-    kt[p] = resampled_policy.plan.NodeTime(p);
-    std::copy(resampled_policy.plan.NodeValues(p), resampled_policy.plan.NodeValues(p) + nu_, kv.begin() + (size_t)p * nu_);
-  }
-  MjpcHipPlanInput in;
-  std::memset(&in, 0, sizeof(in));
-  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
-  in.knot_times = kt.data(); in.knot_values = kv.data(); in.num_spline_points = std::max(P, 1);
-  in.interpolation = (int)resampled_policy.plan.Interpolation(); in.num_trajectory = 1; in.horizon = horizon; in.num_local = 1;
-  MjpcHipPlanOutput out;
-  std::memset(&out, 0, sizeof(out));
-  double ret = 0; int fail = 0;
-  out.returns = &ret; out.failure = &fail;
-  out.states = trajectory_winner.states.data(); out.actions = trajectory_winner.actions.data(); out.times = trajectory_winner.times.data();
-  out.residual = trajectory_winner.residual.data(); out.costs = trajectory_winner.costs.data(); out.trace = trajectory_winner.trace.data();
-  if (mjpc_hip_plan(engine_, &in, &out) != 0) { Fatal(mjpc_hip_last_error()); return; }
-  trajectory_winner.horizon = horizon; trajectory_winner.total_return = ret; trajectory_winner.failure = fail != 0;
-  returns[0] = ret; failures[0] = fail;
+  if (!RolloutNominal(engine_, resampled_policy.plan, horizon, trajectory_winner, &failures[0])) return;
+  returns[0] = trajectory_winner.total_return;
   winner = 0;                                          // BestTrajectory() shows trajectory[0] until the next OptimizePolicy
-}
-
-void SampleGradientPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {   // planner.cc:290-299
-  const std::shared_lock<std::shared_mutex> lock(mtx_);
-  if (use_previous) previous_policy.Action(action, s, t);
-  else policy.Action(action, s, t);
 }
 
 const Trajectory* SampleGradientPlanner::BestTrajectory() { return &trajectory_winner; }
@@ -968,6 +855,23 @@ const Trajectory* SampleGradientPlanner::BestTrajectory() { return &trajectory_w
 // ====================================================================== flat C wrapper (tests / ctypes)
 using mjpc_hip::SamplingPlanner;
 using mjpc_hip::TimeSpline;
+
+// a trajectory for the flat C view: returns its horizon (0 if there is none); copies the arrays that are non-null
+static int CopyTrajectory(const mjpc_hip::Trajectory* t, double* states, double* actions, double* times, double* residual, double* costs,
+                          double* trace, double* total_return, int* failure) {
+  if (!t) return 0;
+  size_t H = (size_t)t->horizon;
+  if (states) std::copy(t->states.begin(), t->states.begin() + H * t->dim_state, states);
+  if (actions) std::copy(t->actions.begin(), t->actions.begin() + H * t->dim_action, actions);
+  if (times) std::copy(t->times.begin(), t->times.begin() + H, times);
+  if (residual) std::copy(t->residual.begin(), t->residual.begin() + H * t->dim_residual, residual);
+  if (costs) std::copy(t->costs.begin(), t->costs.begin() + H, costs);
+  if (trace) std::copy(t->trace.begin(), t->trace.begin() + H * t->dim_trace, trace);
+  if (total_return) *total_return = t->total_return;
+  if (failure) *failure = t->failure ? 1 : 0;
+  return t->horizon;
+}
+
 extern "C" {
 
 void mjpc_planner_set_error_handler(void (*h)(const char*)) { mjpc_hip::g_error_handler = h; }
@@ -1028,32 +932,13 @@ void mjpc_planner_set_seed(void* p, unsigned long long seed, unsigned long long 
 void mjpc_planner_set_num_trajectory(void* p, int n) { ((SamplingPlanner*)p)->num_trajectory_ = n; }
 void mjpc_planner_set_noise(void* p, const double* eps, const int* sel) { auto* q = (SamplingPlanner*)p; q->injected_noise_eps = eps; q->injected_noise_sel = sel; }
 void mjpc_planner_returns(void* p, double* out, int n) { auto* q = (SamplingPlanner*)p; std::copy(q->returns.begin(), q->returns.begin() + n, out); }
-// policy knots: returns P; fills times[P] and values[P*nu] when non-null
 int mjpc_planner_policy(void* p, int which, double* times, double* values) {
   auto* q = (SamplingPlanner*)p;
-  const mjpc_hip::SamplingPolicy& pol = which ? q->previous_policy : q->policy;
-  int P = (int)pol.plan.Size();
-  for (int i = 0; i < P; i++) {
-    if (times) times[i] = pol.plan.NodeTime(i);
-    if (values) std::copy(pol.plan.NodeValues(i), pol.plan.NodeValues(i) + pol.nu, values + (size_t)i * pol.nu);
-  }
-  return P;
+  return mjpc_hip::CopyKnots(which ? q->previous_policy : q->policy, times, values);
 }
-// best trajectory: returns horizon (0 if none); copies the arrays that are non-null
 int mjpc_planner_best_trajectory(void* p, double* states, double* actions, double* times, double* residual, double* costs,
                                  double* trace, double* total_return, int* failure) {
-  const mjpc_hip::Trajectory* t = ((SamplingPlanner*)p)->BestTrajectory();
-  if (!t) return 0;
-  size_t H = (size_t)t->horizon;
-  if (states) std::copy(t->states.begin(), t->states.begin() + H * t->dim_state, states);
-  if (actions) std::copy(t->actions.begin(), t->actions.begin() + H * t->dim_action, actions);
-  if (times) std::copy(t->times.begin(), t->times.begin() + H, times);
-  if (residual) std::copy(t->residual.begin(), t->residual.begin() + H * t->dim_residual, residual);
-  if (costs) std::copy(t->costs.begin(), t->costs.begin() + H, costs);
-  if (trace) std::copy(t->trace.begin(), t->trace.begin() + H * t->dim_trace, trace);
-  if (total_return) *total_return = t->total_return;
-  if (failure) *failure = t->failure ? 1 : 0;
-  return t->horizon;
+  return CopyTrajectory(((SamplingPlanner*)p)->BestTrajectory(), states, actions, times, residual, costs, trace, total_return, failure);
 }
 
 // ---- CrossEntropyPlanner
@@ -1079,23 +964,9 @@ void mjpc_cem_action_from_policy(void* p, double* a, double t, int prev) { ((mjp
 double mjpc_cem_improvement(void* p) { return ((mjpc_hip::CrossEntropyPlanner*)p)->improvement; }
 void mjpc_cem_returns(void* p, double* out, int n) { auto* q = (mjpc_hip::CrossEntropyPlanner*)p; std::copy(q->returns.begin(), q->returns.begin() + n, out); }
 void mjpc_cem_variance(void* p, double* out, int n) { auto* q = (mjpc_hip::CrossEntropyPlanner*)p; std::copy(q->variance.begin(), q->variance.begin() + n, out); }
-int mjpc_cem_policy(void* p, double* times, double* values) {
-  auto* q = (mjpc_hip::CrossEntropyPlanner*)p;
-  int P = (int)q->policy.plan.Size();
-  for (int i = 0; i < P; i++) {
-    if (times) times[i] = q->policy.plan.NodeTime(i);
-    if (values) std::copy(q->policy.plan.NodeValues(i), q->policy.plan.NodeValues(i) + q->policy.nu, values + (size_t)i * q->policy.nu);
-  }
-  return P;
-}
+int mjpc_cem_policy(void* p, double* times, double* values) { return mjpc_hip::CopyKnots(((mjpc_hip::CrossEntropyPlanner*)p)->policy, times, values); }
 int mjpc_cem_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
-  const mjpc_hip::Trajectory* t = ((mjpc_hip::CrossEntropyPlanner*)p)->BestTrajectory();
-  size_t H = (size_t)t->horizon;
-  if (states) std::copy(t->states.begin(), t->states.begin() + H * t->dim_state, states);
-  if (actions) std::copy(t->actions.begin(), t->actions.begin() + H * t->dim_action, actions);
-  if (costs) std::copy(t->costs.begin(), t->costs.begin() + H, costs);
-  if (total_return) *total_return = t->total_return;
-  return t->horizon;
+  return CopyTrajectory(((mjpc_hip::CrossEntropyPlanner*)p)->BestTrajectory(), states, actions, nullptr, nullptr, costs, nullptr, total_return, nullptr);
 }
 
 // ---- SampleGradientPlanner
@@ -1131,24 +1002,10 @@ void mjpc_sg_trajectory_order(void* p, int* out, int n) { std::copy(SGP(p)->traj
 void mjpc_sg_gradient(void* p, double* out, int n) { std::copy(SGP(p)->gradient.begin(), SGP(p)->gradient.begin() + n, out); }
 int mjpc_sg_return_weight(void* p, double* out) { auto& w = SGP(p)->return_weight_; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
 int mjpc_sg_step_size(void* p, double* out) { auto& w = SGP(p)->step_size_; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
-int mjpc_sg_policy(void* p, double* times, double* values) {
-  auto& pol = SGP(p)->policy;
-  int P = (int)pol.plan.Size();
-  for (int i = 0; i < P; i++) {
-    if (times) times[i] = pol.plan.NodeTime(i);
-    if (values) std::copy(pol.plan.NodeValues(i), pol.plan.NodeValues(i) + pol.nu, values + (size_t)i * pol.nu);
-  }
-  return P;
-}
+int mjpc_sg_policy(void* p, double* times, double* values) { return mjpc_hip::CopyKnots(SGP(p)->policy, times, values); }
 int mjpc_sg_candidate_policy(void* p, int index, double* times, double* values) { return SGP(p)->CandidatePolicy(index, times, values); }
 int mjpc_sg_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
-  const mjpc_hip::Trajectory* t = SGP(p)->BestTrajectory();
-  size_t H = (size_t)t->horizon;
-  if (states) std::copy(t->states.begin(), t->states.begin() + H * t->dim_state, states);
-  if (actions) std::copy(t->actions.begin(), t->actions.begin() + H * t->dim_action, actions);
-  if (costs) std::copy(t->costs.begin(), t->costs.begin() + H, costs);
-  if (total_return) *total_return = t->total_return;
-  return t->horizon;
+  return CopyTrajectory(SGP(p)->BestTrajectory(), states, actions, nullptr, nullptr, costs, nullptr, total_return, nullptr);
 }
 void mjpc_sg_timings(void* p, double* noise, double* rollouts, double* update, double* gradient) {
   *noise = SGP(p)->noise_compute_time; *rollouts = SGP(p)->rollouts_compute_time; *update = SGP(p)->policy_update_compute_time;

@@ -435,32 +435,6 @@ TransitionFn TransitionForTask(int task_id, int mode, double mode_time) {
   return [](const MjpcHipModel&, SimState&, HostTask&, const SimFrame&) {};
 }
 
-// ------------------------------------------------------------------ planner adapters
-PlannerOps Ops(SamplingPlanner& p) {
-  PlannerOps o;
-  o.SetState = [&p](const SimState& s) { p.SetState(s.state.data(), s.mocap.data(), s.userdata.data(), s.time); };
-  o.OptimizePolicy = [&p](int h) { p.OptimizePolicy(h); };
-  o.ActionFromPolicy = [&p](double* a, double t) { p.ActionFromPolicy(a, nullptr, t, false); };
-  o.SetTask = [&p](const MjpcHipTask* t) { p.SetTask(t); };
-  return o;
-}
-PlannerOps Ops(CrossEntropyPlanner& p) {
-  PlannerOps o;
-  o.SetState = [&p](const SimState& s) { p.SetState(s.state.data(), s.mocap.data(), s.userdata.data(), s.time); };
-  o.OptimizePolicy = [&p](int h) { p.OptimizePolicy(h); };
-  o.ActionFromPolicy = [&p](double* a, double t) { p.ActionFromPolicy(a, nullptr, t, false); };
-  o.SetTask = [&p](const MjpcHipTask* t) { p.SetTask(t); };
-  return o;
-}
-PlannerOps Ops(SampleGradientPlanner& p) {
-  PlannerOps o;
-  o.SetState = [&p](const SimState& s) { p.SetState(s.state.data(), s.mocap.data(), s.userdata.data(), s.time); };
-  o.OptimizePolicy = [&p](int h) { p.OptimizePolicy(h); };
-  o.ActionFromPolicy = [&p](double* a, double t) { p.ActionFromPolicy(a, nullptr, t, false); };
-  o.SetTask = [&p](const MjpcHipTask* t) { p.SetTask(t); };
-  return o;
-}
-
 // ------------------------------------------------------------------ the loop (testspeed.cc:97-116)
 TestspeedResult SynchronousPlanningCost(const MjpcHipModel& model, HostTask& task, PlannerOps planner, Simulator& sim, SimState& s,
                                         int horizon, int steps_per_planning_iteration, double total_time, const TransitionFn& transition) {

@@ -833,6 +833,125 @@ def test_cpp_robust_planner_matches_oracle_restatement():
     rp.close()
 
 
+# NominalTrajectory() of the three C++ planners: particle, N = 8, H = 6, 3 spline points.  Every equality is bit for bit, and only
+# un-noised candidates are compared: the nominal skips noise and clip, and a rollout does not depend on the batch it rides in.
+_NOM = dict(H=6, N=8, P=3, state=np.array([0.3, -0.2, 0.0, 0.0]))
+
+
+def _one_candidate_plan(m, task, d, state, time, kt, kv, interp, max_samples):
+    H = _NOM["H"]
+    be = HipBackend(m, task, max_samples=max_samples, max_horizon=H)
+    out = be.plan(state=state, mocap=d["mocap"], time=time, knot_times=kt, knot_values=kv, interpolation=interp, num_trajectory=1,
+                  horizon=H, sigma=(0.0, 0.0))
+    be.close()
+    return out
+
+
+@pytest.mark.parametrize("interp", [0, 2])
+def test_cpp_sampling_planner_nominal_trajectory(interp):
+    """SamplingPlanner::NominalTrajectory (planner.cc:211-222): `policy` rolled out alone, the candidates of the last plan step
+    left as they were."""
+    from mujoco_mpc_amd import cplanner
+    m, task, d = particle(timestep=0.1)
+    H, N, P = _NOM["H"], _NOM["N"], _NOM["P"]
+    num = dict(sampling_spline_points=P, sampling_exploration=[0.3, 0.0], sampling_trajectories=N, sampling_representation=interp)
+    pl = cplanner.SamplingPlanner()
+    pl.Initialize(m, task, num, max_samples=N, max_horizon=H)
+    pl.Reset(H); pl.set_seed(21, 0)
+    state = _NOM["state"].copy(); t = 0.0
+    pl.SetState(state, d["mocap"], None, t)
+    pl.NominalTrajectory(H)                                  # before any plan: the empty policy samples zeros
+    first = pl.BestTrajectory()
+    assert first.horizon == H and first.actions.shape == (H, m["nu"]) and not first.actions.any()
+    pl.Reset(H, np.array([0.2, -0.1]))                       # a policy that is non-zero whichever candidate wins
+    pl.SetState(state, d["mocap"], None, t)
+    pl.OptimizePolicy(H)
+    state = pl.BestTrajectory().states[1].copy(); t += m["timestep"]
+    pl.SetState(state, d["mocap"], None, t)
+    pl.OptimizePolicy(H)
+    win = pl.BestTrajectory()
+    returns = pl.returns(N); score = pl.CandidateScore(0)
+    kt, kv = pl.policy_knots()
+    assert len(kt) == P and np.abs(kv).max() > 0
+    pl.NominalTrajectory(H)
+    nom = pl.BestTrajectory()
+    ref = _one_candidate_plan(m, task, d, state, t, kt, kv, interp, 1)
+    assert nom.horizon == H
+    for k in ("states", "actions", "times", "costs"):
+        assert np.array_equal(getattr(nom, k), ref[k]), k
+    assert nom.total_return == ref["returns"][0] and not nom.failure
+    assert np.array_equal(pl.returns(N), returns) and pl.CandidateScore(0) == score
+    pl.CopyCandidateToPolicy(0)                              # the ranked winner's rows come back from the device
+    back = pl.BestTrajectory()
+    for k in ("states", "actions", "times", "residual", "costs", "trace"):
+        assert np.array_equal(getattr(back, k), getattr(win, k)), k
+    assert back.total_return == win.total_return == score
+    pl.close()
+
+
+@pytest.mark.parametrize("interp", [0, 2])
+def test_cpp_cross_entropy_planner_nominal_trajectory(interp):
+    """CrossEntropyPlanner::NominalTrajectory (planner.cc:286-297): `resampled_policy` rolled out alone reproduces candidate N of
+    the plan step's batch."""
+    from mujoco_mpc_amd import cplanner
+    m, task, d = particle(timestep=0.1)
+    H, N, P = _NOM["H"], _NOM["N"], _NOM["P"]
+    num = dict(sampling_spline_points=P, sampling_exploration=0.3, std_min=0.05, sampling_trajectories=N, n_elite=3,
+               sampling_representation=interp)
+    pl = cplanner.CrossEntropyPlanner()
+    pl.Initialize(m, task, num, max_samples=N, max_horizon=H)
+    pl.Reset(H); pl.set_seed(22, 0)
+    state = _NOM["state"].copy(); t = 0.0
+    pl.SetState(state, d["mocap"], None, t)
+    pl.OptimizePolicy(H)
+    state = pl.BestTrajectory().states[1].copy(); t += m["timestep"]
+    pl.SetState(state, d["mocap"], None, t)
+    pl.OptimizePolicy(H)                                     # resamples the first step's elite mean: a non-zero nominal
+    best = pl.BestTrajectory()
+    ret = pl.returns(N + 1)[N]
+    assert best.horizon == H and best.total_return == ret and best.actions.any()
+    pl.NominalTrajectory(H)
+    nom = pl.BestTrajectory()
+    assert nom.horizon == H
+    for k in ("states", "actions", "costs"):
+        assert np.array_equal(getattr(nom, k), getattr(best, k)), k
+    assert nom.total_return == ret
+    pl.close()
+
+
+@pytest.mark.parametrize("interp", [0, 2])
+def test_cpp_sample_gradient_planner_nominal_trajectory(interp):
+    """SampleGradientPlanner::NominalTrajectory (planner.cc:276-287): `resampled_policy` rolled out into trajectory[0]; it is
+    candidate 0 of the plan step's batch."""
+    from mujoco_mpc_amd import cplanner
+    m, task, d = particle(timestep=0.1)
+    H, N, P = _NOM["H"], _NOM["N"], _NOM["P"]
+    num = dict(sampling_spline_points=P, sampling_exploration=0.2, sampling_trajectories=N, sample_gradient_trajectories=2,
+               sampling_representation=interp)
+    pl = cplanner.SampleGradientPlanner()
+    pl.Initialize(m, task, num, max_samples=N, max_horizon=H)
+    pl.Reset(H); pl.set_seed(23, 0)
+    state = _NOM["state"].copy(); t = 0.0
+    for it in range(8):                                      # until the gradient candidates are real and the nominal is non-zero
+        pl.SetState(state, d["mocap"], None, t)
+        pl.OptimizePolicy(H)
+        kt, kv = pl.candidate_policy(0)
+        if it >= 1 and np.abs(kv).max() > 0:
+            break
+        state = pl.BestTrajectory().states[1].copy(); t += m["timestep"]
+    assert pl.num_gradient_ == 2
+    returns = pl.returns(N)
+    assert len(kt) == P and np.abs(kv).max() > 0
+    pl.NominalTrajectory(H)
+    nom = pl.BestTrajectory()
+    assert nom.horizon == H and nom.total_return == returns[0] and pl.winner == 0
+    assert np.array_equal(pl.returns(N), returns)
+    ref = _one_candidate_plan(m, task, d, state, t, kt, kv, interp, N)
+    assert np.array_equal(nom.states, ref["states"]) and np.array_equal(nom.actions, ref["actions"])
+    assert np.array_equal(nom.costs, ref["costs"]) and nom.total_return == ref["returns"][0]
+    pl.close()
+
+
 @pytest.mark.parametrize("name", ["humanoid_stand", "humanoid_walk"])
 def test_humanoid_stand_and_walk_tasks(name):
     """mjpc/tasks/humanoid/stand/stand.cc:41-94 and walk/walk.cc:44-166 (the other two tasks the local humanoid model serves):

@@ -920,7 +920,6 @@ DEV void contact_param(Ctx &c, int g1, int g2, double *prm, int *dim) {
 
 // one batch of (at most) NLANE active pairs: narrow phase per lane, ordered compaction, contact records.
 // returns 0: done; 1 (HEAVY == false only): some pair needs narrow_heavy(), nothing was written; 2: contact buffer full
-#define HX_HEAVY 46      // the previous step's first batch needed an out-of-line collider: this step starts with that flavour
 template <bool HEAVY>
 DEV int narrow_batch(Ctx &c, int base, int nactive, int *used_heavy = nullptr) {
   const DevModel &M = *c.M;

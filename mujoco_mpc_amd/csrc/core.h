@@ -1,4 +1,5 @@
-// core.h — one candidate rollout, written SPMD over the lanes of ONE wavefront.
+// core.h — one candidate rollout, written SPMD over the lanes of a wavefront; the phases below are shared out over the four
+// wavefronts of the candidate's workgroup (spmd.h).
 //
 // Replaces (for every candidate i in parallel) what a ThreadPool worker runs in the reference:
 //   mjpc/planners/sampling/planner.cc:355-376   copy nominal policy, AddNoiseToPolicy, Rollout
@@ -83,7 +84,7 @@ struct Ctx {
   double time;
   int ncon, nefc, nsingle, warning, solver_iter, cross;
   int hseq;            // hand-shake sequence number with the solver's helper wave
-  int role;            // 0: owns the rollout scalars (misc[0..8], time); 1: side wave, only reports warnings (misc[11])
+  int role;            // 0: owns the rollout scalars (MISC_NCON .. MISC_CROSS, time); 1: helper / side wave, only reports warnings (MISC_WARN_OTHERS)
 };
 
 // LDS block at Lay offset `off`, or (spill flavour) the candidate's slab in HBM when the offset is LAY_SLAB-tagged.  Without
@@ -133,15 +134,15 @@ DEV void ctx_init(Ctx &c, const KParams *K, double *base) {
 #endif
 }
 
-// rollout scalars shared between phases live in LDS: misc[0..4] = ncon, nefc, nsingle, warning, solver_iter; red[0] = time
+// rollout scalars shared between phases live in LDS: the MISC_* slots of misc[] (model.h); red[0] = time
 DEV void ctx_open(Ctx &c, KP Kc, int role = 0) {
   ctx_init(c, kp_generic(Kc), lds_base());
   c.role = role;
-  c.ncon = uniform_i(c.misc[0]); c.nefc = uniform_i(c.misc[1]); c.nsingle = uniform_i(c.misc[2]);
-  c.warning = uniform_i(c.misc[3]) | uniform_i(c.misc[11]); c.solver_iter = uniform_i(c.misc[4]); c.cross = uniform_i(c.misc[8]);
+  c.ncon = uniform_i(c.misc[MISC_NCON]); c.nefc = uniform_i(c.misc[MISC_NEFC]); c.nsingle = uniform_i(c.misc[MISC_NSINGLE]);
+  c.warning = uniform_i(c.misc[MISC_WARNING]) | uniform_i(c.misc[MISC_WARN_OTHERS]); c.solver_iter = uniform_i(c.misc[MISC_SOLVER_ITER]); c.cross = uniform_i(c.misc[MISC_CROSS]);
   c.time = c.red[0];
 }
-#ifdef MJPC_NO_MODEL_CACHE     // engine_dense.hip: tables read from HBM / L2 (the 26-29 KB LDS copy would keep a second workgroup off the CU)
+#ifdef MJPC_NO_MODEL_CACHE     // the flavours without the LDS copy (rollout_dense2*.hip, rollout_direct.hip, rollout_spill.hip): tables read from HBM / L2 (the 26-29 KB LDS copy would keep a second workgroup off the CU)
 #define MD(f) (c.M->f)
 #define MI(f) (c.M->f)
 #define MDM() ((const unsigned long long *)c.M->body_dofmask)
@@ -166,16 +167,17 @@ DEV void ctx_close(Ctx &c) {
   if (c.role != 0) {            // the side wave never writes the owner's scalars
     if (LANE == 0 && c.warning) {
 #ifdef MJPC_EMU
-      c.misc[11] |= c.warning;
+      c.misc[MISC_WARN_OTHERS] |= c.warning;
 #else
-      __hip_atomic_fetch_or(c.misc + 11, c.warning, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // several side / helper waves report here
+      __hip_atomic_fetch_or(c.misc + MISC_WARN_OTHERS, c.warning, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // several side / helper waves report here
 #endif
     }
     SYNC();
     return;
   }
   if (LANE == 0) {
-    c.misc[0] = c.ncon; c.misc[1] = c.nefc; c.misc[2] = c.nsingle; c.misc[3] = c.warning; c.misc[4] = c.solver_iter; c.misc[8] = c.cross;
+    c.misc[MISC_NCON] = c.ncon; c.misc[MISC_NEFC] = c.nefc; c.misc[MISC_NSINGLE] = c.nsingle; c.misc[MISC_WARNING] = c.warning;
+    c.misc[MISC_SOLVER_ITER] = c.solver_iter; c.misc[MISC_CROSS] = c.cross;
     c.red[0] = c.time;
   }
   SYNC();
@@ -306,7 +308,7 @@ DEV_NOINLINE void ph_init(KP Kc) {
 }
 
 // role 0, head of a step: policy -> ctrl (policy.cc:52-59), mj_checkPos / mj_checkVel, then kinematics and the
-// com-based quantities every other phase reads.  A bad state raises misc[10] (both roles leave the loop).
+// com-based quantities every other phase reads.  A bad state raises MISC_BAD_STATE (every wave leaves the loop).
 template <int NVT>
 DEV_NOINLINE void ph_head(KP Kc, int t, int last) {
   Ctx c; ctx_open(c, Kc);
@@ -323,7 +325,7 @@ DEV_NOINLINE void ph_head(KP Kc, int t, int last) {
     SYNC();
     if (bad_values(c.qpos, M.nq)) c.warning |= WARN_BADQPOS;
     if (bad_values(c.qvel, M.nv)) c.warning |= WARN_BADQVEL;
-    if (c.warning) { if (LANE == 0) c.misc[10] = 1; ctx_close(c); return; }
+    if (c.warning) { if (LANE == 0) c.misc[MISC_BAD_STATE] = 1; ctx_close(c); return; }
     if (K->xfrc_std > 0) {              // NoisyRollout (trajectory.cc:147-155): Ornstein-Uhlenbeck force/torque noise on every body
       double rate = exp(-M.timestep / K->xfrc_rate), scale = K->xfrc_std * sqrt(1 - rate * rate);
       unsigned gi = (unsigned)(K->offset + cand_index());
@@ -340,7 +342,7 @@ DEV_NOINLINE void ph_head(KP Kc, int t, int last) {
   ctx_close(c);
 }
 // role 0: contacts and constraint rows (needs positions + qvel only).  With helper waves the contact-free rows and their
-// impedance are built by the last helper meanwhile (ph_noncontact); it publishes nsingle / n_nc in misc[25..26], flag misc[24].
+// impedance are built by the last helper meanwhile (ph_noncontact); it publishes nsingle / n_nc in HX_NC_NSINGLE / HX_NC_ROWS, flag HX_NCROWS.
 DEV_NOINLINE void ph_constraints(KP Kc, int t) {
   Ctx c; ctx_open(c, Kc);
   collision(c); PROF(c, 4);
@@ -349,8 +351,8 @@ DEV_NOINLINE void ph_constraints(KP Kc, int t) {
 #if MJPC_SIDE_COM
   if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC;        // cdof / subtree_com for the contact Jacobians (side wave)
 #endif
-  if (!flag_wait(c.misc + 24, t + 1)) c.warning |= WARN_SYNC;
-  nsingle = uniform_i(c.misc[25]); n_nc = uniform_i(c.misc[26]);
+  if (!flag_wait(c.misc + HX_NCROWS, t + 1)) c.warning |= WARN_SYNC;
+  nsingle = uniform_i(c.misc[HX_NC_NSINGLE]); n_nc = uniform_i(c.misc[HX_NC_ROWS]);
   c.nsingle = nsingle;
   make_contact_rows(c, n_nc); PROF(c, 5);
   make_impedance(c, n_nc, c.nefc, 1); PROF(c, 7);
@@ -371,8 +373,8 @@ DEV_NOINLINE void ph_noncontact(KP Kc, int t) {
   if (c.M->neq_connect) { if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC; }
 #endif
   make_noncontact_rows(c, &nsingle, &n_nc);
-  if (LANE == 0) { c.misc[25] = nsingle; c.misc[26] = n_nc; }
-  flag_set(c.misc + 24, t + 1);
+  if (LANE == 0) { c.misc[HX_NC_NSINGLE] = nsingle; c.misc[HX_NC_ROWS] = n_nc; }
+  flag_set(c.misc + HX_NCROWS, t + 1);
   PROFW(c, 1);
   make_impedance(c, 0, n_nc, 0);
   PROFW(c, 4);
@@ -412,29 +414,24 @@ DEV_NOINLINE void ph_inertia(KP Kc, int t) {
   if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC;
 #endif
   crb_and_factor<NVT>(c);
-  flag_set(c.misc + 22, t + 1);
+  flag_set(c.misc + HX_MFACT, t + 1);
   ctx_close(c);
 }
 #endif
-// (inlining it into the kernel trades the ~100 callee-saved register saves per call for register pressure in the hot loops:
-// measured 1 % slower with one candidate per CU; MJPC_INLINE_SOLVE is the A/B switch)
-#ifdef MJPC_INLINE_SOLVE
-#define DEV_SOLVE_PHASE DEV
-#else
-#define DEV_SOLVE_PHASE DEV_NOINLINE
-#endif
+// (inlining it into the kernel instead was measured 1 % slower with one candidate per CU: register pressure in the hot loops)
 template <int NVT>
-DEV_SOLVE_PHASE void ph_solve(KP Kc, int last, int t) {
+DEV_NOINLINE void ph_solve(KP Kc, int last, int t) {
   Ctx c; ctx_open(c, Kc);
   c.hseq = t * 256;
   solve_constraints<NVT>(c); PROF(c, 8);
 #if MJPC_HELPER
-  // release the waves that wait for jobs: the workers of elliptic models (one packed word, solver_reg.h) / the Hessian builders of
-  // the generic path
-  if (MJPC_SOLVER_REG && NVT > 0) { if (c.M->cone == 1) flag_set(c.misc + HX_JOBW, JOBW(++c.hseq, 0, 0)); }
+  // release the waves that wait for jobs: the workers of elliptic models (one packed word, solver_reg.h)
+  if (NVT > 0) { if (c.M->cone == 1) flag_set(c.misc + HX_JOBW, JOBW(++c.hseq, 0, 0)); }
   else {
-    if (LANE == 0) c.misc[HX_KIND] = 0;
-    flag_set(c.misc + HX_JOB, ++c.hseq);
+    // a generic-nv kernel has no such waves (solver_helper_loop): no wave reads these two slots.  The store is kept only because
+    // removing it changes the generic kernels' instructions, which needs a measurement of its own
+    if (LANE == 0) c.misc[HX_UNREAD_KIND] = 0;
+    flag_set(c.misc + HX_UNREAD_SEQ, ++c.hseq);
   }
 #endif
   // (a step that already overflowed a buffer fails with that code alone: what the solver made of the truncated rows does not matter)
@@ -456,7 +453,7 @@ DEV_NOINLINE void ph_noslip(KP Kc, int last) {
 template <int NVT>
 DEV_NOINLINE void ph_solve_helper(KP Kc, int t) {
   Ctx c; ctx_open(c, Kc, 1);
-  // helper k = wave k + 1 (each index is its own instantiation: the column / entry ranges are compile-time)
+  // helper k = wave k + 1 (each index is its own instantiation)
   int k = WAVE_ID() - 1;
   static_for<0, MJPC_NH>([&](auto Kc_) { constexpr int KK = decltype(Kc_)::value; if (k == KK) solver_helper_loop<NVT, KK>(c, t * 256); });
 }
@@ -530,15 +527,6 @@ DEV_NOINLINE void ph_prefactor(KP Kc) {
   PROFW(c, 11);
   ctx_close(c);
 }
-#if MJPC_HELPER
-// role 1, once its own work of the solve phase is done: one more worker for the owner's per-iterate jobs (elliptic models)
-template <int NVT>
-DEV_NOINLINE void ph_side_worker(KP Kc, int t) {
-  Ctx c; ctx_open(c, Kc, 1);
-  if constexpr (NVT > 0 && MJPC_SOLVER_REG) { if (c.nefc > 0) side_worker<NVT>(c, t); }
-}
-#endif
-
 
 // ---- the implicit integrators' dense path (DevModel::int_dense): implicitfast with fluid forces, and mjINT_IMPLICIT -------------
 // A = M - h dF/dv is built dense in qL and LU-solved (mj_implicit: mjd_smooth_vel + mju_factorLUSparse, no pivoting):
@@ -774,7 +762,7 @@ DEV_NOINLINE void ph_finish(KP Kc, double total, int failure, int t_fail, double
     int resumable = failure && (c.warning & (WARN_CONTACTFULL | WARN_CNSTRFULL)) && !(c.warning & ~(WARN_CONTACTFULL | WARN_CNSTRFULL)) && !(K->xfrc_std > 0);
     if (LANE == 0) {
       ck[0] = resumable ? 1.0 : 0.0; ck[1] = (double)t_fail; ck[2] = c.time; ck[3] = total_before;
-      ck[4] = (double)c.misc[5]; ck[5] = (double)c.misc[6]; ck[6] = (double)c.misc[7];
+      ck[4] = (double)c.misc[MISC_SUM_ITER]; ck[5] = (double)c.misc[MISC_MAX_NCON]; ck[6] = (double)c.misc[MISC_MAX_NEFC];
     }
     if (resumable) {
       PFOR(i, M.nq) ck[CKPT_HEAD + i] = c.qpos[i];
@@ -788,7 +776,7 @@ DEV_NOINLINE void ph_finish(KP Kc, double total, int failure, int t_fail, double
 #if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
     if (K->prof) for (int q = 0; q < NPROF; q++) K->prof[(size_t)r * NPROF + q] = c.prof[q];
 #endif
-    if (K->diag) { K->diag[4 * r] = c.misc[5]; K->diag[4 * r + 1] = c.misc[6]; K->diag[4 * r + 2] = c.misc[7]; K->diag[4 * r + 3] = c.warning; }
+    if (K->diag) { K->diag[4 * r] = c.misc[MISC_SUM_ITER]; K->diag[4 * r + 1] = c.misc[MISC_MAX_NCON]; K->diag[4 * r + 2] = c.misc[MISC_MAX_NEFC]; K->diag[4 * r + 3] = c.warning; }
   }
 }
 
@@ -801,7 +789,7 @@ DEV_NOINLINE void ph_resume(KP Kc) {
   PFOR(i, M.nq) c.qpos[i] = ck[CKPT_HEAD + i];
   PFOR(i, M.nv) { c.qvel[i] = ck[CKPT_HEAD + M.nq + i]; c.qacc_ws[i] = ck[CKPT_HEAD + M.nq + M.nv + i]; }
   if (M.na) PFOR(i, M.na) C_ACT(c)[i] = ck[CKPT_HEAD + M.nq + 2 * M.nv + i];
-  if (LANE == 0) { c.misc[5] = (int)ck[4]; c.misc[6] = (int)ck[5]; c.misc[7] = (int)ck[6]; }
+  if (LANE == 0) { c.misc[MISC_SUM_ITER] = (int)ck[4]; c.misc[MISC_MAX_NCON] = (int)ck[5]; c.misc[MISC_MAX_NEFC] = (int)ck[6]; }
   c.time = ck[2];
   ctx_close(c);
 }
@@ -838,7 +826,7 @@ DEV void rollout(KP Kc) {
     t_fail = t; total_before = total;
     if (r0) ph_head<NVT>(Kc, t, last);
     XBAR(); RPROF(2);
-    if (uniform_i(misc[10])) { failure = 1; break; }
+    if (uniform_i(misc[MISC_BAD_STATE])) { failure = 1; break; }
     if (r0) ph_constraints(Kc, t);
     if (r1) ph_smooth<NVT>(Kc, t);
 #if MJPC_HELPER
@@ -853,12 +841,9 @@ DEV void rollout(KP Kc) {
     if (r1) {
       CostOut o = ph_residual_cost(Kc, t, last); total += o.cost;
       if (!last) ph_prefactor<NVT>(Kc);
-#if MJPC_HELPER
-      ph_side_worker<NVT>(Kc, t);
-#endif
     }
     XBAR(); RPROF(6);
-    if (uniform_i(misc[3]) | uniform_i(misc[11])) { failure = 1; break; }
+    if (uniform_i(misc[MISC_WARNING]) | uniform_i(misc[MISC_WARN_OTHERS])) { failure = 1; break; }
     if (r0 && !last) ph_integrate<NVT>(Kc, t);
   }
   XBAR();

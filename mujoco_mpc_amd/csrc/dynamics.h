@@ -100,9 +100,6 @@ DEV void vel_compose(Ctx &c, int i, double *cvel, double *a, int store) {
 
 // subtree sums of the body forces / momenta left by the sweep.  part 0: cfrc_sub components 0..2; part 1: components 3..5 and
 // subtree_linvel
-#define HX_SWEEP 27      // sweep done (side wave -> last helper), value t + 1
-#define HX_SUBSUM 19     // the helper's part of the subtree sums done, value t + 1
-#define HX_COM 44        // com-based quantities of this step done (side wave -> owner, helper 0), value t + 1
 DEV void subtree_sums(Ctx &c, int part) {
   const DevModel &M = *c.M;
   int per = part ? 6 : 3;
@@ -123,9 +120,6 @@ DEV void subtree_sums(Ctx &c, int part) {
   }
 }
 
-#ifndef MJPC_CHAIN33
-#define MJPC_CHAIN33 1      // the per-lane chain walk of the velocity sweep also for the 33-dof hand (-0.5 %; 0 = level sweep)
-#endif
 // site transmission with a reference site (mj_transmission): entry d of the moment (Jp_site - Jp_ref)^T w, w = the gear in the world
 // frame; zero on the dofs both sites hang from
 DEV double rs_moment(Ctx &c, const int *ri, const double *w, int d) {
@@ -305,7 +299,7 @@ DEV_NOINLINE void ph_smooth_extras(KP Kc) {
   }
 }
 
-// mfact_seq != 0: M's factor is produced by a helper wave; wait for its sequence number (misc[22]) before the solve
+// mfact_seq != 0: M's factor is produced by a helper wave; wait for its sequence number (HX_MFACT) before the solve
 template <int NVT>
 DEV void velocity_stage(Ctx &c, KP Kc, int mfact_seq) {
   const DevModel &M = *c.M;
@@ -315,8 +309,8 @@ DEV void velocity_stage(Ctx &c, KP Kc, int mfact_seq) {
   if (LANE < 6) { c.cfrc[LANE] = 0; c.cacc[LANE] = (LANE >= 3) ? -M.gravity[LANE - 3] : 0.0; }
   SYNC();
 #endif
-  if constexpr (NVT == 27 || (NVT == 33 && MJPC_CHAIN33)) {
-    // the humanoid's 8 tree levels: one lane per body walks its ancestor chain with the running velocity / acceleration in
+  if constexpr (NVT == 27 || NVT == 33) {
+    // the humanoid's 8 tree levels (and the 33-dof hand: -0.5 % against the level sweep): one lane per body walks its ancestor chain with the running velocity / acceleration in
     // registers, like kinematics (-1.3 % of its step; the A1's 4 levels are cheaper as a level sweep, and keeping both forms in
     // one instantiation costs it +0.7 %, hence the compile-time choice)
     PFOR(b, M.nbody) {
@@ -408,7 +402,7 @@ DEV void velocity_stage(Ctx &c, KP Kc, int mfact_seq) {
   }
   PFOR(d, nv) c.qacc_smooth[d] = c.qfrc_smooth[d];
   PROFW(c, 5);
-  if (mfact_seq && !flag_wait(c.misc + 22, mfact_seq)) c.warning |= WARN_SYNC;
+  if (mfact_seq && !flag_wait(c.misc + HX_MFACT, mfact_seq)) c.warning |= WARN_SYNC;
   PROFW(c, 7);
   chol_solve<NVT>(c.qL, c.Linv, c.qacc_smooth, nv, M.nvp, M.tree_ok);
   PROFW(c, 8);

@@ -2,7 +2,7 @@
 //
 // Kernels (gfx950, wave64):
 //   noise_kernel    Philox4x32-10 + Box-Muller standard normals  eps[nlocal, P, nu]
-//   rollout_kernel  (rollout_cached.hip / rollout_direct.hip)  ONE WORKGROUP PER CANDIDATE (grid = nlocal blocks x 64*MJPC_WAVES threads: an owner wave on the
+//   rollout_kernel  (rollout_cached / _dense2 / _dense2h / _direct / _spill.hip)  ONE WORKGROUP PER CANDIDATE (grid = nlocal blocks x 64*MJPC_WAVES threads: an owner wave on the
 //                   critical path + helper / side waves on the CU's other SIMDs, see spmd.h); the candidate's
 //                   whole mjData-equivalent lives in dynamic LDS for all H steps; HBM traffic is only
 //                   the Trajectory record (coalesced row writes by the owning wave) + model reads
@@ -25,7 +25,7 @@
 #include "../../include/mjpc_hip_debug.h"
 
 // ------------------------------------------------------------------------------ kernels
-// the rollout kernels live in their own translation units (rollout_cached.hip, rollout_direct.hip; see rollout_tu.inc)
+// the rollout kernels live in their own translation units (rollout_*.hip, one per flavour; see rollout_tu.inc)
 typedef void (*RolloutFn)(const KParams);
 extern "C" RolloutFn mjpc_pick_rollout_cached(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_direct(int nv, int *exact);

@@ -185,7 +185,7 @@ static inline void make_layout(const PackedModel &p, Lay &L, const MjpcHipModel 
   // the register Newton path (solver_reg.h) uses the same block for its gradient scratch (64), the line search's row / contact
   // records (7 per row, 17 per contact) and, on elliptic models, the contacts' dof lists (a byte per dof), their (contact, row) pairs (two bytes each) and one partial Hessian
   // per worker wave (nv x nvp each)
-  int ja_need = 64 + ne * 7 + nc * 17 + (m->cone == MJPC_CONE_ELLIPTIC ? (nc * nv + 7) / 8 + (nc * nv + 3) / 4 + (MJPC_SIDE_JOB > 0 ? 3 : 2) * nv * nvp : 0);
+  int ja_need = 64 + ne * 7 + nc * 17 + (m->cone == MJPC_CONE_ELLIPTIC ? (nc * nv + 7) / 8 + (nc * nv + 3) / 4 + 2 * nv * nvp : 0);
   // reg_solver: the kernel is a compile-time-nv instantiation, whose Newton solve keeps the Hessian in registers and never
   // builds the scaled-row table: the block only has to hold the records / partials above (hand: 12 KB instead of 35 KB)
   int ja_size = reg_solver ? ja_need + 1 : ja_rows * nvp + 1;

@@ -176,14 +176,7 @@ template <int N> constexpr int tree_level_pair(int H, int e, bool pivot) {
   }
   return 0;
 }
-#ifndef MJPC_TREE_CHUNK
-#define MJPC_TREE_CHUNK 8
-#endif
-#ifdef MJPC_TREE_NOBAR
-#define TREE_BAR() ((void)0)
-#else
 #define TREE_BAR() __builtin_amdgcn_sched_barrier(0)
-#endif
 template <int N>
 DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
   static_assert(DofTree<N>::known && N <= 64, "one matrix row per lane");
@@ -211,10 +204,11 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
       }
     });
     constexpr int NP = tree_level_npair<N>(H);            // A[i][j] -= L[k][i] * A[k][j], j ancestor of k
-    static_for<0, (NP + MJPC_TREE_CHUNK - 1) / MJPC_TREE_CHUNK>([&](auto gc) {
-      constexpr int e0 = decltype(gc)::value * MJPC_TREE_CHUNK;
-      double sj[MJPC_TREE_CHUNK];
-      static_for<0, MJPC_TREE_CHUNK>([&](auto qc) {
+    constexpr int CHUNK = 8;                              // pairs fetched (readlane) ahead of their updates
+    static_for<0, (NP + CHUNK - 1) / CHUNK>([&](auto gc) {
+      constexpr int e0 = decltype(gc)::value * CHUNK;
+      double sj[CHUNK];
+      static_for<0, CHUNK>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         if constexpr (e0 + q < NP) {
           constexpr int j = tree_level_pair<N>(H, e0 + q, false), k = tree_level_pair<N>(H, e0 + q, true);
@@ -222,7 +216,7 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
         }
       });
       TREE_BAR();
-      static_for<0, MJPC_TREE_CHUNK>([&](auto qc) {
+      static_for<0, CHUNK>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         if constexpr (e0 + q < NP) {
           constexpr int j = tree_level_pair<N>(H, e0 + q, false), k = tree_level_pair<N>(H, e0 + q, true);

@@ -21,9 +21,6 @@
 #define CON_SOLIMP 21
 #define CON_MU 26
 #define CON_H 27
-#ifndef MJPC_SIDE_JOB
-#define MJPC_SIDE_JOB 0      // elliptic models: the side wave shares the owner's per-iterate jobs from this job of a step on (1 = the first; 0 = never: measured slower on the A1)
-#endif
 #define CONI_STRIDE 4          // ints per contact: dim, geom1, geom2, efc_address
 #define MAX_ACTIVE_PAIRS 192
 // efc_id of a contact row: contact index | contact dim << 8 | first row of the contact << 16
@@ -176,7 +173,44 @@ struct DevModel {
 #define SPILL_EFC_VEC 16u      // the eight efc_* vectors (with their aliases efc_margin / efc_diag)
 #define SPILL_EVERY 31u
 enum { SPILL_NONE = 0, SPILL_AUTO = 1, SPILL_ALL = 2 };
-#define MISC_INTS 48     // per-candidate scalars and hand-shake flags in LDS (core.h / solver.h: misc[])
+#define MISC_INTS 48     // per-candidate scalars and hand-shake flags in LDS: Ctx::misc[], every slot in use is listed here
+// "owner" = wave 0, "helper 0 / 1" = waves 1 / 2, "side" = wave 3 (spmd.h).  A flag carries a sequence number (t + 1 of step t
+// unless noted): the writer flag_set()s it, the waiter flag_wait()s for it.  Slots not listed are free (ph_init clears them all).
+enum {
+  MISC_NCON = 0,          // the owner's scalars between its phases (ctx_close -> ctx_open): contacts,
+  MISC_NEFC = 1,          //   constraint rows,
+  MISC_NSINGLE = 2,       //   single-entry rows,
+  MISC_WARNING = 3,       //   WARN_* bits (the rollout loop of every wave reads it after the solve phase),
+  MISC_SOLVER_ITER = 4,   //   Newton iterations of the last solve,
+  MISC_SUM_ITER = 5,      // diagnostics, owner -> ph_finish (side): Newton iterations of the rollout,
+  MISC_MAX_NCON = 6,      //   most contacts of a step,
+  MISC_MAX_NEFC = 7,      //   most rows of a step
+  MISC_CROSS = 8,         // owner's scalar: this step has a contact across branches of the dof tree (dense Hessian build)
+  MISC_QH_DENSE = 9,      // generic solver: the last Hessian build was a dense one.  Written only, no wave reads it
+  MISC_BAD_STATE = 10,    // ph_head (owner): bad qpos / qvel, every wave leaves the rollout loop
+  MISC_WARN_OTHERS = 11,  // WARN_* bits of the helper and side waves (atomic or), read by the owner and the rollout loop
+  HX_UNREAD_SEQ = 12,     // generic-nv kernels: the owner's release store after the solve (hseq).  No wave reads it
+  HX_UNREAD_KIND = 13,    //   and its job kind (0).  No wave reads it
+  //                 14 - 16 free
+  HX_LSREC = 17,          // line-search records of this step ready: helper 0 -> owner, helper 1
+  HX_JOBW = 18,           // the owner's cone-block job, one packed word JOBW(seq, workers, kind) -> helpers (solver_reg.h)
+  HX_SUBSUM = 19,         // helper 1's part of the subtree sums done -> side
+  //                 20, 21 free
+  HX_MFACT = 22,          // factor of M ready: helper 0 -> side
+  HX_CSM = 23,            // cost at qacc_smooth in red[2]: helper 1 -> owner
+  HX_NCROWS = 24,         // contact-free rows built, their counts in the next two slots: helper 1 -> owner
+  HX_NC_NSINGLE = 25,     //   single-entry rows
+  HX_NC_ROWS = 26,        //   contact-free rows
+  HX_SWEEP = 27,          // velocity sweep done: side -> helper 1
+  //                 28 - 35 free
+  HX_WDONE = 36,          // + w: worker w (= helper w) finished job seq -> owner
+  HX_WDONE_END = 38,
+  //                 38 - 43 free
+  HX_COM = 44,            // com-based quantities of this step done (MJPC_SIDE_COM): side -> owner, helpers
+  HX_NITEMS = 45,         // (contact, row) pairs in CONE_ITEMS: helper 0 -> helpers, published by HX_LSREC
+  HX_HEAVY = 46           // owner's scalar: the previous step's first collision batch needed an out-of-line collider
+};
+static_assert(HX_HEAVY < MISC_INTS && HX_WDONE_END <= MISC_INTS, "misc[] slot beyond MISC_INTS");
 struct Lay {
   int qpos, qvel, ctrl, qacc, qacc_ws, qacc_smooth, qfrc_smooth, qfrc_bias, qfrc_constraint, actuator_force;
   int mocap_pos, mocap_quat;

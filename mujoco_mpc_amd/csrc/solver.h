@@ -1,8 +1,10 @@
 // solver.h — primal Newton solver for  min_a 1/2 (a-a0)^T M (a-a0) + sum_i s_i(J_i a - aref_i)
-// (what MuJoCo's default solver computes inside mj_step, mjpc/trajectory.cc:158): one owner wavefront, optionally helped by
-// the candidate's helper waves for the data-parallel parts of an iteration.
+// (what MuJoCo's default solver computes inside mj_step, mjpc/trajectory.cc:158), run by the owner wavefront.  This file holds
+//   * the pieces both solvers share: constraint_update, mat_rows_times, solver_eval, cost_at_smooth and the helper waves' loop;
+//   * the generic-nv solver (newton_lists .. line_search and the tail of solve_constraints): the <0> kernels and the emulation.
+// A kernel with a compile-time dof count leaves solve_constraints() at once for solver_reg.h.
 //
-// Layout of the work over the 64 lanes of the owner wave:
+// Layout of the generic solver's work over the 64 lanes of the owner wave:
 //   * rows with a single +-1 Jacobian entry (friction loss, joint limits: [0, nsingle)) only touch the Hessian diagonal
 //     (`sgl`); every active contact row becomes one scaled row  sum_b coef_b J[row_b]  (plus one negative row per contact in
 //     the cone zone), so that  H = M + JH+^T JH+ - JH-^T JH-  is a plain contraction over M's sparsity pattern and the
@@ -239,6 +241,7 @@ DEV double solver_eval(Ctx &c, const double *qacc, double *gauss_out) {
   return gauss + cc;
 }
 
+// ---- the generic-nv solver ----
 // gradient and Hessian (lower triangle); newton_direction() then solves Mgrad = H^-1 grad.
 // Every active contact row contributes one scaled row  jh = sum_b coef_b J[row_b]  with  H += jh jh^T:
 //   quadratic row r: sqrt(D_r) J_r;   cone contact: p-row (normal row's slot), sqrt(kap) fr_t J_t for its tangential rows,
@@ -270,12 +273,12 @@ DEV void newton_lists(Ctx &c, int *npos_out, int *nneg_out) {
   *npos_out = npos; *nneg_out = nneg;
 }
 
-// scaled rows JH[e][C0..C1) (+ the phi column when PHI): rows [0, npos8) positives zero-padded to a multiple of 8,
-// rows [npos8, npos8 + nneg4) negatives padded to 4.  The column range lets two waves share the fill.
-template <int NVT, int C0, int C1, int PHI, int DIMT>
+// scaled rows JH[e][0..nv) + the phi column: rows [0, npos8) positives zero-padded to a multiple of 8,
+// rows [npos8, npos8 + nneg4) negatives padded to 4
+template <int DIMT>
 DEV void newton_fill_d(Ctx &c, int npos, int nneg) {
   const DevModel &M = *c.M;
-  const int nv = NVT > 0 ? NVT : M.nv, nvp = NVT > 0 ? NVP_OF(NVT) : M.nvp;
+  const int nv = M.nv, nvp = M.nvp;
   const int negbase = M.nefcmax;
   const int npos8 = (npos + 7) & ~7, nneg4 = (nneg + 3) & ~3;
   int ntot = npos8 + nneg4;
@@ -314,64 +317,37 @@ DEV void newton_fill_d(Ctx &c, int npos, int nneg) {
     }
     nb = caseP ? dim : (caseQ ? dim - 1 : (valid ? 1 : 0));
     phi = caseD ? frc * rs : (caseP ? ct[0] : 0.0);      // sqrt(D) J * phi = J^T force (force = -D jar on a quadratic row)
-    if constexpr (NVT > 0) {
-      constexpr int NC = C1 - C0;
-      double acc[NC > 0 ? NC : 1];
-      // all the Jacobian rows of the combination are fetched before the first use (unused slots: coefficient 0 on a valid row)
-      double Jv[DIMT][NC > 0 ? NC : 1];
+    if (e < ntot) {
+      double *o = JH + e * nvp;
+      for (int j = 0; j < nv; j++) {
+        double a = 0;
 #pragma unroll
-      for (int b = 0; b < DIMT; b++) {
-        const double *Jr = c.efc_J + rowb[b] + C0;
-#pragma unroll
-        for (int j = 0; j < NC; j++) Jv[b][j] = Jr[j];
+        for (int b = 0; b < DIMT; b++) if (b < nb) a += coef[b] * c.efc_J[rowb[b] + j];
+        o[j] = a;
       }
-#pragma unroll
-      for (int j = 0; j < NC; j++) acc[j] = coef[0] * Jv[0][j];
-#pragma unroll
-      for (int b = 1; b < DIMT; b++)
-#pragma unroll
-        for (int j = 0; j < NC; j++) acc[j] += coef[b] * Jv[b][j];
-      if (e < ntot) {
-        double *o = JH + e * nvp + C0;
-#pragma unroll
-        for (int j = 0; j < NC; j++) o[j] = valid ? acc[j] : 0.0;
-        if (PHI) JH[e * nvp + NVT] = phi;
-      }
-    } else {
-      if (e < ntot) {
-        double *o = JH + e * nvp;
-        for (int j = 0; j < nv; j++) {
-          double a = 0;
-#pragma unroll
-          for (int b = 0; b < DIMT; b++) if (b < nb) a += coef[b] * c.efc_J[rowb[b] + j];
-          o[j] = a;
-        }
-        o[nv] = phi;
-      }
+      o[nv] = phi;
     }
   }
 }
 
-template <int NVT, int C0, int C1, int PHI>
 DEV void newton_fill(Ctx &c, int npos, int nneg) {
-  if (c.M->maxdim <= 3) newton_fill_d<NVT, C0, C1, PHI, 3>(c, npos, nneg);
-  else newton_fill_d<NVT, C0, C1, PHI, 6>(c, npos, nneg);
+  if (c.M->maxdim <= 3) newton_fill_d<3>(c, npos, nneg);
+  else newton_fill_d<6>(c, npos, nneg);
 }
 
 // H = M + diag(single-entry rows) + JH+^T JH+ - JH-^T JH-  on the lower triangle (only M's sparsity pattern without
-// cross-branch contacts), and grad = Ma - qfrc_smooth - J^T force  as the entries (i, nv).  Entries e = part*NLANE + LANE
-// + g*NLANE*nparts belong to this wave; each lane carries G of them through the row loop together (G*16 independent LDS
-// reads in flight per trip; the row counts are multiples of 8 / 4).
-template <int NVT, int G>
-DEV void newton_entries(Ctx &c, int npos, int nneg, int grad_only, int part, int nparts) {
+// cross-branch contacts), and grad = Ma - qfrc_smooth - J^T force  as the entries (i, nv).  Each lane carries G entries
+// through the row loop together (G*16 independent LDS reads in flight per trip; the row counts are multiples of 8 / 4).
+DEV void newton_entries(Ctx &c, int npos, int nneg, int grad_only) {
+  constexpr int G = 3;
   const DevModel &M = *c.M;
-  const int nv = NVT > 0 ? NVT : M.nv, nvp = NVT > 0 ? NVP_OF(NVT) : M.nvp;
+  const int nv = M.nv, nvp = M.nvp;
   const int npos8 = (npos + 7) & ~7, ntot = npos8 + ((nneg + 3) & ~3);
   const double *JH = c.efc_JA;
   int nh = c.cross ? nv * (nv + 1) / 2 : M.nhpair;
   int nent = nh + nv;
-  const int stride = NLANE * nparts;
-  for (int e0 = (grad_only ? nh : 0) + part * NLANE + LANE; e0 < nent; e0 += G * stride) {
+  const int stride = NLANE;
+  for (int e0 = (grad_only ? nh : 0) + LANE; e0 < nent; e0 += G * stride) {
     int ii[G], jj[G];
 #pragma unroll
     for (int g = 0; g < G; g++) {
@@ -435,80 +411,30 @@ DEV void newton_entries(Ctx &c, int npos, int nneg, int grad_only, int part, int
   }
 }
 
-// ---- the solver's helper waves (MJPC_WAVES >= 3, compile-time nv): NH = MJPC_WAVES - 2 helpers share the scaled-row fill
-// (column thirds / halves) and the Hessian / gradient entries with the owner wave.  Hand-shake through sequence numbers
-// in LDS (misc[12..]):
-//   owner:    lists -> publish npos/nneg -> post job seq -> fill its columns -> W0FILL=seq -> wait HFILL_k==seq (all k)
-//             -> its entries -> wait HDONE_k==seq (all k)
-//   helper k: wait job seq -> fill its columns -> HFILL_k=seq -> wait W0FILL==seq and the other helpers' HFILL -> its entries
-//             -> HDONE_k=seq
-#define HX_JOB 12
-#define HX_KIND 13
-#define HX_W0FILL 14
-#define HX_NPOS 15
-#define HX_NNEG 16
-#define HX_HFILL 28      // + k (k < 8)
-#define HX_HDONE 36      // + k
-#ifndef MJPC_SPLIT_FILL
-#define MJPC_SPLIT_FILL 1
-#endif
-#define HX_MFACT 22      // factor of M ready (helper 0 -> side wave), value t + 1
-
-// column range of part p of NP for an NVT-wide row
-#define FILL_C0(NVT, p, NP) ((NVT) * (p) / (NP))
-#define FILL_C1(NVT, p, NP) ((NVT) * ((p) + 1) / (NP))
-
-template <int NVT>
 DEV void newton_gradient(Ctx &c, int grad_only) {
   const DevModel &M = *c.M;
-  const int nv = NVT > 0 ? NVT : M.nv, nvp = NVT > 0 ? NVP_OF(NVT) : M.nvp;     // compile-time strides => immediate LDS offsets
+  const int nvp = M.nvp;
   PROF(c, 13);
   int npos, nneg;
   newton_lists(c, &npos, &nneg);
   PROF(c, 15);
-#if MJPC_HELPER
-  if (NVT > 0 && !grad_only) {
-    constexpr int NP = MJPC_NH + 1;
-    int seq = ++c.hseq;
-#if MJPC_SPLIT_FILL
-    if (LANE == 0) { c.misc[HX_NPOS] = npos; c.misc[HX_NNEG] = nneg; c.misc[HX_KIND] = 1; }
-    flag_set(c.misc + HX_JOB, seq);
-    newton_fill<NVT, FILL_C0(NVT, 0, NP), FILL_C1(NVT, 0, NP), 0>(c, npos, nneg);
-    flag_set(c.misc + HX_W0FILL, seq);
-    PROF(c, 19);
-    for (int k = 0; k < MJPC_NH; k++) if (!flag_wait(c.misc + HX_HFILL + k, seq)) c.warning |= WARN_SYNC;
-    PROF(c, 18);
-#else
-    // the owner fills all the scaled rows, then posts the job: one hand-shake (entries done) per call instead of two
-    newton_fill<NVT, 0, NVT, 1>(c, npos, nneg);
-    if (LANE == 0) { c.misc[HX_NPOS] = npos; c.misc[HX_NNEG] = nneg; c.misc[HX_KIND] = 1; }
-    flag_set(c.misc + HX_JOB, seq);
-#endif
-    newton_entries<NVT, (NP >= 3 ? 1 : 2)>(c, npos, nneg, 0, 0, NP);
-    PROF(c, 9);
-    for (int k = 0; k < MJPC_NH; k++) if (!flag_wait(c.misc + HX_HDONE + k, seq)) c.warning |= WARN_SYNC;
-    PROF(c, 10);
-  } else
-#endif
-  {
-    newton_fill<NVT, 0, NVT, 1>(c, npos, nneg);
-    PROF(c, 19);
-    SYNC();
-    newton_entries<NVT, 3>(c, npos, nneg, grad_only, 0, 1);
-  }
-  // structural zeros of the pattern: the register factorisation never writes qH, so they only need clearing after a
-  // dense (cross-branch) build; the generic in-place LDS factor fills them every time
-  if (c.cross) { if (LANE == 0) c.misc[9] = 1; }
-  else if (NVT == 0 || uniform_i(c.misc[9])) {
+  newton_fill(c, npos, nneg);
+  PROF(c, 19);
+  SYNC();
+  newton_entries(c, npos, nneg, grad_only);
+  // structural zeros of the pattern: the in-place LDS factor fills them every time
+  if (c.cross) { if (LANE == 0) c.misc[MISC_QH_DENSE] = 1; }
+  else {
     PFOR(e, M.nzpair) c.qH[MI(zpair_i)[e] * nvp + MI(zpair_j)[e]] = 0;
-    if (LANE == 0) c.misc[9] = 0;
+    if (LANE == 0) c.misc[MISC_QH_DENSE] = 0;
   }
   SYNC();
   PROF(c, 16);
 }
+
+// ---- shared by both solvers: the helper waves' part of a solve phase, the Newton direction from qH in LDS ----
 // helper wave: total cost at qacc_smooth (Gauss term is exactly 0 there), same arithmetic as solver_eval; the residuals go
 // to the scratch array efc_pos (consumed by make_impedance before the solve phase), nothing the owner uses is written
-#define HX_CSM 23
 template <int NVT>
 DEV double cost_at_smooth(Ctx &c) {
   double *jar = c.efc_pos;
@@ -519,44 +445,23 @@ DEV double cost_at_smooth(Ctx &c) {
   return 0.0 + wave_sum(part);
 }
 
-#ifndef MJPC_SOLVER_REG
-#define MJPC_SOLVER_REG 1      // compile-time nv: the owner wave solves alone with the Hessian in registers (solver_reg.h); 0 = scaled-row tables shared with the helper waves
-#endif
 #if MJPC_HELPER
 template <int NVT> DEV void worker_loop(Ctx &c, int W, int last);          // solver_reg.h
 template <int NVT> DEV void ls_records_build(Ctx &c);
-#define HX_LSREC 17      // line-search records of this step ready (helper 0 -> owner), value t + 1
+// helper K of a solve phase: the last one prices the unconstrained acceleration; with a compile-time nv helper 0 builds the line
+// search's records and both then serve the owner's cone-block jobs (solver_reg.h).  A generic-nv kernel has no jobs for them.
 template <int NVT, int K>
 DEV void solver_helper_loop(Ctx &c, int seq) {
   if (K == MJPC_NH - 1 && c.nefc > 0) {            // the last helper prices the unconstrained acceleration for the warm-start choice
     double cs = cost_at_smooth<NVT>(c);
     if (LANE == 0) c.red[2] = cs;
-    // fault injection for the test-suite (fault = 1): the helper of candidate 1 never reports this price in step 2
-    const int mute_csm = MJPC_SOLVER_REG && c.K->fault == 1 && cand_index() == 1 && seq == 2 * 256;
+    // fault injection for the test-suite (diagnostics knob fault_inject = sync, mjpc_hip_debug.h): the helper of candidate 1 never reports this price in step 2
+    const int mute_csm = c.K->fault == 1 && cand_index() == 1 && seq == 2 * 256;
     if (!mute_csm) flag_set(c.misc + HX_CSM, seq / 256 + 1);
   }
-  if constexpr (NVT > 0 && MJPC_SOLVER_REG) {
+  if constexpr (NVT > 0) {
     if (K == 0 && c.nefc > 0) { ls_records_build<NVT>(c); flag_set(c.misc + HX_LSREC, seq / 256 + 1); }     // the line search's per-step constants
     worker_loop<NVT>(c, K, seq);
-  }
-  if constexpr (NVT > 0 && !MJPC_SOLVER_REG) {
-    constexpr int NP = MJPC_NH + 1;
-    // fault injection for the test-suite (diagnostics knob fault_inject = sync, mjpc_hip_debug.h): helper 0 of candidate 1 never reports its fill in step 2
-    const int mute = c.K->fault == 1 && K == 0 && cand_index() == 1 && seq == 2 * 256;
-    for (;;) {
-      seq++;
-      if (!flag_wait(c.misc + HX_JOB, seq)) return;             // timed out: the owner reports the failure
-      if (uniform_i(c.misc[HX_KIND]) == 0) return;
-      int npos = uniform_i(c.misc[HX_NPOS]), nneg = uniform_i(c.misc[HX_NNEG]);
-#if MJPC_SPLIT_FILL
-      newton_fill<NVT, FILL_C0(NVT, K + 1, NP), FILL_C1(NVT, K + 1, NP), (K + 1 == NP - 1)>(c, npos, nneg);
-      if (!mute) flag_set(c.misc + HX_HFILL + K, seq);
-      if (!flag_wait(c.misc + HX_W0FILL, seq)) return;
-      for (int k = 0; k < MJPC_NH; k++) if (k != K && !flag_wait(c.misc + HX_HFILL + k, seq)) return;
-#endif
-      newton_entries<NVT, (NP >= 3 ? 1 : 2)>(c, npos, nneg, 0, K + 1, NP);
-      flag_set(c.misc + HX_HDONE + K, seq);
-    }
   }
 }
 #endif
@@ -575,7 +480,7 @@ DEV void newton_direction_sum(Ctx &c, const LDLExtra &ex) {
 }
 #endif
 
-// ---- exact line search: phi(alpha) = Gauss(alpha) + sum_i s_i(jar + alpha*jv), data in registers
+// ---- the generic solver's exact line search: phi(alpha) = Gauss(alpha) + sum_i s_i(jar + alpha*jv), data in registers
 // Row costs in one branch-free form: with xc = clamp(x, lo, hi),
 //   s(x) = 1/2 D xc^2 + F (|x| - |xc|),  s' = D xc,  s'' = D inside (lo, hi)
 // (friction loss: lo/hi = -+R f, F = f;  unilateral rows: lo = -inf, hi = 0, F = 0;  unused slots: D = F = 0).
@@ -687,12 +592,12 @@ DEV LSPoint ls_eval(const LSData<DIMT> &d, double q0, double q1, double q2, doub
 }
 
 // returns alpha; q1/q2 = Gauss quadratic coefficients along the direction (for the incremental update)
-template <int NVT, int DIMT>
+template <int DIMT>
 DEV double line_search(Ctx &c, double gauss, double cost0, double *q1_out, double *q2_out) {
   const DevModel &M = *c.M;
   int nv = M.nv;
   double p_sn = 0, p_q1 = 0, p_q2 = 0, p_gs = 0;
-  mat_rows_times<NVT>(c, c.search, c.Mv, c.efc_jv);
+  mat_rows_times<0>(c, c.search, c.Mv, c.efc_jv);
   PFOR(i, nv) {
     double si = c.search[i];
     p_sn += si * si; p_q1 += si * (c.Ma[i] - c.qfrc_smooth[i]); p_q2 += 0.5 * si * c.Mv[i]; p_gs += c.grad[i] * si;
@@ -753,47 +658,48 @@ DEV double line_search(Ctx &c, double gauss, double cost0, double *q1_out, doubl
 template <int NVT>
 DEV void solve_constraints(Ctx &c) {
   const DevModel &M = *c.M;
-  int nv = M.nv, nvp = M.nvp;
+  int nv = M.nv;
   c.solver_iter = 0;
   if (c.nefc == 0) {
     PFOR(i, nv) { c.qacc[i] = c.qacc_smooth[i]; c.qfrc_constraint[i] = 0; }
     SYNC();
     return;
   }
-#if !defined(MJPC_EMU) && MJPC_SOLVER_REG
+#ifndef MJPC_EMU
   if constexpr (NVT > 0) { solve_constraints_reg<NVT>(c); return; }
 #endif
+  // from here on the generic-nv solve: only reached with NVT == 0
   PROF(c, 7);
   // warm start: the better of qacc_smooth and qacc_warmstart (evaluated last, so its force/state stay valid)
   double gauss, cost;
   double cost_sm;
 #if MJPC_HELPER
-  double cost_ws = solver_eval<NVT>(c, c.qacc_ws, &gauss);
+  double cost_ws = solver_eval<0>(c, c.qacc_ws, &gauss);
   if (!flag_wait(c.misc + HX_CSM, c.hseq / 256 + 1)) c.warning |= WARN_SYNC;     // priced by the last helper meanwhile
   cost_sm = c.red[2];
 #else
-  cost_sm = solver_eval<NVT>(c, c.qacc_smooth, 0);
-  double cost_ws = solver_eval<NVT>(c, c.qacc_ws, &gauss);
+  cost_sm = solver_eval<0>(c, c.qacc_smooth, 0);
+  double cost_ws = solver_eval<0>(c, c.qacc_ws, &gauss);
 #endif
   if (cost_ws > cost_sm) {
     PFOR(i, nv) c.qacc[i] = c.qacc_smooth[i];
     SYNC();
-    cost = solver_eval<NVT>(c, c.qacc, &gauss);
+    cost = solver_eval<0>(c, c.qacc, &gauss);
   } else {
     PFOR(i, nv) c.qacc[i] = c.qacc_ws[i];
     SYNC();
     cost = cost_ws;
   }
   PROF(c, 12);
-  newton_gradient<NVT>(c, 0);
-  newton_direction<NVT>(c);
+  newton_gradient(c, 0);
+  newton_direction<0>(c);
   PFOR(i, nv) c.search[i] = -c.Mgrad[i];
   SYNC();
   double scale = 1.0 / (M.meaninertia * (nv > 1 ? nv : 1));
   for (int iter = 0; iter < M.iterations; iter++) {
     PROF(c, 13);
     double q1, q2;
-    double alpha = (M.maxdim <= 3) ? line_search<NVT, 3>(c, gauss, cost, &q1, &q2) : line_search<NVT, 6>(c, gauss, cost, &q1, &q2);
+    double alpha = (M.maxdim <= 3) ? line_search<3>(c, gauss, cost, &q1, &q2) : line_search<6>(c, gauss, cost, &q1, &q2);
     PROF(c, 14);
     if (alpha == 0) break;
     PFOR(i, nv) { c.qacc[i] += alpha * c.search[i]; c.Ma[i] += alpha * c.Mv[i]; }
@@ -808,17 +714,17 @@ DEV void solve_constraints(Ctx &c) {
     // about to stop is skipped (its direction would never be used)
     double improvement = scale * (oldcost - cost);
     int stop = improvement < M.tolerance || (c.warning & WARN_SYNC) != 0;      // a lost hand-shake ends the solve (the candidate fails)
-    newton_gradient<NVT>(c, stop);
+    newton_gradient(c, stop);
     c.solver_iter++;
     double pg = 0;
     PFOR(i, nv) pg += c.grad[i] * c.grad[i];
     double gradient = scale * sqrt(wave_sum(pg));
     if (stop || gradient < M.tolerance) break;
-    newton_direction<NVT>(c);
+    newton_direction<0>(c);
     PFOR(i, nv) c.search[i] = -c.Mgrad[i];
     SYNC();
   }
-  if (LANE == 0) { c.misc[5] += c.solver_iter; if (c.ncon > c.misc[6]) c.misc[6] = c.ncon; if (c.nefc > c.misc[7]) c.misc[7] = c.nefc; }
+  if (LANE == 0) { c.misc[MISC_SUM_ITER] += c.solver_iter; if (c.ncon > c.misc[MISC_MAX_NCON]) c.misc[MISC_MAX_NCON] = c.ncon; if (c.nefc > c.misc[MISC_MAX_NEFC]) c.misc[MISC_MAX_NEFC] = c.nefc; }
   // J^T force of the final state: the last newton_gradient() evaluated grad = Ma - qfrc_smooth - J^T force there
   PFOR(i, nv) c.qfrc_constraint[i] = (c.Ma[i] - c.qfrc_smooth[i]) - c.grad[i];
   SYNC();

@@ -1,4 +1,5 @@
-// solver_reg.h — the Newton solve for a compile-time dof count (gfx950 only), run by the owner wave alone.
+// solver_reg.h — the compile-time-nv solver: the Newton solve of a kernel whose dof count is a template argument (gfx950 only; the
+// emulation and the <0> kernels use the generic solver in solver.h), run by the owner wave.
 //
 // Same minimisation as solver.h (MuJoCo's primal Newton inside mj_step, mjpc/trajectory.cc:158), organised around what one
 // wavefront keeps in registers instead of around scaled-row tables in LDS:
@@ -15,9 +16,6 @@
 // contacts (J^T force, the contacts' cone blocks) is one job per iterate for the candidate's other waves (worker_job below).
 #pragma once
 #ifndef MJPC_EMU
-#ifndef LS_PREDICT
-#define LS_PREDICT 1
-#endif
 
 template <int NVT> struct HLay {
   static constexpr int G0 = 64 / NVT;
@@ -131,14 +129,10 @@ DEV void newton_grad_reg(Ctx &c, int hi, int hg, bool hact) {
 // worker's partial Hessian with an LDS fp64 atomic add (ds_add_f64: rows of different contacts meet in the entries of their common
 // dofs).  Worker w of np takes the passes w, w + np, ... of 64 pairs.  The owner posts ONE packed word (sequence number, number of
 // workers, kind), meanwhile updates its register blocks, builds the gradient and stores its own part of H.
-//   workers 0 .. MJPC_NH-1 = the helper waves (in every job); worker MJPC_NH = the side wave from job MJPC_SIDE_JOB of a step on.
+//   workers 0 .. MJPC_NH-1 = the helper waves (in every job).
 // kind: 0 release (solve over) | 1 cone blocks
-#define HX_JOBW 18
-#define HX_SIDEFROM 21
-#define HX_NITEMS 45
-#define HX_WDONE HX_HDONE
 #define JOBW(seq, np, kind) (((seq) << 4) | ((np) << 2) | (kind))
-#define MJPC_NW (MJPC_NH + 1)
+static_assert(HX_WDONE + MJPC_NH <= HX_WDONE_END, "one done slot per worker");
 // behind the line-search records: the contacts' dof lists (one byte per dof, nv per contact), the (contact, row) pairs (two bytes
 // each), then one partial Hessian per worker (nv x nvp each, lower triangle).  The owner never adds them up: its own part goes to
 // qH and the factorisation sums qH and the partials while it loads its rows (ldl_load_row)
@@ -206,25 +200,14 @@ DEV void cone_rows(const Ctx &c, double *part, int p0, int pstep) {
   }
 }
 
-#if MJPC_HELPER
 DEV int jobw_load(const Ctx &c) { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(c.misc + HX_JOBW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 // owner: post the job of the iterate whose zones / cone records are in LDS; returns the number of workers it was cut for
-template <int NVT>
+// (always the same workers: the partition of the sums - and with it every rounding - must not depend on timing).
+// side_in is what is left of the side wave as a third worker (measured slower): always 0.  Dropping the
+// argument changes the order of ph_solve's instructions, so it waits for a change that measures the kernel.
 DEV int job_post(Ctx &c, int kind, int &side_in) {
   if (c.M->cone != 1) return 0;
   const int seq = ++c.hseq;
-  // WHICH jobs the side wave shares is fixed by the job's number, never by who happened to be ready: the partition of the sums -
-  // and with it every rounding - must not depend on timing.  Should the side wave still be busy at its first job, the owner waits.
-  if (MJPC_SIDE_JOB > 0 && !side_in && (seq & 255) >= MJPC_SIDE_JOB) {
-    const int base = seq & ~255;
-    int ok = 0;
-    for (int n = 0; n < (1 << 21); n++) {
-      int from = __builtin_amdgcn_readfirstlane(__hip_atomic_load(c.misc + HX_SIDEFROM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (from > base) { ok = 1; break; }
-    }
-    if (!ok) c.warning |= WARN_SYNC;
-    side_in = 1;
-  }
   const int np = MJPC_NH + (side_in ? 1 : 0);
   flag_set(c.misc + HX_JOBW, JOBW(seq, np, kind));
   return np;
@@ -266,42 +249,16 @@ DEV void worker_loop(Ctx &c, int W, int last) {
   if (c.M->cone != 1) return;
   if (c.M->maxdim <= 3) worker_loop_d<NVT, 3>(c, W, last); else worker_loop_d<NVT, 6>(c, W, last);
 }
-// the side wave joins once its own work of the solve phase is done: it announces the first job it could take
-template <int NVT>
-DEV void side_worker(Ctx &c, int t) {
-  if (c.M->cone != 1 || MJPC_SIDE_JOB <= 0) return;
-  const int base = t * 256;
-  int word = jobw_load(c);
-  int last = base;
-  if ((word >> 4) > base) {
-    if ((word & 3) == 0) return;                              // the solve is already over
-    last = word >> 4;                                         // that job was cut without this wave
-  }
-  if (LANE == 0) __hip_atomic_store(c.misc + HX_SIDEFROM, last + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  worker_loop<NVT>(c, MJPC_NH, last);
-}
-#endif
 
 // qH = hq + diag of the single-entry rows: the owner's part of the Hessian.  The elliptic contacts' blocks are the workers'
-// partials, added by the factorisation (np > 0); a build without worker waves adds them here.
-template <int NVT, int DIMT>
+// partials, added by the factorisation (np > 0).
+template <int NVT>
 DEV void newton_assemble(Ctx &c, const double *hq, int hi, int hg, int j0, bool hact) {
   constexpr int nvp = NVP_OF(NVT), CB = HLay<NVT>::CB;
   double a[CB];
   const double dg = c.sgl[NVT + hi] + c.sgl[3 * NVT + hi];
 #pragma unroll
   for (int q = 0; q < CB; q++) a[q] = hq[q] + ((j0 + q == hi) ? dg : 0.0);
-#if !MJPC_HELPER
-  if (c.M->cone == 1) {
-    // single-wave build: the owner is its own only worker
-    double *part = CONE_PARTIAL(c, 0);
-    PFOR(e, NVT * nvp) part[e] = 0;
-    cone_rows<NVT, DIMT>(c, part, 0, 1);
-    SYNC();
-#pragma unroll
-    for (int q = 0; q < CB; q++) a[q] += (hact && j0 + q <= hi) ? part[hi * nvp + j0 + q] : 0.0;
-  }
-#endif
   if (hact) {
 #pragma unroll
     for (int q = 0; q < CB; q++) if (j0 + q < NVT) c.qH[hi * nvp + j0 + q] = a[q];
@@ -636,7 +593,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
   // one column group in the dense tier's lean layout (the hand): factor straight from the row registers, no Hessian in LDS
   // (with all 512 registers and room in LDS the round trip through qH is the faster form: measured on the hand, 6.94 vs 7.62 ms)
 #ifdef MJPC_LEAN_LDS
-  constexpr bool ROWS = G == 1 && MJPC_HELPER;
+  constexpr bool ROWS = G == 1;
 #else
   constexpr bool ROWS = false;
 #endif
@@ -647,14 +604,9 @@ DEV void solve_constraints_reg_d(Ctx &c) {
   PROF(c, 7);
   // warm start: the better of qacc_smooth and qacc_warmstart (evaluated last, so its force/state stay valid)
   double gauss, cost, cost_sm;
-#if MJPC_HELPER
   double cost_ws = solver_eval<NVT>(c, c.qacc_ws, &gauss);
   if (!flag_wait(c.misc + HX_CSM, c.hseq / 256 + 1)) c.warning |= WARN_SYNC;     // priced by the last helper meanwhile
   cost_sm = c.red[2];
-#else
-  cost_sm = solver_eval<NVT>(c, c.qacc_smooth, 0);
-  double cost_ws = solver_eval<NVT>(c, c.qacc_ws, &gauss);
-#endif
   if (cost_ws > cost_sm) {
     PFOR(i, nv) c.qacc[i] = c.qacc_smooth[i];
     SYNC();
@@ -674,20 +626,14 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     const int stc = c.efc_state[r0c];
     ncone = __builtin_popcountll(__builtin_amdgcn_ballot_w64(LANE < c.ncon && dim > 1 && stc == STATE_CONE));
   }
-#if MJPC_HELPER
-  if (ncone) np = job_post<NVT>(c, 1, side_in);
-#else
-  ls_records_build<NVT>(c);
-#endif
+  if (ncone) np = job_post(c, 1, side_in);
   double hq[CB];
   hblock_init<NVT>(c, hq, hi, j0);
   PROF(c, 15);
   newton_grad_reg<NVT>(c, hi, hg, hact);
   PROF(c, 9);
-  if constexpr (!ROWS) { newton_assemble<NVT, DIMT>(c, hq, hi, hg, j0, hact); PROF(c, 19); }
-#if MJPC_HELPER
+  if constexpr (!ROWS) { newton_assemble<NVT>(c, hq, hi, hg, j0, hact); PROF(c, 19); }
   if (np) { job_wait(c, np); PROF(c, 16); }
-#endif
   if constexpr (!ROWS) newton_direction_np<NVT>(c, np); else newton_direction_rows<NVT>(c, hq, hi, hact, np);
   PFOR(i, nv) c.search[i] = -c.Mgrad[i];
   SYNC();
@@ -708,9 +654,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     if (snorm < D_MINVAL || gs >= 0) break;
     const double gtol = M.tolerance * M.ls_tolerance * snorm / scale;
     LSReg<DIMT> d;
-#if MJPC_HELPER
     if (iter == 0 && !flag_wait(c.misc + HX_LSREC, c.hseq / 256 + 1)) c.warning |= WARN_SYNC;      // helper 0 built the records meanwhile
-#endif
     ls_load_reg<NVT, DIMT>(c, d);
     PROF(c, 21);
     double lo = 0, hi_a = -1, a = 1.0;
@@ -740,12 +684,10 @@ DEV void solve_constraints_reg_d(Ctx &c) {
       double an = bracketed ? an_b : an_e;
       dxold = dx; dx = bracketed ? dx_b : an_e - a;
       if (conv || an == a) break;
-#if LS_PREDICT
       // a plain Newton step on phi' that promises less than a thousandth of the solver's stopping threshold: take it unseen (the
       // commit below prices the point; the evaluation that would only confirm |phi'| < gtol is skipped)
       const int plain = pos2 && (bracketed ? ok : newton > a);
       if (plain && 0.5 * p.d1 * p.d1 * fast_rcp(p.d2) < pred_tol) { a = an; moved = 1; break; }
-#endif
       a = an;
     }
     PROF(c, 22);
@@ -763,9 +705,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     PROF(c, 12);
     const double improvement = scale * (oldcost - cost);
     const int stop = improvement < M.tolerance || (c.warning & WARN_SYNC) != 0;
-#if MJPC_HELPER
-    np = (stop || !ncone) ? 0 : job_post<NVT>(c, 1, side_in);
-#endif
+    np = (stop || !ncone) ? 0 : job_post(c, 1, side_in);
     if (!stop) {
 #pragma unroll
       for (int k = 0; k < LS_RPL; k++) { if (k >= d.nslot) break; hblock_add_rows<NVT>(c, hq, chg_mask[k], NLANE * k, chg_w[k], hi, j0); }
@@ -778,16 +718,14 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     PFOR(i, nv) pg += c.grad[i] * c.grad[i];
     const double gradient = scale * sqrt(wave_sum(pg));
     const int done = stop || gradient < M.tolerance;
-    if constexpr (!ROWS) { if (!done) { newton_assemble<NVT, DIMT>(c, hq, hi, hg, j0, hact); PROF(c, 19); } }
-#if MJPC_HELPER
+    if constexpr (!ROWS) { if (!done) { newton_assemble<NVT>(c, hq, hi, hg, j0, hact); PROF(c, 19); } }
     if (np) { job_wait(c, np); PROF(c, 16); }           // (also when the gradient says stop: no job is left behind unfinished)
-#endif
     if (done) break;
     if constexpr (!ROWS) newton_direction_np<NVT>(c, np); else newton_direction_rows<NVT>(c, hq, hi, hact, np);
     PFOR(i, nv) c.search[i] = -c.Mgrad[i];
     SYNC();
   }
-  if (LANE == 0) { c.misc[5] += c.solver_iter; if (c.ncon > c.misc[6]) c.misc[6] = c.ncon; if (c.nefc > c.misc[7]) c.misc[7] = c.nefc; }
+  if (LANE == 0) { c.misc[MISC_SUM_ITER] += c.solver_iter; if (c.ncon > c.misc[MISC_MAX_NCON]) c.misc[MISC_MAX_NCON] = c.ncon; if (c.nefc > c.misc[MISC_MAX_NEFC]) c.misc[MISC_MAX_NEFC] = c.nefc; }
   PFOR(i, nv) c.qfrc_constraint[i] = (c.Ma[i] - c.qfrc_smooth[i]) - c.grad[i];
   SYNC();
 }

@@ -1,11 +1,13 @@
 // spmd.h — execution-model shim for the rollout engine.
 //
-// Product build (hipcc, gfx950): one 64-lane wavefront owns one candidate rollout; per-candidate
-// mjData-like state lives in LDS; `PFOR` is a lane-strided loop, `SYNC` a workgroup barrier (the
-// workgroup IS one wave, so it only orders LDS traffic), reductions/scans use cross-lane shuffles.
+// Product build (hipcc, gfx950): one workgroup of MJPC_WAVES = 4 64-lane wavefronts owns one candidate rollout, each wave in
+// its own role (below); per-candidate mjData-like state lives in LDS; `PFOR` is a lane-strided loop over the lanes of ONE
+// wave, `SYNC` orders that wave's memory traffic, `XBAR` is the workgroup barrier between the roles and flag_set / flag_wait the
+// point-to-point hand-shake between two of them (slots of misc[], model.h); reductions / scans use cross-lane operations.
 //
-// MJPC_EMU build (g++, tests only): NLANE = 1, the same source runs as plain sequential C++ so
-// that the CPU test tier can exercise the kernel logic (indexing, formulas) before a GPU run.
+// MJPC_EMU build (g++, tests only): NLANE = 1 and one thread plays the owner and the side wave in turn (no helpers,
+// MJPC_HELPER == 0): the same source runs as plain sequential C++ so that the CPU test tier can exercise the kernel
+// logic (indexing, formulas) before a GPU run.
 // The emu library is never loaded by the product (mujoco_mpc_amd/capi.py loads libmjpc_hip.so only).
 #pragma once
 #include <math.h>
@@ -17,7 +19,8 @@
 #define LANE 0
 #define NLANE 1
 #define SYNC() ((void)0)
-// the emulation runs both wave roles of a candidate one after the other in a single thread
+// the emulation runs the owner's and the side wave's phases of a candidate one after the other in a single thread
+#define MJPC_HELPER 0
 #define XBAR() ((void)0)
 #define ROLE0 1
 #define ROLE1 1
@@ -41,11 +44,14 @@ DEV int wave_any(int flag) { return flag != 0; }
 #include <hip/hip_runtime.h>
 #define DEV static __device__ __forceinline__
 #define DEV_NOINLINE static __device__ __noinline__
-// A candidate is owned by MJPC_WAVES (1 or 2) wavefronts of one workgroup on different SIMDs of a CU:
-//   role 0 (wave 0): the serial critical path (kinematics -> collision/constraints -> Newton solver -> integration);
-//   role 1 (last wave): work that only hangs off that path (inertia + factor M + smooth dynamics while role 0 builds
-//   the constraints; residual / cost / trajectory record while role 0 solves);
-//   helpers (waves 1 .. MJPC_WAVES-2): share the data-parallel parts of every Newton iteration with role 0 (solver.h).
+// A candidate is owned by the four wavefronts of one workgroup, one per SIMD of a CU:
+//   owner (wave 0, ROLE0): the serial critical path (kinematics -> collision / contact rows -> Newton solver -> integration);
+//   helper 0 (wave 1): joint-space inertia and its factor while the owner builds the constraints; during the solve the line
+//     search's records, then cone-block jobs of the owner's Newton iterations (elliptic models, solver_reg.h);
+//   helper 1 (wave 2): the contact-free constraint rows and half of the subtree sums; during the solve the price of the
+//     unconstrained acceleration, then cone-block jobs;
+//   side wave (wave 3, ROLE1): work that only hangs off that path (smooth dynamics while the owner builds the constraints;
+//     residual / cost / trajectory record and the integrator's factor while the owner solves).
 // SYNC() orders LDS traffic inside ONE wave (DS operations of a wave execute in order; only the compiler must not
 // reorder them), XBAR() is the workgroup barrier between the roles.
 // The spill flavour (rollout_spill.hip) keeps some of the same state in a per-candidate HBM slab, accessed with global / flat
@@ -58,25 +64,17 @@ DEV int wave_any(int flag) { return flag != 0; }
 //    for the wave's earlier vector memory operations (s_waitcnt vmcnt) before the barrier / flag store, the acquire after it
 //    keeps the later loads behind it.  Checked in the flavour's ISA: every s_barrier follows a vmcnt wait or the return of a
 //    call (which drains all counters).
-#ifndef MJPC_WAVES
 #define MJPC_WAVES 4
-#endif
+#define MJPC_NH 2            // helper waves (ROLEH)
+#define MJPC_HELPER 1        // this is not the emulation: the helper waves exist
 #define LANE ((int)(threadIdx.x & 63))
 #define NLANE 64
 #define SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#if MJPC_WAVES > 1
 #define XBAR() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 #define WAVE_ID() (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)))
 #define ROLE0 (WAVE_ID() == 0)
 #define ROLE1 (WAVE_ID() == MJPC_WAVES - 1)
-#define ROLEH (MJPC_WAVES >= 3 && WAVE_ID() >= 1 && WAVE_ID() < MJPC_WAVES - 1)     // helper k = WAVE_ID() - 1
-#else
-#define XBAR() SYNC()
-#define WAVE_ID() 0
-#define ROLE0 1
-#define ROLE1 1
-#define ROLEH 0
-#endif
+#define ROLEH (WAVE_ID() >= 1 && WAVE_ID() < MJPC_WAVES - 1)     // helper k = WAVE_ID() - 1
 // individually rounded ops (no FMA contraction): used where results must be bit-identical to the CPU path
 DEV double mul_rn(double a, double b) {
 #pragma clang fp contract(off)
@@ -202,14 +200,6 @@ DEV int wave_flag_scan(int flag, int *total) {
   *total = __builtin_popcountll(m);
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
-#endif
-
-#if !defined(MJPC_EMU) && MJPC_WAVES >= 3
-#define MJPC_HELPER 1
-#define MJPC_NH (MJPC_WAVES - 2)
-#else
-#define MJPC_HELPER 0
-#define MJPC_NH 0
 #endif
 
 #define PFOR(i, n) for (int i = LANE; i < (n); i += NLANE)

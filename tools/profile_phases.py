@@ -9,8 +9,7 @@ os.makedirs(os.path.dirname(so), exist_ok=True)
 if os.environ.get("PROFILE_LIB"):      # prebuilt with tools/mkvariant.sh prof_wN "-DMJPC_PROFILE=1 -DMJPC_PROFILE_WAVE=N"
     so = os.path.abspath(os.environ["PROFILE_LIB"])
 else:
-    flags = ["-DMJPC_PROFILE=1"] + (["-DMJPC_WAVES=1"] if os.environ.get("PROFILE_ONE_WAVE") else []) + \
-            ([f"-DMJPC_PROFILE_WAVE={int(os.environ['PROFILE_WAVE'])}"] if os.environ.get("PROFILE_WAVE") else [])
+    flags = ["-DMJPC_PROFILE=1"] + ([f"-DMJPC_PROFILE_WAVE={int(os.environ['PROFILE_WAVE'])}"] if os.environ.get("PROFILE_WAVE") else [])
     objs, jobs = [], []
     for f in sorted(os.listdir(CSRC)):
         if f == "engine.hip" or (f.startswith("rollout_") and f.endswith(".hip")):

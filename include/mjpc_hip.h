@@ -417,6 +417,38 @@ int mjpc_hip_plan_mixed_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, int 
 int mjpc_hip_plan_mixed(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit, MjpcHipPlanOutput *out);
 int mjpc_hip_noise_history_reset(MjpcHipEngine *e);
 int mjpc_hip_sample_gradient(MjpcHipEngine *e, int n, const int *slot, const double *scale, double *gradient_out);
+/* ---- Batched one-step evaluation and finite-difference transition derivatives ---------------------------------------------
+ * What the reference's derivative-based planners spend their time in (mjpc/planners/model_derivatives.cc:45-165: one
+ * mjd_transitionFD per knot, 1 + (2nv+na+nu) independent mj_steps one-sided, about twice that centred).  ds = nq+nv+na.
+ *
+ * mjpc_hip_step_batch: row i of `states` / `ctrl` / `time` is advanced by ONE step; next_states[i] is the state after it,
+ * residual[i] the residual evaluated inside the step (at the pre-integration state with ctrl[i] applied, clamped to ctrlrange:
+ * row 0 of a plan's residual), failure[i] the MJPC_WARN_* bits (0 = ok).  A row is bit for bit the first step of
+ * mjpc_hip_plan(N = 1, H = 2, P = 1, candidate_knots = ctrl[i]) from states[i]: cold warm start, full-capacity kernel flavour.
+ * mocap / userdata are shared by the batch.  n is unbounded: the batch runs in launches of at most max_local workgroups; an
+ * engine created with max_horizon >= 2 serves it.  Blocking.  A failed row (bad state, full buffer) is not an error of the call:
+ * its failure[i] is set, next_states[i] is the state it stopped at and residual[i] is NaN where the step never got there.
+ * Errors (mjpc_hip_last_error): a plan in flight, n < 1, null inputs, max_horizon < 2.
+ *
+ * mjpc_hip_transition_fd: for each knot t < T, with nd = 2nv+na and nr = num_residual, row-major
+ *   A[t][nd][nd] = d next / d state, B[t][nd][nu] = d next / d ctrl, C[t][nr][nd] = d residual / d state, D[t][nr][nu] = d residual / d ctrl,
+ * entry [i][j] = d out_i / d in_j, tangent order [dq(nv), dv(nv), dact(na)] (mjd_transitionFD's).  A position nudge is the
+ * engine's own position integration of a unit velocity over eps (hinge / slide / free translation: + eps; ball / free rotation:
+ * right-multiplied by exp(eps e) and normalised); the position block of an output difference is the tangent between the two next
+ * positions (quaternions: body-frame rotation vector of qa^-1 * qb), everything else a plain difference, each divided by eps or
+ * 2 eps.  The residual differentiated is step_batch's.
+ *   state columns    one-sided (y(+eps) - y(base)) / eps; centred (y(+eps) - y(-eps)) / (2 eps)
+ *   control columns  with [lo, hi] the ctrlrange of a limited actuator: forward nudge iff not limited or u + eps <= hi; backward nudge
+ *                    iff (centered || !forward) and (not limited or u - eps >= lo); both: centred formula; forward only:
+ *                    (y+ - base) / eps; backward only: (base - y-) / eps; neither: a zero column
+ * last_is_terminal: knot T-1 produces C only (state perturbations only); its A / B / D blocks are not written.
+ * failure[t] = OR of the warning bits of every evaluation at t; the columns a failed evaluation feeds are left as computed.
+ * T is unbounded (launches of at most max_local evaluations).  Blocking.  Errors: as above, and eps <= 0. */
+int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const double *ctrl, const double *time, const double *mocap,
+                        const double *userdata, double *next_states, double *residual, int *failure);
+int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
+                           const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
+                           double *D, int *failure);
 /* Bytes of LDS one candidate's workgroup occupies (its whole mjData-equivalent). */
 int mjpc_hip_lds_bytes(MjpcHipEngine *e);
 /* Capacity tiers: when a shard holds more candidates than the GPU has CUs and the model allows it, the engine first runs a

@@ -9,6 +9,7 @@
 //   mjpc/planners/cross_entropy/planner.h:32-147  CrossEntropyPlanner (same rollout engine, elite mean/variance update)
 //   mjpc/planners/robust/robust_planner.h:31-80   RobustPlanner (top-k candidates x R noisy rollouts on a second engine)
 //   mjpc/planners/sample_gradient/planner.h:35-175 SampleGradientPlanner (mixed batch; gradient reduced on the device)
+//   mjpc/planners/model_derivatives.h:30-70  ModelDerivatives (finite-difference A, B, C, D along a trajectory, on the device)
 // Differences forced by the boundary: `mjModel*` / `const Task&` become the ABI's MjpcHipModel / MjpcHipTask views
 // plus the planner's <custom><numeric> settings (Numerics); `ThreadPool&` arguments are gone (the GPU is the pool);
 // `State` is passed as its raw arrays (State::CopyTo, mjpc/states/state.cc:128-135).
@@ -338,6 +339,37 @@ class SampleGradientPlanner : public PlannerBase {
   std::vector<char> candidate_valid_;                  // candidate_policy_[i] is current (else: row i of all_knots_ / empty)
   int last_horizon_ = 0, last_N_ = 0, last_P_ = 0, last_interp_ = kZeroSpline;
   TimeSpline plan_scratch_;
+};
+
+// mjpc/planners/model_derivatives.{h,cc}: transition and sensor (residual) Jacobians along a nominal trajectory, what iLQG, the
+// gradient planner and iLQS linearise around.  The reference runs one mjd_transitionFD per evaluated knot on its thread pool;
+// here the evaluated knots go to the device in ONE mjpc_hip_transition_fd call (gathered rows) and the rest is interpolated on
+// the host with the reference's weights.  Blocks are row-major per knot: A[t] is [nd][nd], B[t] [nd][nu], C[t] [nr][nd],
+// D[t] [nr][nu] (nd = dim_state_derivative, nr = dim_sensor = the task's num_residual; the definition of the entries is
+// mjpc_hip_transition_fd's, include/mjpc_hip.h).  Index T - 1 is the terminal knot: C only, its A / B / D stay zero.
+class ModelDerivatives {
+ public:
+  // dim_state = nq + nv + na, the row length of Compute's x (the reference passes it to Compute; here it is set once)
+  void Allocate(int dim_state_derivative, int dim_action, int dim_sensor, int T, int dim_state = 0);
+  void Reset(int dim_state_derivative, int dim_action, int dim_sensor, int T);    // zero the first T blocks
+  // x [T][dim_state], u [T][dim_action], h [T] = the knots' times; tol = the finite-difference eps, mode = mjd_transitionFD's
+  // flg_centered, skip = knots left out between two evaluated ones.  mocap / userdata are those of the planner's state.  T < 2 is an
+  // error; false after an engine error (mjpc_hip_last_error).
+  bool Compute(MjpcHipEngine* engine, const double* x, const double* u, const double* h, int T, double tol, int mode, int skip,
+               const double* mocap = nullptr, const double* userdata = nullptr);
+  // the two halves of Compute without an engine: the reference's evaluate_ / interpolate_ index sets (an index it lists twice
+  // appears once), and every interpolated block from the evaluated ones, (1 - tt) L + tt U formed as mju_scl then mju_addToScl
+  void IndexSets(int T, int skip);
+  void Interpolate();
+
+  std::vector<double> A, B, C, D;
+  std::vector<int> failure;                            // [T]: MJPC_WARN_* bits of the evaluations at an evaluated knot, 0 elsewhere
+  std::vector<int> evaluate_, interpolate_;
+  int dim_state = 0, dim_state_derivative = 0, dim_action = 0, dim_sensor = 0;
+
+ private:
+  std::vector<double> gx_, gu_, gh_, gA_, gB_, gC_, gD_;
+  std::vector<int> gfail_;
 };
 
 }  // namespace mjpc_hip

@@ -5,6 +5,7 @@
  *   mjpc_planner_*  -> mjpc::SamplingPlanner / RankedPlanner (mjpc/planners/sampling/planner.h:51-162,
  *                                                             mjpc/planners/planner.h:38-101)
  *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
+ *   mjpc_md_*       -> mjpc::ModelDerivatives                 (mjpc/planners/model_derivatives.h:30-70)
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
  */
 #ifndef MJPC_HIP_PLANNER_C_H_
@@ -119,6 +120,22 @@ void mjpc_sg_timings(void *planner, double *noise_us, double *rollouts_us, doubl
  * (planner.cc:437-449) and LogScale (utilities.cc:802-808) */
 void mjpc_sg_return_weights(const int *order, int num_noisy, double *weights);
 void mjpc_sg_log_scale(double *values, double max_value, double min_value, int steps);
+
+/* ModelDerivatives (mjpc/planners/model_derivatives.h:30-70): create = Allocate + Reset.  The engine is the caller's (mjpc_hip_create,
+ * max_horizon >= 2). */
+void *mjpc_md_create(int dim_state /* nq + nv + na */, int dim_state_derivative, int dim_action, int dim_sensor, int T);
+void mjpc_md_destroy(void *md);
+void mjpc_md_reset(void *md, int T);
+/* 0 = ok, -1 = refused (T < 2: through the error handler) or engine error (mjpc_hip_last_error) */
+int mjpc_md_compute(void *md, MjpcHipEngine *engine, const double *x, const double *u, const double *h, int T, double tol, int mode, int skip,
+                    const double *mocap, const double *userdata);
+/* the host halves without an engine (no GPU needed): the index sets of (T, skip); every interpolated block from the evaluated ones */
+void mjpc_md_index_sets(void *md, int T, int skip);
+void mjpc_md_interpolate(void *md);
+/* evaluate_ into evaluate[] and interpolate_ into interpolate[] (either may be NULL); returns their sizes in n[2] */
+void mjpc_md_indices(void *md, int *evaluate, int *interpolate, int *n);
+/* the first T blocks: store != 0 copies the arrays INTO the object (tests fill the evaluated blocks), else out of it; any pointer may be NULL */
+void mjpc_md_blocks(void *md, int T, int store, double *A, double *B, double *C, double *D, int *failure);
 
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
  * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create.  state / mocap are in-out;

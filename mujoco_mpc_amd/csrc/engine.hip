@@ -9,6 +9,10 @@
 //                   that hit L2 / the scalar cache.  Replaces planner.cc:342-380 + trajectory.cc:100-210.
 //   sg_assemble_kernel / sg_gradient_kernel  (gradient.h)  Sample-Gradient planner: the mixed candidate table + noise history of a
 //                   mjpc_hip_plan_mixed step, and the weighted sum of history rows that is the planner's gradient
+//   step_kernel    (rollout_step_cached / _direct / _spill.hip, transition.h)  one workgroup per ROW of a state table: one step of the
+//                   rollout kernel's phases from that row's own state, control and time (mjpc_hip_step_batch)
+//   fd_assemble_kernel / fd_difference_kernel  (transition_fd.h)  mjpc_hip_transition_fd: the perturbed table around the nominal
+//                   knots, and the A / B / C / D entries from the stepped rows
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
 #include <hip/hip_runtime.h>
@@ -21,6 +25,7 @@
 #include "spmd.h"
 #include "philox.h"
 #include "gradient.h"
+#include "transition_fd.h"
 #include "host.h"
 #include "../../include/mjpc_hip_debug.h"
 
@@ -33,6 +38,13 @@ extern "C" RolloutFn mjpc_pick_rollout_dense2(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_dense2h(int nv, int *exact);
 extern "C" RolloutFn mjpc_pick_rollout_spill(int nv, int *exact);
 extern "C" int mjpc_rollout_threads_cached(void);
+// the one-step kernels (rollout_step_*.hip, step_tu.h): opaque here, their parameter block needs core.h
+typedef void (*StepLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *state_tab, const double *ctrl_tab,
+                             const double *time_tab, double *next_state, double *residual_out, int *failure_out);
+#define MJPC_STEP_DECL(tu) extern "C" const void *mjpc_pick_step_##tu(int nv); \
+  extern "C" void mjpc_launch_step_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, double *, double *, int *);
+MJPC_STEP_DECL(cached) MJPC_STEP_DECL(direct) MJPC_STEP_DECL(spill)
+#undef MJPC_STEP_DECL
 
 // Capacity tiers.  One candidate per CU leaves every SIMD with a single, mostly stalled wave; two resident workgroups per CU
 // raise throughput ~1.6x once a shard has more candidates than CUs, but need <= 80 KiB of LDS each.  The dense tier gets
@@ -85,6 +97,40 @@ extern "C" __global__ void __launch_bounds__(256) sg_gradient_kernel(const SgGra
   if (w == 0 && lane < SG_KT && kb * SG_KT + lane < a.PN) a.gradient[kb * SG_KT + lane] = acc;
 }
 static_assert(SG_PROD == 3 * (64 / SG_KT), "sg_gradient_kernel: three producer waves");
+
+// mjpc_hip_transition_fd, table assembly: one wave per table row, its lanes walk the row's ds + nu + 1 elements (the nominal row is read
+// and the table row stored in whole contiguous segments)
+extern "C" __global__ void __launch_bounds__(256) fd_assemble_kernel(const FdArgs a, unsigned rows) {
+  const size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= rows) return;
+  const int n = a.nq + a.nv + a.na + a.nu + 1;
+  for (int i = threadIdx.x & 63; i < n; i += 64) fd_assemble(a, g, i);
+}
+
+// mjpc_hip_transition_fd, differences: block (x, y, z) owns the FD_TILE x FD_TILE tile of knot z's combined matrix [A B; C D] at output
+// rows y * FD_TILE, columns x * FD_TILE.  A column of the matrix is one evaluation pair, whose rows are contiguous in the step kernel's
+// output; the matrices are row-major.  So a tile is read with the output row as the fast index (16 consecutive doubles of a next-state
+// row per column), turned in LDS (odd row stride: no bank conflicts either way) and stored with the column as the fast index (16
+// consecutive doubles of a matrix row): both sides move whole 128-byte segments instead of one double per segment.
+#define FD_TILE 16
+extern "C" __global__ void __launch_bounds__(FD_TILE * FD_TILE) fd_difference_kernel(const FdArgs a) {
+  __shared__ double tile[FD_TILE][FD_TILE + 1];
+  const int t = blockIdx.z, o0 = blockIdx.y * FD_TILE, c0 = blockIdx.x * FD_TILE;
+  const int nd = 2 * a.nv + a.na, no = nd + a.nr, nc = nd + a.nu;
+  {
+    const int oi = threadIdx.x % FD_TILE, ci = threadIdx.x / FD_TILE, o = o0 + oi, c = c0 + ci;
+    if (o < no && c < nc && fd_dest(a, t, o, c)) tile[oi][ci] = fd_entry(a, t, o, c);
+  }
+  __syncthreads();
+  {
+    const int ci = threadIdx.x % FD_TILE, oi = threadIdx.x / FD_TILE, o = o0 + oi, c = c0 + ci;
+    if (o < no && c < nc) { double *d = fd_dest(a, t, o, c); if (d) *d = tile[oi][ci]; }
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
+    int w = wave_or_i(fd_failure(a, t, (int)threadIdx.x, 64));
+    if (threadIdx.x == 0) a.failure[t] = w;
+  }
+}
 
 // winner[0] = local index of the first minimum of returns[0..n), winner_val[0] = its value
 extern "C" __global__ void __launch_bounds__(64) argmin_kernel(const double *returns, int n, int *winner, double *winner_val) {
@@ -172,6 +218,10 @@ struct MjpcHipEngine {
   int last_dense = 0;
   // Sample-Gradient planner (mjpc_hip_plan_mixed / mjpc_hip_sample_gradient): noise history [max_local][P_max * nu], gradient inputs / output
   double *d_hist = nullptr, *d_scale = nullptr, *d_grad = nullptr; int *d_slot = nullptr; int have_mixed = 0;
+  // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour;
+  // d_fd: the call's tables (inputs, stepped rows, matrices), grown on demand
+  const void *step_kernel = nullptr; StepLaunchFn step_launch = nullptr;
+  char *d_fd = nullptr; size_t fd_cap = 0;
   // dense tier (two workgroups per CU), see "Capacity tiers" above
   RolloutFn kernelB = nullptr; Lay layB; int nefcB = 0, nconB = 0, cacheB_i = 0, cacheB_d = 0; size_t ldsB = 0; int num_cu = 256, force_tier = 0;
 };
@@ -362,7 +412,7 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
   void *bufs[] = {e->d_userdata, e->d_cand, e->d_std, e->d_ib, e->d_db, e->d_state, e->d_mocap, e->d_kt, e->d_kv, e->d_eps, e->d_sel, e->d_states, e->d_actions,
                   e->d_times, e->d_residual, e->d_costs, e->d_trace, e->d_knots, e->d_returns, e->d_failure, e->d_diag,
                   e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt, e->d_slab,
-                  e->d_hist, e->d_slot, e->d_scale, e->d_grad};
+                  e->d_hist, e->d_slot, e->d_scale, e->d_grad, e->d_fd};
   for (void *b : bufs) if (b) hipFree(b);
   if (e->h_small) hipHostFree(e->h_small);
   for (int i = 0; i < 2; i++) { if (e->h_task[i]) hipHostFree(e->h_task[i]); if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]); }
@@ -625,6 +675,166 @@ int mjpc_hip_sample_gradient(MjpcHipEngine *e, int n, const int *slot, const dou
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(gradient_out, e->d_grad, sizeof(double) * PN, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ batched one-step evaluation, FD derivatives
+// common front of mjpc_hip_step_batch / mjpc_hip_transition_fd: argument checks that do not depend on the call, the step kernel
+// of the engine's flavour, the shared inputs (mocap, userdata) and the kernel parameters of a one-step launch
+static int step_prepare(MjpcHipEngine *e, const char *who, const double *mocap, const double *userdata, KParams *Kout) {
+  if (e->pending) { set_error(std::string(who) + ": a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
+  if (e->max_horizon < 2) { set_error(std::string(who) + ": the engine was created with max_horizon < 2 (a step records two state rows)"); return -1; }
+  if (e->nmocap > 0 && !mocap) { set_error(std::string(who) + ": null input"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->step_kernel) {
+    // the flavour of the full-capacity rollout kernel (pick_flavour), same compile-time dof count
+    const void *k = e->spill ? mjpc_pick_step_spill(e->nv) : e->cached ? mjpc_pick_step_cached(e->nv) : mjpc_pick_step_direct(e->nv);
+    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
+    e->step_kernel = k;
+    e->step_launch = e->spill ? mjpc_launch_step_spill : e->cached ? mjpc_launch_step_cached : mjpc_launch_step_direct;
+  }
+  const size_t need = (size_t)e->max_local * e->nu;         // P = 1
+  if (need > e->knots_cap) {
+    if (e->d_knots) HIPCHK(hipFree(e->d_knots));
+    e->d_knots = nullptr; e->knots_cap = 0;
+    HIPCHK(hipMalloc(&e->d_knots, sizeof(double) * (need + 1)));
+    e->knots_cap = need;
+  }
+  double *hs = e->h_small;
+  if (e->nmocap) {
+    memcpy(hs, mocap, sizeof(double) * 7 * e->nmocap);
+    HIPCHK(hipMemcpyAsync(e->d_mocap, hs, sizeof(double) * 7 * e->nmocap, hipMemcpyHostToDevice, e->stream));
+  }
+  if (e->nuserdata) {
+    double *hu = hs + 7 * e->nmocap;
+    if (userdata) memcpy(hu, userdata, sizeof(double) * e->nuserdata); else memset(hu, 0, sizeof(double) * e->nuserdata);
+    HIPCHK(hipMemcpyAsync(e->d_userdata, hu, sizeof(double) * e->nuserdata, hipMemcpyHostToDevice, e->stream));
+  }
+  KParams K = e->K;
+  K.state = nullptr; K.mocap = e->d_mocap; K.userdata = e->d_userdata; K.nuserdata = e->nuserdata; K.knot_times = e->d_kt; K.knot_values = e->d_kv;
+  K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  K.time = 0; K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0;
+  K.P = 1; K.interp = 0; K.H = 2; K.N = e->max_local; K.offset = 0; K.nlocal = 0; K.use_device_noise = 0; K.nominal_index = 0;
+  K.fault = e->fault; K.xfrc_std = 0; K.xfrc_rate = 0;
+  K.states = e->d_states; K.actions = e->d_actions; K.times = e->d_times; K.residual = e->d_residual; K.costs = e->d_costs;
+  K.trace = e->d_trace; K.knots = e->d_knots; K.returns = e->d_returns; K.failure = e->d_failure; K.diag = e->d_diag; K.prof = e->d_prof;
+  K.frame = nullptr;                       // (the kinematic frame of the last plan stays what it was)
+  K.retry = 0; K.tier = 0; K.ckpt = e->d_ckpt; K.ckpt_stride = e->ckpt_stride;
+  *Kout = K;
+  // the row buffers are about to be overwritten: the last plan's candidates are no longer there to be fetched
+  e->last_nlocal = 0;
+  return 0;
+}
+
+static int fd_reserve(MjpcHipEngine *e, size_t bytes) {
+  if (bytes <= e->fd_cap) return 0;
+  if (e->d_fd) HIPCHK(hipFree(e->d_fd));
+  e->d_fd = nullptr; e->fd_cap = 0;
+  HIPCHK(hipMalloc(&e->d_fd, bytes));
+  e->fd_cap = bytes;
+  return 0;
+}
+
+// rows [0, rows) of the tables through the step kernel, at most max_local workgroups per launch (stream-ordered: a launch reuses
+// the row buffers, the slab and the CU's LDS of the one before it)
+static void step_rows(MjpcHipEngine *e, const KParams &K, size_t rows, const double *st, const double *ct, const double *tt, double *ns, double *rs, int *fl) {
+  for (size_t r0 = 0; r0 < rows; r0 += (size_t)e->max_local) {
+    const int nl = (int)(rows - r0 < (size_t)e->max_local ? rows - r0 : (size_t)e->max_local);
+    e->step_launch(e->step_kernel, nl, e->lds_bytes, e->stream, &K, st + r0 * e->ds, ct + r0 * e->nu, tt + r0, ns + r0 * e->ds, rs + r0 * e->nr, fl + r0);
+  }
+}
+
+// rows of one pass over the device tables: bounds the memory of a call whose n / T is large (the passes are independent)
+#define STEP_PASS_ROWS 32768
+
+int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const double *ctrl, const double *time, const double *mocap,
+                        const double *userdata, double *next_states, double *residual, int *failure) {
+  if (!e) { set_error("mjpc_hip_step_batch: invalid argument"); return -1; }
+  if (n < 1) { set_error("mjpc_hip_step_batch: n < 1"); return -1; }
+  if (!states || !time || (e->nu > 0 && !ctrl) || !next_states || !residual || !failure) { set_error("mjpc_hip_step_batch: null input"); return -1; }
+  KParams K;
+  int rc = step_prepare(e, "mjpc_hip_step_batch", mocap, userdata, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr;
+  for (size_t p0 = 0; p0 < (size_t)n; p0 += STEP_PASS_ROWS) {
+    const size_t R = (size_t)n - p0 < STEP_PASS_ROWS ? (size_t)n - p0 : STEP_PASS_ROWS;
+    const size_t nd_ = R * (2 * ds + nu + 1 + nr) + 8;
+    rc = fd_reserve(e, nd_ * sizeof(double) + R * sizeof(int));
+    if (rc != 0) return rc;
+    double *st = (double *)e->d_fd, *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
+    int *fl = (int *)((double *)e->d_fd + nd_);
+    HIPCHK(hipMemcpyAsync(st, states + p0 * ds, sizeof(double) * R * ds, hipMemcpyHostToDevice, e->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(ct, ctrl + p0 * nu, sizeof(double) * R * nu, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(tt, time + p0, sizeof(double) * R, hipMemcpyHostToDevice, e->stream));
+    step_rows(e, K, R, st, ct, tt, ns, rs, fl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(next_states + p0 * ds, ns, sizeof(double) * R * ds, hipMemcpyDeviceToHost, e->stream));
+    if (nr) HIPCHK(hipMemcpyAsync(residual + p0 * nr, rs, sizeof(double) * R * nr, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(failure + p0, fl, sizeof(int) * R, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  return 0;
+}
+
+int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
+                           const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
+                           double *D, int *failure) {
+  if (!e) { set_error("mjpc_hip_transition_fd: invalid argument"); return -1; }
+  if (T < 1) { set_error("mjpc_hip_transition_fd: T < 1"); return -1; }
+  if (!(eps > 0)) { set_error("mjpc_hip_transition_fd: eps <= 0"); return -1; }
+  if (!x || !time || (e->nu > 0 && !u) || !A || !B || !C || !D || !failure) { set_error("mjpc_hip_transition_fd: null input"); return -1; }
+  KParams K;
+  int rc = step_prepare(e, "mjpc_hip_transition_fd", mocap, userdata, &K);
+  if (rc != 0) return rc;
+  centered = centered ? 1 : 0; last_is_terminal = last_is_terminal ? 1 : 0;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, na = ds - e->nq - e->nv, nd = 2 * nv + na;
+  // dof -> (qpos address, quaternion axis or -1) from the engine's own packed model
+  std::vector<int> dofmap(2 * nv + 2, -1);
+  {
+    const DevModel hm = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data());
+    for (int j = 0; j < hm.njnt; j++) {
+      const int type = hm.jnt_type[j], qa = hm.jnt_qposadr[j], da = hm.jnt_dofadr[j];
+      if (type == 0) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa + k; dofmap[2 * (da + k) + 1] = -1; dofmap[2 * (da + 3 + k)] = qa + 3; dofmap[2 * (da + 3 + k) + 1] = k; } }
+      else if (type == 1) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa; dofmap[2 * (da + k) + 1] = k; } }
+      else { dofmap[2 * da] = qa; dofmap[2 * da + 1] = -1; }
+    }
+  }
+  const size_t E = centered ? 1 + 2 * (nd + nu) : 1 + nd + nu;
+  size_t Tg_max = STEP_PASS_ROWS / E; if (Tg_max < 1) Tg_max = 1;
+  const double cs = cos(0.5 * eps), sn = sin(0.5 * eps);
+  for (size_t t0 = 0; t0 < (size_t)T; t0 += Tg_max) {
+    const size_t Tg = (size_t)T - t0 < Tg_max ? (size_t)T - t0 : Tg_max, R = Tg * E;
+    const int term = last_is_terminal && t0 + Tg == (size_t)T;
+    const size_t per_t = ds + nu + 1 + nd * nd + nd * nu + nr * nd + nr * nu;
+    const size_t nd_ = R * (2 * ds + nu + 1 + nr) + Tg * per_t + 8;
+    rc = fd_reserve(e, nd_ * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int));
+    if (rc != 0) return rc;
+    double *st = (double *)e->d_fd, *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
+    double *dx = rs + R * nr, *du = dx + Tg * ds, *dt = du + Tg * nu, *dA = dt + Tg, *dB = dA + Tg * nd * nd, *dC = dB + Tg * nd * nu, *dD = dC + Tg * nr * nd;
+    int *fl = (int *)((double *)e->d_fd + nd_), *flT = fl + R, *dmap = flT + Tg;
+    HIPCHK(hipMemcpyAsync(dx, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(du, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(dt, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(dmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+    FdArgs a;
+    a.x = dx; a.u = du; a.time = dt; a.dofmap = dmap; a.ctrllimited = e->K.M.actuator_ctrllimited; a.ctrlrange = e->K.M.actuator_ctrlrange;
+    a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = (int)na; a.nu = e->nu; a.nr = e->nr; a.centered = centered; a.last_is_terminal = term;
+    a.eps = eps; a.cs = cs; a.sn = sn;
+    a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = ns; a.residual = rs; a.fail = fl;
+    a.A = dA; a.B = dB; a.C = dC; a.D = dD; a.failure = flT;
+    hipLaunchKernelGGL(fd_assemble_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a, (unsigned)R);
+    step_rows(e, K, R, st, ct, tt, ns, rs, fl);
+    hipLaunchKernelGGL(fd_difference_kernel, dim3((unsigned)((nd + nu + FD_TILE - 1) / FD_TILE), (unsigned)((nd + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tg),
+                       dim3(FD_TILE * FD_TILE), 0, e->stream, a);
+    HIPCHK(hipGetLastError());
+    const size_t Tw = Tg - (term ? 1 : 0);            // a terminal knot's A / B / D blocks stay the caller's
+    if (Tw && nd) HIPCHK(hipMemcpyAsync(A + t0 * nd * nd, dA, sizeof(double) * Tw * nd * nd, hipMemcpyDeviceToHost, e->stream));
+    if (Tw && nd * nu) HIPCHK(hipMemcpyAsync(B + t0 * nd * nu, dB, sizeof(double) * Tw * nd * nu, hipMemcpyDeviceToHost, e->stream));
+    if (nr * nd) HIPCHK(hipMemcpyAsync(C + t0 * nr * nd, dC, sizeof(double) * Tg * nr * nd, hipMemcpyDeviceToHost, e->stream));
+    if (Tw && nr * nu) HIPCHK(hipMemcpyAsync(D + t0 * nr * nu, dD, sizeof(double) * Tw * nr * nu, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(failure + t0, flT, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
   return 0;
 }
 

@@ -4,6 +4,7 @@
 //   mjpc/planners/sampling/policy.cc:30-78   SamplingPolicy
 //   mjpc/planners/sampling/planner.cc:40-310,525-534   SamplingPlanner host logic
 //   mjpc/planners/sample_gradient/planner.cc:43-493    SampleGradientPlanner host logic (batch + gradient sum on the engine)
+//   mjpc/planners/model_derivatives.cc:24-165          ModelDerivatives (evaluations on the engine, interpolation on the host)
 #include "../../include/mjpc_hip_planner.h"
 #include "../../include/mjpc_hip_planner_c.h"
 
@@ -850,6 +851,96 @@ void SampleGradientPlanner::NominalTrajectory(int horizon) {   // planner.cc:276
 
 const Trajectory* SampleGradientPlanner::BestTrajectory() { return &trajectory_winner; }
 
+// ------------------------------------------------------------------ ModelDerivatives
+void ModelDerivatives::Allocate(int nd, int nu, int nr, int T, int ds) {
+  dim_state_derivative = nd; dim_action = nu; dim_sensor = nr;
+  if (ds > 0) dim_state = ds;
+  A.resize((size_t)T * nd * nd); B.resize((size_t)T * nd * nu); C.resize((size_t)T * nr * nd); D.resize((size_t)T * nr * nu);
+  failure.resize(T);
+}
+
+void ModelDerivatives::Reset(int nd, int nu, int nr, int T) {
+  if (nd != dim_state_derivative || nu != dim_action || nr != dim_sensor || (size_t)T > failure.size()) Allocate(nd, nu, nr, T);
+  std::fill(A.begin(), A.begin() + (size_t)T * nd * nd, 0.0);
+  std::fill(B.begin(), B.begin() + (size_t)T * nd * nu, 0.0);
+  std::fill(C.begin(), C.begin() + (size_t)T * nr * nd, 0.0);
+  std::fill(D.begin(), D.begin() + (size_t)T * nr * nu, 0.0);
+  std::fill(failure.begin(), failure.begin() + T, 0);
+}
+
+// model_derivatives.cc:56-72.  The reference pushes 0, then s, 2s, ... below T - s, then T - 2 and T - 1, which names an index
+// twice when T is small (T = 2: 0, 0, 1); its interpolate_ walk then still skips exactly the indices named at least once.  Here
+// the list is that set, ascending.
+void ModelDerivatives::IndexSets(int T, int skip) {
+  evaluate_.clear(); interpolate_.clear();
+  if (T < 2) { Fatal("ModelDerivatives: T < 2"); return; }
+  const int s = (skip < 0 ? 0 : skip) + 1;
+  evaluate_.push_back(0);
+  for (int t = s; t < T - s; t += s) evaluate_.push_back(t);
+  if (T - 2 > evaluate_.back()) evaluate_.push_back(T - 2);
+  evaluate_.push_back(T - 1);
+  for (int t = 0, e = 0; t < T; t++) {
+    if (e == (int)evaluate_.size() || evaluate_[e] > t) interpolate_.push_back(t);
+    else e++;
+  }
+}
+
+// model_derivatives.cc:108-161: FindInterval (utilities.h:122-141) over evaluate_, tt = (t - e0) / (e1 - e0), then mju_scl by
+// 1 - tt and mju_addToScl by tt (two rounded products and one rounded sum per entry; this file is compiled without contraction)
+void ModelDerivatives::Interpolate() {
+  const size_t n[4] = {(size_t)dim_state_derivative * dim_state_derivative, (size_t)dim_state_derivative * dim_action,
+                       (size_t)dim_sensor * dim_state_derivative, (size_t)dim_sensor * dim_action};
+  std::vector<double>* blk[4] = {&A, &B, &C, &D};
+  for (int t : interpolate_) {
+    int ub = (int)(std::upper_bound(evaluate_.begin(), evaluate_.end(), t) - evaluate_.begin());
+    int b0 = ub - 1, b1 = ub;
+    if (b0 < 0) { b0 = 0; b1 = 0; }
+    else if (b1 > (int)evaluate_.size() - 1) b1 = (int)evaluate_.size() - 1;
+    const int e0 = evaluate_[b0], e1 = evaluate_[b1];
+    double tt = (b0 == b1) ? 0.0 : double(t - e0) / double(e1 - e0);
+    for (int k = 0; k < 4; k++) {
+      double* out = blk[k]->data() + (size_t)t * n[k];
+      const double *L = blk[k]->data() + (size_t)e0 * n[k], *U = blk[k]->data() + (size_t)e1 * n[k];
+      for (size_t i = 0; i < n[k]; i++) out[i] = L[i] * (1.0 - tt);
+      for (size_t i = 0; i < n[k]; i++) out[i] += U[i] * tt;
+    }
+  }
+}
+
+bool ModelDerivatives::Compute(MjpcHipEngine* engine, const double* x, const double* u, const double* h, int T, double tol, int mode, int skip,
+                               const double* mocap, const double* userdata) {
+  if (T < 2) { Fatal("ModelDerivatives: T < 2"); return false; }
+  const int nd = dim_state_derivative, nu = dim_action, nr = dim_sensor;
+  if ((size_t)T > failure.size()) Allocate(nd, nu, nr, T);
+  IndexSets(T, skip);
+  // rows of the evaluated knots, gathered: one device call
+  const size_t ne = evaluate_.size();
+  const int ds = dim_state;
+  if (ds < 1) { Fatal("ModelDerivatives: dim_state is not set (Allocate's last argument: nq + nv + na)"); return false; }
+  gx_.resize(ne * ds); gu_.resize(ne * nu + 1); gh_.resize(ne);
+  gA_.resize(ne * nd * nd); gB_.resize(ne * nd * nu + 1); gC_.resize(ne * nr * nd + 1); gD_.resize(ne * nr * nu + 1); gfail_.resize(ne);
+  for (size_t k = 0; k < ne; k++) {
+    const int t = evaluate_[k];
+    std::copy(x + (size_t)t * ds, x + (size_t)(t + 1) * ds, gx_.begin() + k * ds);
+    std::copy(u + (size_t)t * nu, u + (size_t)(t + 1) * nu, gu_.begin() + k * nu);
+    gh_[k] = h[t];
+  }
+  if (mjpc_hip_transition_fd(engine, (int)ne, gx_.data(), gu_.data(), gh_.data(), mocap, userdata, tol, mode, 1, gA_.data(), gB_.data(), gC_.data(),
+                             gD_.data(), gfail_.data()) != 0) return false;
+  std::fill(failure.begin(), failure.begin() + T, 0);
+  for (size_t k = 0; k < ne; k++) {
+    const size_t t = (size_t)evaluate_[k];
+    failure[t] = gfail_[k];
+    std::copy(gC_.begin() + k * nr * nd, gC_.begin() + (k + 1) * nr * nd, C.begin() + t * nr * nd);
+    if ((int)t == T - 1) continue;                    // terminal knot: C only
+    std::copy(gA_.begin() + k * nd * nd, gA_.begin() + (k + 1) * nd * nd, A.begin() + t * nd * nd);
+    std::copy(gB_.begin() + k * nd * nu, gB_.begin() + (k + 1) * nd * nu, B.begin() + t * nd * nu);
+    std::copy(gD_.begin() + k * nr * nu, gD_.begin() + (k + 1) * nr * nu, D.begin() + t * nr * nu);
+  }
+  Interpolate();
+  return true;
+}
+
 }  // namespace mjpc_hip
 
 // ====================================================================== flat C wrapper (tests / ctypes)
@@ -1015,6 +1106,36 @@ void mjpc_sg_timings(void* p, double* noise, double* rollouts, double* update, d
 void mjpc_sg_return_weights(const int* order, int num_noisy, double* weights) { mjpc_hip::SampleGradientPlanner::ReturnWeights(order, num_noisy, weights); }
 void mjpc_sg_log_scale(double* values, double max_value, double min_value, int steps) { mjpc_hip::SampleGradientPlanner::LogScale(values, max_value, min_value, steps); }
 #undef SGP
+
+// ---- ModelDerivatives
+void* mjpc_md_create(int dim_state, int nd, int nu, int nr, int T) { auto* d = new mjpc_hip::ModelDerivatives(); d->Allocate(nd, nu, nr, T, dim_state); d->Reset(nd, nu, nr, T); return d; }
+void mjpc_md_destroy(void* md) { delete (mjpc_hip::ModelDerivatives*)md; }
+void mjpc_md_reset(void* md, int T) { auto* d = (mjpc_hip::ModelDerivatives*)md; d->Reset(d->dim_state_derivative, d->dim_action, d->dim_sensor, T); }
+int mjpc_md_compute(void* md, MjpcHipEngine* engine, const double* x, const double* u, const double* h, int T, double tol, int mode, int skip,
+                    const double* mocap, const double* userdata) {
+  return ((mjpc_hip::ModelDerivatives*)md)->Compute(engine, x, u, h, T, tol, mode, skip, mocap, userdata) ? 0 : -1;
+}
+void mjpc_md_index_sets(void* md, int T, int skip) { ((mjpc_hip::ModelDerivatives*)md)->IndexSets(T, skip); }
+void mjpc_md_interpolate(void* md) { ((mjpc_hip::ModelDerivatives*)md)->Interpolate(); }
+void mjpc_md_indices(void* md, int* evaluate, int* interpolate, int* n) {
+  auto* d = (mjpc_hip::ModelDerivatives*)md;
+  if (evaluate) std::copy(d->evaluate_.begin(), d->evaluate_.end(), evaluate);
+  if (interpolate) std::copy(d->interpolate_.begin(), d->interpolate_.end(), interpolate);
+  if (n) { n[0] = (int)d->evaluate_.size(); n[1] = (int)d->interpolate_.size(); }
+}
+void mjpc_md_blocks(void* md, int T, int store, double* A, double* B, double* C, double* D, int* failure) {
+  auto* d = (mjpc_hip::ModelDerivatives*)md;
+  const size_t nd = d->dim_state_derivative, nu = d->dim_action, nr = d->dim_sensor, n = (size_t)T;
+  if (n > d->failure.size()) return;
+  double* user[4] = {A, B, C, D};
+  std::vector<double>* own[4] = {&d->A, &d->B, &d->C, &d->D};
+  const size_t cnt[4] = {n * nd * nd, n * nd * nu, n * nr * nd, n * nr * nu};
+  for (int k = 0; k < 4; k++) {
+    if (!user[k]) continue;
+    if (store) std::copy(user[k], user[k] + cnt[k], own[k]->begin()); else std::copy(own[k]->begin(), own[k]->begin() + cnt[k], user[k]);
+  }
+  if (failure) { if (store) std::copy(failure, failure + n, d->failure.begin()); else std::copy(d->failure.begin(), d->failure.begin() + n, failure); }
+}
 
 // ---- RobustPlanner
 void* mjpc_robust_create(const MjpcHipModel* model, const MjpcHipTask* task, const double* exploration, int trajectories, int representation,

@@ -125,6 +125,54 @@ class HipBackend:
         if self.lib.mjpc_hip_noise_history_reset(self.h) != 0:
             raise RuntimeError(self.lib.mjpc_hip_last_error().decode())
 
+    def _dims(self):
+        m = self.model
+        nq, nv, na, nu = m["nq"], m["nv"], m["na"], m["nu"]
+        return nq + nv + na, 2 * nv + na, nu, self.task["num_residual"]
+
+    def _shared(self, mocap, userdata):
+        mo = np.ascontiguousarray(np.zeros(7 * self.model["nmocap"]) if mocap is None else mocap, dtype=np.float64).ravel()
+        if mo.size != 7 * self.model["nmocap"]:
+            raise ValueError("mocap must hold 7 numbers per mocap body")
+        ud = None if userdata is None else np.ascontiguousarray(userdata, dtype=np.float64).ravel()
+        dp = capi.c_double_p
+        return mo, ud, (mo.ctypes.data_as(dp) if mo.size else None), (ud.ctypes.data_as(dp) if ud is not None and ud.size else None)
+
+    def step_batch(self, states, ctrl, time, mocap=None, userdata=None):
+        """One step from each of n different states (mjpc_hip_step_batch): states [n, nq+nv+na], ctrl [n, nu], time [n] ->
+        dict(next_states [n, ds], residual [n, nr] evaluated inside the step, failure [n] MJPC_WARN_* bits).  Row i is bit for bit the
+        first step of plan(N=1, H=2, P=1, candidate_knots=ctrl[i]) from states[i]."""
+        ds, _, nu, nr = self._dims()
+        x = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, ds); n = x.shape[0]
+        u = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(n, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(n)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(next_states=np.zeros((n, ds)), residual=np.zeros((n, nr)), failure=np.zeros(n, np.int32))
+        dp = capi.c_double_p
+        u_ = u if u.size else np.zeros(1); r_ = o["residual"] if nr else np.zeros(1)
+        rc = self.lib.mjpc_hip_step_batch(self.h, n, x.ctypes.data_as(dp), u_.ctypes.data_as(dp), t.ctypes.data_as(dp), pmo, pud,
+                                          o["next_states"].ctypes.data_as(dp), r_.ctypes.data_as(dp), o["failure"].ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_step_batch failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
+    def transition_fd(self, x, u, time, mocap=None, userdata=None, eps=1e-6, centered=False, last_is_terminal=False, fill=0.0):
+        """Finite-difference transition derivatives at T knots (mjpc_hip_transition_fd): dict(A [T, nd, nd], B [T, nd, nu], C [T, nr, nd],
+        D [T, nr, nu], failure [T]), nd = 2 nv + na.  With last_is_terminal the last knot's A / B / D are not written: they keep `fill`."""
+        ds, nd, nu, nr = self._dims()
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(T)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(A=np.full((T, nd, nd), float(fill)), B=np.full((T, nd, nu), float(fill)), C=np.full((T, nr, nd), float(fill)),
+                 D=np.full((T, nr, nu), float(fill)), failure=np.zeros(T, np.int32))
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_transition_fd(self.h, T, x.ctypes.data_as(dp), ptr(u), t.ctypes.data_as(dp), pmo, pud, float(eps), int(bool(centered)),
+                                             int(bool(last_is_terminal)), ptr(o["A"]), ptr(o["B"]), ptr(o["C"]), ptr(o["D"]),
+                                             o["failure"].ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_transition_fd failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
     def candidate(self, local_index, H, P):
         o, c, ntr = self._alloc_out(1, H, P)
         if self.lib.mjpc_hip_get_candidate(self.h, int(local_index), C.byref(c)) != 0:

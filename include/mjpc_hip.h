@@ -152,8 +152,8 @@ enum {
 
 /* ---- model: the subset of mjModel the path reads ------------------------------------- */
 /* ABI revision of this header.  mjpc_hip_version() returns the revision the library was built from; both view structs start
-   with `struct_size` (= sizeof of the struct as the CALLER compiled it): mjpc_hip_create / mjpc_hip_set_task refuse a view whose
-   size differs from the library's, so a stale .so paired with a newer header (or ctypes layout) fails loudly instead of reading
+   with `struct_size` (= sizeof of the struct as the CALLER compiled it): mjpc_hip_create / mjpc_hip_set_task / mjpc_hip_layout_bytes refuse a view
+   whose size differs from the library's, so a stale .so paired with a newer header (or ctypes layout) fails loudly instead of reading
    garbage pointers.  Bindings without the header: mjpc_hip_sizeof_model() / _task() / _plan_input() / _plan_output(). */
 #define MJPC_HIP_ABI_VERSION 4
 
@@ -458,7 +458,7 @@ int mjpc_hip_lds_bytes(MjpcHipEngine *e);
 int mjpc_hip_dense_tier(MjpcHipEngine *e, int *used_last);
 /* The same figure for a model without creating an engine (host-only, no GPU needed): with (1) / without (0) the LDS copy of
  * the model tables; use_cache | 2: the dense tier's lean layout at the model's nefcmax / nconmax.  Negative: mjpc_hip_create
- * would refuse the model (see mjpc_hip_last_error). */
+ * would refuse the model or the views (struct_size) (see mjpc_hip_last_error). */
 int mjpc_hip_layout_bytes(const MjpcHipModel *model, const MjpcHipTask *task, int use_cache);
 /* Kinematic frame of local candidate 0 at the first step of the last plan (the state handed in): what a host-side
  * Task::Transition reads from mjData after a simulation step (mjpc/tasks/quadruped/quadruped.cc:254,290-330: body poses, site

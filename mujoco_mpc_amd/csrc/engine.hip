@@ -15,6 +15,8 @@
 //                   knots, and the A / B / C / D entries from the stepped rows
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
+//   pack_kernel     the plan's result in one contiguous buffer for one D2H copy
+// Host side (from the banner below): the engine's buffers (devbuf.h, enum Buf), flavour and dense-tier choice, the C ABI.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,6 +29,7 @@
 #include "gradient.h"
 #include "transition_fd.h"
 #include "host.h"
+#include "devbuf.h"
 #include "../../include/mjpc_hip_debug.h"
 
 // ------------------------------------------------------------------------------ kernels
@@ -181,58 +184,116 @@ static void set_error(const std::string &s) { g_error = s; }
 // inside mjpc_hip_create only: `e` (when already allocated) and everything it owns are released on the error path
 #define HIPCHKP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); mjpc_hip_destroy(e); return nullptr; } } while (0)
 
+// Every device and pinned buffer of an engine is a DevBuf (devbuf.h) in MjpcHipEngine::buf, named by this enum: mjpc_hip_destroy walks
+// the array, so a buffer added here cannot be forgotten there.  The seven per-candidate row arrays stand together, in the packed
+// order of pack_kernel (row_doubles below); pinned host memory comes last (from H_PACK on).
+enum Buf {
+  B_IB, B_DB,                                                        // the packed model
+  B_STATE, B_MOCAP, B_USERDATA, B_KT, B_KV, B_STD, B_SEL,            // plan inputs (userdata: mjData.userdata of the plan's state, State::CopyTo, states/state.cc:128-135: carried for residuals that read it)
+  B_EPS, B_CAND,                                                     // noise / candidate table, grown on demand
+  B_KNOTS, B_STATES, B_ACTIONS, B_TIMES, B_RESIDUAL, B_COSTS, B_TRACE,      // row arrays (knots grown on demand)
+  B_RETURNS, B_FAILURE, B_DIAG, B_WINNER, B_WINNER_VAL, B_PROF, B_FRAME,
+  B_CKPT,                                                            // dense-tier checkpoints for the retry launch
+  B_SLAB,                                                            // spill flavour: per-candidate HBM slab
+  B_HIST, B_SLOT, B_SCALE, B_GRAD,                                   // Sample-Gradient planner: noise history [max_local][P_max * nu], gradient inputs / output
+  B_FD,                                                              // one-step calls: the call's tables (inputs, stepped rows, matrices), grown on demand
+  B_PACK,                                                            // packed plan result, grown on demand
+  H_PACK, H_SMALL, H_TASK0, H_TASK1,                                 // pinned: packed plan result | small plan inputs (Staging) | set_task staging
+  B_COUNT
+};
+#define NROWS 7
+
+// the dense tier (two workgroups per CU) of a model, see "Capacity tiers" above; k = nullptr: none
+struct DenseTier { RolloutFn k = nullptr; Lay lay; int nefc = 0, ncon = 0, ci = 0, cd = 0; size_t lds = 0; };
+// pinned staging block of the small inputs (H_SMALL), offsets in doubles: one layout for plans and one-step calls
+struct Staging { size_t state, mocap, kt, kv, std, userdata, size; };
+
 struct MjpcHipEngine {
   int device = 0;
   PackedModel pm;
-  int *d_ib = nullptr; double *d_db = nullptr;
+  DevBuf buf[B_COUNT];
+  template <class T = double> T *at(int b) const { return (T *)buf[b].p; }
   KParams K;
   int max_local = 0, max_horizon = 0, P_max = 0;
   int nq = 0, nv = 0, nu = 0, nmocap = 0, nr = 0, ntr = 0, ds = 0, nuserdata = 0;
-  double *d_userdata = nullptr;      // mjData.userdata of the plan's state (State::CopyTo, states/state.cc:128-135): carried for residuals that read it
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  // device buffers
-  double *d_state = nullptr, *d_mocap = nullptr, *d_kt = nullptr, *d_kv = nullptr, *d_eps = nullptr, *d_std = nullptr, *d_cand = nullptr; size_t cand_cap = 0;
-  int *d_sel = nullptr;
-  size_t eps_cap = 0;
-  double *d_states = nullptr, *d_actions = nullptr, *d_times = nullptr, *d_residual = nullptr, *d_costs = nullptr,
-         *d_trace = nullptr, *d_knots = nullptr, *d_returns = nullptr, *d_winner_val = nullptr;
-  size_t knots_cap = 0;
-  int *d_failure = nullptr, *d_diag = nullptr, *d_winner = nullptr;
-  long long *d_prof = nullptr;
-  double *d_frame = nullptr; int nbody = 0, nsite = 0;
-  double *d_ckpt = nullptr; int ckpt_stride = 0;          // dense-tier checkpoints for the retry launch
-  // pinned host staging
-  double *d_pack = nullptr, *h_pack = nullptr; size_t pack_cap = 0;   // packed plan result (device / pinned host)
-  double *h_small = nullptr;   // state | mocap | knot_times | knot_values | noise_std
-  void *h_task[2] = {nullptr, nullptr}; hipEvent_t ev_task[2] = {nullptr, nullptr}; int task_slot = 0;   // set_task staging
+  int nbody = 0, nsite = 0;
+  int ckpt_stride = 0;
+  Staging hs;
+  hipEvent_t ev_task[2] = {nullptr, nullptr}; int task_slot = 0;   // set_task staging
   // last plan
   int last_H = 0, last_P = 0, last_nlocal = 0, last_offset = 0, pending = 0;
   // kernel timing accumulation
   double acc_rollout_us = 0, acc_total_us = 0; int acc_n = 0;
   size_t lds_bytes = 0;
   RolloutFn kernel = nullptr; bool cached = true;
-  bool spill = false; double *d_slab = nullptr; int slab_bytes = 0;   // spill flavour: per-candidate HBM slab (bytes per candidate, whole 256-B blocks)
+  bool spill = false; int slab_bytes = 0;   // spill flavour: bytes of slab per candidate, whole 256-B blocks
   int fault = 0;               // diagnostics knob fault_inject (mjpc_hip_debug.h; test-suite only)
   int summary_only = 0, last_summary = 0;      // mjpc_hip_set_fetch_mode
   int last_dense = 0;
-  // Sample-Gradient planner (mjpc_hip_plan_mixed / mjpc_hip_sample_gradient): noise history [max_local][P_max * nu], gradient inputs / output
-  double *d_hist = nullptr, *d_scale = nullptr, *d_grad = nullptr; int *d_slot = nullptr; int have_mixed = 0;
-  // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour;
-  // d_fd: the call's tables (inputs, stepped rows, matrices), grown on demand
+  int have_mixed = 0;          // a mjpc_hip_plan_mixed step has filled the noise history
+  // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour
   const void *step_kernel = nullptr; StepLaunchFn step_launch = nullptr;
-  char *d_fd = nullptr; size_t fd_cap = 0;
-  // dense tier (two workgroups per CU), see "Capacity tiers" above
-  RolloutFn kernelB = nullptr; Lay layB; int nefcB = 0, nconB = 0, cacheB_i = 0, cacheB_d = 0; size_t ldsB = 0; int num_cu = 256, force_tier = 0;
+  DenseTier tierB; int num_cu = 256, force_tier = 0;
+  MjpcHipEngine() { for (int b = H_PACK; b < B_COUNT; b++) buf[b].kind = DevBuf::PINNED; }
 };
 
+// doubles per candidate of row array k = 0 .. 6 (knots, states, actions, times, residual, costs, trace: buffer B_KNOTS + k, the order
+// of the packed result) in a plan of H steps and P knots; pad: with the spare element per row the allocation of some of them carries
+static size_t row_doubles(const MjpcHipEngine *e, int k, size_t H, size_t P, bool pad = false) {
+  const int width[NROWS] = {e->nu, e->ds, e->nu, 1, e->nr, 1, e->ntr}, spare[NROWS] = {0, 0, 1, 0, 1, 0, 1};
+  return (k == 0 ? P : H) * (size_t)(width[k] + (pad ? spare[k] : 0));
+}
+// where a plan output takes row array k (any may be null)
+static double *out_row(const MjpcHipPlanOutput *out, int k) {
+  double *dst[NROWS] = {out->winner_knots, out->states, out->actions, out->times, out->residual, out->costs, out->trace};
+  return dst[k];
+}
+
 static int upload_model(MjpcHipEngine *e) {
-  HIPCHK(hipMemcpy(e->d_ib, e->pm.ib.data(), e->pm.ib.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_db, e->pm.db.data(), e->pm.db.size() * sizeof(double), hipMemcpyHostToDevice));
-  e->K.M = mjpc_host::relocate(e->pm, e->d_ib, e->d_db);
+  int *d_ib = e->at<int>(B_IB); double *d_db = e->at(B_DB);
+  HIPCHK(hipMemcpy(d_ib, e->pm.ib.data(), e->pm.ib.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_db, e->pm.db.data(), e->pm.db.size() * sizeof(double), hipMemcpyHostToDevice));
+  e->K.M = mjpc_host::relocate(e->pm, d_ib, d_db);
   e->K.L = e->pm.L;
-  e->K.ibase = e->d_ib; e->K.dbase = e->d_db; e->K.cache_i = (int)e->pm.cache_i; e->K.cache_d = (int)e->pm.cache_d;
+  e->K.ibase = d_ib; e->K.dbase = d_db; e->K.cache_i = (int)e->pm.cache_i; e->K.cache_d = (int)e->pm.cache_d;
   return 0;
+}
+
+// everything in e->K that no call decides: the buffers allocated once by mjpc_hip_create and the engine's constants.  A plan sets the
+// rest (plan_async_impl); a one-step call works on a copy and clears what it does not use (step_prepare)
+static void bind_params(MjpcHipEngine *e) {
+  KParams &K = e->K;
+  K.state = e->at(B_STATE); K.mocap = e->at(B_MOCAP); K.userdata = e->at(B_USERDATA); K.nuserdata = e->nuserdata;
+  K.knot_times = e->at(B_KT); K.knot_values = e->at(B_KV); K.noise_sel = e->at<int>(B_SEL);
+  K.states = e->at(B_STATES); K.actions = e->at(B_ACTIONS); K.times = e->at(B_TIMES); K.residual = e->at(B_RESIDUAL); K.costs = e->at(B_COSTS);
+  K.trace = e->at(B_TRACE); K.returns = e->at(B_RETURNS); K.failure = e->at<int>(B_FAILURE); K.diag = e->at<int>(B_DIAG);
+  K.prof = e->at<long long>(B_PROF); K.frame = e->at(B_FRAME);
+  K.retry = 0; K.tier = 0; K.ckpt = e->at(B_CKPT); K.ckpt_stride = e->ckpt_stride;
+  K.fault = e->fault;
+  K.slab = e->at(B_SLAB); K.slab_stride = e->slab_bytes / (long long)sizeof(double);
+}
+
+// the knots array holds max_local rows of P knots (grown on demand); K.knots follows a reallocation
+static hipError_t reserve_knots(MjpcHipEngine *e, int P) {
+  hipError_t rc = e->buf[B_KNOTS].reserve(sizeof(double) * ((size_t)e->max_local * P * e->nu + 1));
+  e->K.knots = e->at(B_KNOTS);
+  return rc;
+}
+
+// n doubles of the caller's (zeros when src is null) through the pinned staging block at offset `at` into device buffer b, stream-ordered
+static hipError_t stage(MjpcHipEngine *e, size_t at, const double *src, size_t n, int b) {
+  double *h = e->at(H_SMALL) + at;
+  if (src) memcpy(h, src, sizeof(double) * n); else memset(h, 0, sizeof(double) * n);
+  return hipMemcpyAsync(e->at(b), h, sizeof(double) * n, hipMemcpyHostToDevice, e->stream);
+}
+
+// the struct_size test of the view structs (model = nullptr: the task alone); hint: appended to the message
+static bool check_views(const MjpcHipModel *model, const MjpcHipTask *task, const char *who, const std::string &hint = "") {
+  if ((!model || model->struct_size == (int)sizeof(MjpcHipModel)) && task->struct_size == (int)sizeof(MjpcHipTask)) return true;
+  set_error(std::string(who) + (model ? ": MjpcHipModel / MjpcHipTask struct_size" : ": MjpcHipTask.struct_size") + " does not match this library" + hint);
+  return false;
 }
 
 // Kernel flavour of the full-capacity launch: tables cached in LDS when that fits next to the candidate's state and a
@@ -273,6 +334,46 @@ static bool pick_flavour(const MjpcHipModel *model, const MjpcHipTask *task, int
   return true;
 }
 
+// dense tier: needs a compile-time-nv kernel of that flavour, a model that asks for more capacity than the tier's and a
+// layout of <= 80 KiB.  pm: the model as pick_flavour packed it (its own capacities)
+static DenseTier pick_dense_tier(const MjpcHipModel *model, const MjpcHipTask *task, int P_max, const PackedModel &pm) {
+  DenseTier plain, hot;
+  int exact_b = 0;
+  RolloutFn kb = mjpc_pick_rollout_dense2(model->nv, &exact_b);
+  // (a model with a noslip pass runs at full capacity only: the pass recomputes qacc from efc_force, and the last commit's
+  // force bits - unlike the iterate - are not pinned across kernel flavours, so the tiers would agree to rounding, not bit for bit)
+  if (!(exact_b && model->noslip_iterations <= 0)) return plain;
+  // capacity of the dense tier: the largest (rows, contacts = rows / 4 + 2) not above the model's own whose lean layout fits
+  // 80 KiB; below 40 rows the retry pass would be the rule, not the exception
+  int cap_e = 0, cap_c = 0;
+  std::string cap;
+  if (mjpc_host::debug_knob("dense_tier_cap", &cap)) {       // diagnostics knob "nefcmax,nconmax": a tiny dense tier forces the retry pass
+    int a = 0, b = 0;
+    if (sscanf(cap.c_str(), "%d,%d", &a, &b) == 2 && a > 0 && b > 0 && a <= pm.M.nefcmax && b <= pm.M.nconmax) { cap_e = a; cap_c = b; }
+  }
+  int first = pm.M.nefcmax < TIERB_NEFCMAX ? pm.M.nefcmax : TIERB_NEFCMAX;
+  // two variants of the flavour: with the hot prefix of the tables in LDS (rollout_dense2h.hip; costs capacity) and without.
+  // The hot-cached one is taken when it exists for this dof count and still holds TIERB_HOT_KEEP of the plain one's rows
+  int exact_h = 0;
+  RolloutFn kh = mjpc_pick_rollout_dense2h(model->nv, &exact_h);
+  for (int variant = 0; variant < 2; variant++) {
+    DenseTier &cd = variant ? hot : plain;
+    if (variant && (!exact_h || cap_e)) break;          // (a forced tiny tier is the plain flavour's test case)
+    for (int ne = cap_e ? cap_e : first; ne >= (cap_e ? cap_e : TIERB_NEFCMIN) && !cd.k; ne -= 4) {
+      MjpcHipModel mb = *model;
+      mb.nefcmax = ne; mb.nconmax = cap_e ? cap_c : ne / 4 + 2;
+      if (mb.nconmax > pm.M.nconmax) mb.nconmax = pm.M.nconmax;
+      PackedModel pmB;
+      if (mjpc_host::build(pmB, &mb, task, P_max, false, true, variant == 1, true) && (size_t)pmB.L.total_doubles * sizeof(double) <= TIERB_LDS_LIMIT) {
+        cd.k = variant ? kh : kb; cd.lay = pmB.L; cd.nefc = pmB.M.nefcmax; cd.ncon = pmB.M.nconmax;
+        cd.ci = (int)pmB.cache_i; cd.cd = (int)pmB.cache_d;
+        cd.lds = (size_t)pmB.L.total_doubles * sizeof(double);
+      }
+    }
+  }
+  return (hot.k && plain.k && hot.nefc * 100 >= plain.nefc * TIERB_HOT_KEEP) ? hot : plain;
+}
+
 extern "C" {
 void mjpc_hip_destroy(MjpcHipEngine *e);
 
@@ -285,12 +386,9 @@ int mjpc_hip_sizeof_plan_input(void) { return (int)sizeof(MjpcHipPlanInput); }
 int mjpc_hip_sizeof_plan_output(void) { return (int)sizeof(MjpcHipPlanOutput); }
 
 MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *task, int max_local, int max_horizon, int device) {
+  // arguments
   if (!model || !task || max_local < 1 || max_horizon < 1 || max_horizon > MJPC_MAX_HORIZON) { set_error("mjpc_hip_create: invalid argument"); return nullptr; }
-  if (model->struct_size != (int)sizeof(MjpcHipModel) || task->struct_size != (int)sizeof(MjpcHipTask)) {
-    set_error("mjpc_hip_create: MjpcHipModel / MjpcHipTask struct_size does not match this library (ABI revision " + std::to_string(MJPC_HIP_ABI_VERSION) +
-              ": header and library out of step, or struct_size not set)");
-    return nullptr;
-  }
+  if (!check_views(model, task, "mjpc_hip_create", " (ABI revision " + std::to_string(MJPC_HIP_ABI_VERSION) + ": header and library out of step, or struct_size not set)")) return nullptr;
   int ndev = 0;
   MjpcHipEngine *e = nullptr;
   HIPCHKP(hipGetDeviceCount(&ndev));
@@ -299,109 +397,46 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   e = new MjpcHipEngine();
   e->device = device;
   e->P_max = 36;     // MaxSamplingSplinePoints (mjpc/planners/sampling/planner.h:35-36)
-  {
-    bool use_cache = true, spill = false;
-    if (!pick_flavour(model, task, e->P_max, e->pm, &e->kernel, &use_cache, &spill, "mjpc_hip_create")) { delete e; return nullptr; }
-    e->spill = spill;
-    // (the compile-time-nv spill kernels' register-solver layout can fit without a slab where the generic direct one did not)
-    if (spill) e->slab_bytes = (int)(((size_t)e->pm.slab_doubles * sizeof(double) + 255) / 256 * 256);
-    // dense tier: needs a compile-time-nv kernel of that flavour, a model that asks for more capacity than the tier's and a
-    // layout of <= 80 KiB
-    int exact_b = 0;
-    RolloutFn kb = mjpc_pick_rollout_dense2(model->nv, &exact_b);
-    // (a model with a noslip pass runs at full capacity only: the pass recomputes qacc from efc_force, and the last commit's
-    // force bits - unlike the iterate - are not pinned across kernel flavours, so the tiers would agree to rounding, not bit for bit)
-    if (exact_b && model->noslip_iterations <= 0) {
-      // capacity of the dense tier: the largest (rows, contacts = rows / 4 + 2) not above the model's own whose lean layout fits
-      // 80 KiB; below 40 rows the retry pass would be the rule, not the exception
-      int cap_e = 0, cap_c = 0;
-      std::string cap;
-      if (mjpc_host::debug_knob("dense_tier_cap", &cap)) {       // diagnostics knob "nefcmax,nconmax": a tiny dense tier forces the retry pass
-        int a = 0, b = 0;
-        if (sscanf(cap.c_str(), "%d,%d", &a, &b) == 2 && a > 0 && b > 0 && a <= e->pm.M.nefcmax && b <= e->pm.M.nconmax) { cap_e = a; cap_c = b; }
-      }
-      int first = e->pm.M.nefcmax < TIERB_NEFCMAX ? e->pm.M.nefcmax : TIERB_NEFCMAX;
-      // two variants of the flavour: with the hot prefix of the tables in LDS (rollout_dense2h.hip; costs capacity) and without.
-      // The hot-cached one is taken when it exists for this dof count and still holds TIERB_HOT_KEEP of the plain one's rows
-      int exact_h = 0;
-      RolloutFn kh = mjpc_pick_rollout_dense2h(model->nv, &exact_h);
-      struct Cand { RolloutFn k = nullptr; Lay lay; int nefc = 0, ncon = 0, ci = 0, cd = 0; size_t lds = 0; } plain, hot;
-      for (int variant = 0; variant < 2; variant++) {
-        Cand &cd = variant ? hot : plain;
-        if (variant && (!exact_h || cap_e)) break;          // (a forced tiny tier is the plain flavour's test case)
-        for (int ne = cap_e ? cap_e : first; ne >= (cap_e ? cap_e : TIERB_NEFCMIN) && !cd.k; ne -= 4) {
-          MjpcHipModel mb = *model;
-          mb.nefcmax = ne; mb.nconmax = cap_e ? cap_c : ne / 4 + 2;
-          if (mb.nconmax > e->pm.M.nconmax) mb.nconmax = e->pm.M.nconmax;
-          PackedModel pmB;
-          if (mjpc_host::build(pmB, &mb, task, e->P_max, false, true, variant == 1, true) && (size_t)pmB.L.total_doubles * sizeof(double) <= TIERB_LDS_LIMIT) {
-            cd.k = variant ? kh : kb; cd.lay = pmB.L; cd.nefc = pmB.M.nefcmax; cd.ncon = pmB.M.nconmax;
-            cd.ci = (int)pmB.cache_i; cd.cd = (int)pmB.cache_d;
-            cd.lds = (size_t)pmB.L.total_doubles * sizeof(double);
-          }
-        }
-      }
-      const Cand &use = (hot.k && plain.k && hot.nefc * 100 >= plain.nefc * TIERB_HOT_KEEP) ? hot : plain;
-      if (use.k) { e->kernelB = use.k; e->layB = use.lay; e->nefcB = use.nefc; e->nconB = use.ncon; e->cacheB_i = use.ci; e->cacheB_d = use.cd; e->ldsB = use.lds; }
-    }
-    std::string tier, fi;                                 // diagnostics knobs: "A" = never the dense tier, "B" = always (when it exists)
-    e->force_tier = mjpc_host::debug_knob("tier", &tier) ? (tier[0] == 'B' ? 2 : 1) : 0;
-    e->fault = (mjpc_host::debug_knob("fault_inject", &fi) && fi == "sync") ? 1 : 0;
-    e->cached = use_cache;
-  }
   memset(&e->K, 0, sizeof(e->K));
   e->max_local = max_local; e->max_horizon = max_horizon;
-  e->nq = model->nq; e->nv = model->nv; e->nu = model->nu; e->nmocap = model->nmocap;
+  e->nq = model->nq; e->nv = model->nv; e->nu = model->nu; e->nmocap = model->nmocap; e->nuserdata = model->nuserdata;
   e->nr = task->num_residual; e->ntr = 3 * task->num_trace; e->ds = model->nq + model->nv + model->na;
+  e->nbody = model->nbody; e->nsite = model->nsite;
+  // flavour of the full-capacity launch, dense tier
+  if (!pick_flavour(model, task, e->P_max, e->pm, &e->kernel, &e->cached, &e->spill, "mjpc_hip_create")) { mjpc_hip_destroy(e); return nullptr; }
+  // (the compile-time-nv spill kernels' register-solver layout can fit without a slab where the generic direct one did not)
+  if (e->spill) e->slab_bytes = (int)(((size_t)e->pm.slab_doubles * sizeof(double) + 255) / 256 * 256);
   e->lds_bytes = (size_t)e->pm.L.total_doubles * sizeof(double);
-  if (e->lds_bytes > 160 * 1024) { set_error("mjpc_hip_create: per-candidate state exceeds 160 KiB of LDS; lower nconmax/nefcmax"); delete e; return nullptr; }
-  HIPCHKP(hipMalloc(&e->d_ib, e->pm.ib.size() * sizeof(int)));
-  HIPCHKP(hipMalloc(&e->d_db, e->pm.db.size() * sizeof(double)));
+  e->tierB = pick_dense_tier(model, task, e->P_max, e->pm);
+  if (e->tierB.k) e->ckpt_stride = 7 + e->nq + 2 * e->nv + model->na + 1;
+  std::string tier, fi;                                 // diagnostics knobs: "A" = never the dense tier, "B" = always (when it exists)
+  e->force_tier = mjpc_host::debug_knob("tier", &tier) ? (tier[0] == 'B' ? 2 : 1) : 0;
+  e->fault = (mjpc_host::debug_knob("fault_inject", &fi) && fi == "sync") ? 1 : 0;
+  // buffers of fixed size (the others grow with the calls), the model's image
+  const size_t NL = (size_t)max_local, H = (size_t)max_horizon, D = sizeof(double), PN = (size_t)e->P_max * e->nu;
+  Staging &s = e->hs;
+  s.state = 0; s.mocap = s.state + e->ds; s.kt = s.mocap + 7 * e->nmocap; s.kv = s.kt + e->P_max; s.std = s.kv + PN; s.userdata = s.std + PN;
+  s.size = s.userdata + e->nuserdata + 16;
+  const struct { int b; size_t bytes; } fixed[] = {
+    {B_IB, e->pm.ib.size() * sizeof(int)}, {B_DB, e->pm.db.size() * D},
+    {B_SLAB, NL * e->slab_bytes},                // spill flavour: one slab per local candidate; holds no state across launches (like LDS)
+    {B_STATE, D * (e->ds + 1)}, {B_MOCAP, D * (7 * e->nmocap + 7)}, {B_USERDATA, D * (e->nuserdata + 1)},
+    {B_KT, D * e->P_max}, {B_KV, D * (PN + 1)}, {B_STD, D * (PN + 1)}, {B_SEL, sizeof(int) * NL},
+    {B_RETURNS, D * NL}, {B_FAILURE, sizeof(int) * NL}, {B_DIAG, sizeof(int) * NL * 4}, {B_WINNER, sizeof(int) * 2}, {B_WINNER_VAL, D * 2},
+    {B_FRAME, D * (18 * (size_t)e->nbody + 3 * (size_t)e->nsite + 1)}, {B_PROF, sizeof(long long) * NL * 24},
+    {B_HIST, D * NL * e->P_max * (e->nu + 1)}, {B_SLOT, sizeof(int) * NL}, {B_SCALE, D * NL}, {B_GRAD, D * (PN + 1)},
+    {B_CKPT, D * NL * e->ckpt_stride}, {H_SMALL, D * s.size}};
+  for (const auto &f : fixed) HIPCHKP(e->buf[f.b].reserve(f.bytes));
+  for (int k = 1; k < NROWS; k++) HIPCHKP(e->buf[B_KNOTS + k].reserve(D * NL * row_doubles(e, k, H, 0, true)));
+  for (int b : {B_PROF, B_HIST, B_CKPT}) if (e->buf[b].p) HIPCHKP(hipMemset(e->buf[b].p, 0, e->buf[b].cap));
   if (upload_model(e) != 0) { mjpc_hip_destroy(e); return nullptr; }
-  if (e->slab_bytes) {          // spill flavour: one slab per local candidate; holds no state across launches (like LDS)
-    HIPCHKP(hipMalloc(&e->d_slab, (size_t)max_local * e->slab_bytes));
-    e->K.slab = e->d_slab; e->K.slab_stride = e->slab_bytes / (long long)sizeof(double);
-  }
   HIPCHKP(hipStreamCreate(&e->stream));
   for (int i = 0; i < 4; i++) HIPCHKP(hipEventCreate(&e->ev[i]));
-  size_t NL = (size_t)max_local, H = (size_t)max_horizon;
-  HIPCHKP(hipMalloc(&e->d_state, sizeof(double) * (e->ds + 1)));
-  HIPCHKP(hipMalloc(&e->d_mocap, sizeof(double) * (7 * e->nmocap + 7)));
-  e->nuserdata = model->nuserdata;
-  HIPCHKP(hipMalloc(&e->d_userdata, sizeof(double) * (e->nuserdata + 1)));
-  HIPCHKP(hipMalloc(&e->d_kt, sizeof(double) * e->P_max));
-  HIPCHKP(hipMalloc(&e->d_kv, sizeof(double) * (e->P_max * e->nu + 1)));
-  HIPCHKP(hipMalloc(&e->d_std, sizeof(double) * (e->P_max * e->nu + 1)));
-  HIPCHKP(hipMalloc(&e->d_sel, sizeof(int) * NL));
-  HIPCHKP(hipMalloc(&e->d_states, sizeof(double) * NL * H * e->ds));
-  HIPCHKP(hipMalloc(&e->d_actions, sizeof(double) * NL * H * (e->nu + 1)));
-  HIPCHKP(hipMalloc(&e->d_times, sizeof(double) * NL * H));
-  HIPCHKP(hipMalloc(&e->d_residual, sizeof(double) * NL * H * (e->nr + 1)));
-  HIPCHKP(hipMalloc(&e->d_costs, sizeof(double) * NL * H));
-  HIPCHKP(hipMalloc(&e->d_trace, sizeof(double) * NL * H * (e->ntr + 1)));
-  HIPCHKP(hipMalloc(&e->d_returns, sizeof(double) * NL));
-  HIPCHKP(hipMalloc(&e->d_failure, sizeof(int) * NL));
-  HIPCHKP(hipMalloc(&e->d_diag, sizeof(int) * NL * 4));
-  HIPCHKP(hipMalloc(&e->d_winner, sizeof(int) * 2));
-  e->nbody = model->nbody; e->nsite = model->nsite;
-  HIPCHKP(hipMalloc(&e->d_frame, sizeof(double) * (18 * (size_t)e->nbody + 3 * (size_t)e->nsite + 1)));
-  HIPCHKP(hipMalloc(&e->d_prof, sizeof(long long) * NL * 24));
-  HIPCHKP(hipMemset(e->d_prof, 0, sizeof(long long) * NL * 24));
-  HIPCHKP(hipMalloc(&e->d_winner_val, sizeof(double) * 2));
-  HIPCHKP(hipMalloc(&e->d_hist, sizeof(double) * NL * e->P_max * (e->nu + 1)));
-  HIPCHKP(hipMemset(e->d_hist, 0, sizeof(double) * NL * e->P_max * (e->nu + 1)));
-  HIPCHKP(hipMalloc(&e->d_slot, sizeof(int) * NL));
-  HIPCHKP(hipMalloc(&e->d_scale, sizeof(double) * NL));
-  HIPCHKP(hipMalloc(&e->d_grad, sizeof(double) * (e->P_max * e->nu + 1)));
-  HIPCHKP(hipHostMalloc(&e->h_small, sizeof(double) * (e->ds + 7 * e->nmocap + e->P_max * (2 * e->nu + 1) + model->nuserdata + 16)));
   HIPCHKP(hipFuncSetAttribute((const void *)e->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
-  if (e->kernelB) {
-    HIPCHKP(hipFuncSetAttribute((const void *)e->kernelB, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->ldsB));
-    e->ckpt_stride = 7 + e->nq + 2 * e->nv + model->na + 1;
-    HIPCHKP(hipMalloc(&e->d_ckpt, sizeof(double) * NL * e->ckpt_stride));
-    HIPCHKP(hipMemset(e->d_ckpt, 0, sizeof(double) * NL * e->ckpt_stride));
-  }
+  if (e->tierB.k) HIPCHKP(hipFuncSetAttribute((const void *)e->tierB.k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->tierB.lds));
   { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cu = prop.multiProcessorCount; }
+  // kernel parameters that no call decides
+  bind_params(e);
   return e;
 }
 
@@ -409,15 +444,8 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
   if (!e) return;
   hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
-  void *bufs[] = {e->d_userdata, e->d_cand, e->d_std, e->d_ib, e->d_db, e->d_state, e->d_mocap, e->d_kt, e->d_kv, e->d_eps, e->d_sel, e->d_states, e->d_actions,
-                  e->d_times, e->d_residual, e->d_costs, e->d_trace, e->d_knots, e->d_returns, e->d_failure, e->d_diag,
-                  e->d_winner, e->d_winner_val, e->d_prof, e->d_frame, e->d_ckpt, e->d_slab,
-                  e->d_hist, e->d_slot, e->d_scale, e->d_grad, e->d_fd};
-  for (void *b : bufs) if (b) hipFree(b);
-  if (e->h_small) hipHostFree(e->h_small);
-  for (int i = 0; i < 2; i++) { if (e->h_task[i]) hipHostFree(e->h_task[i]); if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]); }
-  if (e->h_pack) hipHostFree(e->h_pack);
-  if (e->d_pack) hipFree(e->d_pack);
+  for (DevBuf &b : e->buf) b.release();
+  for (int i = 0; i < 2; i++) if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]);
   for (int i = 0; i < 4; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
@@ -425,7 +453,7 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
 
 int mjpc_hip_set_task(MjpcHipEngine *e, const MjpcHipTask *task) {
   if (!e || !task) { set_error("mjpc_hip_set_task: invalid argument"); return -1; }
-  if (task->struct_size != (int)sizeof(MjpcHipTask)) { set_error("mjpc_hip_set_task: MjpcHipTask.struct_size does not match this library"); return -1; }
+  if (!check_views(nullptr, task, "mjpc_hip_set_task")) return -1;
   HIPCHK(hipSetDevice(e->device));
   if (task->num_residual != e->nr || 3 * task->num_trace != e->ntr) { set_error("mjpc_hip_set_task: residual/trace dimensions changed"); return -1; }
   if (e->pending) { set_error("mjpc_hip_set_task: a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
@@ -435,17 +463,16 @@ int mjpc_hip_set_task(MjpcHipEngine *e, const MjpcHipTask *task) {
   const PackedModel &pm = e->pm;
   size_t bi = pm.task_i_cap * sizeof(int), bd = pm.task_d_cap * sizeof(double);
   int slot = e->task_slot ^= 1;                       // two pinned staging slots: the copy of the previous call may still be in flight
-  if (!e->h_task[slot]) {
-    HIPCHK(hipHostMalloc(&e->h_task[slot], bi + bd + 16));
-    HIPCHK(hipEventCreateWithFlags(&e->ev_task[slot], hipEventDisableTiming));
-  } else HIPCHK(hipEventSynchronize(e->ev_task[slot]));
-  char *stage = (char *)e->h_task[slot];
-  memcpy(stage, pm.db.data() + pm.task_d0, bd);
-  memcpy(stage + bd, pm.ib.data() + pm.task_i0, bi);
-  HIPCHK(hipMemcpyAsync(e->d_db + pm.task_d0, stage, bd, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(e->d_ib + pm.task_i0, stage + bd, bi, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e->buf[H_TASK0 + slot].reserve(bi + bd + 16));
+  if (!e->ev_task[slot]) HIPCHK(hipEventCreateWithFlags(&e->ev_task[slot], hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->ev_task[slot]));
+  char *h = e->at<char>(H_TASK0 + slot);
+  memcpy(h, pm.db.data() + pm.task_d0, bd);
+  memcpy(h + bd, pm.ib.data() + pm.task_i0, bi);
+  HIPCHK(hipMemcpyAsync(e->at(B_DB) + pm.task_d0, h, bd, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(e->at<int>(B_IB) + pm.task_i0, h + bd, bi, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipEventRecord(e->ev_task[slot], e->stream));
-  e->K.M = mjpc_host::relocate(e->pm, e->d_ib, e->d_db);
+  e->K.M = mjpc_host::relocate(e->pm, e->at<int>(B_IB), e->at(B_DB));
   return 0;
 }
 
@@ -465,114 +492,81 @@ static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int fir
     if (!in->noise_std) { set_error("mjpc_hip_plan_mixed: noise_std is required"); return -1; }
     if (first_explicit < in->num_trajectory && !in->candidate_knots) { set_error("mjpc_hip_plan_mixed: candidate_knots is required for the rows from first_explicit on"); return -1; }
   }
+  if (in->xfrc_std > 0 && !(in->xfrc_rate > 0)) { set_error("mjpc_hip_plan: xfrc_rate must be positive when xfrc_std > 0"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  size_t need = (size_t)nl * P * nu;
-  if (need > e->eps_cap) {
-    if (e->d_eps) HIPCHK(hipFree(e->d_eps));
-    HIPCHK(hipMalloc(&e->d_eps, sizeof(double) * (need + 1)));
-    e->eps_cap = need;
-  }
-  if (need > e->knots_cap) {
-    if (e->d_knots) HIPCHK(hipFree(e->d_knots));
-    HIPCHK(hipMalloc(&e->d_knots, sizeof(double) * ((size_t)e->max_local * P * nu + 1)));
-    e->knots_cap = (size_t)e->max_local * P * nu;
-  }
+  // the buffers that grow with the plan (a repeated plan allocates nothing); the packed result: pack_kernel
+  const size_t need = (size_t)nl * P * nu;
+  const bool table = in->candidate_knots || mixed;
+  size_t need_pack = 2 + 2 * (size_t)nl;
+  for (int k = 0; k < (e->summary_only ? 1 : NROWS); k++) need_pack += row_doubles(e, k, H, P);
+  HIPCHK(e->buf[B_EPS].reserve(sizeof(double) * (need + 1)));
+  HIPCHK(reserve_knots(e, P));
+  if (table) HIPCHK(e->buf[B_CAND].reserve(sizeof(double) * (need + 1)));
+  HIPCHK(e->buf[B_PACK].reserve(sizeof(double) * need_pack));
+  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * need_pack));
+  double *d_eps = e->at(B_EPS), *d_cand = e->at(B_CAND), *d_std = e->at(B_STD);
+  int *d_sel = e->at<int>(B_SEL);
   // small inputs through pinned staging
-  double *hs = e->h_small;
-  memcpy(hs, in->state, sizeof(double) * e->ds);
-  if (e->nmocap) memcpy(hs + e->ds, in->mocap, sizeof(double) * 7 * e->nmocap);
-  double *hkt = hs + e->ds + 7 * e->nmocap, *hkv = hkt + e->P_max;
-  memcpy(hkt, in->knot_times, sizeof(double) * P);
-  memcpy(hkv, in->knot_values, sizeof(double) * P * nu);
-  HIPCHK(hipMemcpyAsync(e->d_state, hs, sizeof(double) * e->ds, hipMemcpyHostToDevice, e->stream));
-  if (e->nmocap) HIPCHK(hipMemcpyAsync(e->d_mocap, hs + e->ds, sizeof(double) * 7 * e->nmocap, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(e->d_kt, hkt, sizeof(double) * P, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(e->d_kv, hkv, sizeof(double) * P * nu, hipMemcpyHostToDevice, e->stream));
-  if (e->nuserdata) {
-    double *hu = hkv + 2 * e->P_max * nu;
-    if (in->userdata) memcpy(hu, in->userdata, sizeof(double) * e->nuserdata); else memset(hu, 0, sizeof(double) * e->nuserdata);
-    HIPCHK(hipMemcpyAsync(e->d_userdata, hu, sizeof(double) * e->nuserdata, hipMemcpyHostToDevice, e->stream));
-  }
-  if (in->noise_std) {
-    memcpy(hkv + e->P_max * nu, in->noise_std, sizeof(double) * P * nu);
-    HIPCHK(hipMemcpyAsync(e->d_std, hkv + e->P_max * nu, sizeof(double) * P * nu, hipMemcpyHostToDevice, e->stream));
-  }
+  const Staging &s = e->hs;
+  HIPCHK(stage(e, s.state, in->state, e->ds, B_STATE));
+  if (e->nmocap) HIPCHK(stage(e, s.mocap, in->mocap, 7 * e->nmocap, B_MOCAP));
+  HIPCHK(stage(e, s.kt, in->knot_times, P, B_KT));
+  HIPCHK(stage(e, s.kv, in->knot_values, P * nu, B_KV));
+  if (e->nuserdata) HIPCHK(stage(e, s.userdata, in->userdata, e->nuserdata, B_USERDATA));
+  if (in->noise_std) HIPCHK(stage(e, s.std, in->noise_std, P * nu, B_STD));
   HIPCHK(hipEventRecord(e->ev[0], e->stream));
   if (in->noise_eps) {
-    HIPCHK(hipMemcpyAsync(e->d_eps, in->noise_eps + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
-    if (in->noise_sel) HIPCHK(hipMemcpyAsync(e->d_sel, in->noise_sel + in->candidate_offset, sizeof(int) * nl, hipMemcpyHostToDevice, e->stream));
-    else HIPCHK(hipMemsetAsync(e->d_sel, 0, sizeof(int) * nl, e->stream));
+    HIPCHK(hipMemcpyAsync(d_eps, in->noise_eps + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+    if (in->noise_sel) HIPCHK(hipMemcpyAsync(d_sel, in->noise_sel + in->candidate_offset, sizeof(int) * nl, hipMemcpyHostToDevice, e->stream));
+    else HIPCHK(hipMemsetAsync(d_sel, 0, sizeof(int) * nl, e->stream));
   } else {
     size_t total = need > (size_t)nl ? need : (size_t)nl;
     int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, e->stream, e->d_eps, e->d_sel, (unsigned long long)in->seed,
+    hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, e->stream, d_eps, d_sel, (unsigned long long)in->seed,
                        (unsigned long long)in->stream, in->candidate_offset, nl, P * nu, in->noise_exploration[1]);
   }
+  // what this plan decides of the kernel parameters (the rest: bind_params)
   KParams &K = e->K;
-  K.state = e->d_state; K.mocap = e->d_mocap; K.userdata = e->d_userdata; K.nuserdata = e->nuserdata; K.knot_times = e->d_kt; K.knot_values = e->d_kv; K.noise_eps = e->d_eps; K.noise_sel = e->d_sel;
+  K.noise_eps = d_eps; K.noise_std = in->noise_std ? d_std : nullptr; K.cand_knots = table ? d_cand : nullptr;
   K.time = in->time; K.sigma0 = in->noise_exploration[0]; K.sigma1 = in->noise_exploration[1];
   K.seed = in->seed; K.stream = in->stream;
   K.P = P; K.interp = in->interpolation; K.H = H; K.N = in->num_trajectory; K.offset = in->candidate_offset; K.nlocal = nl;
   K.use_device_noise = in->noise_eps ? 0 : 1;
-  K.fault = e->fault;
-  K.noise_std = in->noise_std ? e->d_std : nullptr; K.nominal_index = in->nominal_index;
-  K.cand_knots = nullptr; K.xfrc_std = in->xfrc_std; K.xfrc_rate = in->xfrc_rate;
-  if (in->xfrc_std > 0 && !(in->xfrc_rate > 0)) { set_error("mjpc_hip_plan: xfrc_rate must be positive when xfrc_std > 0"); return -1; }
-  if (in->candidate_knots || mixed) {
-    if (need > e->cand_cap) {
-      if (e->d_cand) HIPCHK(hipFree(e->d_cand));
-      HIPCHK(hipMalloc(&e->d_cand, sizeof(double) * (need + 1)));
-      e->cand_cap = need;
+  K.nominal_index = in->nominal_index; K.xfrc_std = in->xfrc_std; K.xfrc_rate = in->xfrc_rate;
+  if (table && !mixed) HIPCHK(hipMemcpyAsync(d_cand, in->candidate_knots + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
+  if (mixed) {
+    // the caller's rows [first_explicit, offset + nl) verbatim, straight into the table; the kernel builds the rows below them
+    const size_t row = (size_t)P * nu;
+    const int r0 = first_explicit > in->candidate_offset ? first_explicit - in->candidate_offset : 0;      // first explicit local row
+    if (r0 < nl) HIPCHK(hipMemcpyAsync(d_cand + r0 * row, in->candidate_knots + ((size_t)in->candidate_offset + r0) * row, sizeof(double) * (nl - r0) * row,
+                                       hipMemcpyHostToDevice, e->stream));
+    if (r0 > 0) {
+      SgAssembleArgs sa{e->at(B_KV), d_std, d_eps, e->K.M.actuator_ctrlrange, d_cand, e->at(B_HIST), (long long)e->P_max * nu,
+                        in->candidate_offset, nl, P * nu, nu, in->nominal_index, first_explicit};
+      hipLaunchKernelGGL(sg_assemble_kernel, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, e->stream, sa);
     }
-    if (!mixed) HIPCHK(hipMemcpyAsync(e->d_cand, in->candidate_knots + (size_t)in->candidate_offset * P * nu, sizeof(double) * need, hipMemcpyHostToDevice, e->stream));
-    else {
-      // the caller's rows [first_explicit, offset + nl) verbatim, straight into the table; the kernel builds the rows below them
-      const size_t row = (size_t)P * nu;
-      const int r0 = first_explicit > in->candidate_offset ? first_explicit - in->candidate_offset : 0;      // first explicit local row
-      if (r0 < nl) HIPCHK(hipMemcpyAsync(e->d_cand + r0 * row, in->candidate_knots + ((size_t)in->candidate_offset + r0) * row, sizeof(double) * (nl - r0) * row,
-                                         hipMemcpyHostToDevice, e->stream));
-      if (r0 > 0) {
-        SgAssembleArgs sa{e->d_kv, e->d_std, e->d_eps, e->K.M.actuator_ctrlrange, e->d_cand, e->d_hist, (long long)e->P_max * nu,
-                          in->candidate_offset, nl, P * nu, nu, in->nominal_index, first_explicit};
-        hipLaunchKernelGGL(sg_assemble_kernel, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, e->stream, sa);
-      }
-      e->have_mixed = 1;
-    }
-    K.cand_knots = e->d_cand;
+    e->have_mixed = 1;
   }
-  K.states = e->d_states; K.actions = e->d_actions; K.times = e->d_times; K.residual = e->d_residual; K.costs = e->d_costs;
-  K.trace = e->d_trace; K.knots = e->d_knots; K.returns = e->d_returns; K.failure = e->d_failure; K.diag = e->d_diag; K.prof = e->d_prof; K.frame = e->d_frame;
   HIPCHK(hipEventRecord(e->ev[1], e->stream));
-  K.retry = 0; K.tier = 0; K.ckpt = e->d_ckpt; K.ckpt_stride = e->ckpt_stride;
-  const bool dense = e->kernelB && e->force_tier != 1 && (nl > e->num_cu || e->force_tier == 2) && !(in->xfrc_std > 0);   // (the lean layout has no body-force block)
+  const DenseTier &B = e->tierB;
+  const bool dense = B.k && e->force_tier != 1 && (nl > e->num_cu || e->force_tier == 2) && !(in->xfrc_std > 0);   // (the lean layout has no body-force block)
   if (dense) {
     KParams KB = K;
-    KB.M.nefcmax = e->nefcB; KB.M.nconmax = e->nconB; KB.L = e->layB; KB.cache_i = e->cacheB_i; KB.cache_d = e->cacheB_d; KB.tier = 1;
-    hipLaunchKernelGGL(e->kernelB, dim3(nl), dim3(mjpc_rollout_threads_cached()), e->ldsB, e->stream, KB);
+    KB.M.nefcmax = B.nefc; KB.M.nconmax = B.ncon; KB.L = B.lay; KB.cache_i = B.ci; KB.cache_d = B.cd; KB.tier = 1;
+    hipLaunchKernelGGL(B.k, dim3(nl), dim3(mjpc_rollout_threads_cached()), B.lds, e->stream, KB);
     K.retry = 1;                       // full capacity for whoever overflowed the dense tier (usually nobody: the launch drains at once)
   }
   hipLaunchKernelGGL(e->kernel, dim3(nl), dim3(mjpc_rollout_threads_cached()), e->lds_bytes, e->stream, K);
   K.retry = 0;
   e->last_dense = dense;
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
-  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->d_returns, nl, e->d_winner, e->d_winner_val);
+  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
   HIPCHK(hipEventRecord(e->ev[3], e->stream));
-  {
-    size_t rows = (e->summary_only ? 0 : (size_t)H * (e->ds + nu + 2 + e->nr + e->ntr)) + (size_t)P * nu;
-    size_t need_pack = 2 + 2 * (size_t)nl + rows;
-    if (need_pack > e->pack_cap) {
-      if (e->d_pack) HIPCHK(hipFree(e->d_pack));
-      if (e->h_pack) HIPCHK(hipHostFree(e->h_pack));
-      HIPCHK(hipMalloc(&e->d_pack, sizeof(double) * need_pack));
-      HIPCHK(hipHostMalloc(&e->h_pack, sizeof(double) * need_pack));
-      e->pack_cap = need_pack;
-    }
-    PackArgs pa{e->d_winner, e->d_winner_val, e->d_returns, e->d_failure, e->d_states, e->d_actions, e->d_times, e->d_residual,
-                e->d_costs, e->d_trace, e->d_knots, nl, H, P, e->ds, nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->d_pack};
-    e->last_summary = e->summary_only;
-    hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
-    HIPCHK(hipMemcpyAsync(e->h_pack, e->d_pack, sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
-  }
+  PackArgs pa{e->at<int>(B_WINNER), e->at(B_WINNER_VAL), e->at(B_RETURNS), e->at<int>(B_FAILURE), e->at(B_KNOTS + 1), e->at(B_KNOTS + 2), e->at(B_KNOTS + 3),
+              e->at(B_KNOTS + 4), e->at(B_KNOTS + 5), e->at(B_KNOTS + 6), e->at(B_KNOTS), nl, H, P, e->ds, nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->at(B_PACK)};
+  e->last_summary = e->summary_only;
+  hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
+  HIPCHK(hipMemcpyAsync(e->at(H_PACK), e->at(B_PACK), sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipGetLastError());
   e->last_H = H; e->last_P = P; e->last_nlocal = nl; e->last_offset = in->candidate_offset; e->pending = 1;
   return 0;
@@ -580,15 +574,12 @@ static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int fir
 
 int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) { return plan_async_impl(e, in, -1); }
 
+// row arrays of local candidate `local` of the last plan from the device into the caller's (non-null) arrays
 static int fetch_rows(MjpcHipEngine *e, int local, MjpcHipPlanOutput *out) {
-  size_t H = (size_t)e->last_H, P = (size_t)e->last_P, r = (size_t)local;
-  if (out->states) HIPCHK(hipMemcpyAsync(out->states, e->d_states + r * H * e->ds, sizeof(double) * H * e->ds, hipMemcpyDeviceToHost, e->stream));
-  if (out->actions) HIPCHK(hipMemcpyAsync(out->actions, e->d_actions + r * H * e->nu, sizeof(double) * H * e->nu, hipMemcpyDeviceToHost, e->stream));
-  if (out->times) HIPCHK(hipMemcpyAsync(out->times, e->d_times + r * H, sizeof(double) * H, hipMemcpyDeviceToHost, e->stream));
-  if (out->residual) HIPCHK(hipMemcpyAsync(out->residual, e->d_residual + r * H * e->nr, sizeof(double) * H * e->nr, hipMemcpyDeviceToHost, e->stream));
-  if (out->costs) HIPCHK(hipMemcpyAsync(out->costs, e->d_costs + r * H, sizeof(double) * H, hipMemcpyDeviceToHost, e->stream));
-  if (out->trace && e->ntr) HIPCHK(hipMemcpyAsync(out->trace, e->d_trace + r * H * e->ntr, sizeof(double) * H * e->ntr, hipMemcpyDeviceToHost, e->stream));
-  if (out->winner_knots) HIPCHK(hipMemcpyAsync(out->winner_knots, e->d_knots + r * P * e->nu, sizeof(double) * P * e->nu, hipMemcpyDeviceToHost, e->stream));
+  for (int k = 0; k < NROWS; k++) {
+    const size_t n = row_doubles(e, k, e->last_H, e->last_P);
+    if (out_row(out, k) && n) HIPCHK(hipMemcpyAsync(out_row(out, k), e->at(B_KNOTS + k) + local * n, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
+  }
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -608,7 +599,7 @@ int mjpc_hip_plan_fetch(MjpcHipEngine *e, MjpcHipPlanOutput *out) {
     out->noise_compute_time_us = 1e3 * t01; out->rollouts_compute_time_us = 1e3 * t12;
     e->acc_rollout_us += 1e3 * t12; e->acc_total_us += 1e3 * t03; e->acc_n++;
   }
-  const double *p = e->h_pack;
+  const double *p = e->at(H_PACK);
   int nl = e->last_nlocal;
   int wl = (int)p[0]; double wv = p[1];
   p += 2;
@@ -619,12 +610,10 @@ int mjpc_hip_plan_fetch(MjpcHipEngine *e, MjpcHipPlanOutput *out) {
   // there is no winner
   if (wl < 0 || wl >= nl) { set_error("mjpc_hip_plan_fetch: no finite return among the candidates (argmin out of range)"); return -3; }
   out->winner = e->last_offset + wl; out->winner_return = wv;
-  size_t H = (size_t)e->last_H, P = (size_t)e->last_P;
-  double *dst[7] = {out->winner_knots, out->states, out->actions, out->times, out->residual, out->costs, out->trace};
-  size_t cnt[7] = {P * e->nu, H * e->ds, H * e->nu, H, H * e->nr, H, H * e->ntr};
-  for (int k = 0; k < (e->last_summary ? 1 : 7); k++) {        // summary mode: the rows stay on the device (mjpc_hip_get_candidate)
-    if (dst[k] && cnt[k]) memcpy(dst[k], p, sizeof(double) * cnt[k]);
-    p += cnt[k];
+  for (int k = 0; k < (e->last_summary ? 1 : NROWS); k++) {        // summary mode: the rows stay on the device (mjpc_hip_get_candidate)
+    const size_t n = row_doubles(e, k, e->last_H, e->last_P);
+    if (out_row(out, k) && n) memcpy(out_row(out, k), p, sizeof(double) * n);
+    p += n;
   }
   return 0;
 }
@@ -655,7 +644,7 @@ int mjpc_hip_plan_mixed(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_
 int mjpc_hip_noise_history_reset(MjpcHipEngine *e) {
   if (!e) { set_error("mjpc_hip_noise_history_reset: invalid argument"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(double) * (size_t)e->max_local * e->P_max * e->nu, e->stream));     // stream-ordered: behind a plan in flight
+  HIPCHK(hipMemsetAsync(e->at(B_HIST), 0, sizeof(double) * (size_t)e->max_local * e->P_max * e->nu, e->stream));     // stream-ordered: behind a plan in flight
   return 0;
 }
 
@@ -668,12 +657,12 @@ int mjpc_hip_sample_gradient(MjpcHipEngine *e, int n, const int *slot, const dou
     if (slot[i] < 0 || slot[i] >= e->max_local) { set_error("mjpc_hip_sample_gradient: slot[" + std::to_string(i) + "] = " + std::to_string(slot[i]) + " out of range (0..max_local-1)"); return -1; }
   HIPCHK(hipSetDevice(e->device));
   const int PN = e->last_P * e->nu;
-  HIPCHK(hipMemcpyAsync(e->d_slot, slot, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(e->d_scale, scale, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
-  SgGradArgs ga{e->d_hist, (long long)e->P_max * e->nu, e->d_slot, e->d_scale, n, PN, e->d_grad};
+  HIPCHK(hipMemcpyAsync(e->at(B_SLOT), slot, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(e->at(B_SCALE), scale, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
+  SgGradArgs ga{e->at(B_HIST), (long long)e->P_max * e->nu, e->at<int>(B_SLOT), e->at(B_SCALE), n, PN, e->at(B_GRAD)};
   hipLaunchKernelGGL(sg_gradient_kernel, dim3((PN + SG_KT - 1) / SG_KT), dim3(256), 0, e->stream, ga);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(gradient_out, e->d_grad, sizeof(double) * PN, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(gradient_out, e->at(B_GRAD), sizeof(double) * PN, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -693,45 +682,20 @@ static int step_prepare(MjpcHipEngine *e, const char *who, const double *mocap, 
     e->step_kernel = k;
     e->step_launch = e->spill ? mjpc_launch_step_spill : e->cached ? mjpc_launch_step_cached : mjpc_launch_step_direct;
   }
-  const size_t need = (size_t)e->max_local * e->nu;         // P = 1
-  if (need > e->knots_cap) {
-    if (e->d_knots) HIPCHK(hipFree(e->d_knots));
-    e->d_knots = nullptr; e->knots_cap = 0;
-    HIPCHK(hipMalloc(&e->d_knots, sizeof(double) * (need + 1)));
-    e->knots_cap = need;
-  }
-  double *hs = e->h_small;
-  if (e->nmocap) {
-    memcpy(hs, mocap, sizeof(double) * 7 * e->nmocap);
-    HIPCHK(hipMemcpyAsync(e->d_mocap, hs, sizeof(double) * 7 * e->nmocap, hipMemcpyHostToDevice, e->stream));
-  }
-  if (e->nuserdata) {
-    double *hu = hs + 7 * e->nmocap;
-    if (userdata) memcpy(hu, userdata, sizeof(double) * e->nuserdata); else memset(hu, 0, sizeof(double) * e->nuserdata);
-    HIPCHK(hipMemcpyAsync(e->d_userdata, hu, sizeof(double) * e->nuserdata, hipMemcpyHostToDevice, e->stream));
-  }
+  HIPCHK(reserve_knots(e, 1));
+  if (e->nmocap) HIPCHK(stage(e, e->hs.mocap, mocap, 7 * e->nmocap, B_MOCAP));
+  if (e->nuserdata) HIPCHK(stage(e, e->hs.userdata, userdata, e->nuserdata, B_USERDATA));
+  // a copy of the engine's parameters: a step has no plan state, no noise and no candidate table, one knot (its control), two
+  // state rows per workgroup
   KParams K = e->K;
-  K.state = nullptr; K.mocap = e->d_mocap; K.userdata = e->d_userdata; K.nuserdata = e->nuserdata; K.knot_times = e->d_kt; K.knot_values = e->d_kv;
-  K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  K.state = nullptr; K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  K.frame = nullptr;                       // (the kinematic frame of the last plan stays what it was)
   K.time = 0; K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0;
   K.P = 1; K.interp = 0; K.H = 2; K.N = e->max_local; K.offset = 0; K.nlocal = 0; K.use_device_noise = 0; K.nominal_index = 0;
-  K.fault = e->fault; K.xfrc_std = 0; K.xfrc_rate = 0;
-  K.states = e->d_states; K.actions = e->d_actions; K.times = e->d_times; K.residual = e->d_residual; K.costs = e->d_costs;
-  K.trace = e->d_trace; K.knots = e->d_knots; K.returns = e->d_returns; K.failure = e->d_failure; K.diag = e->d_diag; K.prof = e->d_prof;
-  K.frame = nullptr;                       // (the kinematic frame of the last plan stays what it was)
-  K.retry = 0; K.tier = 0; K.ckpt = e->d_ckpt; K.ckpt_stride = e->ckpt_stride;
+  K.xfrc_std = 0; K.xfrc_rate = 0;
   *Kout = K;
   // the row buffers are about to be overwritten: the last plan's candidates are no longer there to be fetched
   e->last_nlocal = 0;
-  return 0;
-}
-
-static int fd_reserve(MjpcHipEngine *e, size_t bytes) {
-  if (bytes <= e->fd_cap) return 0;
-  if (e->d_fd) HIPCHK(hipFree(e->d_fd));
-  e->d_fd = nullptr; e->fd_cap = 0;
-  HIPCHK(hipMalloc(&e->d_fd, bytes));
-  e->fd_cap = bytes;
   return 0;
 }
 
@@ -759,10 +723,9 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
   for (size_t p0 = 0; p0 < (size_t)n; p0 += STEP_PASS_ROWS) {
     const size_t R = (size_t)n - p0 < STEP_PASS_ROWS ? (size_t)n - p0 : STEP_PASS_ROWS;
     const size_t nd_ = R * (2 * ds + nu + 1 + nr) + 8;
-    rc = fd_reserve(e, nd_ * sizeof(double) + R * sizeof(int));
-    if (rc != 0) return rc;
-    double *st = (double *)e->d_fd, *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
-    int *fl = (int *)((double *)e->d_fd + nd_);
+    HIPCHK(e->buf[B_FD].reserve(nd_ * sizeof(double) + R * sizeof(int)));
+    double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
+    int *fl = (int *)(st + nd_);
     HIPCHK(hipMemcpyAsync(st, states + p0 * ds, sizeof(double) * R * ds, hipMemcpyHostToDevice, e->stream));
     if (nu) HIPCHK(hipMemcpyAsync(ct, ctrl + p0 * nu, sizeof(double) * R * nu, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(tt, time + p0, sizeof(double) * R, hipMemcpyHostToDevice, e->stream));
@@ -807,11 +770,10 @@ int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const doubl
     const int term = last_is_terminal && t0 + Tg == (size_t)T;
     const size_t per_t = ds + nu + 1 + nd * nd + nd * nu + nr * nd + nr * nu;
     const size_t nd_ = R * (2 * ds + nu + 1 + nr) + Tg * per_t + 8;
-    rc = fd_reserve(e, nd_ * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int));
-    if (rc != 0) return rc;
-    double *st = (double *)e->d_fd, *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
+    HIPCHK(e->buf[B_FD].reserve(nd_ * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int)));
+    double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
     double *dx = rs + R * nr, *du = dx + Tg * ds, *dt = du + Tg * nu, *dA = dt + Tg, *dB = dA + Tg * nd * nd, *dC = dB + Tg * nd * nu, *dD = dC + Tg * nr * nd;
-    int *fl = (int *)((double *)e->d_fd + nd_), *flT = fl + R, *dmap = flT + Tg;
+    int *fl = (int *)(st + nd_), *flT = fl + R, *dmap = flT + Tg;
     HIPCHK(hipMemcpyAsync(dx, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
     if (nu) HIPCHK(hipMemcpyAsync(du, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(dt, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
@@ -843,11 +805,12 @@ int mjpc_hip_get_frame(MjpcHipEngine *e, double *xpos, double *xmat, double *sit
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   size_t nb = (size_t)e->nbody, ns = (size_t)e->nsite;
-  if (xpos) HIPCHK(hipMemcpy(xpos, e->d_frame, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
-  if (xmat) HIPCHK(hipMemcpy(xmat, e->d_frame + 3 * nb, sizeof(double) * 9 * nb, hipMemcpyDeviceToHost));
-  if (site_xpos && ns) HIPCHK(hipMemcpy(site_xpos, e->d_frame + 12 * nb, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost));
-  if (subtree_com) HIPCHK(hipMemcpy(subtree_com, e->d_frame + 12 * nb + 3 * ns, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
-  if (subtree_linvel) HIPCHK(hipMemcpy(subtree_linvel, e->d_frame + 15 * nb + 3 * ns, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
+  const double *d_frame = e->at(B_FRAME);
+  if (xpos) HIPCHK(hipMemcpy(xpos, d_frame, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
+  if (xmat) HIPCHK(hipMemcpy(xmat, d_frame + 3 * nb, sizeof(double) * 9 * nb, hipMemcpyDeviceToHost));
+  if (site_xpos && ns) HIPCHK(hipMemcpy(site_xpos, d_frame + 12 * nb, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost));
+  if (subtree_com) HIPCHK(hipMemcpy(subtree_com, d_frame + 12 * nb + 3 * ns, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
+  if (subtree_linvel) HIPCHK(hipMemcpy(subtree_linvel, d_frame + 15 * nb + 3 * ns, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -855,15 +818,15 @@ int mjpc_hip_get_knots(MjpcHipEngine *e, double *knots) {
   if (!e || !knots || e->last_nlocal < 1) { set_error("mjpc_hip_get_knots: no finished plan"); return -1; }
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(knots, e->d_knots, sizeof(double) * (size_t)e->last_nlocal * e->last_P * e->nu, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(knots, e->at(B_KNOTS), sizeof(double) * e->last_nlocal * row_doubles(e, 0, e->last_H, e->last_P), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int mjpc_hip_get_candidate(MjpcHipEngine *e, int local_index, MjpcHipPlanOutput *out) {
   if (!e || !out || local_index < 0 || local_index >= e->last_nlocal) { set_error("mjpc_hip_get_candidate: index out of range"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  if (out->returns) HIPCHK(hipMemcpyAsync(out->returns, e->d_returns + local_index, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (out->failure) HIPCHK(hipMemcpyAsync(out->failure, e->d_failure + local_index, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (out->returns) HIPCHK(hipMemcpyAsync(out->returns, e->at(B_RETURNS) + local_index, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (out->failure) HIPCHK(hipMemcpyAsync(out->failure, e->at<int>(B_FAILURE) + local_index, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   out->winner = e->last_offset + local_index;
   return fetch_rows(e, local_index, out);
 }
@@ -879,9 +842,9 @@ int mjpc_hip_kernel_time(MjpcHipEngine *e, double *avg_rollout_us, double *avg_t
 
 int mjpc_hip_device_ptrs(MjpcHipEngine *e, void **returns, void **states, void **residual) {
   if (!e) return -1;
-  if (returns) *returns = e->d_returns;
-  if (states) *states = e->d_states;
-  if (residual) *residual = e->d_residual;
+  if (returns) *returns = e->at(B_RETURNS);
+  if (states) *states = e->at(B_STATES);
+  if (residual) *residual = e->at(B_RESIDUAL);
   return 0;
 }
 
@@ -891,7 +854,7 @@ int mjpc_hip_get_traces(MjpcHipEngine *e, double *traces) {
   if (!e->ntr) return 0;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(traces, e->d_trace, sizeof(double) * (size_t)e->last_nlocal * e->last_H * e->ntr, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(traces, e->at(B_TRACE), sizeof(double) * e->last_nlocal * row_doubles(e, 6, e->last_H, e->last_P), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -901,16 +864,14 @@ int mjpc_hip_get_all_candidates(MjpcHipEngine *e, double *states, double *action
                              double *costs, double *trace, double *knots, int *diag) {
   if (!e || !e->last_nlocal) { set_error("mjpc_hip_get_all_candidates: no finished plan"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  size_t n = (size_t)e->last_nlocal, H = (size_t)e->last_H, P = (size_t)e->last_P;
+  const size_t n = (size_t)e->last_nlocal;
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (states) HIPCHK(hipMemcpy(states, e->d_states, sizeof(double) * n * H * e->ds, hipMemcpyDeviceToHost));
-  if (actions) HIPCHK(hipMemcpy(actions, e->d_actions, sizeof(double) * n * H * e->nu, hipMemcpyDeviceToHost));
-  if (times) HIPCHK(hipMemcpy(times, e->d_times, sizeof(double) * n * H, hipMemcpyDeviceToHost));
-  if (residual) HIPCHK(hipMemcpy(residual, e->d_residual, sizeof(double) * n * H * e->nr, hipMemcpyDeviceToHost));
-  if (costs) HIPCHK(hipMemcpy(costs, e->d_costs, sizeof(double) * n * H, hipMemcpyDeviceToHost));
-  if (trace && e->ntr) HIPCHK(hipMemcpy(trace, e->d_trace, sizeof(double) * n * H * e->ntr, hipMemcpyDeviceToHost));
-  if (knots) HIPCHK(hipMemcpy(knots, e->d_knots, sizeof(double) * n * P * e->nu, hipMemcpyDeviceToHost));
-  if (diag) HIPCHK(hipMemcpy(diag, e->d_diag, sizeof(int) * n * 4, hipMemcpyDeviceToHost));
+  double *dst[NROWS] = {knots, states, actions, times, residual, costs, trace};
+  for (int k = 0; k < NROWS; k++) {
+    const size_t cnt = n * row_doubles(e, k, e->last_H, e->last_P);
+    if (dst[k] && cnt) HIPCHK(hipMemcpy(dst[k], e->at(B_KNOTS + k), sizeof(double) * cnt, hipMemcpyDeviceToHost));
+  }
+  if (diag) HIPCHK(hipMemcpy(diag, e->at(B_DIAG), sizeof(int) * n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -924,8 +885,7 @@ int mjpc_hip_debug_spill(MjpcHipEngine *e, int *slab_bytes) {
 // this model under the current knobs; returns 1 when that is the spill flavour, 0 otherwise, < 0: refused (mjpc_hip_last_error)
 int mjpc_hip_debug_spill_layout(const MjpcHipModel *model, const MjpcHipTask *task, int *lds_bytes, int *slab_bytes) {
   if (!model || !task) { set_error("mjpc_hip_debug_spill_layout: invalid argument"); return -1; }
-  if (model->struct_size != (int)sizeof(MjpcHipModel) || task->struct_size != (int)sizeof(MjpcHipTask)) {
-    set_error("mjpc_hip_debug_spill_layout: MjpcHipModel / MjpcHipTask struct_size does not match this library"); return -1; }
+  if (!check_views(model, task, "mjpc_hip_debug_spill_layout")) return -1;
   PackedModel pm;
   RolloutFn k = nullptr; bool cached = true, spill = false;
   if (!pick_flavour(model, task, 36, pm, &k, &cached, &spill, "mjpc_hip_debug_spill_layout")) return -1;
@@ -934,15 +894,15 @@ int mjpc_hip_debug_spill_layout(const MjpcHipModel *model, const MjpcHipTask *ta
   return spill ? 1 : 0;
 }
 void mjpc_hip_debug_dense_capacity(MjpcHipEngine *e, int *nefc, int *ncon, int *hot) {
-  if (nefc) *nefc = (e && e->kernelB) ? e->nefcB : 0;
-  if (ncon) *ncon = (e && e->kernelB) ? e->nconB : 0;
-  if (hot) *hot = (e && e->kernelB && e->cacheB_d > 0) ? 1 : 0;
+  if (nefc) *nefc = (e && e->tierB.k) ? e->tierB.nefc : 0;
+  if (ncon) *ncon = (e && e->tierB.k) ? e->tierB.ncon : 0;
+  if (hot) *hot = (e && e->tierB.k && e->tierB.cd > 0) ? 1 : 0;
 }
 // LDS bytes of the dense (two workgroups per CU) tier, 0 when the model has none; *used_last = 1 when the last plan ran on it
 int mjpc_hip_dense_tier(MjpcHipEngine *e, int *used_last) {
   if (!e) return 0;
   if (used_last) *used_last = e->last_dense;
-  return e->kernelB ? (int)e->ldsB : 0;
+  return e->tierB.k ? (int)e->tierB.lds : 0;
 }
 
 // host-only (no HIP call): bytes of LDS one candidate would occupy; use_cache bit 0: with / without the LDS copy of the model
@@ -950,6 +910,7 @@ int mjpc_hip_dense_tier(MjpcHipEngine *e, int *used_last) {
 // < 0: the model is refused (mjpc_hip_last_error tells why)
 int mjpc_hip_layout_bytes(const MjpcHipModel *model, const MjpcHipTask *task, int use_cache) {
   if (!model || !task) { set_error("mjpc_hip_layout_bytes: invalid argument"); return -1; }
+  if (!check_views(model, task, "mjpc_hip_layout_bytes")) return -1;
   PackedModel pm;
   int exact = 0;
   if (use_cache & 2) mjpc_pick_rollout_dense2(model->nv, &exact); else if (use_cache & 1) mjpc_pick_rollout_cached(model->nv, &exact); else mjpc_pick_rollout_direct(model->nv, &exact);
@@ -963,7 +924,7 @@ int mjpc_hip_debug_fetch_prof(MjpcHipEngine *e, long long *prof) {
   if (!e || !e->last_nlocal) return -1;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipMemcpy(prof, e->d_prof, sizeof(long long) * (size_t)e->last_nlocal * 24, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(prof, e->at(B_PROF), sizeof(long long) * (size_t)e->last_nlocal * 24, hipMemcpyDeviceToHost));
   return 0;
 }
 #endif

@@ -18,8 +18,7 @@ def _accepted(m, room=160 * 1024):
     """host-only query: would mjpc_hip_create take this model?"""
     import ctypes
     from mujoco_mpc_amd import capi
-    lib = ctypes.CDLL(capi.ENGINE_PATH)
-    lib.mjpc_hip_layout_bytes.argtypes = [ctypes.POINTER(capi.MjpcHipModel), ctypes.POINTER(capi.MjpcHipTask), ctypes.c_int]
+    lib = capi.load_engine()
     cm = capi.CModel(m, make_task(TASK_COPYSTATE, [(m["nq"], 0, 1.0), (m["nv"], 0, 0.1)]))
     n = lib.mjpc_hip_layout_bytes(ctypes.byref(cm.c_model), ctypes.byref(cm.c_task), 0)
     return 0 < n <= room

@@ -1,12 +1,15 @@
 """CPU tier of the spill flavour (rollout_spill.hip: the row- and contact-sized blocks of a candidate's state in an HBM slab when
 the state does not fit 160 KiB of LDS): the host-only flavour query, and the kernel source in its 1-lane emulation built like the
 spill flavour (tests/emu/emu_spill.cpp) against today's emulation and against the oracle."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import emu_lib
 import emu_spill_lib as es
 import oracle_lib as ol
+from mujoco_mpc_amd import capi
 from mujoco_mpc_amd.modelgen import REGISTRY, cartpole, humanoid_track, quadruped, shadow_hand
 from random_models import random_model
 from spill_common import LDS_LIMIT, chosen_layout, plain_layout, refused_seeds, with_capacity
@@ -17,6 +20,32 @@ def test_models_that_fit_keep_their_flavour(make):
     m, task, _ = make()
     lds, slab, spill = chosen_layout(m, task)
     assert not spill and slab == 0 and lds == plain_layout(m, task)
+
+
+def test_host_only_queries_refuse_a_view_of_the_wrong_struct_size():
+    """mjpc_hip_layout_bytes and mjpc_hip_debug_spill_layout read the views like mjpc_hip_create does: a model view whose struct_size
+    is not the library's is refused by both before anything is read out of it; the unmodified view answers as it did"""
+    lib = capi.load_engine()
+    m, task, _ = quadruped()
+    cm = capi.CModel(m, task)
+    a = C.c_int(0); b = C.c_int(0)
+
+    def ask():
+        rc = lib.mjpc_hip_debug_spill_layout(C.byref(cm.c_model), C.byref(cm.c_task), C.byref(a), C.byref(b))
+        return [lib.mjpc_hip_layout_bytes(C.byref(cm.c_model), C.byref(cm.c_task), u) for u in (0, 1, 2)] + [rc, a.value, b.value]
+    good = ask()
+    assert min(good[:3]) > 0 and good[3:] == [0, plain_layout(m, task), 0] and good[4] == chosen_layout(m, task)[0]
+    cm.c_model.struct_size -= 8
+    for u in (0, 1, 2):
+        assert lib.mjpc_hip_layout_bytes(C.byref(cm.c_model), C.byref(cm.c_task), u) < 0
+        assert b"mjpc_hip_layout_bytes" in lib.mjpc_hip_last_error() and b"struct_size" in lib.mjpc_hip_last_error()
+    assert lib.mjpc_hip_debug_spill_layout(C.byref(cm.c_model), C.byref(cm.c_task), C.byref(a), C.byref(b)) < 0
+    assert b"mjpc_hip_debug_spill_layout" in lib.mjpc_hip_last_error() and b"struct_size" in lib.mjpc_hip_last_error()
+    cm.c_model.struct_size += 8
+    cm.c_task.struct_size -= 8
+    assert lib.mjpc_hip_layout_bytes(C.byref(cm.c_model), C.byref(cm.c_task), 1) < 0 and b"struct_size" in lib.mjpc_hip_last_error()
+    cm.c_task.struct_size += 8
+    assert ask() == good
 
 
 @pytest.mark.parametrize("capacity", [(32, 128), (64, 192)])

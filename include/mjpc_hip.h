@@ -449,6 +449,37 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
 int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
                            const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
                            double *D, int *failure);
+/* ---- Cost derivatives and the gradient planner's backward pass --------------------------------------------------------------
+ * The other half of a derivative-based planner's iteration (mjpc/planners/cost_derivatives.cc, planners/gradient/gradient.cc),
+ * on the device.  nd = 2nv+na, nr = num_residual; the cost table (norms, parameters, weights) and risk are the engine's current
+ * task (mjpc_hip_set_task).  Host pointers in and out, row-major.
+ *
+ * mjpc_hip_cost_derivatives: for each knot t < T, with J = [C_t | D_t] and w_i = weight[i] / T, over the cost terms i in ascending
+ * order and each term's own residual rows:  cr = the norm's gradient (Norm of mjpc/norm.cc, types -1, 0, 1, 2, 3, 5, 6, 7, 8),
+ *   g = J_i' cr_i,  S = crr_i J_i,  G = J_i' S,  c{x,u} += w_i g,  c{xx,xu,uu} += w_i G   (Gauss-Newton)
+ * cx[T][nd], cu[T][nu], cxx[T][nd][nd] the top-left block of G, cxu[T][nd][nu] the top-right, cuu[T][nu][nu] the bottom-right.
+ * Summation: every contraction starts at 0.0 and runs over the ascending contraction index, one rounded product and one rounded
+ * add per step (no fused multiply-add); `+= w_i v` is one rounded product and one rounded add; the Hessian of a type other than
+ * 1 and 2 is diagonal and S its row scaling.  With |risk| >= 1e-6 and s = exp(risk * sum_i w_i Norm_i): cx and cu are scaled by s,
+ * then c** = s c** + (risk s) (scaled c*) (scaled c*)' - the outer products use the ALREADY scaled gradients, as the reference does.
+ * last_is_terminal: knot T-1 has no D (D[T-1] is not read): its cu, cuu, cxu are zero, cx and cxx come from C alone.
+ * hessians = 0: cr, cx, cu only (cxx, cuu, cxu are not touched).  Any output may be NULL.  Blocking.
+ * Errors: a plan in flight, T < 1, null inputs.
+ *
+ * mjpc_hip_trajectory_gradient: one iteration's derivative work with no host round trip in between: mjpc_hip_transition_fd over
+ * the T knots with last_is_terminal = 1, the cost gradients (hessians = 0) over the matrices where that left them, with the
+ * caller's residual[T][nr] (the nominal trajectory's), and Gradient::Compute:
+ *   Vx[T-1] = cx[T-1];  for t = T-1 .. 1:  Qx[t-1] = A[t-1]' Vx[t] + cx[t-1],  Qu[t-1] = B[t-1]' Vx[t] + cu[t-1],
+ *   k[t-1] = -Qu[t-1],  Vx[t-1] = Qx[t-1],  dV[0] += k[t-1] . Qu[t-1];   then k[T-1] = k[T-2];  dV[1] = 0
+ * by the same summation rule, so a host loop over the downloaded matrices gives the same bits.  k[T][nu], Vx[T][nd], Qx[T-1][nd],
+ * Qu[T-1][nu], dV[2] (any may be NULL), failure[T] as for mjpc_hip_transition_fd.  A failed evaluation is not an error of the call.
+ * Blocking; one download.  Errors: a plan in flight, T < 2, null inputs, eps <= 0, max_horizon < 2, T beyond one pass of the step
+ * tables (32768 evaluations). */
+int mjpc_hip_cost_derivatives(MjpcHipEngine *e, int T, const double *residual, const double *C, const double *D, int last_is_terminal,
+                              int hessians, double *cr, double *cx, double *cu, double *cxx, double *cuu, double *cxu);
+int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual,
+                                 const double *mocap, const double *userdata, double eps, int centered, double *k, double *Vx, double *Qx,
+                                 double *Qu, double *dV, int *failure);
 /* Bytes of LDS one candidate's workgroup occupies (its whole mjData-equivalent). */
 int mjpc_hip_lds_bytes(MjpcHipEngine *e);
 /* Capacity tiers: when a shard holds more candidates than the GPU has CUs and the model allows it, the engine first runs a

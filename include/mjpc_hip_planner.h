@@ -10,6 +10,7 @@
 //   mjpc/planners/robust/robust_planner.h:31-80   RobustPlanner (top-k candidates x R noisy rollouts on a second engine)
 //   mjpc/planners/sample_gradient/planner.h:35-175 SampleGradientPlanner (mixed batch; gradient reduced on the device)
 //   mjpc/planners/model_derivatives.h:30-70  ModelDerivatives (finite-difference A, B, C, D along a trajectory, on the device)
+//   mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h  CostDerivatives (on the device), Gradient (backward recursion, host)
 // Differences forced by the boundary: `mjModel*` / `const Task&` become the ABI's MjpcHipModel / MjpcHipTask views
 // plus the planner's <custom><numeric> settings (Numerics); `ThreadPool&` arguments are gone (the GPU is the pool);
 // `State` is passed as its raw arrays (State::CopyTo, mjpc/states/state.cc:128-135).
@@ -19,6 +20,7 @@
 #include <array>
 #include <deque>
 #include <shared_mutex>
+#include <memory>
 #include <vector>
 
 #include "mjpc_hip.h"
@@ -99,6 +101,10 @@ struct Numerics {                       // the planner's <custom><numeric> entri
   std::vector<int> devices;            // optional explicit ordinals (repeats allowed); default device, device+1, ...
   int sample_gradient_trajectories = 0;    // sample gradient: gradient candidates among sampling_trajectories (sample_gradient/planner.cc:66)
   double sample_gradient_filter = 1.0;     // weight of the new gradient against the previous one (planner.cc:69)
+  int gradient_num_trajectory = 32;        // gradient planner: line-search candidates (gradient/planner.cc:47)
+  int gradient_spline_points = 10;         // policy knots; at most kMaxGradientSplinePoints (the reference's default, the horizon cap, overflows its own mapping)
+  int gradient_representation = kLinearSpline;   // gradient/policy.cc:44-45
+  int derivative_skip = 0;                 // knots left out between two evaluated ones (gradient/planner.cc:131)
 };
 
 // What the three planners on the rollout engine share: the planner's state, its policies, the bookkeeping of a plan step and the
@@ -370,6 +376,151 @@ class ModelDerivatives {
  private:
   std::vector<double> gx_, gu_, gh_, gA_, gB_, gC_, gD_;
   std::vector<int> gfail_;
+};
+
+// mjpc/planners/cost_derivatives.{h,cc}: derivatives of the cost along a trajectory from the residual and its Jacobians.  The
+// reference's third thread-pool fan-out (one task per knot) is ONE mjpc_hip_cost_derivatives call; the cost table and risk are the
+// engine's current task, so Compute takes no norms / weights / parameters.  crr is not materialised (a dense type's Hessian is
+// rebuilt from two scalars on the device).  Index T - 1 is the terminal knot: cx / cxx from rx alone, cu / cuu / cxu zero.
+class CostDerivatives {
+ public:
+  void Allocate(int dim_state_derivative, int dim_action, int dim_residual, int T);
+  void Reset(int dim_state_derivative, int dim_action, int dim_residual, int T);
+  // r [T][nr], rx [T][nr][nd], ru [T][nr][nu]; hessians = false: cr, cx, cu only.  false after an engine error (mjpc_hip_last_error)
+  bool Compute(MjpcHipEngine* engine, const double* r, const double* rx, const double* ru, int dim_state_derivative, int dim_action,
+               int dim_residual, int T, bool hessians = true);
+
+  std::vector<double> cr, cx, cu, cxx, cuu, cxu;
+  int dim_state_derivative = 0, dim_action = 0, dim_residual = 0, horizon = 0;
+};
+
+// mjpc/planners/gradient/gradient.{h,cc}: the gradient planner's backward recursion over given model and cost derivatives, on the
+// host, by the summation rule of mjpc_hip_cost_derivatives (include/mjpc_hip.h): bit-equal to the device's
+// mjpc_hip_trajectory_gradient on the same matrices.  k [T][dim_action] stands in for GradientPolicy::k.
+class Gradient {
+ public:
+  void Allocate(int dim_state_derivative, int dim_action, int T);
+  void Reset(int dim_state_derivative, int dim_action, int T);
+  // 0 = complete (the reference's return value); T < 2 is an error
+  int Compute(double* k, const ModelDerivatives* md, const CostDerivatives* cd, int dim_state_derivative, int dim_action, int T);
+  // the same over plain arrays: A [T-1][nd][nd], B [T-1][nd][nu], cx [T][nd], cu [T][nu]
+  int Compute(double* k, const double* A, const double* B, const double* cx, const double* cu, int dim_state_derivative, int dim_action, int T);
+
+  std::vector<double> Vx, Qx, Qu;                     // [T][nd], [T-1][nd], [T-1][nu]
+  double dV[2] = {0.0, 0.0};
+};
+
+// ---- the gradient planner (mjpc/planners/gradient/): open-loop spline policy improved along the return's gradient
+inline constexpr int kMaxGradientSplinePoints = 25;   // gradient/spline_mapping.h:27
+
+// utilities.h:122-141, utilities.cc:286-404: the interval of `value` in an ascending sequence, and zero / linear / cubic interpolation of
+// ys [length][dim] over xs (host arithmetic of GradientPolicy::Action; this library is compiled without contraction)
+void FindInterval(int* bounds, const std::vector<double>& sequence, double value, int length);
+void ZeroInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length);
+void LinearInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length);
+void CubicInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length);
+
+// gradient/policy.{h,cc}
+class GradientPolicy {
+ public:
+  void Allocate(const MjpcHipModel* model, const Numerics& numerics, int horizon);
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  void Action(double* action, const double* state, double time) const;     // FindInterval + interpolation, clamped to the ctrlrange
+  void CopyFrom(const GradientPolicy& policy, int horizon);
+  void CopyParametersFrom(const std::vector<double>& src_parameters, const std::vector<double>& src_times);
+
+  std::vector<double> k;                  // action improvement [horizon][nu]
+  std::vector<double> parameters, parameter_update, times;
+  int num_parameters = 0, num_spline_points = 0, representation = kLinearSpline;
+  int nu = 0;
+  std::vector<double> ctrlrange;
+};
+
+// gradient/spline_mapping.{h,cc}: the linear operator from the policy's knot values [num_input][dim] to the actions at output_times
+// [num_output][dim], row-major [(dim num_output)][(dim num_input)]
+class SplineMapping {
+ public:
+  virtual ~SplineMapping() = default;
+  virtual void Allocate(int dim);
+  virtual void Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) = 0;
+  double* Get() { return mapping.data(); }
+  int dim = 0;
+  std::vector<double> mapping;
+};
+class ZeroSplineMapping : public SplineMapping {
+ public:
+  void Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) override;
+};
+class LinearSplineMapping : public SplineMapping {
+ public:
+  void Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) override;
+};
+class CubicSplineMapping : public SplineMapping {
+ public:
+  void Allocate(int dim) override;
+  void Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) override;
+  std::vector<double> point_slope_mapping, output_mapping;
+};
+
+struct GradientPlannerSettings {          // gradient/settings.h
+  int max_rollout = 1;                    // planner iterations per OptimizePolicy
+  double min_linesearch_step = 1.0e-8;
+  double fd_tolerance = 1.0e-5;
+  int fd_mode = 0;                        // 0 one-sided, 1 centred
+};
+
+// gradient/planner.{h,cc}.  Stands alone (no SamplingPolicy members to carry).  One iteration: derivatives and gradient of the nominal
+// trajectory (derivative_skip == 0: one mjpc_hip_trajectory_gradient; else ModelDerivatives, CostDerivatives, Gradient composed),
+// parameter_update = M' k, num_trajectory candidates nominal + step_i * update at LogScale(1, min_linesearch_step) steps with the last
+// step 0, rolled out as ONE explicit-candidate plan; the winner is picked on the host in the reference's order (j = N-1 .. 0, strict <
+// against the best so far, starting from the nominal's return: a NaN return never wins) and fetched with mjpc_hip_get_candidate.
+// Rollouts sample the knots with the engine's spline; ActionFromPolicy uses GradientPolicy::Action.  A failed derivative evaluation
+// ends OptimizePolicy like gd_status != 0: the policy is left as it was (failed = true).
+class GradientPlanner {
+ public:
+  GradientPlanner() = default;
+  ~GradientPlanner();
+  GradientPlanner(const GradientPlanner&) = delete;
+  GradientPlanner& operator=(const GradientPlanner&) = delete;
+
+  void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
+  void Allocate();
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void SetTask(const MjpcHipTask* task);
+  void OptimizePolicy(int horizon);
+  void NominalTrajectory(int horizon);
+  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
+  void ResamplePolicy(int horizon);
+  const Trajectory* BestTrajectory() { return winner >= 0 ? &trajectory_winner : nullptr; }
+  int NumParameters() { return policy.num_spline_points * nu_; }
+  static void Refuse(const char* msg);                 // the planner error handler (abort unless one is installed)
+
+  GradientPolicy policy, previous_policy, nominal_policy;      // nominal_policy: candidate_policy[0]
+  GradientPlannerSettings settings;
+  Gradient gradient;
+  ModelDerivatives model_derivative;
+  CostDerivatives cost_derivative;
+  std::unique_ptr<SplineMapping> mappings[3];
+  std::vector<double> state, mocap, userdata;
+  double time = 0;
+  std::vector<double> returns, linesearch_steps;       // of the last iteration
+  std::vector<int> failures;
+  Trajectory trajectory_nominal, trajectory_winner;
+  int num_trajectory = 32, winner = -1, derivative_skip_ = 0;
+  bool failed = false;                                 // the last OptimizePolicy stopped at a failed derivative
+  double action_step = 0, expected = 0, improvement = 0, surprise = 0;
+  double nominal_compute_time = 0, derivative_compute_time = 0, gradient_compute_time = 0, rollouts_compute_time = 0,
+         policy_update_compute_time = 0;               // microseconds; derivative = model + cost (+ backward pass when fused)
+
+ private:
+  bool Rollout(const double* knots, int n, int horizon);       // n explicit candidates over nominal_policy.times -> returns / failures
+  MjpcHipEngine* engine_ = nullptr;
+  Numerics numerics_;
+  int ns_ = 0, nd_ = 0, nu_ = 0, nr_ = 0, ntrace_ = 0, nmocap_ = 0, nuserdata_ = 0;
+  double timestep_ = 0;
+  std::vector<double> cand_knots_, parameters_scratch_, times_scratch_;
+  mutable std::shared_mutex mtx_;
 };
 
 }  // namespace mjpc_hip

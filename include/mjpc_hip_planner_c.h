@@ -6,6 +6,7 @@
  *                                                             mjpc/planners/planner.h:38-101)
  *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
  *   mjpc_md_*       -> mjpc::ModelDerivatives                 (mjpc/planners/model_derivatives.h:30-70)
+ *   mjpc_cd_* / mjpc_gd_* -> mjpc::CostDerivatives, mjpc::Gradient (mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h)
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
  */
 #ifndef MJPC_HIP_PLANNER_C_H_
@@ -137,8 +138,50 @@ void mjpc_md_indices(void *md, int *evaluate, int *interpolate, int *n);
 /* the first T blocks: store != 0 copies the arrays INTO the object (tests fill the evaluated blocks), else out of it; any pointer may be NULL */
 void mjpc_md_blocks(void *md, int T, int store, double *A, double *B, double *C, double *D, int *failure);
 
+/* CostDerivatives (mjpc/planners/cost_derivatives.h): create = Allocate + Reset; compute on the caller's engine under its current task.
+ * 0 = ok, -1 = engine error (mjpc_hip_last_error). */
+void *mjpc_cd_create(int dim_state_derivative, int dim_action, int dim_residual, int T);
+void mjpc_cd_destroy(void *cd);
+void mjpc_cd_reset(void *cd, int T);
+int mjpc_cd_compute(void *cd, MjpcHipEngine *engine, const double *r, const double *rx, const double *ru, int T, int hessians);
+/* the first T rows out of the object; any pointer may be NULL */
+void mjpc_cd_blocks(void *cd, int T, double *cr, double *cx, double *cu, double *cxx, double *cuu, double *cxu);
+/* Gradient::Compute (mjpc/planners/gradient/gradient.cc:43-108) on given arrays, host only (no GPU needed): A [T-1][nd][nd], B [T-1][nd][nu],
+ * cx [T][nd], cu [T][nu] -> k [T][nu], Vx [T][nd], Qx [T-1][nd], Qu [T-1][nu], dV [2] (outputs may be NULL).  Returns the reference's
+ * status (0 = complete); T < 2 goes through the error handler. */
+int mjpc_gd_gradient_compute(int dim_state_derivative, int dim_action, int T, const double *A, const double *B, const double *cx, const double *cu,
+                             double *k, double *Vx, double *Qx, double *Qu, double *dV);
+
+/* GradientPlanner (mjpc/planners/gradient/planner.h): create = Initialize + Allocate.  representation 0 zero, 1 linear, 2 cubic; more than 25
+ * spline points is refused through the error handler.  values out[6] = {action_step, expected, improvement, surprise, winner, failed};
+ * timings out[5] = {nominal, derivatives, gradient (mapping), rollouts, policy update} in microseconds. */
+void *mjpc_gd_create(const MjpcHipModel *model, const MjpcHipTask *task, int num_trajectory, int spline_points, int representation, int derivative_skip,
+                     int max_rollout, double min_linesearch_step, double fd_tolerance, int fd_mode, int max_samples, int max_horizon, int device);
+void mjpc_gd_destroy(void *planner);
+void mjpc_gd_reset(void *planner, int horizon, const double *initial_repeated_action);
+void mjpc_gd_set_state(void *planner, const double *state, const double *mocap, const double *userdata, double time);
+void mjpc_gd_set_task(void *planner, const MjpcHipTask *task);
+void mjpc_gd_set_num_trajectory(void *planner, int num_trajectory);
+void mjpc_gd_optimize_policy(void *planner, int horizon);
+void mjpc_gd_nominal_trajectory(void *planner, int horizon);
+void mjpc_gd_action_from_policy(void *planner, double *action, double time, int use_previous);
+double mjpc_gd_improvement(void *planner);
+int mjpc_gd_policy(void *planner, double *times, double *values);                                  /* returns P */
+void mjpc_gd_set_policy(void *planner, const double *times, const double *values);                 /* [P], [P][nu] */
+int mjpc_gd_best_trajectory(void *planner, double *states, double *actions, double *costs, double *total_return);   /* returns H */
+void mjpc_gd_values(void *planner, double *out);
+void mjpc_gd_timings(void *planner, double *out);
+void mjpc_gd_returns(void *planner, double *out, int n);          /* the last line search's returns */
+int mjpc_gd_linesearch_steps(void *planner, double *out /* NULL: size only */);
+int mjpc_gd_parameter_update(void *planner, double *out /* NULL: size only */);   /* M' k of the last iteration */
+/* host closed forms without a planner (no GPU needed): a spline mapping [(dim num_output)][(dim num_input)], GradientPolicy::Action */
+void mjpc_gd_spline_mapping(int representation, int dim, const double *input_times, int num_input, const double *output_times, int num_output,
+                            double *mapping);
+void mjpc_gd_policy_action(int representation, int nu, const double *ctrlrange, const double *times, const double *parameters, int num_spline_points,
+                           double time, double *action);
+
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
- * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create.  state / mocap are in-out;
+ * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create.  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,
  * plan_steps, failure}.  Returns the total cost. */
 double mjpc_testspeed_run(const MjpcHipModel *model, const MjpcHipTask *task, void *planner, int planner_kind, double *state,

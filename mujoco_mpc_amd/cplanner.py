@@ -125,6 +125,18 @@ def lib():
         "mjpc_sg_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
         "mjpc_sg_timings": (None, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
         "mjpc_sg_return_weights": (None, [c_int_p, i, c_double_p]), "mjpc_sg_log_scale": (None, [c_double_p, d, d, i]),
+        "mjpc_gd_create": (vp, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), i, i, i, i, i, d, d, i, i, i, i]),
+        "mjpc_gd_destroy": (None, [vp]), "mjpc_gd_reset": (None, [vp, i, c_double_p]),
+        "mjpc_gd_set_state": (None, [vp, c_double_p, c_double_p, c_double_p, d]),
+        "mjpc_gd_set_task": (None, [vp, C.POINTER(capi.MjpcHipTask)]), "mjpc_gd_set_num_trajectory": (None, [vp, i]),
+        "mjpc_gd_optimize_policy": (None, [vp, i]), "mjpc_gd_nominal_trajectory": (None, [vp, i]),
+        "mjpc_gd_action_from_policy": (None, [vp, c_double_p, d, i]), "mjpc_gd_improvement": (d, [vp]),
+        "mjpc_gd_policy": (i, [vp, c_double_p, c_double_p]), "mjpc_gd_set_policy": (None, [vp, c_double_p, c_double_p]),
+        "mjpc_gd_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_gd_values": (None, [vp, c_double_p]), "mjpc_gd_timings": (None, [vp, c_double_p]), "mjpc_gd_returns": (None, [vp, c_double_p, i]),
+        "mjpc_gd_linesearch_steps": (i, [vp, c_double_p]), "mjpc_gd_parameter_update": (i, [vp, c_double_p]),
+        "mjpc_gd_spline_mapping": (None, [i, i, c_double_p, i, c_double_p, i, c_double_p]),
+        "mjpc_gd_policy_action": (None, [i, i, c_double_p, c_double_p, c_double_p, i, d, c_double_p]),
         "mjpc_testspeed_run": (d, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), vp, i, c_double_p, c_double_p, d, i, i, d, i,
                                    c_double_p, c_double_p, i, d, c_double_p]),
     }
@@ -399,6 +411,66 @@ class SampleGradientPlanner(_Planner):
         return dict(noise_us=a.value, rollouts_us=b.value, policy_update_us=c.value, gradient_candidates_us=g.value)
 
 
+class GradientPlanner(_Planner):
+    """mjpc_hip::GradientPlanner (C++) driven from Python; names follow planners/gradient/planner.h."""
+    _prefix = "mjpc_gd_"
+    kMaxGradientSplinePoints = 25
+
+    def Initialize(self, model: dict, task: dict, numerics: dict | None = None, settings: dict | None = None, max_samples=128, max_horizon=512, device=0):
+        numerics = numerics or {}; settings = settings or {}
+        self.cm = capi.CModel(model, task)
+        self.nu = int(model["nu"]); self.ns = int(model["nq"] + model["nv"] + model["na"])
+        self.max_samples, self.max_horizon = int(max_samples), int(max_horizon)
+        self.P = int(numerics.get("gradient_spline_points", 10))
+        self.close()
+        h = self._L.mjpc_gd_create(C.byref(self.cm.c_model), C.byref(self.cm.c_task), int(numerics.get("gradient_num_trajectory", 32)), self.P,
+                                   int(numerics.get("gradient_representation", 1)), int(numerics.get("derivative_skip", 0)),
+                                   int(settings.get("max_rollout", 1)), float(settings.get("min_linesearch_step", 1.0e-8)),
+                                   float(settings.get("fd_tolerance", 1.0e-5)), int(settings.get("fd_mode", 0)), self.max_samples, self.max_horizon, int(device))
+        self._h = C.c_void_p(h)
+        _check()
+
+    def set_num_trajectory(self, n): self._L.mjpc_gd_set_num_trajectory(self._h, int(n))
+
+    def set_policy(self, times, values):
+        t = np.ascontiguousarray(times, dtype=np.float64); v = np.ascontiguousarray(values, dtype=np.float64)
+        assert t.size == self.P and v.size == self.P * self.nu
+        self._L.mjpc_gd_set_policy(self._h, _dp(t), _dp(v))
+
+    def values(self):
+        o = np.zeros(6); self._L.mjpc_gd_values(self._h, _dp(o))
+        return dict(action_step=o[0], expected=o[1], improvement=o[2], surprise=o[3], winner=int(o[4]), failed=bool(o[5]))
+
+    def timings(self):
+        o = np.zeros(5); self._L.mjpc_gd_timings(self._h, _dp(o))
+        return dict(nominal_us=o[0], derivative_us=o[1], gradient_us=o[2], rollouts_us=o[3], policy_update_us=o[4])
+
+    def linesearch_steps(self):
+        out = np.zeros(max(self._L.mjpc_gd_linesearch_steps(self._h, None), 1)); n = self._L.mjpc_gd_linesearch_steps(self._h, _dp(out)); return out[:n]
+
+    def parameter_update(self):
+        out = np.zeros(max(self._L.mjpc_gd_parameter_update(self._h, None), 1)); n = self._L.mjpc_gd_parameter_update(self._h, _dp(out))
+        return out[:n].reshape(-1, self.nu)
+
+
+def gradient_spline_mapping(representation, dim, input_times, output_times):
+    """Zero / Linear / CubicSplineMapping::Compute (host closed form, no GPU needed): [(dim * num_output), (dim * num_input)]"""
+    ti = np.ascontiguousarray(input_times, dtype=np.float64); to = np.ascontiguousarray(output_times, dtype=np.float64)
+    out = np.zeros((int(dim) * to.size, int(dim) * ti.size))
+    lib().mjpc_gd_spline_mapping(int(representation), int(dim), _dp(ti), int(ti.size), _dp(to), int(to.size), _dp(out))
+    _check()
+    return out
+
+
+def gradient_policy_action(representation, ctrlrange, times, parameters, time):
+    """GradientPolicy::Action (host closed form, no GPU needed)"""
+    cr = np.ascontiguousarray(ctrlrange, dtype=np.float64).ravel(); nu = cr.size // 2
+    t = np.ascontiguousarray(times, dtype=np.float64); p = np.ascontiguousarray(parameters, dtype=np.float64)
+    a = np.zeros(nu)
+    lib().mjpc_gd_policy_action(int(representation), nu, _dp(cr), _dp(t), _dp(p), int(t.size), float(time), _dp(a))
+    return a
+
+
 def sample_gradient_return_weights(order):
     """the planner's fitness-shaping weights over an order of candidate indices (host closed form, no GPU needed)"""
     o = np.ascontiguousarray(order, dtype=np.int32); w = np.zeros(o.size)
@@ -415,7 +487,7 @@ def sample_gradient_step_sizes(steps, max_value=2.0, min_value=1.0e-3):
 
 def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_planning_iteration=1, total_time=1.0, device=0, mode=0, mode_time=0.0):
     """mjpc/testspeed.cc:44-129 (`SynchronousPlanningCost`) through the C++ harness: `planner` is a cplanner.SamplingPlanner or
-    cplanner.CrossEntropyPlanner / cplanner.SampleGradientPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
+    cplanner.CrossEntropyPlanner / cplanner.SampleGradientPlanner / cplanner.GradientPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
     L = lib()
     cm = planner.cm
     m = cm.model
@@ -423,7 +495,7 @@ def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_pla
     st = np.ascontiguousarray(state, dtype=np.float64).copy()
     mc = None if (mocap is None or m["nmocap"] == 0) else np.ascontiguousarray(mocap, dtype=np.float64).copy()
     costs = np.zeros(nsteps); out = np.zeros(6); params = np.zeros(max(int(cm.task["num_parameter"]), 1))
-    kind = 1 if isinstance(planner, CrossEntropyPlanner) else 2 if isinstance(planner, SampleGradientPlanner) else 0
+    kind = 1 if isinstance(planner, CrossEntropyPlanner) else 2 if isinstance(planner, SampleGradientPlanner) else 3 if isinstance(planner, GradientPlanner) else 0
     total = L.mjpc_testspeed_run(C.byref(cm.c_model), C.byref(cm.c_task), planner._h, kind, _dp(st), _dp(mc), float(time0), int(horizon),
                                  int(steps_per_planning_iteration), float(total_time), int(device), _dp(costs), _dp(out), int(mode), float(mode_time), _dp(params))
     _check()

@@ -13,6 +13,8 @@
 //                   rollout kernel's phases from that row's own state, control and time (mjpc_hip_step_batch)
 //   fd_assemble_kernel / fd_difference_kernel  (transition_fd.h)  mjpc_hip_transition_fd: the perturbed table around the nominal
 //                   knots, and the A / B / C / D entries from the stepped rows
+//   cd_kernel / gd_backward_kernel  (cost_derivatives.h)  mjpc_hip_cost_derivatives / mjpc_hip_trajectory_gradient: the cost derivatives of
+//                   every knot from the residual and its Jacobian, and the gradient planner's backward recursion
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
 //   pack_kernel     the plan's result in one contiguous buffer for one D2H copy
@@ -28,6 +30,7 @@
 #include "philox.h"
 #include "gradient.h"
 #include "transition_fd.h"
+#include "cost_derivatives.h"
 #include "host.h"
 #include "devbuf.h"
 #include "../../include/mjpc_hip_debug.h"
@@ -135,6 +138,95 @@ extern "C" __global__ void __launch_bounds__(FD_TILE * FD_TILE) fd_difference_ke
   }
 }
 
+// mjpc_hip_cost_derivatives: block (x, y, z) owns the CD_TILE x CD_TILE tile of knot z's (nd + nu)^2 Gauss-Newton matrix at rows
+// y * CD_TILE, columns x * CD_TILE (hessians = 0: gridDim.y = 1 and the gradient alone).  The lanes of a wave run along the output
+// column j: a row of J = [C | D] is contiguous in j, so J[r][j] is read in whole 128-byte segments and J[r][i] is a broadcast.  The
+// knot's norm derivatives are computed once per workgroup into LDS; crr J of a dense term is staged there for the tile's columns
+// (the tile's width is the column chunk), read back with one address per column: no bank conflicts.
+extern "C" __global__ void __launch_bounds__(CD_TILE * CD_TILE) cd_kernel(const CdArgs a) {
+  extern __shared__ double cd_sm[];
+  const CdLds L = cd_lds(a, cd_sm);
+  const int t = blockIdx.z, i0 = blockIdx.y * CD_TILE, j0 = blockIdx.x * CD_TILE, n = a.nd + a.nu, tid = threadIdx.x;
+  for (int k = tid; k < a.num_term; k += CD_TILE * CD_TILE) cd_term(a, t, k, L);
+  __syncthreads();
+  const double s = cd_risk_scale(a, L);
+  if (tid < (a.hessians ? 2 : 1) * CD_TILE) {
+    const int j = tid < CD_TILE ? j0 + tid : i0 + (tid - CD_TILE);
+    L.gv[tid] = j < n ? cd_gradient(a, t, j, L, s) : 0.0;
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && a.cr) for (int r = tid; r < a.nr; r += CD_TILE * CD_TILE) a.cr[(size_t)t * a.nr + r] = L.cr[r];
+  __syncthreads();
+  if (blockIdx.y == 0 && tid < CD_TILE && j0 + tid < n) {
+    const int j = j0 + tid;
+    if (j < a.nd) { if (a.cx) a.cx[(size_t)t * a.nd + j] = L.gv[tid]; }
+    else if (a.cu) a.cu[(size_t)t * a.nu + (j - a.nd)] = L.gv[tid];
+  }
+  if (!a.hessians) return;
+  const int term = cd_terminal(a, t);
+  if (term && blockIdx.x == 0 && blockIdx.y == 0)
+    for (size_t e = tid; e < (size_t)(a.nd > a.nu ? a.nd : a.nu) * a.nu; e += CD_TILE * CD_TILE) { cd_zero_terminal(a, 0, e); cd_zero_terminal(a, 1, e); }
+  if (i0 >= a.nd && j0 + CD_TILE <= a.nd) return;             // the tile lies in the bottom-left block, which is not stored
+  const int jj = tid % CD_TILE, ii = tid / CD_TILE, i = i0 + ii, j = j0 + jj;
+  double *dst = cd_dest(a, t, i, j);
+  double acc = 0;
+  int fs = 0;
+  for (int k = 0; k < a.num_term; k++) {
+    const int ni = a.dim_norm_residual[k], dense = norm_dense(a.norm[k]);
+    if (dense) {          // (uniform over the workgroup)
+      __syncthreads();
+      for (int idx = tid; idx < ni * CD_TILE; idx += CD_TILE * CD_TILE) {
+        const int c = j0 + idx % CD_TILE;
+        L.S[idx] = (c < n && !(term && c >= a.nd)) ? cd_S_dense(a, t, k, fs, ni, idx / CD_TILE, c, L) : 0.0;
+      }
+      __syncthreads();
+    }
+    if (dst) acc = add_rn(acc, mul_rn(cd_weight(a, k), cd_G(a, t, fs, ni, dense, i, j, jj, L)));
+    fs += ni;
+  }
+  if (dst) *dst = cd_risk_entry(a, acc, L.gv[CD_TILE + ii], L.gv[jj], s);
+}
+
+// mjpc_hip_trajectory_gradient, backward recursion: one workgroup, one lane per column of [A | B]; Vx_t and Qu_{t-1} pass through LDS
+// (two buffers each).  Only Vx is on the serial chain: the block of step t - 1 is fetched into registers before step t's chain starts
+// and stored to LDS behind it (cost_derivatives.h), so a step's memory latency runs under the previous step's adds.  LDS (doubles):
+// vx[2][nd] | qu[2][nu] | block[nd][nd + nu] (the block only when it fits, gd_staged)
+extern "C" __global__ void __launch_bounds__(GD_THREADS) gd_backward_kernel(const GdArgs a) {
+  extern __shared__ double gd_sm[];
+  const int nd = a.nd, nu = a.nu, n = nd + nu, T = a.T, tid = threadIdx.x, nb = nd * n;
+  double *vx[2] = {gd_sm, gd_sm + nd}, *qu[2] = {gd_sm + 2 * nd, gd_sm + 2 * nd + nu};
+  const bool staged = gd_staged(a);
+  double *blk = staged ? gd_sm + 2 * n : nullptr;
+  for (int c = tid; c < nd; c += GD_THREADS) { const double v = a.cx[(size_t)(T - 1) * nd + c]; vx[0][c] = v; a.Vx[(size_t)(T - 1) * nd + c] = v; }
+  if (staged) for (int i = tid; i < nb; i += GD_THREADS) blk[i] = gd_block(a, T - 1, i);
+  double dv = 0;
+  __syncthreads();
+  for (int t = T - 1; t > 0; t--) {
+    const int b = (T - 1 - t) & 1;
+    double next[GD_R];
+    if (staged && t > 1) {
+#pragma unroll
+      for (int u = 0; u < GD_R; u++) { const int i = tid + u * GD_THREADS; next[u] = i < nb ? gd_block(a, t - 1, i) : 0.0; }
+    }
+    for (int c = tid; c < n; c += GD_THREADS) {
+      const double q = gd_column(a, t, c, vx[b], blk);
+      if (c < nd) { a.Qx[(size_t)(t - 1) * nd + c] = q; a.Vx[(size_t)(t - 1) * nd + c] = q; vx[b ^ 1][c] = q; }
+      else {
+        const int kk = c - nd;
+        a.Qu[(size_t)(t - 1) * nu + kk] = q; a.k[(size_t)(t - 1) * nu + kk] = -q; qu[b][kk] = q;
+        if (t == T - 1) a.k[(size_t)(T - 1) * nu + kk] = -q;         // k_{T-1} = k_{T-2}
+      }
+    }
+    __syncthreads();
+    if (tid == 0) dv = gd_dv(a, qu[b], dv);
+    if (staged && t > 1) {
+#pragma unroll
+      for (int u = 0; u < GD_R; u++) { const int i = tid + u * GD_THREADS; if (i < nb) blk[i] = next[u]; }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) { a.dV[0] = dv; a.dV[1] = 0.0; }
+}
+
 // winner[0] = local index of the first minimum of returns[0..n), winner_val[0] = its value
 extern "C" __global__ void __launch_bounds__(64) argmin_kernel(const double *returns, int n, int *winner, double *winner_val) {
   int lane = threadIdx.x;
@@ -233,6 +325,7 @@ struct MjpcHipEngine {
   int summary_only = 0, last_summary = 0;      // mjpc_hip_set_fetch_mode
   int last_dense = 0;
   int have_mixed = 0;          // a mjpc_hip_plan_mixed step has filled the noise history
+  bool cost_rows_ok = false;   // cost_rows_tile of the current task
   // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour
   const void *step_kernel = nullptr; StepLaunchFn step_launch = nullptr;
   DenseTier tierB; int num_cu = 256, force_tier = 0;
@@ -249,6 +342,14 @@ static size_t row_doubles(const MjpcHipEngine *e, int k, size_t H, size_t P, boo
 static double *out_row(const MjpcHipPlanOutput *out, int k) {
   double *dst[NROWS] = {out->winner_knots, out->states, out->actions, out->times, out->residual, out->costs, out->trace};
   return dst[k];
+}
+
+// the cost terms' rows tile the residual (the cost-derivative kernel indexes its LDS rows by them): checked when the task is packed
+static bool cost_rows_tile(const MjpcHipEngine *e) {
+  const DevTask ht = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data()).task;
+  long rows = 0;
+  for (int k = 0; k < ht.num_term; k++) rows += ht.dim_norm_residual[k] > 0 ? ht.dim_norm_residual[k] : (long)e->nr + 1;
+  return rows == e->nr;
 }
 
 static int upload_model(MjpcHipEngine *e) {
@@ -430,6 +531,7 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   for (int k = 1; k < NROWS; k++) HIPCHKP(e->buf[B_KNOTS + k].reserve(D * NL * row_doubles(e, k, H, 0, true)));
   for (int b : {B_PROF, B_HIST, B_CKPT}) if (e->buf[b].p) HIPCHKP(hipMemset(e->buf[b].p, 0, e->buf[b].cap));
   if (upload_model(e) != 0) { mjpc_hip_destroy(e); return nullptr; }
+  e->cost_rows_ok = cost_rows_tile(e);
   HIPCHKP(hipStreamCreate(&e->stream));
   for (int i = 0; i < 4; i++) HIPCHKP(hipEventCreate(&e->ev[i]));
   HIPCHKP(hipFuncSetAttribute((const void *)e->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
@@ -458,6 +560,7 @@ int mjpc_hip_set_task(MjpcHipEngine *e, const MjpcHipTask *task) {
   if (task->num_residual != e->nr || 3 * task->num_trace != e->ntr) { set_error("mjpc_hip_set_task: residual/trace dimensions changed"); return -1; }
   if (e->pending) { set_error("mjpc_hip_set_task: a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
   if (!mjpc_host::repack_task(e->pm, task)) { set_error("mjpc_hip_set_task: " + e->pm.error); return -1; }
+  e->cost_rows_ok = cost_rows_tile(e);
   // only the task block changes (cost table, residual parameters, frozen ResidualFn state): one small stream-ordered copy per
   // buffer out of the engine's own packed image, ahead of the next plan's kernels; the model and key-frame tables stay put
   const PackedModel &pm = e->pm;
@@ -739,6 +842,58 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
   return 0;
 }
 
+// dof -> (qpos address, quaternion axis or -1) from the engine's own packed model
+static std::vector<int> fd_dofmap(const MjpcHipEngine *e) {
+  const int nv = e->nv;
+  std::vector<int> dofmap(2 * nv + 2, -1);
+  const DevModel hm = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data());
+  for (int j = 0; j < hm.njnt; j++) {
+    const int type = hm.jnt_type[j], qa = hm.jnt_qposadr[j], da = hm.jnt_dofadr[j];
+    if (type == 0) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa + k; dofmap[2 * (da + k) + 1] = -1; dofmap[2 * (da + 3 + k)] = qa + 3; dofmap[2 * (da + 3 + k) + 1] = k; } }
+    else if (type == 1) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa; dofmap[2 * (da + k) + 1] = k; } }
+    else { dofmap[2 * da] = qa; dofmap[2 * da + 1] = -1; }
+  }
+  return dofmap;
+}
+
+// one pass of mjpc_hip_transition_fd over the Tg knots from t0 on, everything stream-ordered and nothing downloaded: the nominal rows
+// go up, the table is assembled, stepped and differenced; the matrices and failure[] stay in B_FD where `a` points.  extra: doubles
+// the caller wants behind the pass's own (B_FD is reserved once, here), returned in *extra_out
+static int fd_pass(MjpcHipEngine *e, const KParams &K, const std::vector<int> &dofmap, size_t t0, size_t Tg, int term, const double *x, const double *u,
+                   const double *time, double eps, int centered, size_t extra, FdArgs *out, double **extra_out) {
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, na = ds - e->nq - e->nv, nd = 2 * nv + na;
+  const size_t E = centered ? 1 + 2 * (nd + nu) : 1 + nd + nu, R = Tg * E;
+  const size_t per_t = ds + nu + 1 + nd * nd + nd * nu + nr * nd + nr * nu;
+  const size_t nd_ = R * (2 * ds + nu + 1 + nr) + Tg * per_t + 8;
+  HIPCHK(e->buf[B_FD].reserve((nd_ + extra) * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int)));
+  double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
+  double *dx = rs + R * nr, *du = dx + Tg * ds, *dt = du + Tg * nu, *dA = dt + Tg, *dB = dA + Tg * nd * nd, *dC = dB + Tg * nd * nu, *dD = dC + Tg * nr * nd;
+  int *fl = (int *)(st + nd_ + extra), *flT = fl + R, *dmap = flT + Tg;
+  HIPCHK(hipMemcpyAsync(dx, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
+  if (nu) HIPCHK(hipMemcpyAsync(du, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(dt, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(dmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+  FdArgs a;
+  a.x = dx; a.u = du; a.time = dt; a.dofmap = dmap; a.ctrllimited = e->K.M.actuator_ctrllimited; a.ctrlrange = e->K.M.actuator_ctrlrange;
+  a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = (int)na; a.nu = e->nu; a.nr = e->nr; a.centered = centered; a.last_is_terminal = term;
+  a.eps = eps; a.cs = cos(0.5 * eps); a.sn = sin(0.5 * eps);
+  a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = ns; a.residual = rs; a.fail = fl;
+  a.A = dA; a.B = dB; a.C = dC; a.D = dD; a.failure = flT;
+  hipLaunchKernelGGL(fd_assemble_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a, (unsigned)R);
+  step_rows(e, K, R, st, ct, tt, ns, rs, fl);
+  hipLaunchKernelGGL(fd_difference_kernel, dim3((unsigned)((nd + nu + FD_TILE - 1) / FD_TILE), (unsigned)((nd + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tg),
+                     dim3(FD_TILE * FD_TILE), 0, e->stream, a);
+  HIPCHK(hipGetLastError());
+  *out = a;
+  if (extra_out) *extra_out = st + nd_;
+  return 0;
+}
+// knots of one pass: its table stays below STEP_PASS_ROWS rows
+static size_t fd_pass_knots(const MjpcHipEngine *e, int centered) {
+  const size_t nc = 2 * (size_t)e->nv + (e->ds - e->nq - e->nv) + e->nu, E = centered ? 1 + 2 * nc : 1 + nc;
+  return STEP_PASS_ROWS / E < 1 ? 1 : STEP_PASS_ROWS / E;
+}
+
 int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
                            const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
                            double *D, int *failure) {
@@ -751,52 +906,117 @@ int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const doubl
   if (rc != 0) return rc;
   centered = centered ? 1 : 0; last_is_terminal = last_is_terminal ? 1 : 0;
   const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, na = ds - e->nq - e->nv, nd = 2 * nv + na;
-  // dof -> (qpos address, quaternion axis or -1) from the engine's own packed model
-  std::vector<int> dofmap(2 * nv + 2, -1);
-  {
-    const DevModel hm = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data());
-    for (int j = 0; j < hm.njnt; j++) {
-      const int type = hm.jnt_type[j], qa = hm.jnt_qposadr[j], da = hm.jnt_dofadr[j];
-      if (type == 0) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa + k; dofmap[2 * (da + k) + 1] = -1; dofmap[2 * (da + 3 + k)] = qa + 3; dofmap[2 * (da + 3 + k) + 1] = k; } }
-      else if (type == 1) { for (int k = 0; k < 3; k++) { dofmap[2 * (da + k)] = qa; dofmap[2 * (da + k) + 1] = k; } }
-      else { dofmap[2 * da] = qa; dofmap[2 * da + 1] = -1; }
-    }
-  }
-  const size_t E = centered ? 1 + 2 * (nd + nu) : 1 + nd + nu;
-  size_t Tg_max = STEP_PASS_ROWS / E; if (Tg_max < 1) Tg_max = 1;
-  const double cs = cos(0.5 * eps), sn = sin(0.5 * eps);
+  const std::vector<int> dofmap = fd_dofmap(e);
+  const size_t Tg_max = fd_pass_knots(e, centered);
   for (size_t t0 = 0; t0 < (size_t)T; t0 += Tg_max) {
-    const size_t Tg = (size_t)T - t0 < Tg_max ? (size_t)T - t0 : Tg_max, R = Tg * E;
+    const size_t Tg = (size_t)T - t0 < Tg_max ? (size_t)T - t0 : Tg_max;
     const int term = last_is_terminal && t0 + Tg == (size_t)T;
-    const size_t per_t = ds + nu + 1 + nd * nd + nd * nu + nr * nd + nr * nu;
-    const size_t nd_ = R * (2 * ds + nu + 1 + nr) + Tg * per_t + 8;
-    HIPCHK(e->buf[B_FD].reserve(nd_ * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int)));
-    double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
-    double *dx = rs + R * nr, *du = dx + Tg * ds, *dt = du + Tg * nu, *dA = dt + Tg, *dB = dA + Tg * nd * nd, *dC = dB + Tg * nd * nu, *dD = dC + Tg * nr * nd;
-    int *fl = (int *)(st + nd_), *flT = fl + R, *dmap = flT + Tg;
-    HIPCHK(hipMemcpyAsync(dx, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
-    if (nu) HIPCHK(hipMemcpyAsync(du, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(dt, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(dmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
     FdArgs a;
-    a.x = dx; a.u = du; a.time = dt; a.dofmap = dmap; a.ctrllimited = e->K.M.actuator_ctrllimited; a.ctrlrange = e->K.M.actuator_ctrlrange;
-    a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = (int)na; a.nu = e->nu; a.nr = e->nr; a.centered = centered; a.last_is_terminal = term;
-    a.eps = eps; a.cs = cs; a.sn = sn;
-    a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = ns; a.residual = rs; a.fail = fl;
-    a.A = dA; a.B = dB; a.C = dC; a.D = dD; a.failure = flT;
-    hipLaunchKernelGGL(fd_assemble_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a, (unsigned)R);
-    step_rows(e, K, R, st, ct, tt, ns, rs, fl);
-    hipLaunchKernelGGL(fd_difference_kernel, dim3((unsigned)((nd + nu + FD_TILE - 1) / FD_TILE), (unsigned)((nd + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tg),
-                       dim3(FD_TILE * FD_TILE), 0, e->stream, a);
-    HIPCHK(hipGetLastError());
+    rc = fd_pass(e, K, dofmap, t0, Tg, term, x, u, time, eps, centered, 0, &a, nullptr);
+    if (rc != 0) return rc;
     const size_t Tw = Tg - (term ? 1 : 0);            // a terminal knot's A / B / D blocks stay the caller's
-    if (Tw && nd) HIPCHK(hipMemcpyAsync(A + t0 * nd * nd, dA, sizeof(double) * Tw * nd * nd, hipMemcpyDeviceToHost, e->stream));
-    if (Tw && nd * nu) HIPCHK(hipMemcpyAsync(B + t0 * nd * nu, dB, sizeof(double) * Tw * nd * nu, hipMemcpyDeviceToHost, e->stream));
-    if (nr * nd) HIPCHK(hipMemcpyAsync(C + t0 * nr * nd, dC, sizeof(double) * Tg * nr * nd, hipMemcpyDeviceToHost, e->stream));
-    if (Tw && nr * nu) HIPCHK(hipMemcpyAsync(D + t0 * nr * nu, dD, sizeof(double) * Tw * nr * nu, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(failure + t0, flT, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
+    if (Tw && nd) HIPCHK(hipMemcpyAsync(A + t0 * nd * nd, a.A, sizeof(double) * Tw * nd * nd, hipMemcpyDeviceToHost, e->stream));
+    if (Tw && nd * nu) HIPCHK(hipMemcpyAsync(B + t0 * nd * nu, a.B, sizeof(double) * Tw * nd * nu, hipMemcpyDeviceToHost, e->stream));
+    if (nr * nd) HIPCHK(hipMemcpyAsync(C + t0 * nr * nd, a.C, sizeof(double) * Tg * nr * nd, hipMemcpyDeviceToHost, e->stream));
+    if (Tw && nr * nu) HIPCHK(hipMemcpyAsync(D + t0 * nr * nu, a.D, sizeof(double) * Tw * nr * nu, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(failure + t0, a.failure, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ cost derivatives, trajectory gradient
+// the cost-derivative kernel over T knots whose inputs and outputs are on the device already (a.residual .. a.cxu set by the caller)
+static int cd_launch(MjpcHipEngine *e, CdArgs a, const char *who) {
+  const DevTask &tk = e->K.M.task;
+  a.dim_norm_residual = tk.dim_norm_residual; a.norm = tk.norm; a.num_norm_parameter = tk.num_norm_parameter;
+  a.weight = tk.weight; a.norm_parameter = tk.norm_parameter; a.num_term = tk.num_term; a.risk = tk.risk;
+  if (!e->cost_rows_ok) { set_error(std::string(who) + ": the cost terms' residual dimensions do not add up to num_residual"); return -1; }
+  const size_t lds = CD_LDS_DOUBLES(a.nr, a.num_term) * sizeof(double);
+  if (lds > 64 * 1024) { set_error(std::string(who) + ": num_residual too large for the cost-derivative kernel's LDS (64 KiB)"); return -1; }
+  const unsigned tiles = (unsigned)((a.nd + a.nu + CD_TILE - 1) / CD_TILE);
+  hipLaunchKernelGGL(cd_kernel, dim3(tiles, a.hessians ? tiles : 1, (unsigned)a.T), dim3(CD_TILE * CD_TILE), lds, e->stream, a);
+  return 0;
+}
+
+int mjpc_hip_cost_derivatives(MjpcHipEngine *e, int T, const double *residual, const double *C, const double *D, int last_is_terminal, int hessians,
+                              double *cr, double *cx, double *cu, double *cxx, double *cuu, double *cxu) {
+  if (!e) { set_error("mjpc_hip_cost_derivatives: invalid argument"); return -1; }
+  if (T < 1) { set_error("mjpc_hip_cost_derivatives: T < 1"); return -1; }
+  if (e->pending) { set_error("mjpc_hip_cost_derivatives: a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
+  last_is_terminal = last_is_terminal ? 1 : 0; hessians = hessians ? 1 : 0;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv);
+  const size_t Td = (size_t)T - last_is_terminal;          // knots that have a D
+  if ((nr && !residual) || (nr * nd && !C) || (nr * nu * Td && !D)) { set_error("mjpc_hip_cost_derivatives: null input"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  const size_t n_in = (size_t)T * (nr + nr * nd + nr * nu), n_g = (size_t)T * (nr + nd + nu), n_h = hessians ? (size_t)T * (nd * nd + nu * nu + nd * nu) : 0;
+  HIPCHK(e->buf[B_FD].reserve((n_in + n_g + n_h + 8) * sizeof(double)));
+  double *dr = e->at(B_FD), *dC = dr + (size_t)T * nr, *dD = dC + (size_t)T * nr * nd, *o = dD + (size_t)T * nr * nu;
+  CdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.residual = dr; a.C = dC; a.D = dD; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = last_is_terminal; a.hessians = hessians;
+  a.cr = o; a.cx = a.cr + (size_t)T * nr; a.cu = a.cx + (size_t)T * nd;
+  if (hessians) { a.cxx = a.cu + (size_t)T * nu; a.cuu = a.cxx + (size_t)T * nd * nd; a.cxu = a.cuu + (size_t)T * nu * nu; }
+  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * T * nr, hipMemcpyHostToDevice, e->stream));
+  if (nr * nd) HIPCHK(hipMemcpyAsync(dC, C, sizeof(double) * T * nr * nd, hipMemcpyHostToDevice, e->stream));
+  if (nr * nu * Td) HIPCHK(hipMemcpyAsync(dD, D, sizeof(double) * Td * nr * nu, hipMemcpyHostToDevice, e->stream));
+  int rc = cd_launch(e, a, "mjpc_hip_cost_derivatives");
+  if (rc != 0) return rc;
+  HIPCHK(hipGetLastError());
+  const struct { double *dst; const double *src; size_t n; } outs[] = {
+    {cr, a.cr, (size_t)T * nr}, {cx, a.cx, (size_t)T * nd}, {cu, a.cu, (size_t)T * nu},
+    {cxx, a.cxx, (size_t)T * nd * nd}, {cuu, a.cuu, (size_t)T * nu * nu}, {cxu, a.cxu, (size_t)T * nd * nu}};
+  for (int k = 0; k < (hessians ? 6 : 3); k++)
+    if (outs[k].dst && outs[k].n) HIPCHK(hipMemcpyAsync(outs[k].dst, outs[k].src, sizeof(double) * outs[k].n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual, const double *mocap,
+                                 const double *userdata, double eps, int centered, double *k, double *Vx, double *Qx, double *Qu, double *dV, int *failure) {
+  if (!e) { set_error("mjpc_hip_trajectory_gradient: invalid argument"); return -1; }
+  if (T < 2) { set_error("mjpc_hip_trajectory_gradient: T < 2"); return -1; }
+  if (!(eps > 0)) { set_error("mjpc_hip_trajectory_gradient: eps <= 0"); return -1; }
+  if (!x || !time || (e->nu > 0 && !u) || (e->nr > 0 && !residual) || !failure) { set_error("mjpc_hip_trajectory_gradient: null input"); return -1; }
+  centered = centered ? 1 : 0;
+  if ((size_t)T > fd_pass_knots(e, centered)) { set_error("mjpc_hip_trajectory_gradient: T too large for one pass of the step tables (" + std::to_string(fd_pass_knots(e, centered)) + " knots for this model)"); return -1; }
+  KParams K;
+  int rc = step_prepare(e, "mjpc_hip_trajectory_gradient", mocap, userdata, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv), Tz = (size_t)T;
+  // behind the pass's tables: the residual rows, cr / cx / cu, and the block that goes back in one copy:
+  //   k [T][nu] | Vx [T][nd] | Qx [T-1][nd] | Qu [T-1][nu] | dV [2] | failure [T] (ints, two to a double)
+  const size_t n_out = Tz * nu + Tz * nd + (Tz - 1) * nd + (Tz - 1) * nu + 2, n_fail = (Tz + 1) / 2;
+  const size_t extra = Tz * (2 * nr + nd + nu) + n_out + n_fail;
+  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * (n_out + n_fail)));
+  FdArgs f;
+  double *x0 = nullptr;
+  const std::vector<int> dofmap = fd_dofmap(e);          // (outlives the stream's copy of it)
+  rc = fd_pass(e, K, dofmap, 0, Tz, 1, x, u, time, eps, centered, extra, &f, &x0);
+  if (rc != 0) return rc;
+  double *dr = x0, *dcr = dr + Tz * nr, *dcx = dcr + Tz * nr, *dcu = dcx + Tz * nd, *ob = dcu + Tz * nu;
+  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
+  CdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.residual = dr; a.C = f.C; a.D = f.D; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = 1; a.hessians = 0;
+  a.cr = dcr; a.cx = dcx; a.cu = dcu;
+  rc = cd_launch(e, a, "mjpc_hip_trajectory_gradient");
+  if (rc != 0) return rc;
+  GdArgs g;
+  g.A = f.A; g.B = f.B; g.cx = dcx; g.cu = dcu; g.T = T; g.nd = (int)nd; g.nu = (int)nu;
+  g.k = ob; g.Vx = g.k + Tz * nu; g.Qx = g.Vx + Tz * nd; g.Qu = g.Qx + (Tz - 1) * nd; g.dV = g.Qu + (Tz - 1) * nu;
+  const size_t gd_lds = sizeof(double) * (2 * (nd + nu) + (nd * (nd + nu) <= (size_t)GD_THREADS * GD_R ? nd * (nd + nu) : 0));
+  if (gd_lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)gd_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gd_lds));
+  hipLaunchKernelGGL(gd_backward_kernel, dim3(1), dim3(GD_THREADS), gd_lds, e->stream, g);
+  HIPCHK(hipGetLastError());
+  int *dfail = (int *)(ob + n_out);
+  HIPCHK(hipMemcpyAsync(dfail, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
+  double *h = e->at(H_PACK);
+  HIPCHK(hipMemcpyAsync(h, ob, sizeof(double) * (n_out + n_fail), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const struct { double *dst; size_t n; } outs[] = {{k, Tz * nu}, {Vx, Tz * nd}, {Qx, (Tz - 1) * nd}, {Qu, (Tz - 1) * nu}, {dV, 2}};
+  for (const auto &o : outs) { if (o.dst && o.n) memcpy(o.dst, h, sizeof(double) * o.n); h += o.n; }
+  memcpy(failure, h, sizeof(int) * Tz);
   return 0;
 }
 

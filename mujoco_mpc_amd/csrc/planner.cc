@@ -941,6 +941,433 @@ bool ModelDerivatives::Compute(MjpcHipEngine* engine, const double* x, const dou
   return true;
 }
 
+// ------------------------------------------------------------------ CostDerivatives
+void CostDerivatives::Allocate(int nd, int nu, int nr, int T) {
+  dim_state_derivative = nd; dim_action = nu; dim_residual = nr; horizon = T;
+  cr.resize((size_t)T * nr); cx.resize((size_t)T * nd); cu.resize((size_t)T * nu);
+  cxx.resize((size_t)T * nd * nd); cuu.resize((size_t)T * nu * nu); cxu.resize((size_t)T * nd * nu);
+}
+
+void CostDerivatives::Reset(int nd, int nu, int nr, int T) {
+  if (nd != dim_state_derivative || nu != dim_action || nr != dim_residual || T > horizon) Allocate(nd, nu, nr, T);
+  for (std::vector<double>* v : {&cr, &cx, &cu, &cxx, &cuu, &cxu}) std::fill(v->begin(), v->end(), 0.0);
+}
+
+bool CostDerivatives::Compute(MjpcHipEngine* engine, const double* r, const double* rx, const double* ru, int nd, int nu, int nr, int T, bool hessians) {
+  Reset(nd, nu, nr, T);
+  return mjpc_hip_cost_derivatives(engine, T, r, rx, ru, 1, hessians ? 1 : 0, cr.data(), cx.data(), cu.data(), cxx.data(), cuu.data(), cxu.data()) == 0;
+}
+
+// ------------------------------------------------------------------ Gradient
+void Gradient::Allocate(int nd, int nu, int T) {
+  Vx.resize((size_t)nd * T); Qx.resize((size_t)nd * (T > 1 ? T - 1 : 0)); Qu.resize((size_t)nu * (T > 1 ? T - 1 : 0));
+}
+
+void Gradient::Reset(int nd, int nu, int T) {
+  if (Vx.size() < (size_t)nd * T || Qx.size() + nd < (size_t)nd * T || Qu.size() + nu < (size_t)nu * T) Allocate(nd, nu, T);
+  std::fill(Vx.begin(), Vx.end(), 0.0); std::fill(Qx.begin(), Qx.end(), 0.0); std::fill(Qu.begin(), Qu.end(), 0.0);
+  dV[0] = 0.0; dV[1] = 0.0;
+}
+
+int Gradient::Compute(double* k, const ModelDerivatives* md, const CostDerivatives* cd, int nd, int nu, int T) {
+  return Compute(k, md->A.data(), md->B.data(), cd->cx.data(), cd->cu.data(), nd, nu, T);
+}
+
+// gradient.cc:43-108.  Every contraction starts at 0.0 and runs over the ascending row of A / B, a rounded product and a rounded add
+// per step (this file is compiled without contraction): the device's gd_column / gd_dv (csrc/cost_derivatives.h) bit for bit.
+// GradientStep cannot fail, so the reference's early exit is not restated and the status is always 0.
+int Gradient::Compute(double* k, const double* A, const double* B, const double* cx, const double* cu, int nd, int nu, int T) {
+  if (T < 2) { Fatal("Gradient: T < 2"); return -1; }
+  if (Vx.size() < (size_t)nd * T || Qx.size() < (size_t)nd * (T - 1) || Qu.size() < (size_t)nu * (T - 1)) Allocate(nd, nu, T);
+  dV[0] = 0.0; dV[1] = 0.0;
+  std::copy(cx + (size_t)(T - 1) * nd, cx + (size_t)T * nd, Vx.begin() + (size_t)(T - 1) * nd);
+  for (int t = T - 1; t > 0; t--) {
+    const double *Wx = Vx.data() + (size_t)t * nd, *At = A + (size_t)(t - 1) * nd * nd, *Bt = B + (size_t)(t - 1) * nd * nu;
+    double *Qxt = Qx.data() + (size_t)(t - 1) * nd, *Qut = Qu.data() + (size_t)(t - 1) * nu, *kt = k + (size_t)(t - 1) * nu;
+    for (int c = 0; c < nd; c++) {
+      double q = 0.0;
+      for (int r = 0; r < nd; r++) q += At[(size_t)r * nd + c] * Wx[r];
+      Qxt[c] = q + cx[(size_t)(t - 1) * nd + c];
+    }
+    for (int c = 0; c < nu; c++) {
+      double q = 0.0;
+      for (int r = 0; r < nd; r++) q += Bt[(size_t)r * nu + c] * Wx[r];
+      Qut[c] = q + cu[(size_t)(t - 1) * nu + c];
+    }
+    double d = 0.0;
+    for (int c = 0; c < nu; c++) { kt[c] = -Qut[c]; d += kt[c] * Qut[c]; }
+    std::copy(Qxt, Qxt + nd, Vx.begin() + (size_t)(t - 1) * nd);
+    dV[0] += d;
+  }
+  std::copy(k + (size_t)(T - 2) * nu, k + (size_t)(T - 1) * nu, k + (size_t)(T - 1) * nu);
+  return 0;
+}
+
+// ------------------------------------------------------------------ interpolation helpers (utilities.h:122-141, utilities.cc:286-404)
+void FindInterval(int* bounds, const std::vector<double>& sequence, double value, int length) {
+  auto it = std::upper_bound(sequence.begin(), sequence.begin() + length, value);
+  int upper_bound = (int)(it - sequence.begin()), lower_bound = upper_bound - 1;
+  if (lower_bound < 0) { bounds[0] = 0; bounds[1] = 0; }
+  else if (lower_bound > length - 1) { bounds[0] = length - 1; bounds[1] = length - 1; }
+  else { bounds[0] = std::max(lower_bound, 0); bounds[1] = std::min(upper_bound, length - 1); }
+}
+void ZeroInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length) {
+  int bounds[2];
+  FindInterval(bounds, xs, x, length);
+  std::copy(ys + dim * bounds[0], ys + dim * (bounds[0] + 1), output);
+}
+void LinearInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length) {
+  int bounds[2];
+  FindInterval(bounds, xs, x, length);
+  if (bounds[0] == bounds[1]) { std::copy(ys + dim * bounds[0], ys + dim * (bounds[0] + 1), output); return; }
+  double t = (x - xs[bounds[0]]) / (xs[bounds[1]] - xs[bounds[0]]);
+  for (int i = 0; i < dim; i++) output[i] = ys[dim * bounds[0] + i] * (1.0 - t);       // mju_scl, then mju_addScl
+  for (int i = 0; i < dim; i++) output[i] = output[i] + ys[dim * bounds[1] + i] * t;
+}
+static void CubicCoefficients(double* c, double x, const std::vector<double>& xs, int T) {
+  int bounds[2];
+  FindInterval(bounds, xs, x, T);
+  if (bounds[0] == bounds[1]) { c[0] = 1.0; c[1] = 0.0; c[2] = 0.0; c[3] = 0.0; return; }
+  double dx = xs[bounds[1]] - xs[bounds[0]], t = (x - xs[bounds[0]]) / dx;
+  c[0] = 2.0 * t * t * t - 3.0 * t * t + 1.0;
+  c[1] = (t * t * t - 2.0 * t * t + t) * dx;
+  c[2] = -2.0 * t * t * t + 3 * t * t;
+  c[3] = (t * t * t - t * t) * dx;
+}
+static double FiniteDifferenceSlope(double x, const std::vector<double>& xs, const double* ys, int dim, int length, int i) {
+  int b[2];
+  FindInterval(b, xs, x, length);
+  if (b[0] == 0 && b[1] == 0) return length > 2 ? (ys[dim * (b[1] + 1) + i] - ys[dim * b[1] + i]) / (xs[b[1] + 1] - xs[b[1]]) : 0.0;
+  if (b[0] == length - 1 && b[1] == length - 1) return length > 2 ? (ys[dim * b[0] + i] - ys[dim * (b[0] - 1) + i]) / (xs[b[0]] - xs[b[0] - 1]) : 0.0;
+  if (b[0] == 0) return (ys[dim * b[1] + i] - ys[dim * b[0] + i]) / (xs[b[1]] - xs[b[0]]);
+  return 0.5 * (ys[dim * b[1] + i] - ys[dim * b[0] + i]) / (xs[b[1]] - xs[b[0]]) +
+         0.5 * (ys[dim * b[0] + i] - ys[dim * (b[0] - 1) + i]) / (xs[b[0]] - xs[b[0] - 1]);
+}
+void CubicInterpolation(double* output, double x, const std::vector<double>& xs, const double* ys, int dim, int length) {
+  int bounds[2];
+  FindInterval(bounds, xs, x, length);
+  if (bounds[0] == bounds[1]) { std::copy(ys + dim * bounds[0], ys + dim * (bounds[0] + 1), output); return; }
+  double c[4];
+  CubicCoefficients(c, x, xs, length);
+  for (int i = 0; i < dim; i++) {
+    double p0 = ys[bounds[0] * dim + i], p1 = ys[bounds[1] * dim + i];
+    double m0 = FiniteDifferenceSlope(xs[bounds[0]], xs, ys, dim, length, i), m1 = FiniteDifferenceSlope(xs[bounds[1]], xs, ys, dim, length, i);
+    output[i] = c[0] * p0 + c[1] * m0 + c[2] * p1 + c[3] * m1;
+  }
+}
+
+// ------------------------------------------------------------------ GradientPolicy (gradient/policy.cc)
+void GradientPolicy::Allocate(const MjpcHipModel* model, const Numerics& numerics, int horizon) {
+  nu = model->nu;
+  ctrlrange.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu);
+  k.assign((size_t)nu * horizon, 0.0);
+  parameters.assign((size_t)nu * horizon, 0.0); parameter_update.assign((size_t)nu * horizon, 0.0); times.assign(horizon, 0.0);
+  num_spline_points = numerics.gradient_spline_points;
+  num_parameters = nu * num_spline_points;
+  representation = numerics.gradient_representation;
+}
+void GradientPolicy::Reset(int horizon, const double* initial_repeated_action) {
+  const size_t n = std::min((size_t)nu * horizon, parameters.size());
+  std::fill(k.begin(), k.begin() + n, 0.0);
+  for (size_t i = 0; i < n; i++) parameters[i] = initial_repeated_action ? initial_repeated_action[i % nu] : 0.0;
+  std::fill(parameter_update.begin(), parameter_update.begin() + n, 0.0);
+  std::fill(times.begin(), times.begin() + std::min((size_t)horizon, times.size()), 0.0);
+}
+void GradientPolicy::Action(double* action, const double*, double time) const {
+  int bounds[2];
+  FindInterval(bounds, times, time, num_spline_points);
+  if (bounds[0] == bounds[1] || representation == kZeroSpline) ZeroInterpolation(action, time, times, parameters.data(), nu, num_spline_points);
+  else if (representation == kLinearSpline) LinearInterpolation(action, time, times, parameters.data(), nu, num_spline_points);
+  else if (representation == kCubicSpline) CubicInterpolation(action, time, times, parameters.data(), nu, num_spline_points);
+  for (int i = 0; i < nu; i++) action[i] = std::max(ctrlrange[2 * i], std::min(ctrlrange[2 * i + 1], action[i]));
+}
+void GradientPolicy::CopyFrom(const GradientPolicy& p, int horizon) {
+  std::copy(p.k.begin(), p.k.begin() + std::min((size_t)horizon * nu, p.k.size()), k.begin());
+  std::copy(p.parameters.begin(), p.parameters.begin() + p.num_parameters, parameters.begin());
+  std::copy(p.parameter_update.begin(), p.parameter_update.begin() + p.num_parameters, parameter_update.begin());
+  std::copy(p.times.begin(), p.times.begin() + p.num_spline_points, times.begin());
+  num_spline_points = p.num_spline_points; num_parameters = p.num_parameters; representation = p.representation;
+}
+void GradientPolicy::CopyParametersFrom(const std::vector<double>& src_parameters, const std::vector<double>& src_times) {
+  std::copy(src_parameters.begin(), src_parameters.begin() + (size_t)num_spline_points * nu, parameters.begin());
+  std::copy(src_times.begin(), src_times.begin() + num_spline_points, times.begin());
+}
+
+// ------------------------------------------------------------------ spline mappings (gradient/spline_mapping.cc)
+void SplineMapping::Allocate(int d) {
+  dim = d;
+  mapping.assign((size_t)(dim * kMaxTrajectoryHorizon) * (dim * kMaxGradientSplinePoints), 0.0);
+}
+void ZeroSplineMapping::Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) {
+  std::fill(mapping.begin(), mapping.begin() + (size_t)(dim * num_output) * (dim * num_input), 0.0);
+  int bounds[2];
+  for (int i = 0; i < num_output; i++) {
+    FindInterval(bounds, input_times, output_times[i], num_input);
+    for (int j = 0; j < dim; j++) mapping[(size_t)dim * num_input * (dim * i + j) + dim * bounds[0] + j] = 1.0;
+  }
+}
+void LinearSplineMapping::Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) {
+  std::fill(mapping.begin(), mapping.begin() + (size_t)(dim * num_output) * (dim * num_input), 0.0);
+  int bounds[2];
+  for (int i = 0; i < num_output; i++) {
+    FindInterval(bounds, input_times, output_times[i], num_input);
+    for (int j = 0; j < dim; j++) {
+      const size_t row = (size_t)dim * num_input * (dim * i + j);
+      if (bounds[0] == bounds[1]) { mapping[row + dim * bounds[0] + j] = 1.0; continue; }
+      double a = (output_times[i] - input_times[bounds[0]]) / (input_times[bounds[1]] - input_times[bounds[0]]);
+      mapping[row + dim * bounds[0] + j] = 1.0 - a;
+      mapping[row + dim * bounds[1] + j] = a;
+    }
+  }
+}
+void CubicSplineMapping::Allocate(int d) {
+  SplineMapping::Allocate(d);
+  point_slope_mapping.assign((size_t)(2 * dim * kMaxGradientSplinePoints) * (dim * kMaxGradientSplinePoints), 0.0);
+  output_mapping.assign((size_t)(dim * kMaxTrajectoryHorizon) * (2 * dim * kMaxGradientSplinePoints), 0.0);
+}
+void CubicSplineMapping::Compute(const std::vector<double>& input_times, int num_input, const double* output_times, int num_output) {
+  const size_t ni = (size_t)dim * num_input;
+  std::fill(point_slope_mapping.begin(), point_slope_mapping.begin() + 2 * ni * ni, 0.0);
+  for (size_t r = 0; r < ni; r++) point_slope_mapping[ni * r + r] = 1.0;                  // point-to-point
+  const size_t shift = ni * ni;                                                            // point-to-FiniteDifferenceSlope
+  for (int i = 0; i < num_input; i++) {
+    double dt1 = i > 0 ? 1.0 / (input_times[i] - input_times[i - 1]) : 0.0;
+    double dt2 = i < num_input - 1 ? 1.0 / (input_times[i + 1] - input_times[i]) : 0.0;
+    if (i > 0 && i < num_input - 1) { dt1 *= 0.5; dt2 *= 0.5; }
+    for (int j = 0; j < dim; j++) {
+      const size_t row = shift + ni * (dim * i + j);
+      if (i - 1 >= 0) point_slope_mapping[row + dim * (i - 1) + j] = -dt1;
+      point_slope_mapping[row + dim * i + j] = dt1 - dt2;
+      if (i + 1 <= num_input - 1) point_slope_mapping[row + dim * (i + 1) + j] = dt2;
+    }
+  }
+  const size_t no = (size_t)dim * num_output;
+  std::fill(output_mapping.begin(), output_mapping.begin() + no * 2 * ni, 0.0);
+  int bounds[2];
+  double c[4];
+  for (int i = 0; i < num_output; i++) {
+    FindInterval(bounds, input_times, output_times[i], num_input);
+    CubicCoefficients(c, output_times[i], input_times, num_input);
+    for (int j = 0; j < dim; j++) {
+      const size_t row = 2 * ni * (dim * i + j);
+      output_mapping[row + dim * bounds[0] + j] = c[0];
+      output_mapping[row + ni + dim * bounds[0] + j] = c[1];
+      if (bounds[0] != bounds[1]) {
+        output_mapping[row + dim * bounds[1] + j] = c[2];
+        output_mapping[row + ni + dim * bounds[1] + j] = c[3];
+      }
+    }
+  }
+  for (size_t r = 0; r < no; r++)                                                          // mapping = output_mapping * point_slope_mapping
+    for (size_t cc = 0; cc < ni; cc++) {
+      double acc = 0.0;
+      for (size_t q = 0; q < 2 * ni; q++) acc += output_mapping[r * 2 * ni + q] * point_slope_mapping[q * ni + cc];
+      mapping[r * ni + cc] = acc;
+    }
+}
+
+// ------------------------------------------------------------------ GradientPlanner (gradient/planner.cc:40-415)
+void GradientPlanner::Refuse(const char* msg) { Fatal(msg); }
+GradientPlanner::~GradientPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
+
+void GradientPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
+  numerics_ = numerics;
+  ns_ = model->nq + model->nv + model->na; nd_ = 2 * model->nv + model->na; nu_ = model->nu; nr_ = task->num_residual; ntrace_ = task->num_trace;
+  nmocap_ = model->nmocap; nuserdata_ = model->nuserdata; timestep_ = model->timestep;
+  num_trajectory = numerics.gradient_num_trajectory;
+  derivative_skip_ = numerics.derivative_skip;
+  if (numerics.gradient_spline_points > kMaxGradientSplinePoints || numerics.gradient_spline_points < 2) {
+    char msg[128]; std::snprintf(msg, sizeof(msg), "gradient_spline_points must be 2 .. %d (kMaxGradientSplinePoints).", kMaxGradientSplinePoints);
+    Fatal(msg);
+    return;
+  }
+  if (numerics.gradient_representation < kZeroSpline || numerics.gradient_representation > kCubicSpline) { Fatal("Unknown gradient_representation"); return; }
+  if (engine_) { mjpc_hip_destroy(engine_); engine_ = nullptr; }
+  engine_ = mjpc_hip_create(model, task, std::max(numerics.max_samples, std::max(num_trajectory, 1)), std::max(numerics.max_horizon, 2), numerics.device);
+  if (!engine_) { Fatal(mjpc_hip_last_error()); return; }
+  const int Hm = numerics.max_horizon;
+  for (GradientPolicy* p : {&policy, &previous_policy, &nominal_policy}) p->Allocate(model, numerics, std::max(Hm, kMaxGradientSplinePoints));
+  mappings[kZeroSpline].reset(new ZeroSplineMapping()); mappings[kLinearSpline].reset(new LinearSplineMapping()); mappings[kCubicSpline].reset(new CubicSplineMapping());
+}
+
+void GradientPlanner::Allocate() {
+  if (!engine_) return;
+  const size_t Hm = (size_t)numerics_.max_horizon;
+  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  for (Trajectory* tr : {&trajectory_nominal, &trajectory_winner}) {
+    tr->dim_state = ns_; tr->dim_action = nu_; tr->dim_residual = nr_; tr->dim_trace = 3 * ntrace_;
+    tr->states.assign(Hm * ns_, 0.0); tr->actions.assign(Hm * nu_, 0.0); tr->times.assign(Hm, 0.0); tr->residual.assign(Hm * nr_, 0.0);
+    tr->costs.assign(Hm, 0.0); tr->trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+  }
+  model_derivative.Allocate(nd_, nu_, nr_, (int)Hm, ns_);
+  cost_derivative.Allocate(nd_, nu_, nr_, (int)Hm);
+  gradient.Allocate(nd_, nu_, (int)Hm);
+  for (auto& m : mappings) m->Allocate(nu_);
+  parameters_scratch_.assign((size_t)nu_ * kMaxGradientSplinePoints, 0.0); times_scratch_.assign(kMaxGradientSplinePoints, 0.0);
+  winner = -1;
+}
+
+void GradientPlanner::Reset(int horizon, const double* initial_repeated_action) {
+  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0); std::fill(userdata.begin(), userdata.end(), 0.0);
+  time = 0.0;
+  const int h = horizon > 0 ? std::min(horizon, numerics_.max_horizon) : numerics_.max_horizon;
+  model_derivative.Reset(nd_, nu_, nr_, h); cost_derivative.Reset(nd_, nu_, nr_, h); gradient.Reset(nd_, nu_, h);
+  for (GradientPolicy* p : {&policy, &previous_policy, &nominal_policy}) p->Reset(std::max(h, kMaxGradientSplinePoints), initial_repeated_action);
+  action_step = 0.0; expected = 0.0; improvement = 0.0; surprise = 0.0;
+  winner = -1; failed = false;
+  derivative_skip_ = numerics_.derivative_skip;
+}
+
+void GradientPlanner::SetState(const double* s, const double* m, const double* u, double t) {
+  std::copy(s, s + ns_, state.begin());
+  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
+  if (u) std::copy(u, u + nuserdata_, userdata.begin());
+  time = t;
+}
+
+void GradientPlanner::SetTask(const MjpcHipTask* task) { if (mjpc_hip_set_task(engine_, task) != 0) Fatal(mjpc_hip_last_error()); }
+
+void GradientPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {
+  const std::shared_lock<std::shared_mutex> lock(mtx_);
+  (use_previous ? previous_policy : policy).Action(action, s, t);
+}
+
+void GradientPlanner::ResamplePolicy(int horizon) {   // planner.cc:330-358
+  GradientPolicy& cp = nominal_policy;
+  const int P = cp.num_spline_points;
+  double nominal_time = time;
+  const double time_shift = std::max((horizon - 1) * timestep_ / (P - 1), 1.0e-5);
+  for (int t = 0; t < P; t++) {
+    times_scratch_[t] = nominal_time;
+    cp.Action(parameters_scratch_.data() + (size_t)t * nu_, nullptr, nominal_time);
+    nominal_time += time_shift;
+  }
+  std::copy(parameters_scratch_.begin(), parameters_scratch_.begin() + (size_t)P * nu_, cp.parameters.begin());
+  const double t0 = times_scratch_[0];
+  for (int t = 0; t < P; t++) cp.times[t] = t0 + t * time_shift;                         // LinearRange
+}
+
+bool GradientPlanner::Rollout(const double* knots, int n, int horizon) {
+  returns.assign(n, 0.0); failures.assign(n, 0);
+  MjpcHipPlanInput in = MakePlanInput(state.data(), mocap.data(), userdata.data(), time, nominal_policy.times.data(), knots, nominal_policy.num_spline_points,
+                                      nominal_policy.representation, n, horizon);
+  in.candidate_knots = knots;
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.returns = returns.data(); out.failure = failures.data();
+  const int rc = mjpc_hip_plan(engine_, &in, &out);
+  if (rc != 0 && rc != -3) { Fatal(mjpc_hip_last_error()); return false; }               // -3: no finite return; returns[] are valid
+  return true;
+}
+
+// trajectory `index` of the last plan into tr
+static bool FetchCandidate(MjpcHipEngine* engine, int index, int horizon, double total_return, int failure, Trajectory& tr) {
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.states = tr.states.data(); out.actions = tr.actions.data(); out.times = tr.times.data();
+  out.residual = tr.residual.data(); out.costs = tr.costs.data(); out.trace = tr.trace.data();
+  if (mjpc_hip_get_candidate(engine, index, &out) != 0) { Fatal(mjpc_hip_last_error()); return false; }
+  tr.horizon = horizon; tr.total_return = total_return; tr.failure = failure != 0;
+  return true;
+}
+
+void GradientPlanner::NominalTrajectory(int horizon) {
+  if (!Rollout(nominal_policy.parameters.data(), 1, horizon)) return;
+  FetchCandidate(engine_, 0, horizon, returns[0], failures[0], trajectory_nominal);
+}
+
+void GradientPlanner::OptimizePolicy(int horizon) {
+  using clock = std::chrono::steady_clock;
+  auto us = [](clock::time_point t0) { return std::chrono::duration<double, std::micro>(clock::now() - t0).count(); };
+  if (!engine_) return;
+  if (horizon < 2 || horizon > numerics_.max_horizon) { Fatal("GradientPlanner: horizon out of range (2 .. max_horizon)"); return; }
+  nominal_compute_time = derivative_compute_time = gradient_compute_time = rollouts_compute_time = policy_update_compute_time = 0.0;
+  failed = false;
+  num_trajectory = std::max(1, std::min(num_trajectory, numerics_.max_samples));
+  const int N = num_trajectory, P = policy.num_spline_points, PN = P * nu_;
+
+  // ----- nominal rollout -----
+  auto t0 = clock::now();
+  policy.num_parameters = PN;
+  { const std::shared_lock<std::shared_mutex> lock(mtx_); nominal_policy.CopyFrom(policy, P); }
+  ResamplePolicy(horizon);
+  NominalTrajectory(horizon);
+  const double c_prev = trajectory_nominal.total_return;
+  nominal_compute_time = us(t0);
+
+  double c_best = c_prev;
+  cand_knots_.assign((size_t)N * PN, 0.0);
+  linesearch_steps.assign(N, 0.0);
+  std::vector<int> fail(horizon, 0);
+  for (int it = 0; it < settings.max_rollout; it++) {
+    // ----- derivatives and gradient of the nominal trajectory -----
+    t0 = clock::now();
+    const Trajectory& tr = trajectory_nominal;
+    bool ok;
+    if (derivative_skip_ <= 0) {
+      ok = mjpc_hip_trajectory_gradient(engine_, horizon, tr.states.data(), tr.actions.data(), tr.times.data(), tr.residual.data(), mocap.data(), userdata.data(),
+                                        settings.fd_tolerance, settings.fd_mode, nominal_policy.k.data(), gradient.Vx.data(), gradient.Qx.data(),
+                                        gradient.Qu.data(), gradient.dV, fail.data()) == 0;
+    } else {
+      ok = model_derivative.Compute(engine_, tr.states.data(), tr.actions.data(), tr.times.data(), horizon, settings.fd_tolerance, settings.fd_mode,
+                                    derivative_skip_, mocap.data(), userdata.data()) &&
+           cost_derivative.Compute(engine_, tr.residual.data(), model_derivative.C.data(), model_derivative.D.data(), nd_, nu_, nr_, horizon, false);
+      if (ok) {
+        std::copy(model_derivative.failure.begin(), model_derivative.failure.begin() + horizon, fail.begin());
+        ok = gradient.Compute(nominal_policy.k.data(), &model_derivative, &cost_derivative, nd_, nu_, horizon) == 0;
+      }
+    }
+    derivative_compute_time += us(t0);
+    if (!ok) { Fatal(mjpc_hip_last_error()); failed = true; return; }
+    for (int t = 0; t < horizon; t++) if (fail[t]) { failed = true; return; }             // like gd_status != 0: the policy stays as it was
+
+    // ----- total derivative: parameter_update = M' k -----
+    t0 = clock::now();
+    SplineMapping& map = *mappings[policy.representation];
+    map.Compute(nominal_policy.times, P, tr.times.data(), horizon - 1);
+    const int rows = nu_ * (horizon - 1);
+    for (int c = 0; c < PN; c++) {
+      double acc = 0.0;
+      for (int r = 0; r < rows; r++) acc += map.mapping[(size_t)r * PN + c] * nominal_policy.k[r];
+      nominal_policy.parameter_update[c] = acc;
+    }
+    gradient_compute_time += us(t0);
+
+    // ----- line search: one plan of N explicit candidates -----
+    t0 = clock::now();
+    if (N > 1) {     // LogScale as the reference spells it: exp(log(min) + i * step), no pinned first value
+      const double lo = std::log(settings.min_linesearch_step), step = (std::log(1.0) - lo) / std::max(N - 2, 1);
+      for (int i = 0; i < N - 1; i++) linesearch_steps[i] = std::exp(lo + i * step);
+    }
+    linesearch_steps[N - 1] = 0.0;
+    for (int i = 0; i < N; i++)
+      for (int c = 0; c < PN; c++) cand_knots_[(size_t)i * PN + c] = nominal_policy.parameters[c] + nominal_policy.parameter_update[c] * linesearch_steps[i];
+    if (!Rollout(cand_knots_.data(), N, horizon)) return;
+    winner = N - 1;
+    for (int j = N - 1; j >= 0; j--)
+      if (returns[j] < c_best) { c_best = returns[j]; winner = j; }
+    std::copy(cand_knots_.begin() + (size_t)winner * PN, cand_knots_.begin() + (size_t)(winner + 1) * PN, nominal_policy.parameters.begin());
+    if (!FetchCandidate(engine_, winner, horizon, returns[winner], failures[winner], trajectory_nominal)) return;
+    action_step = linesearch_steps[winner];
+    expected = -action_step * gradient.dV[0] - 1.0e-16;
+    improvement = c_prev - c_best;
+    surprise = std::min(std::max(0.0, improvement / expected), 2.0);
+    rollouts_compute_time += us(t0);
+  }
+
+  // ----- update the nominal policy -----
+  t0 = clock::now();
+  if (settings.max_rollout < 1) { winner = -1; return; }
+  if (c_best >= c_prev) winner = N - 1;
+  trajectory_winner = trajectory_nominal;               // (candidate N - 1 is the nominal itself: step 0)
+  {
+    const std::unique_lock<std::shared_mutex> lock(mtx_);
+    previous_policy.CopyFrom(policy, P);
+    policy.CopyParametersFrom(nominal_policy.parameters, nominal_policy.times);
+  }
+  policy_update_compute_time = us(t0);
+}
+
 }  // namespace mjpc_hip
 
 // ====================================================================== flat C wrapper (tests / ctypes)
@@ -1106,6 +1533,110 @@ void mjpc_sg_timings(void* p, double* noise, double* rollouts, double* update, d
 void mjpc_sg_return_weights(const int* order, int num_noisy, double* weights) { mjpc_hip::SampleGradientPlanner::ReturnWeights(order, num_noisy, weights); }
 void mjpc_sg_log_scale(double* values, double max_value, double min_value, int steps) { mjpc_hip::SampleGradientPlanner::LogScale(values, max_value, min_value, steps); }
 #undef SGP
+
+// ---- CostDerivatives, Gradient
+void* mjpc_cd_create(int nd, int nu, int nr, int T) { auto* d = new mjpc_hip::CostDerivatives(); d->Allocate(nd, nu, nr, T); d->Reset(nd, nu, nr, T); return d; }
+void mjpc_cd_destroy(void* cd) { delete (mjpc_hip::CostDerivatives*)cd; }
+void mjpc_cd_reset(void* cd, int T) { auto* d = (mjpc_hip::CostDerivatives*)cd; d->Reset(d->dim_state_derivative, d->dim_action, d->dim_residual, T); }
+int mjpc_cd_compute(void* cd, MjpcHipEngine* engine, const double* r, const double* rx, const double* ru, int T, int hessians) {
+  auto* d = (mjpc_hip::CostDerivatives*)cd;
+  return d->Compute(engine, r, rx, ru, d->dim_state_derivative, d->dim_action, d->dim_residual, T, hessians != 0) ? 0 : -1;
+}
+void mjpc_cd_blocks(void* cd, int T, double* cr, double* cx, double* cu, double* cxx, double* cuu, double* cxu) {
+  auto* d = (mjpc_hip::CostDerivatives*)cd;
+  const size_t nd = d->dim_state_derivative, nu = d->dim_action, nr = d->dim_residual, Tz = (size_t)T;
+  if (T > d->horizon) return;
+  if (cr) std::copy(d->cr.begin(), d->cr.begin() + Tz * nr, cr);
+  if (cx) std::copy(d->cx.begin(), d->cx.begin() + Tz * nd, cx);
+  if (cu) std::copy(d->cu.begin(), d->cu.begin() + Tz * nu, cu);
+  if (cxx) std::copy(d->cxx.begin(), d->cxx.begin() + Tz * nd * nd, cxx);
+  if (cuu) std::copy(d->cuu.begin(), d->cuu.begin() + Tz * nu * nu, cuu);
+  if (cxu) std::copy(d->cxu.begin(), d->cxu.begin() + Tz * nd * nu, cxu);
+}
+int mjpc_gd_gradient_compute(int nd, int nu, int T, const double* A, const double* B, const double* cx, const double* cu, double* k, double* Vx,
+                             double* Qx, double* Qu, double* dV) {
+  mjpc_hip::Gradient g;
+  if (T < 2) { g.Compute(nullptr, A, B, cx, cu, nd, nu, T); return -1; }
+  std::vector<double> kk((size_t)T * nu + 1);
+  const int rc = g.Compute(kk.data(), A, B, cx, cu, nd, nu, T);
+  const size_t Tz = (size_t)T;
+  if (k) std::copy(kk.begin(), kk.begin() + Tz * nu, k);
+  if (Vx) std::copy(g.Vx.begin(), g.Vx.begin() + Tz * nd, Vx);
+  if (Qx) std::copy(g.Qx.begin(), g.Qx.begin() + (Tz - 1) * nd, Qx);
+  if (Qu) std::copy(g.Qu.begin(), g.Qu.begin() + (Tz - 1) * nu, Qu);
+  if (dV) { dV[0] = g.dV[0]; dV[1] = g.dV[1]; }
+  return rc;
+}
+
+// ---- GradientPlanner
+#define GDP(p) ((mjpc_hip::GradientPlanner*)(p))
+void* mjpc_gd_create(const MjpcHipModel* model, const MjpcHipTask* task, int num_trajectory, int spline_points, int representation, int derivative_skip,
+                     int max_rollout, double min_linesearch_step, double fd_tolerance, int fd_mode, int max_samples, int max_horizon, int device) {
+  auto* p = new mjpc_hip::GradientPlanner();
+  mjpc_hip::Numerics n;
+  n.gradient_num_trajectory = num_trajectory; n.gradient_spline_points = spline_points; n.gradient_representation = representation;
+  n.derivative_skip = derivative_skip; n.max_samples = max_samples; n.max_horizon = max_horizon; n.device = device;
+  p->settings.max_rollout = max_rollout; p->settings.min_linesearch_step = min_linesearch_step; p->settings.fd_tolerance = fd_tolerance; p->settings.fd_mode = fd_mode;
+  p->Initialize(model, task, n);
+  p->Allocate();
+  return p;
+}
+void mjpc_gd_destroy(void* p) { delete GDP(p); }
+void mjpc_gd_reset(void* p, int horizon, const double* a) { GDP(p)->Reset(horizon, a); }
+void mjpc_gd_set_state(void* p, const double* s, const double* m, const double* u, double t) { GDP(p)->SetState(s, m, u, t); }
+void mjpc_gd_set_task(void* p, const MjpcHipTask* task) { GDP(p)->SetTask(task); }
+void mjpc_gd_set_num_trajectory(void* p, int n) { GDP(p)->num_trajectory = n; }
+void mjpc_gd_optimize_policy(void* p, int horizon) { GDP(p)->OptimizePolicy(horizon); }
+void mjpc_gd_nominal_trajectory(void* p, int horizon) { GDP(p)->NominalTrajectory(horizon); }
+void mjpc_gd_action_from_policy(void* p, double* a, double t, int prev) { GDP(p)->ActionFromPolicy(a, nullptr, t, prev != 0); }
+double mjpc_gd_improvement(void* p) { return GDP(p)->improvement; }
+int mjpc_gd_policy(void* p, double* times, double* values) {
+  const mjpc_hip::GradientPolicy& pol = GDP(p)->policy;
+  if (times) std::copy(pol.times.begin(), pol.times.begin() + pol.num_spline_points, times);
+  if (values) std::copy(pol.parameters.begin(), pol.parameters.begin() + (size_t)pol.num_spline_points * pol.nu, values);
+  return pol.num_spline_points;
+}
+void mjpc_gd_set_policy(void* p, const double* times, const double* values) {
+  mjpc_hip::GradientPolicy& pol = GDP(p)->policy;
+  std::copy(times, times + pol.num_spline_points, pol.times.begin());
+  std::copy(values, values + (size_t)pol.num_spline_points * pol.nu, pol.parameters.begin());
+}
+int mjpc_gd_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
+  return CopyTrajectory(GDP(p)->BestTrajectory(), states, actions, nullptr, nullptr, costs, nullptr, total_return, nullptr);
+}
+void mjpc_gd_values(void* p, double* out) {
+  auto* g = GDP(p);
+  out[0] = g->action_step; out[1] = g->expected; out[2] = g->improvement; out[3] = g->surprise; out[4] = g->winner; out[5] = g->failed ? 1 : 0;
+}
+void mjpc_gd_timings(void* p, double* out) {
+  auto* g = GDP(p);
+  out[0] = g->nominal_compute_time; out[1] = g->derivative_compute_time; out[2] = g->gradient_compute_time; out[3] = g->rollouts_compute_time;
+  out[4] = g->policy_update_compute_time;
+}
+void mjpc_gd_returns(void* p, double* out, int n) { std::copy(GDP(p)->returns.begin(), GDP(p)->returns.begin() + std::min(n, (int)GDP(p)->returns.size()), out); }
+int mjpc_gd_linesearch_steps(void* p, double* out) { auto& w = GDP(p)->linesearch_steps; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
+int mjpc_gd_parameter_update(void* p, double* out) {
+  auto& pol = GDP(p)->nominal_policy; const int n = pol.num_spline_points * pol.nu;
+  if (out) std::copy(pol.parameter_update.begin(), pol.parameter_update.begin() + n, out);
+  return n;
+}
+void mjpc_gd_spline_mapping(int representation, int dim, const double* input_times, int num_input, const double* output_times, int num_output, double* mapping) {
+  if (num_input > mjpc_hip::kMaxGradientSplinePoints || num_output > mjpc_hip::kMaxTrajectoryHorizon || representation < 0 || representation > 2) {
+    mjpc_hip::GradientPlanner::Refuse("mjpc_gd_spline_mapping: representation 0..2, at most 25 inputs and kMaxTrajectoryHorizon outputs"); return; }
+  std::unique_ptr<mjpc_hip::SplineMapping> m;
+  if (representation == 0) m.reset(new mjpc_hip::ZeroSplineMapping()); else if (representation == 1) m.reset(new mjpc_hip::LinearSplineMapping());
+  else m.reset(new mjpc_hip::CubicSplineMapping());
+  m->Allocate(dim);
+  m->Compute(std::vector<double>(input_times, input_times + num_input), num_input, output_times, num_output);
+  std::copy(m->mapping.begin(), m->mapping.begin() + (size_t)(dim * num_output) * (dim * num_input), mapping);
+}
+void mjpc_gd_policy_action(int representation, int nu, const double* ctrlrange, const double* times, const double* parameters, int num_spline_points, double time,
+                           double* action) {
+  mjpc_hip::GradientPolicy pol;
+  pol.nu = nu; pol.ctrlrange.assign(ctrlrange, ctrlrange + 2 * nu); pol.representation = representation; pol.num_spline_points = num_spline_points;
+  pol.times.assign(times, times + num_spline_points); pol.parameters.assign(parameters, parameters + (size_t)num_spline_points * nu);
+  pol.Action(action, nullptr, time);
+}
 
 // ---- ModelDerivatives
 void* mjpc_md_create(int dim_state, int nd, int nu, int nr, int T) { auto* d = new mjpc_hip::ModelDerivatives(); d->Allocate(nd, nu, nr, T, dim_state); d->Reset(nd, nu, nr, T); return d; }

@@ -473,7 +473,7 @@ TestspeedResult SynchronousPlanningCost(const MjpcHipModel& model, HostTask& tas
 // ====================================================================== flat C view (ctypes tests / Python front end)
 extern "C" {
 // planner_kind: 0 = SamplingPlanner handle (mjpc_planner_create), 1 = CrossEntropyPlanner handle (mjpc_cem_create),
-// 2 = SampleGradientPlanner handle (mjpc_sg_create).
+// 2 = SampleGradientPlanner handle (mjpc_sg_create), 3 = GradientPlanner handle (mjpc_gd_create).
 // state/mocap are in-out (final simulator state); cost_per_step[total_steps] optional.  Returns the total cost
 // (testspeed.cc:128) and fills out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds, plan_steps, failure}.
 double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, void* planner, int planner_kind, double* state, double* mocap,
@@ -488,7 +488,8 @@ double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, vo
   if (mocap) std::copy(mocap, mocap + 7 * model->nmocap, s.mocap.begin());
   s.userdata.assign((size_t)std::max(model->nuserdata, 1), 0.0);
   s.time = time0;
-  PlannerOps ops = planner_kind == 0 ? Ops(*(SamplingPlanner*)planner) : planner_kind == 2 ? Ops(*(SampleGradientPlanner*)planner) : Ops(*(CrossEntropyPlanner*)planner);
+  PlannerOps ops = planner_kind == 0 ? Ops(*(SamplingPlanner*)planner) : planner_kind == 2 ? Ops(*(SampleGradientPlanner*)planner)
+                   : planner_kind == 3 ? Ops(*(GradientPlanner*)planner) : Ops(*(CrossEntropyPlanner*)planner);
   TestspeedResult r = SynchronousPlanningCost(*model, ht, ops, sim, s, horizon, steps_per_planning_iteration, total_time,
                                               TransitionForTask(task->task_id, mode, mode_time));
   if (task_parameters_io) std::copy(ht.parameters.begin(), ht.parameters.end(), task_parameters_io);   // what Transition left behind

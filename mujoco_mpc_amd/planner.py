@@ -173,6 +173,45 @@ class HipBackend:
             raise RuntimeError("mjpc_hip_transition_fd failed: " + self.lib.mjpc_hip_last_error().decode())
         return o
 
+    def cost_derivatives(self, residual, C_, D, last_is_terminal=False, hessians=True, fill=0.0):
+        """Cost derivatives of T knots from the residual [T, nr] and its Jacobian C [T, nr, nd], D [T, nr, nu] under the engine's current
+        cost table and risk (mjpc_hip_cost_derivatives): dict(cr [T, nr], cx [T, nd], cu [T, nu], and with hessians cxx [T, nd, nd],
+        cuu [T, nu, nu], cxu [T, nd, nu]).  With last_is_terminal the last knot's D is not read.  `fill`: what an entry the call does
+        not write would keep."""
+        _, nd, nu, nr = self._dims()
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1, nr) if nr else np.zeros((len(C_), 0)); T = r.shape[0]
+        Cm = np.ascontiguousarray(C_, dtype=np.float64).reshape(T, nr, nd); Dm = np.ascontiguousarray(D, dtype=np.float64).reshape(T, nr, nu)
+        o = dict(cr=np.full((T, nr), float(fill)), cx=np.full((T, nd), float(fill)), cu=np.full((T, nu), float(fill)))
+        if hessians:
+            o.update(cxx=np.full((T, nd, nd), float(fill)), cuu=np.full((T, nu, nu), float(fill)), cxu=np.full((T, nd, nu), float(fill)))
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        outs = [ptr(o[k]) if k in o else None for k in ("cr", "cx", "cu", "cxx", "cuu", "cxu")]
+        rc = self.lib.mjpc_hip_cost_derivatives(self.h, T, ptr(r), ptr(Cm), ptr(Dm), int(bool(last_is_terminal)), int(bool(hessians)), *outs)
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_cost_derivatives failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
+    def trajectory_gradient(self, x, u, time, residual, mocap=None, userdata=None, eps=1e-6, centered=False):
+        """One derivative iteration of the gradient planner on the device (mjpc_hip_trajectory_gradient): transition_fd with the last knot
+        terminal, cost gradients, backward recursion -> dict(k [T, nu], Vx [T, nd], Qx [T-1, nd], Qu [T-1, nu], dV [2], failure [T])."""
+        ds, nd, nu, nr = self._dims()
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(T)
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(T, nr)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(k=np.zeros((T, nu)), Vx=np.zeros((T, nd)), Qx=np.zeros((max(T - 1, 0), nd)), Qu=np.zeros((max(T - 1, 0), nu)), dV=np.zeros(2),
+                 failure=np.zeros(max(T, 1), np.int32))
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_trajectory_gradient(self.h, T, x.ctypes.data_as(dp), ptr(u), t.ctypes.data_as(dp), ptr(r), pmo, pud, float(eps),
+                                                   int(bool(centered)), ptr(o["k"]), ptr(o["Vx"]), ptr(o["Qx"]), ptr(o["Qu"]), ptr(o["dV"]),
+                                                   o["failure"].ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_trajectory_gradient failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["failure"] = o["failure"][:T]
+        return o
+
     def candidate(self, local_index, H, P):
         o, c, ntr = self._alloc_out(1, H, P)
         if self.lib.mjpc_hip_get_candidate(self.h, int(local_index), C.byref(c)) != 0:

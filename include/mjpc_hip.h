@@ -480,6 +480,49 @@ int mjpc_hip_cost_derivatives(MjpcHipEngine *e, int T, const double *residual, c
 int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual,
                                  const double *mocap, const double *userdata, double eps, int centered, double *k, double *Vx, double *Qx,
                                  double *Qu, double *dV, int *failure);
+/* ---- The iLQG backward pass ---------------------------------------------------------------------------------------------------
+ * mjpc/planners/ilqg/backward_pass.cc with its box-constrained control solve and the regularisation loop of ilqg/planner.cc:429-520,
+ * in one kernel (csrc/riccati.h).  Host pointers, row-major: A [T-1][nd][nd], B [T-1][nd][nu] (or more blocks), cx [T][nd],
+ * cxx [T][nd][nd] (index T-1 is the terminal knot), cu [T-1][nu], cxu [T-1][nd][nu], cuu [T-1][nu][nu] (or T blocks: the last is not
+ * read), actions [T-1][nu] and action_limits [nu][2] (read when settings->action_limits == 1; an unlimited control has -inf, +inf).
+ * A sweep runs t = T-2 .. 0 from Vx[T-1] = cx[T-1], Vxx[T-1] = cxx[T-1]; with W = Vxx[t+1], mu = *regularization:
+ *   Qx = A'Vx[t+1] + cx,  Qu = B'Vx[t+1] + cu,  Qxx = (A'W)A + cxx,  Qxu = (A'W)B + cxu,  Quu = (B'W)B + cuu
+ *   Quu_reg by regularization_type: 0 Quu + mu I; 1 Quu + mu B'B (both only when mu != 0); 2 (B'(W + mu I))B + cuu; other: Quu
+ *   action_limits == 1: k = argmin 0.5 k'Quu_reg k + Qu'k over action_limits - actions[t] (projected Newton, warm-started from the
+ *     previous knot's k, zero at the start of a call); K = -H_free^-1 Qxu_free' on the free controls, zero rows on the clamped ones
+ *   else: K = -Quu_reg^-1 Qxu', k = -Quu_reg^-1 Qu by Cholesky; a pivot <= 0 fails the step   (Qxu is NOT regularised: the reference's)
+ *   dV[0] += k.Qu,  dV[1] += 0.5 k'Quu k,  Vx[t] = Qx + K'(Quu k + Qu) + Qxu k,  Vxx[t] = sym(Qxx + K'QuuK + QxuK + K'Qxu')
+ * A failed step ends the sweep: rate = max(rate * factor, factor), regularization = clamp(regularization * rate, min, max) (factor <= 1:
+ * min in place of max for the rate), and the next sweep starts over with dV = 0, at most max_regularization_iterations times; a
+ * regularisation above the maximum ends the call.  A complete sweep copies k[T-2], K[T-2] to index T-1.  status[3] = {1 complete / 0
+ * failed, the failing time index (-1 when complete), regularisation increases}; a failed pass is not an error of the call: the outputs
+ * hold what the sweeps stored (rows never reached are zero).  regularization / regularization_rate are in/out.
+ * K [T][nu][nd], k [T][nu], Vx [T][nd], Vxx [T][nd][nd], Qx, Qu, Qxx, Qxu, Quu [T-1][..], dV [2]; any output may be NULL.  Summation
+ * rule as for mjpc_hip_cost_derivatives, `/` and sqrt correctly rounded: mjpc_hip::iLQGBackwardPass on the host gives the same bits.
+ * The engine lends its device and stream only (nd, nu are the caller's).  Blocking.  Errors: a plan in flight, T < 2, nd < 1, nu < 1,
+ * null inputs, settings->struct_size.
+ *
+ * mjpc_hip_trajectory_ilqg: mjpc_hip_transition_fd (last_is_terminal = 1), the cost derivatives with Hessians where the matrices
+ * lie, and the backward pass, with one download.  nd, nu and action_limits are the model's (an unlimited actuator gets -inf, +inf),
+ * actions = the u rows.  Inputs and errors as for mjpc_hip_trajectory_gradient, plus a model without actuators. */
+typedef struct MjpcHipRiccatiSettings {
+  int struct_size;                        /* sizeof(MjpcHipRiccatiSettings) */
+  int regularization_type;                /* 0 control, 1 state-control, 2 value, other: none */
+  int action_limits;                      /* 1: box-QP over the action limits */
+  int max_regularization_iterations;
+  double min_regularization, max_regularization, regularization_factor;
+} MjpcHipRiccatiSettings;
+int mjpc_hip_ilqg_backward_pass(MjpcHipEngine *e, int T, int nd, int nu, const double *A, const double *B, const double *cx, const double *cu,
+                                const double *cxx, const double *cxu, const double *cuu, const double *actions, const double *action_limits,
+                                const MjpcHipRiccatiSettings *s, double *regularization, double *regularization_rate, double *k, double *K,
+                                double *Vx, double *Vxx, double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status);
+int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual,
+                             const double *mocap, const double *userdata, double eps, int centered, const MjpcHipRiccatiSettings *s,
+                             double *regularization, double *regularization_rate, double *k, double *K, double *Vx, double *Vxx, double *Qx,
+                             double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status, int *failure);
+/* Bytes of the backward-pass kernel's work image at (nd, nu), and where it lies: *in_lds = 1 in the workgroup's LDS (up to 160 KiB),
+ * 0 in a global-memory scratch of the same layout.  Host only, no GPU needed. */
+int mjpc_hip_riccati_layout_bytes(int nd, int nu, int *in_lds);
 /* Bytes of LDS one candidate's workgroup occupies (its whole mjData-equivalent). */
 int mjpc_hip_lds_bytes(MjpcHipEngine *e);
 /* Capacity tiers: when a shard holds more candidates than the GPU has CUs and the model allows it, the engine first runs a

@@ -523,5 +523,98 @@ class GradientPlanner {
   mutable std::shared_mutex mtx_;
 };
 
+// ---- the iLQG backward pass (mjpc/planners/ilqg/): boxqp.h, settings.h, policy.{h,cc}, backward_pass.{h,cc}.  The planner around it
+// (feedback rollouts, line search) is not built; these are the reference's public components, which its iLQS drives as well.
+// ilqg/boxqp.h: storage of the box-constrained control solve
+class BoxQP {
+ public:
+  void Allocate(int n);
+  std::vector<double> res, R, H, g, lower, upper;      // [n], [n][n], [n][n], [n], [n], [n]; res is the warm start and the solution
+  std::vector<int> index;                              // [n] the free dimensions, ascending
+};
+// mju_boxQP's signature; MuJoCo is not part of this project: the method is defined in csrc/riccati.h (projected Newton; at most 100
+// iterations, backtrack 0.5, Armijo 0.1, minimum step 1e-22, squared free gradient below 1e-16 stops) and restated here bit for bit.
+// Returns the number of free dimensions (index lists them, R [nfree][nfree] row-major is the lower Cholesky factor of H_free), or -1
+// when H_free is not positive definite.  lower / upper may be nullptr (unbounded).
+int BoxQPSolve(double* res, double* R, int* index, const double* H, const double* g, int n, const double* lower, const double* upper);
+
+struct iLQGSettings {                     // ilqg/settings.h
+  double min_linesearch_step = 1.0e-3;
+  double fd_tolerance = 1.0e-6;
+  double fd_mode = 0;
+  double min_regularization = 1.0e-6;
+  double max_regularization = 1.0e6;
+  int regularization_type = 0;           // 0: control; 1: feedback; 2: value; 3: none
+  int max_regularization_iterations = 5;
+  int action_limits = 1;
+  int nominal_feedback_scaling = 1;
+  int verbose = 0;
+};
+enum iLQGRegularizationType : int { kControlRegularization = 0, kStateControlRegularization, kValueRegularization, kNoRegularization };
+
+// ilqg/policy.{h,cc}: time-varying affine feedback around a nominal trajectory
+class iLQGPolicy {
+ public:
+  void Allocate(const MjpcHipModel* model, int num_residual, int num_trace, int horizon, int representation = kLinearSpline);
+  // the same from the tables Action reads: dimensions, joint types / addresses (StateDiff), ctrlrange [nu][2]
+  void Allocate(int nq, int nv, int na, int nu, int njnt, const int* jnt_type, const int* jnt_qposadr, const int* jnt_dofadr, const double* ctrlrange,
+                int num_residual, int num_trace, int horizon, int representation = kLinearSpline);
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  // policy.cc:82-161: the interpolated nominal action, plus feedback_scaling * K (state (-) nominal state) when state != nullptr,
+  // clamped to the ctrlrange.  The state difference is StateDiff (utilities.cc:525-535): for a ball or free joint's quaternion the
+  // body-frame rotation vector of qa^-1 qb, the tangent of mjpc_hip_transition_fd.
+  void Action(double* action, const double* state, double time) const;
+  void CopyFrom(const iLQGPolicy& policy, int horizon);
+
+  Trajectory trajectory;
+  std::vector<double> feedback_gain;          // [horizon][nu][nd]
+  std::vector<double> action_improvement;     // [horizon][nu]
+  double feedback_scaling = 1.0;
+  int representation = kLinearSpline;
+  int nq = 0, nv = 0, na = 0, nu = 0;
+  std::vector<double> ctrlrange;
+  std::vector<int> jnt_type, jnt_qposadr, jnt_dofadr;
+
+ private:
+  mutable std::vector<double> state_scratch, action_scratch, feedback_gain_scratch, state_interp;
+};
+// utilities.cc:525-535 over the joint tables above: ds [2nv+na] = (s2 (-) s1) / h
+void StateDiff(const iLQGPolicy& dims, double* ds, const double* s1, const double* s2, double h);
+
+// ilqg/backward_pass.{h,cc}.  RiccatiStep and Riccati run on the host by the summation rule of csrc/riccati.h, bit-equal to the device's
+// mjpc_hip_ilqg_backward_pass; Compute / ComputeFused run the device.
+class iLQGBackwardPass {
+ public:
+  void Allocate(int dim_dstate, int dim_action, int T);
+  void Reset(int dim_dstate, int dim_action, int T);
+  // backward_pass.cc:65-250.  1 = ok, 0 = the control solve failed
+  int RiccatiStep(int n, int m, double mu, const double* Wx, const double* Wxx, const double* At, const double* Bt, const double* cxt,
+                  const double* cut, const double* cxxt, const double* cxut, const double* cuut, double* Vxt, double* Vxxt, double* dut,
+                  double* Kt, double* dV, double* Qxt, double* Qut, double* Qxxt, double* Qxut, double* Quut, double* scratch, BoxQP& boxqp,
+                  const double* action, const double* action_limits, int reg_type, int limits);
+  // backward_pass.cc:253-324: 0 = complete, else the failing time index.  As in the reference, every retry is handed `reg`, not the
+  // scaled member, and the box-QP's warm start is whatever boxqp.res holds.
+  int Riccati(iLQGPolicy* p, const ModelDerivatives* md, const CostDerivatives* cd, int dim_dstate, int dim_action, int T, double reg,
+              BoxQP& boxqp, const double* actions, const double* action_limits, const iLQGSettings& settings);
+  // the regularisation loop of ilqg/planner.cc:429-520 on the host over plain arrays (the layout of mjpc_hip_ilqg_backward_pass), with
+  // this object's regularization / regularization_rate: what the device kernel restates.  boxqp.res is zeroed first.  status [3].
+  void RiccatiRegularized(double* k, double* K, const double* A, const double* B, const double* cx, const double* cu, const double* cxx,
+                          const double* cxu, const double* cuu, int dim_dstate, int dim_action, int T, BoxQP& boxqp, const double* actions,
+                          const double* action_limits, const iLQGSettings& settings, int* status);
+  // the same on the device, into policy->action_improvement / feedback_gain and this object's blocks.  false after an engine error.
+  bool Compute(MjpcHipEngine* engine, iLQGPolicy* policy, const ModelDerivatives* md, const CostDerivatives* cd, int dim_dstate, int dim_action,
+               int T, const double* actions, const double* action_limits, const iLQGSettings& settings, int* status);
+  // mjpc_hip_trajectory_ilqg: derivatives and backward pass in one call (x, u, h as for ModelDerivatives::Compute; residual [T][nr])
+  bool ComputeFused(MjpcHipEngine* engine, iLQGPolicy* policy, const double* x, const double* u, const double* h, const double* residual,
+                    int dim_dstate, int dim_action, int T, const iLQGSettings& settings, int* status, int* failure,
+                    const double* mocap = nullptr, const double* userdata = nullptr);
+  void ScaleRegularization(double factor, double reg_min, double reg_max);
+  void UpdateRegularization(double reg_min, double reg_max, double z, double s);
+
+  std::vector<double> Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, Q_scratch;
+  double dV[2] = {0.0, 0.0};
+  double regularization = 1.0, regularization_rate = 1.0, regularization_factor = 2.0;
+};
+
 }  // namespace mjpc_hip
 #endif  // MJPC_HIP_PLANNER_H_

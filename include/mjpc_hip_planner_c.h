@@ -180,6 +180,45 @@ void mjpc_gd_spline_mapping(int representation, int dim, const double *input_tim
 void mjpc_gd_policy_action(int representation, int nu, const double *ctrlrange, const double *times, const double *parameters, int num_spline_points,
                            double time, double *action);
 
+/* iLQGBackwardPass, BoxQP, iLQGPolicy (mjpc/planners/ilqg/): create = Allocate + Reset, with a BoxQP and the k / K rows of a policy inside.
+ * Arrays as for mjpc_hip_ilqg_backward_pass (include/mjpc_hip.h): A [T-1][nd][nd], B [T-1][nd][nu], cx [T][nd], cu [T][nu], cxx [T][nd][nd],
+ * cxu [T][nd][nu], cuu [T][nu][nu], actions [T-1][nu], action_limits [nu][2] (the two may be NULL without limits).  settings_i[3] =
+ * {regularization_type, action_limits, max_regularization_iterations}, settings_d[2] = {min_regularization, max_regularization}; the
+ * factor is the object's (2 after a reset).  k [T][nu], K [T][nu][nd] start as zeros; status[3] as the engine's.
+ *   riccati_host     iLQGBackwardPass::RiccatiRegularized: the regularisation loop on the host (no GPU), bit-equal to the device
+ *   riccati          iLQGBackwardPass::Riccati, the reference's signature: every sweep is handed `reg`; returns its status (0 = complete)
+ *   compute          mjpc_hip_ilqg_backward_pass through iLQGBackwardPass::Compute; 0 = ok, -1 = engine error (mjpc_hip_last_error)
+ *   compute_fused    mjpc_hip_trajectory_ilqg through ComputeFused: x [T][nq+nv+na], u [T][nu], h [T], residual [T][nr]; failure [T] */
+void *mjpc_ilqg_bp_create(int dim_state_derivative, int dim_action, int T);
+void mjpc_ilqg_bp_destroy(void *bp);
+void mjpc_ilqg_bp_reset(void *bp, int T);
+void mjpc_ilqg_bp_riccati_host(void *bp, int T, const double *A, const double *B, const double *cx, const double *cu, const double *cxx, const double *cxu,
+                               const double *cuu, const double *actions, const double *action_limits, const int *settings_i, const double *settings_d,
+                               double *k, double *K, int *status);
+int mjpc_ilqg_bp_riccati(void *bp, int T, double reg, const double *A, const double *B, const double *cx, const double *cu, const double *cxx,
+                         const double *cxu, const double *cuu, const double *actions, const double *action_limits, const int *settings_i,
+                         const double *settings_d, double *k, double *K);
+int mjpc_ilqg_bp_compute(void *bp, MjpcHipEngine *engine, int T, const double *A, const double *B, const double *cx, const double *cu, const double *cxx,
+                         const double *cxu, const double *cuu, const double *actions, const double *action_limits, const int *settings_i,
+                         const double *settings_d, double *k, double *K, int *status);
+int mjpc_ilqg_bp_compute_fused(void *bp, MjpcHipEngine *engine, int T, const double *x, const double *u, const double *h, const double *residual,
+                               const double *mocap, const double *userdata, double fd_tolerance, int fd_mode, const int *settings_i,
+                               const double *settings_d, double *k, double *K, int *status, int *failure);
+/* the first T rows out of the object (Q blocks: T - 1); any pointer may be NULL */
+void mjpc_ilqg_bp_blocks(void *bp, int T, double *Vx, double *Vxx, double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV);
+/* {regularization, regularization_rate, regularization_factor}: set from `set` when not NULL, then read into `out` when not NULL */
+void mjpc_ilqg_bp_regularization(void *bp, const double *set, double *out);
+void mjpc_ilqg_bp_scale_regularization(void *bp, double factor, double reg_min, double reg_max);
+void mjpc_ilqg_bp_update_regularization(void *bp, double reg_min, double reg_max, double z, double s);
+/* BoxQPSolve (host, no GPU): res [n] warm start in, solution out; R [n][n] (its first nfree^2 entries: the factor of H_free), index [n];
+ * lower / upper may be NULL.  Returns the number of free dimensions or -1. */
+int mjpc_ilqg_boxqp(int n, const double *H, const double *g, const double *lower, const double *upper, double *res, double *R, int *index);
+/* iLQGPolicy::Action (host, no GPU) of a policy given by its rows: times [horizon], states [horizon][nq+nv+na], actions [horizon][nu],
+ * feedback_gain [horizon][nu][2nv+na]; the model's joint tables [njnt] and ctrlrange [nu][2]; state may be NULL (open loop) */
+void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int *jnt_type, const int *jnt_qposadr, const int *jnt_dofadr,
+                             const double *ctrlrange, int representation, int horizon, const double *times, const double *states, const double *actions,
+                             const double *feedback_gain, double feedback_scaling, const double *state, double time, double *action);
+
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
  * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create.  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,

@@ -232,6 +232,22 @@ def make_plan_input(cm: CModel, state, mocap, time, knot_times, knot_values, int
     return inp
 
 
+class MjpcHipRiccatiSettings(C.Structure):
+    """include/mjpc_hip.h: the iLQG backward pass's settings (ilqg/settings.h, plus the regularisation factor)"""
+    _fields_ = [("struct_size", C.c_int), ("regularization_type", C.c_int), ("action_limits", C.c_int), ("max_regularization_iterations", C.c_int),
+                ("min_regularization", C.c_double), ("max_regularization", C.c_double), ("regularization_factor", C.c_double)]
+
+
+def riccati_settings(regularization_type=0, action_limits_on=1, max_regularization_iterations=5, min_regularization=1.0e-6, max_regularization=1.0e6,
+                     regularization_factor=2.0):
+    s = MjpcHipRiccatiSettings()
+    s.struct_size = C.sizeof(MjpcHipRiccatiSettings)
+    s.regularization_type = int(regularization_type); s.action_limits = int(action_limits_on)
+    s.max_regularization_iterations = int(max_regularization_iterations)
+    s.min_regularization = float(min_regularization); s.max_regularization = float(max_regularization); s.regularization_factor = float(regularization_factor)
+    return s
+
+
 _engine = None
 
 
@@ -260,6 +276,10 @@ def load_engine():
     lib.mjpc_hip_transition_fd.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [C.c_double, C.c_int, C.c_int] + [c_double_p] * 4 + [c_int_p]
     lib.mjpc_hip_cost_derivatives.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 3 + [C.c_int, C.c_int] + [c_double_p] * 6
     lib.mjpc_hip_trajectory_gradient.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 6 + [C.c_double, C.c_int] + [c_double_p] * 5 + [c_int_p]
+    lib.mjpc_hip_ilqg_backward_pass.argtypes = [C.c_void_p] + [C.c_int] * 3 + [c_double_p] * 9 + [C.POINTER(MjpcHipRiccatiSettings)] + [c_double_p] * 12 + [c_int_p]
+    lib.mjpc_hip_trajectory_ilqg.argtypes = ([C.c_void_p, C.c_int] + [c_double_p] * 6 + [C.c_double, C.c_int, C.POINTER(MjpcHipRiccatiSettings)]
+                                             + [c_double_p] * 12 + [c_int_p, c_int_p])
+    lib.mjpc_hip_riccati_layout_bytes.argtypes = [C.c_int, C.c_int, c_int_p]
     lib.mjpc_hip_get_knots.argtypes = [C.c_void_p, c_double_p]
     lib.mjpc_hip_get_frame.argtypes = [C.c_void_p] + [c_double_p] * 5
     lib.mjpc_hip_kernel_time.argtypes = [C.c_void_p, c_double_p, c_double_p]
@@ -316,6 +336,7 @@ EXPORTED_SYMBOLS = [
     "mjpc_hip_debug_spill", "mjpc_hip_debug_spill_layout",
     "mjpc_hip_plan_mixed_async", "mjpc_hip_plan_mixed", "mjpc_hip_noise_history_reset", "mjpc_hip_sample_gradient",
     "mjpc_hip_step_batch", "mjpc_hip_transition_fd", "mjpc_hip_cost_derivatives", "mjpc_hip_trajectory_gradient",
+    "mjpc_hip_ilqg_backward_pass", "mjpc_hip_trajectory_ilqg", "mjpc_hip_riccati_layout_bytes",
     "mjpc_hip_multi_create", "mjpc_hip_multi_destroy", "mjpc_hip_multi_set_task", "mjpc_hip_multi_plan", "mjpc_hip_multi_get_candidate",
     "mjpc_hip_multi_get_knots", "mjpc_hip_multi_get_traces", "mjpc_hip_multi_num_devices", "mjpc_hip_multi_engine",
 ]

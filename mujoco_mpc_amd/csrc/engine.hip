@@ -15,6 +15,8 @@
 //                   knots, and the A / B / C / D entries from the stepped rows
 //   cd_kernel / gd_backward_kernel  (cost_derivatives.h)  mjpc_hip_cost_derivatives / mjpc_hip_trajectory_gradient: the cost derivatives of
 //                   every knot from the residual and its Jacobian, and the gradient planner's backward recursion
+//   rc_backward_kernel  (riccati.h)  mjpc_hip_ilqg_backward_pass / mjpc_hip_trajectory_ilqg: iLQG's backward pass, one workgroup: Riccati
+//                   recursion, box-QP controls and the regularisation loop
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
 //   pack_kernel     the plan's result in one contiguous buffer for one D2H copy
@@ -31,6 +33,7 @@
 #include "gradient.h"
 #include "transition_fd.h"
 #include "cost_derivatives.h"
+#include "riccati.h"
 #include "host.h"
 #include "devbuf.h"
 #include "../../include/mjpc_hip_debug.h"
@@ -225,6 +228,15 @@ extern "C" __global__ void __launch_bounds__(GD_THREADS) gd_backward_kernel(cons
     }
   }
   if (tid == 0) { a.dV[0] = dv; a.dV[1] = 0.0; }
+}
+
+// mjpc_hip_ilqg_backward_pass / mjpc_hip_trajectory_ilqg: the whole regularised backward pass in ONE workgroup (riccati.h).  The work
+// image lies in LDS when it fits (rc_fits) and in the call's global scratch otherwise; the two branches are the same function, so
+// that the compiler sees which address space each copy works in.
+extern "C" __global__ void __launch_bounds__(RC_THREADS) rc_backward_kernel(const RcArgs a) {
+  extern __shared__ double rc_sm[];
+  if (rc_fits(a.nd, a.nu)) rc_backward(a, rc_work(a.nd, a.nu, rc_sm), (int)threadIdx.x, RC_THREADS);
+  else rc_backward(a, rc_work(a.nd, a.nu, a.scratch), (int)threadIdx.x, RC_THREADS);
 }
 
 // winner[0] = local index of the first minimum of returns[0..n), winner_val[0] = its value
@@ -1017,6 +1029,159 @@ int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const
   const struct { double *dst; size_t n; } outs[] = {{k, Tz * nu}, {Vx, Tz * nd}, {Qx, (Tz - 1) * nd}, {Qu, (Tz - 1) * nu}, {dV, 2}};
   for (const auto &o : outs) { if (o.dst && o.n) memcpy(o.dst, h, sizeof(double) * o.n); h += o.n; }
   memcpy(failure, h, sizeof(int) * Tz);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ iLQG backward pass
+// the block that comes back in one copy (doubles): k [T][nu] | K [T][nu][nd] | Vx [T][nd] | Vxx [T][nd][nd] | Qx | Qu | Qxx | Qxu | Quu
+// ([T-1] each) | dV [2] | regularization, rate [2] | status [3] (ints, in two doubles)
+static size_t rc_out_doubles(size_t T, size_t n, size_t m) {
+  return T * (m + m * n + n + n * n) + (T - 1) * (n + m + n * n + n * m + m * m) + 6;
+}
+static void rc_point(RcArgs &g, double *ob, size_t T, size_t n, size_t m) {
+  g.k = ob; g.K = g.k + T * m; g.Vx = g.K + T * m * n; g.Vxx = g.Vx + T * n;
+  g.Qx = g.Vxx + T * n * n; g.Qu = g.Qx + (T - 1) * n; g.Qxx = g.Qu + (T - 1) * m; g.Qxu = g.Qxx + (T - 1) * n * n; g.Quu = g.Qxu + (T - 1) * n * m;
+  g.dV = g.Quu + (T - 1) * m * m; g.reg = g.dV + 2; g.status = (int *)(g.reg + 2);
+}
+static int rc_settings(RcArgs &g, const MjpcHipRiccatiSettings *s, const char *who) {
+  if (!s || s->struct_size != (int)sizeof(MjpcHipRiccatiSettings)) { set_error(std::string(who) + ": MjpcHipRiccatiSettings.struct_size does not match this library"); return -1; }
+  g.reg_type = s->regularization_type; g.action_limits = s->action_limits ? 1 : 0; g.max_iter = s->max_regularization_iterations;
+  g.reg_min = s->min_regularization; g.reg_max = s->max_regularization; g.reg_factor = s->regularization_factor;
+  return 0;
+}
+// zero the outputs, hand in the regularisation, run the kernel, bring the block back (pinned) and hand it out.  ob: the block on the
+// device (rc_out_doubles + tail doubles the caller copies back with it); scratch: RC_WORK_DOUBLES behind it when the image is not in LDS
+static int rc_run(MjpcHipEngine *e, RcArgs g, double *ob, size_t tail, double *scratch, double *regularization, double *rate, double **host_tail) {
+  const size_t T = g.T, n = g.nd, m = g.nu, n_out = rc_out_doubles(T, n, m);
+  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * (n_out + tail)));
+  rc_point(g, ob, T, n, m);
+  g.scratch = scratch;
+  double *h = e->at(H_PACK);
+  h[0] = *regularization; h[1] = *rate;
+  HIPCHK(hipMemsetAsync(ob, 0, sizeof(double) * n_out, e->stream));
+  HIPCHK(hipMemcpyAsync(g.reg, h, sizeof(double) * 2, hipMemcpyHostToDevice, e->stream));
+  const bool fits = RC_WORK_DOUBLES(n, m) * sizeof(double) <= RC_LDS_LIMIT;
+  const size_t lds = fits ? RC_WORK_DOUBLES(n, m) * sizeof(double) : 0;
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)rc_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(rc_backward_kernel, dim3(1), dim3(RC_THREADS), lds, e->stream, g);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, ob, sizeof(double) * (n_out + tail), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *host_tail = h + n_out;
+  return 0;
+}
+static void rc_hand_out(const double *h, size_t T, size_t n, size_t m, double *regularization, double *rate, double *k, double *K, double *Vx, double *Vxx,
+                        double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status) {
+  const struct { double *dst; size_t n; } outs[] = {{k, T * m}, {K, T * m * n}, {Vx, T * n}, {Vxx, T * n * n}, {Qx, (T - 1) * n}, {Qu, (T - 1) * m},
+                                                    {Qxx, (T - 1) * n * n}, {Qxu, (T - 1) * n * m}, {Quu, (T - 1) * m * m}, {dV, 2}};
+  for (const auto &o : outs) { if (o.dst && o.n) memcpy(o.dst, h, sizeof(double) * o.n); h += o.n; }
+  *regularization = h[0]; *rate = h[1];
+  if (status) memcpy(status, h + 2, sizeof(int) * 3);
+}
+
+int mjpc_hip_ilqg_backward_pass(MjpcHipEngine *e, int T, int nd, int nu, const double *A, const double *B, const double *cx, const double *cu,
+                                const double *cxx, const double *cxu, const double *cuu, const double *actions, const double *action_limits,
+                                const MjpcHipRiccatiSettings *s, double *regularization, double *regularization_rate, double *k, double *K,
+                                double *Vx, double *Vxx, double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status) {
+  const char *who = "mjpc_hip_ilqg_backward_pass";
+  if (!e) { set_error(std::string(who) + ": invalid argument"); return -1; }
+  if (T < 2) { set_error(std::string(who) + ": T < 2"); return -1; }
+  if (nd < 1 || nu < 1) { set_error(std::string(who) + ": nd < 1 or nu < 1"); return -1; }
+  if (e->pending) { set_error(std::string(who) + ": a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
+  RcArgs g;
+  memset(&g, 0, sizeof(g));
+  if (rc_settings(g, s, who) != 0) return -1;
+  if (!A || !B || !cx || !cu || !cxx || !cxu || !cuu || !regularization || !regularization_rate || (g.action_limits && (!actions || !action_limits))) {
+    set_error(std::string(who) + ": null input"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  const size_t Tz = T, n = nd, m = nu, nn = n * n, nm = n * m, mm = m * m;
+  const size_t cnt[9] = {(Tz - 1) * nn, (Tz - 1) * nm, Tz * n, (Tz - 1) * m, Tz * nn, (Tz - 1) * nm, (Tz - 1) * mm, g.action_limits ? (Tz - 1) * m : 0, g.action_limits ? 2 * m : 0};
+  const double *src[9] = {A, B, cx, cu, cxx, cxu, cuu, actions, action_limits};
+  size_t n_in = 0;
+  for (size_t c : cnt) n_in += c;
+  const bool fits = RC_WORK_DOUBLES(n, m) * sizeof(double) <= RC_LDS_LIMIT;
+  HIPCHK(e->buf[B_FD].reserve((n_in + rc_out_doubles(Tz, n, m) + (fits ? 0 : RC_WORK_DOUBLES(n, m)) + 8) * sizeof(double)));
+  double *d = e->at(B_FD);
+  const double *dev[9];
+  for (int i = 0; i < 9; i++) {
+    dev[i] = d;
+    if (cnt[i]) HIPCHK(hipMemcpyAsync(d, src[i], sizeof(double) * cnt[i], hipMemcpyHostToDevice, e->stream));
+    d += cnt[i];
+  }
+  g.A = dev[0]; g.B = dev[1]; g.cx = dev[2]; g.cu = dev[3]; g.cxx = dev[4]; g.cxu = dev[5]; g.cuu = dev[6]; g.actions = dev[7]; g.limits = dev[8];
+  g.T = T; g.nd = nd; g.nu = nu;
+  double *ht = nullptr;
+  const int rc = rc_run(e, g, d, 0, d + rc_out_doubles(Tz, n, m), regularization, regularization_rate, &ht);
+  if (rc != 0) return rc;
+  rc_hand_out(e->at(H_PACK), Tz, n, m, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status);
+  return 0;
+}
+
+int mjpc_hip_riccati_layout_bytes(int nd, int nu, int *in_lds) {
+  if (nd < 1 || nu < 1) { set_error("mjpc_hip_riccati_layout_bytes: nd < 1 or nu < 1"); return -1; }
+  const size_t bytes = RC_WORK_DOUBLES(nd, nu) * sizeof(double);
+  if (in_lds) *in_lds = bytes <= RC_LDS_LIMIT ? 1 : 0;
+  return bytes > 0x7fffffff ? 0x7fffffff : (int)bytes;
+}
+
+int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual, const double *mocap,
+                             const double *userdata, double eps, int centered, const MjpcHipRiccatiSettings *s, double *regularization,
+                             double *regularization_rate, double *k, double *K, double *Vx, double *Vxx, double *Qx, double *Qu, double *Qxx, double *Qxu,
+                             double *Quu, double *dV, int *status, int *failure) {
+  const char *who = "mjpc_hip_trajectory_ilqg";
+  if (!e) { set_error(std::string(who) + ": invalid argument"); return -1; }
+  if (T < 2) { set_error(std::string(who) + ": T < 2"); return -1; }
+  if (!(eps > 0)) { set_error(std::string(who) + ": eps <= 0"); return -1; }
+  if (e->nu < 1) { set_error(std::string(who) + ": the model has no actuator"); return -1; }
+  if (!x || !time || !u || (e->nr > 0 && !residual) || !failure || !regularization || !regularization_rate) { set_error(std::string(who) + ": null input"); return -1; }
+  RcArgs g;
+  memset(&g, 0, sizeof(g));
+  if (rc_settings(g, s, who) != 0) return -1;
+  centered = centered ? 1 : 0;
+  if ((size_t)T > fd_pass_knots(e, centered)) { set_error(std::string(who) + ": T too large for one pass of the step tables (" + std::to_string(fd_pass_knots(e, centered)) + " knots for this model)"); return -1; }
+  KParams K_;
+  int rc = step_prepare(e, who, mocap, userdata, &K_);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv), Tz = (size_t)T;
+  const size_t n_out = rc_out_doubles(Tz, nd, nu), n_fail = (Tz + 1) / 2;
+  const bool fits = RC_WORK_DOUBLES(nd, nu) * sizeof(double) <= RC_LDS_LIMIT;
+  // behind the pass's tables: the residual rows, cr, cx, cu, cxx, cuu, cxu, the limits, the block that goes back, the scratch
+  const size_t n_cd = Tz * (2 * nr + nd + nu + nd * nd + nu * nu + nd * nu);
+  const size_t extra = n_cd + 2 * nu + n_out + n_fail + (fits ? 0 : RC_WORK_DOUBLES(nd, nu));
+  FdArgs f;
+  double *x0 = nullptr;
+  const std::vector<int> dofmap = fd_dofmap(e);
+  rc = fd_pass(e, K_, dofmap, 0, Tz, 1, x, u, time, eps, centered, extra, &f, &x0);
+  if (rc != 0) return rc;
+  CdArgs a;
+  memset(&a, 0, sizeof(a));
+  double *dr = x0;
+  a.residual = dr; a.C = f.C; a.D = f.D; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = 1; a.hessians = 1;
+  a.cr = dr + Tz * nr; a.cx = a.cr + Tz * nr; a.cu = a.cx + Tz * nd; a.cxx = a.cu + Tz * nu; a.cuu = a.cxx + Tz * nd * nd; a.cxu = a.cuu + Tz * nu * nu;
+  double *dlim = x0 + n_cd, *ob = dlim + 2 * nu;
+  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
+  // the model's ctrlrange; an unlimited actuator gets -inf, +inf (kept alive until the stream has been synchronised in rc_run)
+  std::vector<double> lim(2 * nu);
+  {
+    const DevModel hm = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data());
+    for (size_t i = 0; i < nu; i++) {
+      const bool limited = hm.actuator_ctrllimited[i] != 0;
+      lim[2 * i] = limited ? hm.actuator_ctrlrange[2 * i] : -HUGE_VAL;
+      lim[2 * i + 1] = limited ? hm.actuator_ctrlrange[2 * i + 1] : HUGE_VAL;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(dlim, lim.data(), sizeof(double) * 2 * nu, hipMemcpyHostToDevice, e->stream));
+  rc = cd_launch(e, a, who);
+  if (rc != 0) return rc;
+  g.A = f.A; g.B = f.B; g.cx = a.cx; g.cu = a.cu; g.cxx = a.cxx; g.cxu = a.cxu; g.cuu = a.cuu; g.actions = f.u; g.limits = dlim;
+  g.T = T; g.nd = (int)nd; g.nu = (int)nu;
+  // failure[] travels behind the block; rc_run zeroes the block alone, so this copy may be queued first
+  HIPCHK(hipMemcpyAsync(ob + n_out, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
+  double *ht = nullptr;
+  rc = rc_run(e, g, ob, n_fail, ob + n_out + n_fail, regularization, regularization_rate, &ht);
+  if (rc != 0) return rc;
+  rc_hand_out(e->at(H_PACK), Tz, nd, nu, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status);
+  memcpy(failure, ht, sizeof(int) * Tz);
   return 0;
 }
 

@@ -5,6 +5,7 @@
 //   mjpc/planners/sampling/planner.cc:40-310,525-534   SamplingPlanner host logic
 //   mjpc/planners/sample_gradient/planner.cc:43-493    SampleGradientPlanner host logic (batch + gradient sum on the engine)
 //   mjpc/planners/model_derivatives.cc:24-165          ModelDerivatives (evaluations on the engine, interpolation on the host)
+//   mjpc/planners/ilqg/backward_pass.cc, policy.cc, planner.cc:429-520   BoxQP, iLQGPolicy, iLQGBackwardPass (host, and the engine's kernel)
 #include "../../include/mjpc_hip_planner.h"
 #include "../../include/mjpc_hip_planner_c.h"
 
@@ -1093,6 +1094,473 @@ void GradientPolicy::CopyParametersFrom(const std::vector<double>& src_parameter
   std::copy(src_times.begin(), src_times.begin() + num_spline_points, times.begin());
 }
 
+// ------------------------------------------------------------------ BoxQP, iLQGPolicy, iLQGBackwardPass (mjpc/planners/ilqg/)
+// Host restatement of csrc/riccati.h by its summation rule (this file is compiled without contraction): ascending contraction index
+// from 0.0, a rounded product and a rounded add per step, `/` and sqrt correctly rounded.
+namespace {
+// res [c1][c2] = A' B, A [r1][c1], B [r1][c2]
+void MulMatTMat(double* res, const double* A, const double* B, int r1, int c1, int c2) {
+  for (int i = 0; i < c1; i++)
+    for (int j = 0; j < c2; j++) {
+      double s = 0.0;
+      for (int k = 0; k < r1; k++) s += A[(size_t)k * c1 + i] * B[(size_t)k * c2 + j];
+      res[(size_t)i * c2 + j] = s;
+    }
+}
+// res [r1][c2] = A B, A [r1][c1], B [c1][c2]
+void MulMatMat(double* res, const double* A, const double* B, int r1, int c1, int c2) {
+  for (int i = 0; i < r1; i++)
+    for (int j = 0; j < c2; j++) {
+      double s = 0.0;
+      for (int k = 0; k < c1; k++) s += A[(size_t)i * c1 + k] * B[(size_t)k * c2 + j];
+      res[(size_t)i * c2 + j] = s;
+    }
+}
+// Cholesky of H[index][index] (leading dimension ldh) into R [nf][nf], lower triangle, zeros above; false: a pivot is not > 0
+bool CholFactorSub(double* R, const double* H, int ldh, const int* index, int nf) {
+  for (int j = 0; j < nf; j++) {
+    double s = 0.0;
+    for (int k = 0; k < j; k++) s += R[j * nf + k] * R[j * nf + k];
+    const double d = H[index[j] * ldh + index[j]] + -s;
+    if (!(d > 0)) return false;
+    const double l = std::sqrt(d);
+    R[j * nf + j] = l;
+    for (int i = j + 1; i < nf; i++) {
+      double q = 0.0;
+      for (int k = 0; k < j; k++) q += R[i * nf + k] * R[j * nf + k];
+      R[i * nf + j] = (H[index[i] * ldh + index[j]] + -q) / l;
+      R[j * nf + i] = 0.0;
+    }
+  }
+  return true;
+}
+void CholSolveSub(double* x, const double* R, int nf, const double* b) {
+  for (int i = 0; i < nf; i++) {
+    double s = 0.0;
+    for (int k = 0; k < i; k++) s += R[i * nf + k] * x[k];
+    x[i] = (b[i] + -s) / R[i * nf + i];
+  }
+  for (int i = nf - 1; i >= 0; i--) {
+    double s = 0.0;
+    for (int k = i + 1; k < nf; k++) s += R[k * nf + i] * x[k];
+    x[i] = (x[i] + -s) / R[i * nf + i];
+  }
+}
+double ClampTo(double v, double lo, double hi) { v = v < hi ? v : hi; return v > lo ? v : lo; }
+double QPValue(const double* H, const double* g, int n, const double* x) {
+  double q = 0.0, l = 0.0;
+  for (int i = 0; i < n; i++) {
+    double s = 0.0;
+    for (int j = 0; j < n; j++) s += H[i * n + j] * x[j];
+    q += x[i] * s;
+    l += x[i] * g[i];
+  }
+  return 0.5 * q + l;
+}
+}  // namespace
+
+void BoxQP::Allocate(int n) {
+  res.assign(n, 0.0); R.assign((size_t)n * n, 0.0); H.assign((size_t)n * n, 0.0); g.assign(n, 0.0); lower.assign(n, 0.0); upper.assign(n, 0.0);
+  index.assign(n, 0);
+}
+
+int BoxQPSolve(double* res, double* R, int* index, const double* H, const double* g, int n, const double* lower, const double* upper) {
+  const double inf = std::numeric_limits<double>::infinity();
+  std::vector<double> buf(6 * (size_t)n);
+  std::vector<int> mask(n, -1);
+  double *grad = buf.data(), *search = grad + n, *cand = search + n, *y = cand + n, *lo = y + n, *hi = lo + n;
+  for (int i = 0; i < n; i++) { lo[i] = lower ? lower[i] : -inf; hi[i] = upper ? upper[i] : inf; res[i] = ClampTo(res[i], lo[i], hi[i]); }
+  double value = QPValue(H, g, n, res);
+  int nf = 0;
+  for (int iter = 0; iter < 100; iter++) {
+    bool changed = false;
+    nf = 0;
+    for (int i = 0; i < n; i++) {
+      double s = 0.0;
+      for (int j = 0; j < n; j++) s += H[i * n + j] * res[j];
+      grad[i] = g[i] + s;
+      const int c = (res[i] == lo[i] && grad[i] > 0) || (res[i] == hi[i] && grad[i] < 0);
+      if (mask[i] != c) changed = true;
+      mask[i] = c;
+      if (!c) index[nf++] = i;
+    }
+    if (nf == 0) break;
+    if (changed && !CholFactorSub(R, H, n, index, nf)) return -1;
+    double gn = 0.0;
+    for (int i = 0; i < nf; i++) gn += grad[index[i]] * grad[index[i]];
+    if (gn < 1.0e-16) break;
+    for (int i = 0; i < nf; i++) y[i] = grad[index[i]];
+    CholSolveSub(y, R, nf, y);
+    std::fill(search, search + n, 0.0);
+    double sdotg = 0.0;
+    for (int i = 0; i < nf; i++) { search[index[i]] = -y[i]; sdotg += -y[i] * grad[index[i]]; }
+    if (!(sdotg < 0)) break;
+    double step = 1.0, nv = value;
+    bool accepted = false;
+    while (step >= 1.0e-22) {
+      for (int i = 0; i < n; i++) cand[i] = ClampTo(res[i] + step * search[i], lo[i], hi[i]);
+      nv = QPValue(H, g, n, cand);
+      if (nv + -value <= 0.1 * (step * sdotg)) { accepted = true; break; }
+      step = step * 0.5;
+    }
+    if (!accepted) break;
+    std::copy(cand, cand + n, res);
+    value = nv;
+  }
+  return nf;
+}
+
+void iLQGPolicy::Allocate(const MjpcHipModel* model, int num_residual, int num_trace, int horizon, int representation_) {
+  Allocate(model->nq, model->nv, model->na, model->nu, model->njnt, model->jnt_type, model->jnt_qposadr, model->jnt_dofadr, model->actuator_ctrlrange,
+           num_residual, num_trace, horizon, representation_);
+}
+void iLQGPolicy::Allocate(int nq_, int nv_, int na_, int nu_, int njnt, const int* type, const int* qposadr, const int* dofadr, const double* range,
+                          int num_residual, int num_trace, int horizon, int representation_) {
+  nq = nq_; nv = nv_; na = na_; nu = nu_;
+  const int ds = nq + nv + na, nd = 2 * nv + na;
+  ctrlrange.assign(range, range + 2 * nu);
+  jnt_type.assign(type, type + njnt); jnt_qposadr.assign(qposadr, qposadr + njnt); jnt_dofadr.assign(dofadr, dofadr + njnt);
+  trajectory.horizon = horizon; trajectory.dim_state = ds; trajectory.dim_action = nu; trajectory.dim_residual = num_residual; trajectory.dim_trace = 3 * num_trace;
+  trajectory.states.assign((size_t)ds * horizon, 0.0); trajectory.actions.assign((size_t)nu * horizon, 0.0); trajectory.times.assign(horizon, 0.0);
+  trajectory.residual.assign((size_t)num_residual * horizon, 0.0); trajectory.costs.assign(horizon, 0.0); trajectory.trace.assign((size_t)3 * num_trace * horizon, 0.0);
+  feedback_gain.assign((size_t)nu * nd * horizon, 0.0);
+  action_improvement.assign((size_t)nu * horizon, 0.0);
+  state_scratch.assign(ds, 0.0); action_scratch.assign(nu, 0.0); feedback_gain_scratch.assign((size_t)nu * nd, 0.0); state_interp.assign(ds, 0.0);
+  representation = representation_;
+}
+void iLQGPolicy::Reset(int horizon, const double* initial_repeated_action) {
+  const int nd = 2 * nv + na;
+  const size_t H = std::min((size_t)horizon, trajectory.times.size());
+  trajectory.horizon = (int)H;
+  std::fill(trajectory.states.begin(), trajectory.states.end(), 0.0);
+  for (size_t i = 0; i < H * nu; i++) trajectory.actions[i] = initial_repeated_action ? initial_repeated_action[i % nu] : 0.0;
+  std::fill(trajectory.times.begin(), trajectory.times.end(), 0.0);
+  std::fill(trajectory.residual.begin(), trajectory.residual.end(), 0.0);
+  std::fill(trajectory.costs.begin(), trajectory.costs.end(), 0.0);
+  std::fill(trajectory.trace.begin(), trajectory.trace.end(), 0.0);
+  trajectory.total_return = 0.0; trajectory.failure = false;
+  std::fill(feedback_gain.begin(), feedback_gain.begin() + H * nu * nd, 0.0);
+  std::fill(action_improvement.begin(), action_improvement.begin() + H * nu, 0.0);
+  std::fill(state_scratch.begin(), state_scratch.end(), 0.0); std::fill(action_scratch.begin(), action_scratch.end(), 0.0);
+  std::fill(feedback_gain_scratch.begin(), feedback_gain_scratch.end(), 0.0); std::fill(state_interp.begin(), state_interp.end(), 0.0);
+  feedback_scaling = 1.0;
+}
+void StateDiff(const iLQGPolicy& p, double* ds, const double* s1, const double* s2, double h) {
+  const int nq = p.nq, nv = p.nv, na = p.na;
+  if (nq == nv) { for (int i = 0; i < nq + nv + na; i++) ds[i] = (s2[i] - s1[i]) / h; return; }
+  // mj_differentiatePos: per joint, (qb - qa) / h, and for a quaternion the body-frame rotation vector of qa^-1 qb over h (mju_subQuat)
+  auto quat = [&](double* res, const double* qa, const double* qb) {
+    const double d[4] = {qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2] + qa[3] * qb[3],
+                         qa[0] * qb[1] - qa[1] * qb[0] - qa[2] * qb[3] + qa[3] * qb[2],
+                         qa[0] * qb[2] + qa[1] * qb[3] - qa[2] * qb[0] - qa[3] * qb[1],
+                         qa[0] * qb[3] - qa[1] * qb[2] + qa[2] * qb[1] - qa[3] * qb[0]};     // conj(qa) * qb
+    double axis[3] = {d[1], d[2], d[3]};
+    const double sn = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (sn < 1e-15) { axis[0] = 1.0; axis[1] = 0.0; axis[2] = 0.0; }        // mju_normalize3 of a zero vector
+    else for (double& a : axis) a /= sn;
+    double speed = 2 * std::atan2(sn, d[0]);
+    if (speed > M_PI) speed -= 2 * M_PI;
+    for (int k = 0; k < 3; k++) res[k] = axis[k] * speed / h;
+  };
+  for (size_t j = 0; j < p.jnt_type.size(); j++) {
+    const int qa = p.jnt_qposadr[j], da = p.jnt_dofadr[j];
+    if (p.jnt_type[j] == 0) {
+      for (int k = 0; k < 3; k++) ds[da + k] = (s2[qa + k] - s1[qa + k]) / h;
+      quat(ds + da + 3, s1 + qa + 3, s2 + qa + 3);
+    } else if (p.jnt_type[j] == 1) quat(ds + da, s1 + qa, s2 + qa);
+    else ds[da] = (s2[qa] - s1[qa]) / h;
+  }
+  for (int i = 0; i < nv + na; i++) ds[nv + i] = (s2[nq + i] - s1[nq + i]) / h;
+}
+void iLQGPolicy::Action(double* action, const double* state, double time) const {
+  const int ds = nq + nv + na, nd = 2 * nv + na, H = trajectory.horizon;
+  int bounds[2];
+  FindInterval(bounds, trajectory.times, time, H);
+  auto normalize = [&]() {          // mj_normalizeQuat
+    for (size_t j = 0; j < jnt_type.size(); j++) {
+      if (jnt_type[j] > 1) continue;
+      double* q = state_interp.data() + jnt_qposadr[j] + (jnt_type[j] == 0 ? 3 : 0);
+      const double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      if (nrm < 1e-15) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
+      else for (int k = 0; k < 4; k++) q[k] /= nrm;
+    }
+  };
+  if (bounds[0] == bounds[1] || representation == kZeroSpline) {
+    ZeroInterpolation(action, time, trajectory.times, trajectory.actions.data(), nu, H - 1);
+    if (state) {
+      ZeroInterpolation(state_interp.data(), time, trajectory.times, trajectory.states.data(), ds, H);
+      ZeroInterpolation(feedback_gain_scratch.data(), time, trajectory.times, feedback_gain.data(), nu * nd, H - 1);
+    }
+  } else if (representation == kLinearSpline) {
+    LinearInterpolation(action, time, trajectory.times, trajectory.actions.data(), nu, H - 1);
+    if (state) {
+      LinearInterpolation(state_interp.data(), time, trajectory.times, trajectory.states.data(), ds, H);
+      normalize();
+      LinearInterpolation(feedback_gain_scratch.data(), time, trajectory.times, feedback_gain.data(), nu * nd, H - 1);
+    }
+  } else if (representation == kCubicSpline) {
+    CubicInterpolation(action, time, trajectory.times, trajectory.actions.data(), nu, H - 1);
+    if (state) {
+      CubicInterpolation(state_interp.data(), time, trajectory.times, trajectory.states.data(), ds, H);
+      normalize();
+      CubicInterpolation(feedback_gain_scratch.data(), time, trajectory.times, feedback_gain.data(), nu * nd, H - 1);
+    }
+  }
+  if (state) {
+    StateDiff(*this, state_scratch.data(), state_interp.data(), state, 1.0);
+    for (int i = 0; i < nu; i++) {
+      double s = 0.0;
+      for (int j = 0; j < nd; j++) s += feedback_gain_scratch[(size_t)i * nd + j] * state_scratch[j];
+      action[i] += s * feedback_scaling;
+    }
+  }
+  for (int i = 0; i < nu; i++) action[i] = std::max(ctrlrange[2 * i], std::min(ctrlrange[2 * i + 1], action[i]));
+}
+void iLQGPolicy::CopyFrom(const iLQGPolicy& policy, int horizon) {
+  trajectory = policy.trajectory;
+  const int nd = 2 * nv + na;
+  std::copy(policy.feedback_gain.begin(), policy.feedback_gain.begin() + std::min((size_t)horizon * nu * nd, policy.feedback_gain.size()), feedback_gain.begin());
+  std::copy(policy.action_improvement.begin(), policy.action_improvement.begin() + std::min((size_t)horizon * nu, policy.action_improvement.size()), action_improvement.begin());
+}
+
+void iLQGBackwardPass::Allocate(int n, int m, int T) {
+  const size_t Tz = T, T1 = T > 1 ? T - 1 : 0, mmn = std::max(n, m);
+  Vx.assign(n * Tz, 0.0); Vxx.assign((size_t)n * n * Tz, 0.0);
+  Qx.assign(n * T1, 0.0); Qu.assign(m * T1, 0.0); Qxx.assign((size_t)n * n * T1, 0.0); Qxu.assign((size_t)n * m * T1, 0.0); Quu.assign((size_t)m * m * T1, 0.0);
+  Q_scratch.assign(10 * ((size_t)n * n + 7 * m + 2 * (size_t)m * m + (size_t)n * m + 3 * mmn * mmn), 0.0);
+  regularization = 1.0; regularization_rate = 1.0; regularization_factor = 2.0;
+}
+void iLQGBackwardPass::Reset(int n, int m, int T) {
+  const size_t Tz = T;
+  if (Vx.size() < n * Tz || Vxx.size() < (size_t)n * n * Tz || Qu.size() + m < m * Tz || Qxu.size() + (size_t)n * m < (size_t)n * m * Tz ||
+      Quu.size() + (size_t)m * m < (size_t)m * m * Tz) Allocate(n, m, T);
+  dV[0] = 0.0; dV[1] = 0.0;
+  for (std::vector<double>* v : {&Vx, &Vxx, &Qx, &Qu, &Qxx, &Qxu, &Quu}) std::fill(v->begin(), v->end(), 0.0);
+  regularization = 1.0; regularization_rate = 1.0; regularization_factor = 2.0;
+}
+
+int iLQGBackwardPass::RiccatiStep(int n, int m, double mu, const double* Wx, const double* Wxx, const double* At, const double* Bt, const double* cxt,
+                                  const double* cut, const double* cxxt, const double* cxut, const double* cuut, double* Vxt, double* Vxxt, double* dut,
+                                  double* Kt, double* dV_, double* Qxt, double* Qut, double* Qxxt, double* Qxut, double* Quut, double* scratch,
+                                  BoxQP& boxqp, const double* action, const double* action_limits, int reg_type, int limits) {
+  const int mmn = std::max(m, n);
+  double* Vxx_reg = scratch; scratch += n * n;
+  double* Quu_reg = scratch; scratch += m * m;
+  double* tmp = scratch; scratch += mmn * mmn;
+  double* tmp2 = scratch; scratch += mmn * mmn;
+  double* tmp3 = scratch; scratch += mmn * mmn;
+  std::vector<int> identity;
+
+  // Qx, Qxx, Qu, Qxu, Quu
+  MulMatTMat(tmp, At, Wxx, n, n, n);
+  MulMatTMat(Qxt, At, Wx, n, n, 1);
+  for (int i = 0; i < n; i++) Qxt[i] += cxt[i];
+  MulMatMat(Qxxt, tmp, At, n, n, n);
+  for (int i = 0; i < n * n; i++) Qxxt[i] += cxxt[i];
+  MulMatTMat(Qut, Bt, Wx, n, m, 1);
+  for (int i = 0; i < m; i++) Qut[i] += cut[i];
+  MulMatMat(Qxut, tmp, Bt, n, n, m);
+  for (int i = 0; i < n * m; i++) Qxut[i] += cxut[i];
+  MulMatTMat(tmp2, Bt, Wxx, n, m, n);
+  MulMatMat(Quut, tmp2, Bt, m, n, m);
+  for (int i = 0; i < m * m; i++) Quut[i] += cuut[i];
+
+  // regularise (Qxu_reg, which the reference forms and never reads, is not formed)
+  if (reg_type == kValueRegularization) {
+    std::copy(Wxx, Wxx + n * n, Vxx_reg);
+    for (int i = 0; i < n; i++) Vxx_reg[n * i + i] += mu;
+    MulMatTMat(tmp2, Bt, Vxx_reg, n, m, n);
+    MulMatMat(Quu_reg, tmp2, Bt, m, n, m);
+    for (int i = 0; i < m * m; i++) Quu_reg[i] += cuut[i];
+  } else {
+    std::copy(Quut, Quut + m * m, Quu_reg);
+  }
+  if (mu) {
+    if (reg_type == kControlRegularization) {
+      for (int i = 0; i < m; i++) Quu_reg[i * m + i] += mu;
+    } else if (reg_type == kStateControlRegularization) {
+      MulMatTMat(tmp, Bt, Bt, n, m, m);
+      for (int i = 0; i < m * m; i++) Quu_reg[i] += tmp[i] * mu;
+    }
+  }
+
+  std::fill(Kt, Kt + n * m, 0.0);
+  int mFree = m;
+  const int* index = nullptr;
+  const double* R = nullptr;
+  if (limits == 1) {
+    std::copy(Quu_reg, Quu_reg + m * m, boxqp.H.begin());
+    std::copy(Qut, Qut + m, boxqp.g.begin());
+    for (int i = 0; i < m; i++) {
+      boxqp.lower[i] = action_limits[2 * i] - action[i];
+      boxqp.upper[i] = action_limits[2 * i + 1] - action[i];
+    }
+    mFree = BoxQPSolve(boxqp.res.data(), boxqp.R.data(), boxqp.index.data(), boxqp.H.data(), boxqp.g.data(), m, boxqp.lower.data(), boxqp.upper.data());
+    if (mFree < 0) return 0;
+    index = boxqp.index.data(); R = boxqp.R.data();
+    std::copy(boxqp.res.begin(), boxqp.res.begin() + m, dut);
+  } else {
+    identity.resize(m);
+    for (int i = 0; i < m; i++) identity[i] = i;
+    if (!CholFactorSub(tmp3, Quu_reg, m, identity.data(), m)) return 0;        // "backward pass failure": rank below m
+    index = identity.data(); R = tmp3;
+    CholSolveSub(dut, R, m, Qut);
+    for (int i = 0; i < m; i++) dut[i] = -dut[i];
+  }
+  // K = -H_free \ Qxu_free', zero rows for the clamped controls (the UNREGULARISED Qxu, as the reference)
+  for (int j = 0; j < n; j++) {
+    double* y = tmp + (size_t)j * m;
+    for (int i = 0; i < mFree; i++) y[i] = Qxut[j * m + index[i]];
+    CholSolveSub(y, R, mFree, y);
+    for (int i = 0; i < mFree; i++) Kt[index[i] * n + j] = -y[i];
+  }
+
+  // cost-to-go
+  double d0 = 0.0, d1 = 0.0;
+  for (int i = 0; i < m; i++) d0 += dut[i] * Qut[i];
+  dV_[0] += d0;
+  MulMatMat(tmp, Quut, dut, m, m, 1);
+  for (int i = 0; i < m; i++) d1 += dut[i] * tmp[i];
+  dV_[1] += 0.5 * d1;
+  for (int i = 0; i < m; i++) tmp2[i] = tmp[i] + Qut[i];
+  MulMatTMat(tmp, Kt, tmp2, m, n, 1);
+  for (int i = 0; i < n; i++) Vxt[i] = Qxt[i] + tmp[i];
+  MulMatMat(tmp, Qxut, dut, n, m, 1);
+  for (int i = 0; i < n; i++) Vxt[i] += tmp[i];
+  MulMatMat(tmp2, Quut, Kt, m, m, n);               // Quu K
+  MulMatTMat(tmp3, Kt, tmp2, m, n, n);              // K' Quu K
+  for (int i = 0; i < n * n; i++) Vxxt[i] = Qxxt[i] + tmp3[i];
+  MulMatMat(tmp2, Qxut, Kt, n, m, n);               // Qxu K
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) tmp[i * n + j] = tmp2[i * n + j] + tmp2[j * n + i];
+  for (int i = 0; i < n * n; i++) Vxxt[i] += tmp[i];
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) tmp[i * n + j] = 0.5 * (Vxxt[i * n + j] + Vxxt[j * n + i]);
+  std::copy(tmp, tmp + n * n, Vxxt);
+  return 1;
+}
+
+int iLQGBackwardPass::Riccati(iLQGPolicy* p, const ModelDerivatives* md, const CostDerivatives* cd, int n, int m, int T, double reg, BoxQP& boxqp,
+                              const double* actions, const double* action_limits, const iLQGSettings& settings) {
+  if (T < 2) { Fatal("iLQGBackwardPass: T < 2"); return -1; }
+  const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+  dV[0] = 0.0; dV[1] = 0.0;
+  std::copy(cd->cx.begin() + (size_t)(T - 1) * n, cd->cx.begin() + (size_t)T * n, Vx.begin() + (size_t)(T - 1) * n);
+  std::copy(cd->cxx.begin() + (T - 1) * nn, cd->cxx.begin() + T * nn, Vxx.begin() + (T - 1) * nn);
+  int bp_iter = 0, time_index = T - 1;
+  while (bp_iter < settings.max_regularization_iterations) {
+    for (int t = T - 1; t > 0; t--) {
+      const size_t u = t - 1;
+      const int status = RiccatiStep(n, m, reg, Vx.data() + (size_t)t * n, Vxx.data() + t * nn, md->A.data() + u * nn, md->B.data() + u * nm,
+                                     cd->cx.data() + u * n, cd->cu.data() + u * m, cd->cxx.data() + u * nn, cd->cxu.data() + u * nm, cd->cuu.data() + u * mm,
+                                     Vx.data() + u * n, Vxx.data() + u * nn, p->action_improvement.data() + u * m, p->feedback_gain.data() + u * nm, dV,
+                                     Qx.data() + u * n, Qu.data() + u * m, Qxx.data() + u * nn, Qxu.data() + u * nm, Quu.data() + u * mm, Q_scratch.data(),
+                                     boxqp, actions + u * m, action_limits, settings.regularization_type, settings.action_limits);
+      if (!status) { time_index = t - 1; break; }
+      if (t == 1) {
+        std::copy(p->feedback_gain.begin() + (T - 2) * nm, p->feedback_gain.begin() + (T - 1) * nm, p->feedback_gain.begin() + (T - 1) * nm);
+        std::copy(p->action_improvement.begin() + (size_t)(T - 2) * m, p->action_improvement.begin() + (size_t)(T - 1) * m, p->action_improvement.begin() + (size_t)(T - 1) * m);
+        return 0;
+      }
+    }
+    if (regularization <= settings.max_regularization) {
+      ScaleRegularization(regularization_factor, settings.min_regularization, settings.max_regularization);
+      bp_iter += 1;
+    } else {
+      return time_index;
+    }
+  }
+  return time_index;
+}
+
+void iLQGBackwardPass::RiccatiRegularized(double* k, double* K, const double* A, const double* B, const double* cx, const double* cu, const double* cxx,
+                                          const double* cxu, const double* cuu, int n, int m, int T, BoxQP& boxqp, const double* actions,
+                                          const double* action_limits, const iLQGSettings& settings, int* status) {
+  if (T < 2) { Fatal("iLQGBackwardPass: T < 2"); return; }
+  const size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+  if (Vx.size() < (size_t)n * T || Vxx.size() < nn * T || Qx.size() < (size_t)n * (T - 1) || Qu.size() < (size_t)m * (T - 1) || Qxx.size() < nn * (T - 1) ||
+      Qxu.size() < nm * (T - 1) || Quu.size() < mm * (T - 1) || Q_scratch.empty()) {
+    const double r = regularization, rr = regularization_rate, f = regularization_factor;
+    Allocate(n, m, T);
+    regularization = r; regularization_rate = rr; regularization_factor = f;
+  }
+  if ((int)boxqp.res.size() < m) boxqp.Allocate(m);
+  std::fill(boxqp.res.begin(), boxqp.res.end(), 0.0);
+  int iter = 0, done = 0, failed = -1;
+  dV[0] = 0.0; dV[1] = 0.0;
+  std::copy(cx + (size_t)(T - 1) * n, cx + (size_t)T * n, Vx.begin() + (size_t)(T - 1) * n);
+  std::copy(cxx + (T - 1) * nn, cxx + T * nn, Vxx.begin() + (T - 1) * nn);
+  while (iter < settings.max_regularization_iterations && !done) {
+    dV[0] = 0.0; dV[1] = 0.0;
+    failed = -1;
+    for (int t = T - 2; t >= 0; t--) {
+      const size_t u = t;
+      const int ok = RiccatiStep(n, m, regularization, Vx.data() + (u + 1) * n, Vxx.data() + (u + 1) * nn, A + u * nn, B + u * nm, cx + u * n, cu + u * m,
+                                 cxx + u * nn, cxu + u * nm, cuu + u * mm, Vx.data() + u * n, Vxx.data() + u * nn, k + u * m, K + u * nm, dV,
+                                 Qx.data() + u * n, Qu.data() + u * m, Qxx.data() + u * nn, Qxu.data() + u * nm, Quu.data() + u * mm, Q_scratch.data(),
+                                 boxqp, actions ? actions + u * m : nullptr, action_limits, settings.regularization_type, settings.action_limits);
+      if (!ok) { failed = t; break; }
+    }
+    if (failed < 0) {
+      done = 1;
+      std::copy(K + (T - 2) * nm, K + (T - 1) * nm, K + (T - 1) * nm);
+      std::copy(k + (size_t)(T - 2) * m, k + (size_t)(T - 1) * m, k + (size_t)(T - 1) * m);
+    } else if (regularization <= settings.max_regularization) {
+      ScaleRegularization(regularization_factor, settings.min_regularization, settings.max_regularization);
+      iter += 1;
+    } else {
+      break;         // (the reference's loop would neither scale nor count from here on)
+    }
+  }
+  if (status) { status[0] = done; status[1] = done ? -1 : failed; status[2] = iter; }
+}
+
+static MjpcHipRiccatiSettings RiccatiSettingsOf(const iLQGSettings& s, double factor) {
+  MjpcHipRiccatiSettings r;
+  r.struct_size = (int)sizeof(MjpcHipRiccatiSettings);
+  r.regularization_type = s.regularization_type; r.action_limits = s.action_limits; r.max_regularization_iterations = s.max_regularization_iterations;
+  r.min_regularization = s.min_regularization; r.max_regularization = s.max_regularization; r.regularization_factor = factor;
+  return r;
+}
+
+bool iLQGBackwardPass::Compute(MjpcHipEngine* engine, iLQGPolicy* policy, const ModelDerivatives* md, const CostDerivatives* cd, int n, int m, int T,
+                               const double* actions, const double* action_limits, const iLQGSettings& settings, int* status) {
+  const double r = regularization, rr = regularization_rate, f = regularization_factor;
+  Reset(n, m, T);
+  regularization = r; regularization_rate = rr; regularization_factor = f;
+  const MjpcHipRiccatiSettings s = RiccatiSettingsOf(settings, regularization_factor);
+  return mjpc_hip_ilqg_backward_pass(engine, T, n, m, md->A.data(), md->B.data(), cd->cx.data(), cd->cu.data(), cd->cxx.data(), cd->cxu.data(), cd->cuu.data(),
+                                     actions, action_limits, &s, &regularization, &regularization_rate, policy->action_improvement.data(),
+                                     policy->feedback_gain.data(), Vx.data(), Vxx.data(), Qx.data(), Qu.data(), Qxx.data(), Qxu.data(), Quu.data(), dV, status) == 0;
+}
+
+bool iLQGBackwardPass::ComputeFused(MjpcHipEngine* engine, iLQGPolicy* policy, const double* x, const double* u, const double* h, const double* residual,
+                                    int n, int m, int T, const iLQGSettings& settings, int* status, int* failure, const double* mocap, const double* userdata) {
+  const double r = regularization, rr = regularization_rate, f = regularization_factor;
+  Reset(n, m, T);
+  regularization = r; regularization_rate = rr; regularization_factor = f;
+  const MjpcHipRiccatiSettings s = RiccatiSettingsOf(settings, regularization_factor);
+  return mjpc_hip_trajectory_ilqg(engine, T, x, u, h, residual, mocap, userdata, settings.fd_tolerance, settings.fd_mode != 0 ? 1 : 0, &s, &regularization,
+                                  &regularization_rate, policy->action_improvement.data(), policy->feedback_gain.data(), Vx.data(), Vxx.data(), Qx.data(),
+                                  Qu.data(), Qxx.data(), Qxu.data(), Quu.data(), dV, status, failure) == 0;
+}
+
+void iLQGBackwardPass::ScaleRegularization(double factor, double reg_min, double reg_max) {
+  const double s = regularization_rate * factor;
+  if (factor > 1) regularization_rate = s > factor ? s : factor;
+  else regularization_rate = s < factor ? s : factor;
+  double v = regularization * regularization_rate;
+  v = v > reg_min ? v : reg_min;
+  regularization = v < reg_max ? v : reg_max;
+}
+
+void iLQGBackwardPass::UpdateRegularization(double reg_min, double reg_max, double z, double s) {
+  auto bad = [](double v) { return std::isnan(v) || v > 1e10 || v < -1e10; };          // mju_isBad: NaN or beyond mjMAXVAL
+  if (bad(z) || bad(s)) ScaleRegularization(regularization_factor * regularization_factor, reg_min, reg_max);
+  else if (z > 0.5 || s > 0.3) ScaleRegularization(1.0 / regularization_factor, reg_min, reg_max);
+  else if (z < 0.1 || s < 0.06) ScaleRegularization(regularization_factor, reg_min, reg_max);
+}
+
 // ------------------------------------------------------------------ spline mappings (gradient/spline_mapping.cc)
 void SplineMapping::Allocate(int d) {
   dim = d;
@@ -1636,6 +2104,135 @@ void mjpc_gd_policy_action(int representation, int nu, const double* ctrlrange, 
   pol.nu = nu; pol.ctrlrange.assign(ctrlrange, ctrlrange + 2 * nu); pol.representation = representation; pol.num_spline_points = num_spline_points;
   pol.times.assign(times, times + num_spline_points); pol.parameters.assign(parameters, parameters + (size_t)num_spline_points * nu);
   pol.Action(action, nullptr, time);
+}
+
+// ---- iLQGBackwardPass, BoxQP, iLQGPolicy
+namespace {
+struct IlqgBp {
+  mjpc_hip::iLQGBackwardPass bp;
+  mjpc_hip::BoxQP qp;
+  mjpc_hip::iLQGPolicy policy;
+  mjpc_hip::ModelDerivatives md;
+  mjpc_hip::CostDerivatives cd;
+  int n = 0, m = 0;
+  void Rows(int T) {
+    policy.nu = m;
+    policy.action_improvement.assign((size_t)m * T, 0.0); policy.feedback_gain.assign((size_t)m * n * T, 0.0);
+  }
+  void Load(int T, const double* A, const double* B, const double* cx, const double* cu, const double* cxx, const double* cxu, const double* cuu) {
+    const size_t Tz = T, nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+    md.A.assign(A, A + (Tz - 1) * nn); md.B.assign(B, B + (Tz - 1) * nm);
+    cd.cx.assign(cx, cx + Tz * n); cd.cu.assign(cu, cu + Tz * m); cd.cxx.assign(cxx, cxx + Tz * nn); cd.cxu.assign(cxu, cxu + Tz * nm); cd.cuu.assign(cuu, cuu + Tz * mm);
+  }
+  void Out(int T, double* k, double* K) {
+    if (k) std::copy(policy.action_improvement.begin(), policy.action_improvement.begin() + (size_t)m * T, k);
+    if (K) std::copy(policy.feedback_gain.begin(), policy.feedback_gain.begin() + (size_t)m * n * T, K);
+  }
+  static mjpc_hip::iLQGSettings Settings(const int* si, const double* sd) {
+    mjpc_hip::iLQGSettings s;
+    s.regularization_type = si[0]; s.action_limits = si[1]; s.max_regularization_iterations = si[2];
+    s.min_regularization = sd[0]; s.max_regularization = sd[1];
+    return s;
+  }
+  // Reset keeps the object's regularisation: the C view's reset is the only place that restores the defaults
+  void Zero(int T) {
+    const double r = bp.regularization, rr = bp.regularization_rate, f = bp.regularization_factor;
+    bp.Reset(n, m, T);
+    bp.regularization = r; bp.regularization_rate = rr; bp.regularization_factor = f;
+  }
+};
+}  // namespace
+#define IBP(p) ((IlqgBp*)(p))
+void* mjpc_ilqg_bp_create(int nd, int nu, int T) {
+  auto* d = new IlqgBp();
+  d->n = nd; d->m = nu;
+  d->bp.Allocate(nd, nu, T); d->bp.Reset(nd, nu, T); d->qp.Allocate(nu);
+  return d;
+}
+void mjpc_ilqg_bp_destroy(void* p) { delete IBP(p); }
+void mjpc_ilqg_bp_reset(void* p, int T) { IBP(p)->bp.Reset(IBP(p)->n, IBP(p)->m, T); IBP(p)->qp.Allocate(IBP(p)->m); }
+void mjpc_ilqg_bp_riccati_host(void* p, int T, const double* A, const double* B, const double* cx, const double* cu, const double* cxx, const double* cxu,
+                               const double* cuu, const double* actions, const double* action_limits, const int* si, const double* sd, double* k, double* K,
+                               int* status) {
+  IlqgBp* d = IBP(p);
+  if (T < 2) { d->bp.RiccatiRegularized(nullptr, nullptr, A, B, cx, cu, cxx, cxu, cuu, d->n, d->m, T, d->qp, actions, action_limits, IlqgBp::Settings(si, sd), status); return; }
+  d->Zero(T); d->Rows(T);
+  d->bp.RiccatiRegularized(d->policy.action_improvement.data(), d->policy.feedback_gain.data(), A, B, cx, cu, cxx, cxu, cuu, d->n, d->m, T, d->qp, actions,
+                           action_limits, IlqgBp::Settings(si, sd), status);
+  d->Out(T, k, K);
+}
+int mjpc_ilqg_bp_riccati(void* p, int T, double reg, const double* A, const double* B, const double* cx, const double* cu, const double* cxx, const double* cxu,
+                         const double* cuu, const double* actions, const double* action_limits, const int* si, const double* sd, double* k, double* K) {
+  IlqgBp* d = IBP(p);
+  if (T < 2) return d->bp.Riccati(nullptr, nullptr, nullptr, d->n, d->m, T, reg, d->qp, actions, action_limits, IlqgBp::Settings(si, sd));
+  d->Zero(T); d->Rows(T); d->Load(T, A, B, cx, cu, cxx, cxu, cuu);
+  const int rc = d->bp.Riccati(&d->policy, &d->md, &d->cd, d->n, d->m, T, reg, d->qp, actions, action_limits, IlqgBp::Settings(si, sd));
+  d->Out(T, k, K);
+  return rc;
+}
+int mjpc_ilqg_bp_compute(void* p, MjpcHipEngine* engine, int T, const double* A, const double* B, const double* cx, const double* cu, const double* cxx,
+                         const double* cxu, const double* cuu, const double* actions, const double* action_limits, const int* si, const double* sd, double* k,
+                         double* K, int* status) {
+  IlqgBp* d = IBP(p);
+  if (T < 2 || !A || !B || !cx || !cu || !cxx || !cxu || !cuu) {        // the engine names the error
+    MjpcHipRiccatiSettings s;
+    s.struct_size = (int)sizeof(s); s.regularization_type = si[0]; s.action_limits = si[1]; s.max_regularization_iterations = si[2];
+    s.min_regularization = sd[0]; s.max_regularization = sd[1]; s.regularization_factor = d->bp.regularization_factor;
+    return mjpc_hip_ilqg_backward_pass(engine, T, d->n, d->m, A, B, cx, cu, cxx, cxu, cuu, actions, action_limits, &s, &d->bp.regularization,
+                                       &d->bp.regularization_rate, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, status);
+  }
+  d->Rows(T); d->Load(T, A, B, cx, cu, cxx, cxu, cuu);
+  const bool ok = d->bp.Compute(engine, &d->policy, &d->md, &d->cd, d->n, d->m, T, actions, action_limits, IlqgBp::Settings(si, sd), status);
+  d->Out(T, k, K);
+  return ok ? 0 : -1;
+}
+int mjpc_ilqg_bp_compute_fused(void* p, MjpcHipEngine* engine, int T, const double* x, const double* u, const double* h, const double* residual,
+                               const double* mocap, const double* userdata, double fd_tolerance, int fd_mode, const int* si, const double* sd, double* k,
+                               double* K, int* status, int* failure) {
+  IlqgBp* d = IBP(p);
+  mjpc_hip::iLQGSettings s = IlqgBp::Settings(si, sd);
+  s.fd_tolerance = fd_tolerance; s.fd_mode = fd_mode;
+  d->Rows(T > 0 ? T : 1);
+  const bool ok = d->bp.ComputeFused(engine, &d->policy, x, u, h, residual, d->n, d->m, T > 0 ? T : 1, s, status, failure, mocap, userdata);
+  if (ok) d->Out(T, k, K);
+  return ok ? 0 : -1;
+}
+void mjpc_ilqg_bp_blocks(void* p, int T, double* Vx, double* Vxx, double* Qx, double* Qu, double* Qxx, double* Qxu, double* Quu, double* dV) {
+  IlqgBp* d = IBP(p);
+  const size_t Tz = T, n = d->n, m = d->m;
+  if (d->bp.Vx.size() < Tz * n || T < 1) return;
+  if (Vx) std::copy(d->bp.Vx.begin(), d->bp.Vx.begin() + Tz * n, Vx);
+  if (Vxx) std::copy(d->bp.Vxx.begin(), d->bp.Vxx.begin() + Tz * n * n, Vxx);
+  if (Qx) std::copy(d->bp.Qx.begin(), d->bp.Qx.begin() + (Tz - 1) * n, Qx);
+  if (Qu) std::copy(d->bp.Qu.begin(), d->bp.Qu.begin() + (Tz - 1) * m, Qu);
+  if (Qxx) std::copy(d->bp.Qxx.begin(), d->bp.Qxx.begin() + (Tz - 1) * n * n, Qxx);
+  if (Qxu) std::copy(d->bp.Qxu.begin(), d->bp.Qxu.begin() + (Tz - 1) * n * m, Qxu);
+  if (Quu) std::copy(d->bp.Quu.begin(), d->bp.Quu.begin() + (Tz - 1) * m * m, Quu);
+  if (dV) { dV[0] = d->bp.dV[0]; dV[1] = d->bp.dV[1]; }
+}
+void mjpc_ilqg_bp_regularization(void* p, const double* set, double* out) {
+  auto& b = IBP(p)->bp;
+  if (set) { b.regularization = set[0]; b.regularization_rate = set[1]; b.regularization_factor = set[2]; }
+  if (out) { out[0] = b.regularization; out[1] = b.regularization_rate; out[2] = b.regularization_factor; }
+}
+void mjpc_ilqg_bp_scale_regularization(void* p, double factor, double reg_min, double reg_max) { IBP(p)->bp.ScaleRegularization(factor, reg_min, reg_max); }
+void mjpc_ilqg_bp_update_regularization(void* p, double reg_min, double reg_max, double z, double s) { IBP(p)->bp.UpdateRegularization(reg_min, reg_max, z, s); }
+#undef IBP
+int mjpc_ilqg_boxqp(int n, const double* H, const double* g, const double* lower, const double* upper, double* res, double* R, int* index) {
+  return mjpc_hip::BoxQPSolve(res, R, index, H, g, n, lower, upper);
+}
+void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int* jnt_type, const int* jnt_qposadr, const int* jnt_dofadr, const double* ctrlrange,
+                             int representation, int horizon, const double* times, const double* states, const double* actions, const double* feedback_gain,
+                             double feedback_scaling, const double* state, double time, double* action) {
+  mjpc_hip::iLQGPolicy p;
+  p.Allocate(nq, nv, na, nu, njnt, jnt_type, jnt_qposadr, jnt_dofadr, ctrlrange, 0, 0, horizon, representation);
+  const size_t H = horizon, ds = nq + nv + na, nd = 2 * nv + na;
+  p.trajectory.times.assign(times, times + H);
+  p.trajectory.states.assign(states, states + H * ds);
+  p.trajectory.actions.assign(actions, actions + H * nu);
+  p.feedback_gain.assign(feedback_gain, feedback_gain + H * nu * nd);
+  p.feedback_scaling = feedback_scaling;
+  p.Action(action, state, time);
 }
 
 // ---- ModelDerivatives

@@ -6,7 +6,9 @@ ModelDerivatives: the evaluated knots go to the device in one mjpc_hip_transitio
 interpolated on the host with the reference's weights.  CostDerivatives: one mjpc_hip_cost_derivatives call under the engine's
 current cost table.  gradient_compute: the gradient planner's backward recursion on the host, bit-equal to the one
 HipBackend.trajectory_gradient runs on the device behind the two.  What iLQG, the gradient planner and iLQS linearise around; the gradient
-planner itself is cplanner.GradientPlanner, the host algorithms of iLQG and iLQS are not part of this package.  No CPU fallback: the step evaluations and the cost derivatives
+planner itself is cplanner.GradientPlanner.  ILQGBackwardPass, boxqp and ilqg_policy_action are iLQG's backward pass (Riccati recursion, box-constrained
+control solve, regularisation loop) and policy, on the host and on the device (HipBackend.ilqg_backward_pass / trajectory_ilqg); iLQG's feedback rollouts
+and line search, and iLQS, are not part of this package.  No CPU fallback: the step evaluations and the cost derivatives
 are the engine's kernels.
 """
 from __future__ import annotations
@@ -42,6 +44,21 @@ def _lib():
         lib.mjpc_cd_compute.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, _dp, C.c_int, C.c_int]
         lib.mjpc_cd_blocks.argtypes = [C.c_void_p, C.c_int] + [_dp] * 6; lib.mjpc_cd_blocks.restype = None
         lib.mjpc_gd_gradient_compute.argtypes = [C.c_int] * 3 + [_dp] * 9
+        lib.mjpc_ilqg_bp_create.restype = C.c_void_p
+        lib.mjpc_ilqg_bp_create.argtypes = [C.c_int] * 3
+        lib.mjpc_ilqg_bp_destroy.argtypes = [C.c_void_p]; lib.mjpc_ilqg_bp_destroy.restype = None
+        lib.mjpc_ilqg_bp_reset.argtypes = [C.c_void_p, C.c_int]; lib.mjpc_ilqg_bp_reset.restype = None
+        lib.mjpc_ilqg_bp_riccati_host.argtypes = [C.c_void_p, C.c_int] + [_dp] * 9 + [_ip, _dp, _dp, _dp, _ip]; lib.mjpc_ilqg_bp_riccati_host.restype = None
+        lib.mjpc_ilqg_bp_riccati.argtypes = [C.c_void_p, C.c_int, C.c_double] + [_dp] * 9 + [_ip, _dp, _dp, _dp]
+        lib.mjpc_ilqg_bp_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [_dp] * 9 + [_ip, _dp, _dp, _dp, _ip]
+        lib.mjpc_ilqg_bp_compute_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [_dp] * 6 + [C.c_double, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip]
+        lib.mjpc_ilqg_bp_blocks.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8; lib.mjpc_ilqg_bp_blocks.restype = None
+        lib.mjpc_ilqg_bp_regularization.argtypes = [C.c_void_p, _dp, _dp]; lib.mjpc_ilqg_bp_regularization.restype = None
+        lib.mjpc_ilqg_bp_scale_regularization.argtypes = [C.c_void_p] + [C.c_double] * 3; lib.mjpc_ilqg_bp_scale_regularization.restype = None
+        lib.mjpc_ilqg_bp_update_regularization.argtypes = [C.c_void_p] + [C.c_double] * 4; lib.mjpc_ilqg_bp_update_regularization.restype = None
+        lib.mjpc_ilqg_boxqp.argtypes = [C.c_int] + [_dp] * 6 + [_ip]
+        lib.mjpc_ilqg_policy_action.argtypes = [C.c_int] * 5 + [_ip] * 3 + [_dp, C.c_int, C.c_int] + [_dp] * 4 + [C.c_double, _dp, C.c_double, _dp]
+        lib.mjpc_ilqg_policy_action.restype = None
         _bound = True
     return lib
 
@@ -175,4 +192,171 @@ class ModelDerivatives:
         keep = {k: (v if v.size else np.zeros(1)) for k, v in o.items()}
         self.lib.mjpc_md_blocks(self.h, int(T), 0, *[keep[k].ctypes.data_as(_dp) for k in "ABCD"], keep["failure"].ctypes.data_as(_ip))
         o["evaluate"], o["interpolate"] = self._indices()
+        return o
+
+
+def boxqp(H, g, lower=None, upper=None, warm=None):
+    """BoxQPSolve on the host (no GPU): minimise 0.5 x'Hx + g'x over lower <= x <= upper by projected Newton steps (csrc/riccati.h has the
+    definition) from `warm` (zeros) clamped into the box -> dict(nfree (-1: H not positive definite on the free set), x [n], index [nfree]
+    the free dimensions ascending, R [nfree, nfree] the lower Cholesky factor of H[index][:, index])."""
+    H = np.ascontiguousarray(H, dtype=np.float64); n = H.shape[0]
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(n)
+    lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(n)
+    hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(n)
+    x = np.zeros(n) if warm is None else np.array(warm, dtype=np.float64).reshape(n)
+    R = np.zeros(n * n); index = np.zeros(max(n, 1), np.int32)
+    p = lambda a: None if a is None else a.ctypes.data_as(_dp)      # noqa: E731
+    nf = _lib().mjpc_ilqg_boxqp(n, p(H), p(g), p(lo), p(hi), p(x), p(R), index.ctypes.data_as(_ip))
+    k = max(nf, 0)
+    return dict(nfree=int(nf), x=x, index=index[:k].copy(), R=R[:k * k].reshape(k, k).copy())
+
+
+def ilqg_policy_action(model, times, states, actions, feedback_gain, time, state=None, representation=1, feedback_scaling=1.0):
+    """iLQGPolicy::Action on the host (no GPU): the nominal action interpolated at `time` (0 zero-order, 1 linear, 2 cubic), plus
+    feedback_scaling * K (state (-) nominal state) when a state is given, clamped to the ctrlrange.  times [H], states [H, nq+nv+na],
+    actions [H, nu], feedback_gain [H, nu, 2nv+na]."""
+    nq, nv, na, nu, njnt = (int(model[k]) for k in ("nq", "nv", "na", "nu", "njnt"))
+    ints = [np.ascontiguousarray(np.asarray(model[k], dtype=np.int32).reshape(-1)) for k in ("jnt_type", "jnt_qposadr", "jnt_dofadr")]
+    ints = [a if a.size else np.zeros(1, np.int32) for a in ints]
+    rng = np.ascontiguousarray(np.asarray(model["actuator_ctrlrange"], dtype=np.float64).reshape(-1))
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1); H = t.size
+    xs = np.ascontiguousarray(states, dtype=np.float64).reshape(H, nq + nv + na); us = np.ascontiguousarray(actions, dtype=np.float64).reshape(H, nu)
+    K = np.ascontiguousarray(feedback_gain, dtype=np.float64).reshape(H, nu * (2 * nv + na))
+    st = None if state is None else np.ascontiguousarray(state, dtype=np.float64).reshape(nq + nv + na)
+    out = np.zeros(nu)
+    _lib().mjpc_ilqg_policy_action(nq, nv, na, nu, njnt, *[a.ctypes.data_as(_ip) for a in ints], _ptr(rng), int(representation), H, _ptr(t), _ptr(xs),
+                                   _ptr(us), _ptr(K), float(feedback_scaling), None if st is None else _ptr(st), float(time), _ptr(out))
+    cplanner._check()
+    return out
+
+
+class ILQGBackwardPass:
+    """mjpc_hip::iLQGBackwardPass with its BoxQP: the backward pass of iLQG over given model and cost derivatives, on the host
+    (riccati_host, riccati: no GPU) or on the device (compute, compute_fused), bit-equal to each other.  Arrays as
+    HipBackend.ilqg_backward_pass; the results are dicts like its."""
+
+    def __init__(self, nd, nu, T=2):
+        self.nd, self.nu, self.T = int(nd), int(nu), int(T)
+        self.lib = _lib()
+        self.h = C.c_void_p(self.lib.mjpc_ilqg_bp_create(self.nd, self.nu, self.T))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mjpc_ilqg_bp_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, T=None):
+        self.lib.mjpc_ilqg_bp_reset(self.h, int(self.T if T is None else T))
+
+    @property
+    def regularization(self):
+        """(regularization, regularization_rate, regularization_factor)"""
+        o = np.zeros(3)
+        self.lib.mjpc_ilqg_bp_regularization(self.h, None, _ptr(o))
+        return tuple(float(v) for v in o)
+
+    @regularization.setter
+    def regularization(self, v):
+        s = np.array(v, dtype=np.float64).reshape(3)
+        self.lib.mjpc_ilqg_bp_regularization(self.h, _ptr(s), None)
+
+    def scale_regularization(self, factor, reg_min=1.0e-6, reg_max=1.0e6):
+        self.lib.mjpc_ilqg_bp_scale_regularization(self.h, float(factor), float(reg_min), float(reg_max))
+        return self.regularization
+
+    def update_regularization(self, z, s, reg_min=1.0e-6, reg_max=1.0e6):
+        self.lib.mjpc_ilqg_bp_update_regularization(self.h, float(reg_min), float(reg_max), float(z), float(s))
+        return self.regularization
+
+    def _args(self, A, B, cx, cu, cxx, cxu, cuu, actions, action_limits, regularization_type, action_limits_on, max_regularization_iterations,
+              min_regularization, max_regularization):
+        cx = np.ascontiguousarray(cx, dtype=np.float64).reshape(-1, self.nd); T = cx.shape[0]
+        nd, nu = self.nd, self.nu
+        need = dict(A=(T - 1) * nd * nd, B=(T - 1) * nd * nu, cu=T * nu, cxx=T * nd * nd, cxu=T * nd * nu, cuu=T * nu * nu)
+        arrs = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (A, B, cx, cu, cxx, cxu, cuu)]
+        for a, name in zip(arrs, ("A", "B", "cx", "cu", "cxx", "cxu", "cuu")):
+            if name in need and a.size < need[name]:
+                raise ValueError(f"ILQGBackwardPass: {name} holds {a.size} numbers, {need[name]} are needed")
+        if action_limits_on and (actions is None or action_limits is None):
+            raise ValueError("ILQGBackwardPass: actions and action_limits are needed with action_limits = 1")
+        act = None if actions is None else np.ascontiguousarray(actions, dtype=np.float64).reshape(-1)
+        lim = None if action_limits is None else np.ascontiguousarray(action_limits, dtype=np.float64).reshape(-1)
+        si = np.array([regularization_type, action_limits_on, max_regularization_iterations], np.int32)
+        sd = np.array([min_regularization, max_regularization], np.float64)
+        self.T = max(self.T, T)
+        return T, arrs, act, lim, si, sd
+
+    def _result(self, T, k, K, status):
+        nd, nu = self.nd, self.nu
+        o = dict(k=k, K=K, Vx=np.zeros((T, nd)), Vxx=np.zeros((T, nd, nd)), Qx=np.zeros((T - 1, nd)), Qu=np.zeros((T - 1, nu)), Qxx=np.zeros((T - 1, nd, nd)),
+                 Qxu=np.zeros((T - 1, nd, nu)), Quu=np.zeros((T - 1, nu, nu)), dV=np.zeros(2))
+        self.lib.mjpc_ilqg_bp_blocks(self.h, T, *[_ptr(o[n_]) for n_ in ("Vx", "Vxx", "Qx", "Qu", "Qxx", "Qxu", "Quu", "dV")])
+        reg = self.regularization
+        o["status"] = status; o["regularization"] = reg[0]; o["regularization_rate"] = reg[1]
+        return o
+
+    def _run(self, fn, head, A, B, cx, cu, cxx, cxu, cuu, actions, action_limits, regularization_type, action_limits_on, max_regularization_iterations,
+             min_regularization, max_regularization, fill, with_status=True):
+        T, arrs, act, lim, si, sd = self._args(A, B, cx, cu, cxx, cxu, cuu, actions, action_limits, regularization_type, action_limits_on,
+                                               max_regularization_iterations, min_regularization, max_regularization)
+        k = np.full((T, self.nu), float(fill)); K = np.full((T, self.nu, self.nd), float(fill)); st = np.zeros(3, np.int32)
+        p = lambda a: None if a is None else _ptr(a)      # noqa: E731
+        tail = [st.ctypes.data_as(_ip)] if with_status else []
+        rc = fn(self.h, *head(T), *[_ptr(a) for a in arrs], p(act), p(lim), si.ctypes.data_as(_ip), _ptr(sd), _ptr(k), _ptr(K), *tail)
+        cplanner._check()
+        return T, k, K, st, rc
+
+    def riccati_host(self, A, B, cx, cu, cxx, cxu, cuu, actions=None, action_limits=None, regularization_type=0, action_limits_on=1,
+                     max_regularization_iterations=5, min_regularization=1.0e-6, max_regularization=1.0e6, fill=0.0):
+        """the regularisation loop on the host (no GPU), from this object's regularization / rate / factor"""
+        T, k, K, st, _ = self._run(self.lib.mjpc_ilqg_bp_riccati_host, lambda T: (T,), A, B, cx, cu, cxx, cxu, cuu, actions, action_limits, regularization_type,
+                                   action_limits_on, max_regularization_iterations, min_regularization, max_regularization, fill)
+        return self._result(T, k, K, st)
+
+    def riccati(self, reg, A, B, cx, cu, cxx, cxu, cuu, actions=None, action_limits=None, regularization_type=0, action_limits_on=1,
+                max_regularization_iterations=5, min_regularization=1.0e-6, max_regularization=1.0e6, fill=0.0):
+        """iLQGBackwardPass::Riccati as the reference calls it: every sweep uses `reg`; status[0] is its return value (0 = complete, else
+        the failing time index).  The box-QP's warm start is the object's (zero after reset())."""
+        T, k, K, st, rc = self._run(self.lib.mjpc_ilqg_bp_riccati, lambda T: (T, float(reg)), A, B, cx, cu, cxx, cxu, cuu, actions, action_limits,
+                                    regularization_type, action_limits_on, max_regularization_iterations, min_regularization, max_regularization, fill,
+                                    with_status=False)
+        o = self._result(T, k, K, st)
+        o["status"] = int(rc)
+        return o
+
+    def compute(self, backend: HipBackend, A, B, cx, cu, cxx, cxu, cuu, actions=None, action_limits=None, regularization_type=0, action_limits_on=1,
+                max_regularization_iterations=5, min_regularization=1.0e-6, max_regularization=1.0e6, fill=0.0):
+        """the same on the device (mjpc_hip_ilqg_backward_pass)"""
+        T, k, K, st, rc = self._run(self.lib.mjpc_ilqg_bp_compute, lambda T: (backend.h, T), A, B, cx, cu, cxx, cxu, cuu, actions, action_limits,
+                                    regularization_type, action_limits_on, max_regularization_iterations, min_regularization, max_regularization, fill)
+        if rc != 0:
+            raise RuntimeError("ILQGBackwardPass.compute failed: " + self.lib.mjpc_hip_last_error().decode())
+        return self._result(T, k, K, st)
+
+    def compute_fused(self, backend: HipBackend, x, u, h, residual, mocap=None, userdata=None, tol=1e-6, mode=0, regularization_type=0,
+                      action_limits_on=1, max_regularization_iterations=5, min_regularization=1.0e-6, max_regularization=1.0e6):
+        """derivatives and backward pass in one device call (mjpc_hip_trajectory_ilqg); the object's dimensions must be the backend's model's"""
+        ds, nd, nu, nr = backend._dims()
+        if (nd, nu) != (self.nd, self.nu):
+            raise ValueError("ILQGBackwardPass.compute_fused: the object's dimensions are not the model's")
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, nu); h = np.ascontiguousarray(h, dtype=np.float64).reshape(T)
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(T, nr)
+        mo, ud, pmo, pud = backend._shared(mocap, userdata)
+        si = np.array([regularization_type, action_limits_on, max_regularization_iterations], np.int32)
+        sd = np.array([min_regularization, max_regularization], np.float64)
+        k = np.zeros((max(T, 1), nu)); K = np.zeros((max(T, 1), nu, nd)); st = np.zeros(3, np.int32); fail = np.zeros(max(T, 1), np.int32)
+        rc = self.lib.mjpc_ilqg_bp_compute_fused(self.h, backend.h, T, _ptr(x), _ptr(u), _ptr(h), _ptr(r), pmo, pud, float(tol), int(mode), si.ctypes.data_as(_ip),
+                                                 _ptr(sd), _ptr(k), _ptr(K), st.ctypes.data_as(_ip), fail.ctypes.data_as(_ip))
+        cplanner._check()
+        if rc != 0:
+            raise RuntimeError("ILQGBackwardPass.compute_fused failed: " + self.lib.mjpc_hip_last_error().decode())
+        self.T = max(self.T, T)
+        o = self._result(T, k, K, st)
+        o["failure"] = fail[:T]
         return o

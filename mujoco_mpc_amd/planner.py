@@ -212,6 +212,65 @@ class HipBackend:
         o["failure"] = o["failure"][:T]
         return o
 
+    @staticmethod
+    def _riccati_out(T, nd, nu):
+        return dict(k=np.zeros((T, nu)), K=np.zeros((T, nu, nd)), Vx=np.zeros((T, nd)), Vxx=np.zeros((T, nd, nd)), Qx=np.zeros((T - 1, nd)),
+                    Qu=np.zeros((T - 1, nu)), Qxx=np.zeros((T - 1, nd, nd)), Qxu=np.zeros((T - 1, nd, nu)), Quu=np.zeros((T - 1, nu, nu)), dV=np.zeros(2))
+
+    def ilqg_backward_pass(self, A, B, cx, cu, cxx, cxu, cuu, actions=None, action_limits=None, regularization=1.0, regularization_rate=1.0,
+                           settings=None, **kw):
+        """The iLQG backward pass on the device (mjpc_hip_ilqg_backward_pass): Riccati recursion with the box-constrained control solve and the
+        regularisation loop in one kernel.  cx [T, nd], cu [T, nu] give the dimensions (they need not be the engine's model's); A [T-1 or more,
+        nd, nd], B [.., nd, nu], cxx [T, nd, nd], cxu [T, nd, nu], cuu [T, nu, nu], actions [T-1 or more, nu], action_limits [nu, 2].  settings: a
+        capi.MjpcHipRiccatiSettings, or the keywords of capi.riccati_settings (regularization_type, action_limits_on, ...).  -> dict(k, K [T, nu, nd], Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status [3],
+        regularization, regularization_rate)."""
+        cx = np.ascontiguousarray(cx, dtype=np.float64); cu = np.ascontiguousarray(cu, dtype=np.float64)
+        T, nd = cx.shape; nu = cu.shape[1]
+        s = settings if settings is not None else capi.riccati_settings(**kw)
+        flat = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1)      # noqa: E731
+        ins = [flat(a) for a in (A, B, cx, cu, cxx, cxu, cuu, actions, action_limits)]
+        need = [(T - 1) * nd * nd, (T - 1) * nd * nu, T * nd, (T - 1) * nu, T * nd * nd, (T - 1) * nd * nu, (T - 1) * nu * nu, (T - 1) * nu, 2 * nu]
+        if T >= 2:
+            for a, n_, name in zip(ins, need, ("A", "B", "cx", "cu", "cxx", "cxu", "cuu", "actions", "action_limits")):
+                if a is not None and a.size < n_:
+                    raise ValueError(f"ilqg_backward_pass: {name} holds {a.size} numbers, {n_} are read")
+        o = self._riccati_out(max(T, 1), nd, nu)
+        reg = np.array([regularization, regularization_rate], dtype=np.float64); st = np.zeros(3, np.int32)
+        dp = capi.c_double_p
+        ptr = lambda a: None if a is None else (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_ilqg_backward_pass(self.h, T, nd, nu, *[ptr(a) for a in ins], C.byref(s), reg[0:].ctypes.data_as(dp), reg[1:].ctypes.data_as(dp),
+                                                  *[ptr(o[k]) for k in ("k", "K", "Vx", "Vxx", "Qx", "Qu", "Qxx", "Qxu", "Quu", "dV")],
+                                                  st.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_ilqg_backward_pass failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["status"] = st; o["regularization"] = float(reg[0]); o["regularization_rate"] = float(reg[1])
+        return o
+
+    def trajectory_ilqg(self, x, u, time, residual, mocap=None, userdata=None, eps=1e-6, centered=False, regularization=1.0, regularization_rate=1.0,
+                        settings=None, **kw):
+        """One derivative iteration of iLQG on the device (mjpc_hip_trajectory_ilqg): transition_fd with the last knot terminal, cost derivatives
+        with Hessians, backward pass; one download.  The action limits are the model's ctrlrange (an unlimited actuator: -inf, +inf).
+        -> the dict of ilqg_backward_pass plus failure [T]."""
+        ds, nd, nu, nr = self._dims()
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(T)
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(T, nr)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        s = settings if settings is not None else capi.riccati_settings(**kw)
+        o = self._riccati_out(max(T, 1), nd, nu)
+        fail = np.zeros(max(T, 1), np.int32)
+        reg = np.array([regularization, regularization_rate], dtype=np.float64); st = np.zeros(3, np.int32)
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_trajectory_ilqg(self.h, T, x.ctypes.data_as(dp), ptr(u), t.ctypes.data_as(dp), ptr(r), pmo, pud, float(eps), int(bool(centered)),
+                                               C.byref(s), reg[0:].ctypes.data_as(dp), reg[1:].ctypes.data_as(dp),
+                                               *[ptr(o[k]) for k in ("k", "K", "Vx", "Vxx", "Qx", "Qu", "Qxx", "Qxu", "Quu", "dV")],
+                                               st.ctypes.data_as(capi.c_int_p), fail.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_trajectory_ilqg failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["status"] = st; o["regularization"] = float(reg[0]); o["regularization_rate"] = float(reg[1]); o["failure"] = fail[:T]
+        return o
+
     def candidate(self, local_index, H, P):
         o, c, ntr = self._alloc_out(1, H, P)
         if self.lib.mjpc_hip_get_candidate(self.h, int(local_index), C.byref(c)) != 0:

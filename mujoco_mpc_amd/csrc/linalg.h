@@ -3,8 +3,9 @@
 //  * generic (any n, also the 1-lane emulation build): A = L L^T, left-looking in LDS, one SYNC pair per column,
 //    Linv[j] = 1/L[j][j];
 //  * NVT > 0 (gfx950 only, n == NVT known at compile time): A = L^T D L with lane i keeping ROW i of the matrix in VGPRs;
-//    pivots and rows are broadcast with v_readlane (no LDS traffic, no waits on the pivot chain); the substitutions keep x
-//    in a VGPR per lane.  A factor/solve pair always uses the same form (the layouts in LDS differ).
+//    pivots and rows are broadcast lane to lane (a 64-bit row DPP move where every consumer sits in the pivot's 16-lane row,
+//    v_readlane otherwise: no LDS traffic, no waits on the pivot chain); the substitutions keep x in a VGPR per lane.
+//    A factor/solve pair always uses the same form (the layouts in LDS differ).
 // One wave per matrix is latency-bound, so the register form is several times faster than the LDS form.
 #pragma once
 #include <type_traits>
@@ -18,6 +19,22 @@ DEV double readlane_d(double v, int lane) {
   int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
+}
+// Every lane reads lane (K & 15) of ITS OWN 16-lane row: one v_mov_b64_dpp row_newbcast, no SGPR pair and none of the wait
+// states between a v_readlane and the VALU instruction that consumes its SGPRs.  Needs full EXEC: a disabled source lane
+// yields zero, not its value.  The register factorisations below are therefore called with all 64 lanes enabled (they sit
+// between wave-uniform SYNCs) and mask their inactive lanes with `act ? ... : 0.0` selects, never with a divergent branch.
+// bound_ctrl is set although a row broadcast has no out-of-range source: with it (and full row / bank masks) the compiler
+// knows the old value of the destination is dead and does not zero the register pair ahead of every move.
+template <int K>
+DEV double rowbcast_d(double v) {
+  return __longlong_as_double(__builtin_amdgcn_update_dpp((long long)0, __double_as_longlong(v), 0x150 + (K & 15), 0xf, 0xf, true));
+}
+// broadcast of lane K: within the rows when LOCAL says that no lane outside K's row uses the value (see below), to the wave otherwise
+template <int K, bool LOCAL>
+DEV double bcast_d(double v) {
+  if constexpr (LOCAL) return rowbcast_d<K>(v);
+  else return readlane_d(v, K);
 }
 #endif
 
@@ -69,7 +86,18 @@ DEV void chol_solve_lds(const double *L, const double *Linv, double *x, int n, i
 //   readlane(d_k) -> rcp + 2 Newton steps -> l = a[k]*r -> d_{k-1} update;
 // the rank-1 update of the other columns is independent work the scheduler overlaps with that chain.
 // Afterwards lane i holds  up[k] = L[k][i] (k > i, else 0)  and  lo[j] = L[i][j] (j < i, else 0),
-// so both substitutions are "readlane + one FMA" per step.
+// so both substitutions are "broadcast + one FMA" per step.
+//
+// Row-local broadcasts keep the bits.  v_readlane hands lane k's value to all 64 lanes; rowbcast_d hands it to the lanes of
+// k's row only, the lanes of the other rows receive the value of THEIR row's lane k & 15 instead.  It is used where every
+// lane that multiplies the value by something non-zero lies in k's row (dense_up_local / dense_down_local here,
+// tree_up_local / tree_down_local for the level order).  A lane of another row receives a different but finite value (a
+// matrix entry, a positive reciprocal, a solution entry; 0.0 / 1.0 on inactive lanes) and multiplies it by a factor that is
+// exactly zero there: l = (i < k) ? .. : 0.0, or an entry of L outside the pattern, a product of a structural +0 with a
+// positive reciprocal.  The FMA then adds a zero to its accumulator: a non-zero accumulator is unchanged, and a +0 one stays
+// +0 whatever the sign of the product, exactly as with the value v_readlane would have delivered.
+template <int N> constexpr bool dense_up_local(int k) { return k < 16; }                               // consumers i < k: pivots 1..15, any N
+template <int N> constexpr bool dense_down_local(int j) { return (j >> 4) == ((N - 1) >> 4); }         // consumers j < i < N
 #ifndef MJPC_EMU
 template <int N>
 struct LDLRegs { double lo[N], up[N], rinv; };
@@ -125,16 +153,18 @@ DEV void ldl_factor_regs(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
   ldl_load_row<N>(A, nvp, ex, a, dg);
   static_for<1, N>([&](auto kc) {
     constexpr int k = N - decltype(kc)::value;                                 // N-1 ... 1
-    double rk = readlane_d(fast_rcp(dg < D_MINVAL ? D_MINVAL : dg), k);      // reciprocal in the vector domain, then broadcast
+    constexpr bool loc = dense_up_local<N>(k);
+    double rk = bcast_d<k, loc>(fast_rcp(dg < D_MINVAL ? D_MINVAL : dg));      // reciprocal in the vector domain, then broadcast
     double hk = a[k];
     double l = (i < k) ? hk * rk : 0.0;
     dg -= l * hk;
     // A[i][j] -= L[k][i] * A[k][j]: broadcast row k in groups of 8 first, then the FMAs, so that the SGPR written by a
-    // v_readlane is not consumed by the very next VALU instruction (that hazard costs an s_nop per update otherwise)
+    // v_readlane (or the VGPR a DPP move reads) is not touched by the very next VALU instruction (those hazards cost an
+    // s_nop per update otherwise)
     static_for<0, (k + 7) / 8>([&](auto gc) {
       constexpr int j0 = decltype(gc)::value * 8;
       double sj[8];
-      static_for<0, 8>([&](auto qc) { constexpr int q = decltype(qc)::value; if constexpr (j0 + q < k) sj[q] = readlane_d(a[j0 + q], k); });
+      static_for<0, 8>([&](auto qc) { constexpr int q = decltype(qc)::value; if constexpr (j0 + q < k) sj[q] = bcast_d<k, loc>(a[j0 + q]); });
       __builtin_amdgcn_sched_barrier(0);
       static_for<0, 8>([&](auto qc) { constexpr int q = decltype(qc)::value; if constexpr (j0 + q < k) a[j0 + q] -= l * sj[q]; });
       __builtin_amdgcn_sched_barrier(0);
@@ -148,9 +178,9 @@ DEV void ldl_factor_regs(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
 }
 template <int N>
 DEV double ldl_solve_regs(const LDLRegs<N> &f, double xi) {
-  static_for<1, N>([&](auto kc) { constexpr int k = N - decltype(kc)::value; xi -= f.up[k] * readlane_d(xi, k); });      // L^T u = b
+  static_for<1, N>([&](auto kc) { constexpr int k = N - decltype(kc)::value; xi -= f.up[k] * bcast_d<k, dense_up_local<N>(k)>(xi); });      // L^T u = b
   xi *= f.rinv;                                                                                                          // D v = u
-  static_for<0, N - 1>([&](auto jc) { constexpr int j = decltype(jc)::value; xi -= f.lo[j] * readlane_d(xi, j); });      // L x = v
+  static_for<0, N - 1>([&](auto jc) { constexpr int j = decltype(jc)::value; xi -= f.lo[j] * bcast_d<j, dense_down_local<N>(j)>(xi); });      // L x = v
   return xi;
 }
 // ---- tree-structured elimination (DofTree<N>::known, DevModel::tree_ok) ----------------------------------------------
@@ -176,6 +206,20 @@ template <int N> constexpr int tree_level_pair(int H, int e, bool pivot) {
   }
   return 0;
 }
+// Row-local broadcasts (rowbcast_d, see the argument above the dense routines).  Pivot k's reciprocal, its row and its
+// L^T u = b step are consumed by the ancestors of k only: local when all of them sit in k's 16-lane row.  Step j of L x = v
+// is consumed by the descendants of j: local when all of those sit in j's row.
+template <int N> constexpr bool tree_up_local(int k) { for (int a = DofTree<N>::parent(k); a >= 0; a = DofTree<N>::parent(a)) if ((a >> 4) != (k >> 4)) return false; return true; }
+template <int N> constexpr bool tree_is_anc(int j, int c) { for (int a = DofTree<N>::parent(c); a >= 0; a = DofTree<N>::parent(a)) if (a == j) return true; return false; }
+template <int N> constexpr bool tree_down_local(int j) { for (int c = j + 1; c < N; c++) if (tree_is_anc<N>(j, c) && (c >> 4) != (j >> 4)) return false; return true; }
+template <int N> constexpr int tree_npair(bool local_only) { int n = 0; for (int k = 1; k < N; k++) if (!local_only || tree_up_local<N>(k)) n += tree_depth<N>(k); return n; }
+template <int N> constexpr int tree_nup_local() { int n = 0; for (int k = 1; k < N; k++) n += tree_up_local<N>(k); return n; }
+template <int N> constexpr int tree_ndown(bool local_only) { int n = 0; for (int j = 0; j < N; j++) if (tree_height<N>(j) > 0 && (!local_only || tree_down_local<N>(j))) n++; return n; }
+// the quadruped (lane = dof): 84 of the 99 (pivot, ancestor) pairs are row-local, only the last two dofs of the fourth leg
+// reach back across the row boundary; 7 of the 14 steps of L x = v
+static_assert(tree_npair<18>(false) == 99 && tree_npair<18>(true) == 84, "DofTree<18>: row-local pairs");
+static_assert(tree_nup_local<18>() == 15 && !tree_up_local<18>(16) && !tree_up_local<18>(17), "DofTree<18>: pivots 16 and 17 cross the row boundary");
+static_assert(tree_ndown<18>(false) == 14 && tree_ndown<18>(true) == 7, "DofTree<18>: row-local steps of L x = v");
 #define TREE_BAR() __builtin_amdgcn_sched_barrier(0)
 template <int N>
 DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
@@ -192,7 +236,7 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
     const double rv = fast_rcp(dg < D_MINVAL ? D_MINVAL : dg);
     static_for<1, N>([&](auto kc) {
       constexpr int k = N - decltype(kc)::value;
-      if constexpr (tree_height<N>(k) == H) f.up[k] = readlane_d(rv, k);
+      if constexpr (tree_height<N>(k) == H) f.up[k] = bcast_d<k, tree_up_local<N>(k)>(rv);
     });
     static_for<1, N>([&](auto kc) {                       // l = L[k][i] on the ancestors of k, diagonal update
       constexpr int k = N - decltype(kc)::value;
@@ -204,7 +248,7 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
       }
     });
     constexpr int NP = tree_level_npair<N>(H);            // A[i][j] -= L[k][i] * A[k][j], j ancestor of k
-    constexpr int CHUNK = 8;                              // pairs fetched (readlane) ahead of their updates
+    constexpr int CHUNK = 8;                              // pairs fetched (broadcast) ahead of their updates
     static_for<0, (NP + CHUNK - 1) / CHUNK>([&](auto gc) {
       constexpr int e0 = decltype(gc)::value * CHUNK;
       double sj[CHUNK];
@@ -212,7 +256,7 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
         constexpr int q = decltype(qc)::value;
         if constexpr (e0 + q < NP) {
           constexpr int j = tree_level_pair<N>(H, e0 + q, false), k = tree_level_pair<N>(H, e0 + q, true);
-          sj[q] = readlane_d(a[j], k);
+          sj[q] = bcast_d<k, tree_up_local<N>(k)>(a[j]);
         }
       });
       TREE_BAR();
@@ -237,14 +281,14 @@ DEV double ldl_solve_tree(const LDLRegs<N> &f, double xi) {
   static_for<0, tree_nlevel<N>()>([&](auto hc) {          // L^T u = b, leaves first
     constexpr int H = decltype(hc)::value;
     double s[N];
-    static_for<1, N>([&](auto kc) { constexpr int k = N - decltype(kc)::value; if constexpr (tree_height<N>(k) == H) s[k] = readlane_d(xi, k); });
+    static_for<1, N>([&](auto kc) { constexpr int k = N - decltype(kc)::value; if constexpr (tree_height<N>(k) == H) s[k] = bcast_d<k, tree_up_local<N>(k)>(xi); });
     static_for<1, N>([&](auto kc) { constexpr int k = N - decltype(kc)::value; if constexpr (tree_height<N>(k) == H) xi -= f.up[k] * s[k]; });
   });
   xi *= f.rinv;                                           // D v = u
   static_for<1, tree_nlevel<N>()>([&](auto hc) {          // L x = v, root first (leaves have no descendants)
     constexpr int H = tree_nlevel<N>() - decltype(hc)::value;
     double s[N];
-    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; if constexpr (tree_height<N>(j) == H) s[j] = readlane_d(xi, j); });
+    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; if constexpr (tree_height<N>(j) == H) s[j] = bcast_d<j, tree_down_local<N>(j)>(xi); });
     static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; if constexpr (tree_height<N>(j) == H) xi -= f.lo[j] * s[j]; });
   });
   return xi;

@@ -455,7 +455,7 @@ DEV_NOINLINE void ph_solve_helper(KP Kc, int t) {
   Ctx c; ctx_open(c, Kc, 1);
   // helper k = wave k + 1 (each index is its own instantiation)
   int k = WAVE_ID() - 1;
-  static_for<0, MJPC_NH>([&](auto Kc_) { constexpr int KK = decltype(Kc_)::value; if (k == KK) solver_helper_loop<NVT, KK>(c, t * 256); });
+  static_for<0, MJPC_NH>([&](auto Kc_) { constexpr int KK = decltype(Kc_)::value; if (k == KK) solver_helper_loop<NVT, KK>(Kc, c, t * 256); });
 }
 #endif
 

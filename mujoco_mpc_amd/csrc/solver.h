@@ -446,12 +446,12 @@ DEV double cost_at_smooth(Ctx &c) {
 }
 
 #if MJPC_HELPER
-template <int NVT> DEV void worker_loop(Ctx &c, int W, int last);          // solver_reg.h
+template <int NVT> DEV void worker_loop(KP Kc, Ctx &c, int W, int last);          // solver_reg.h
 template <int NVT> DEV void ls_records_build(Ctx &c);
 // helper K of a solve phase: the last one prices the unconstrained acceleration; with a compile-time nv helper 0 builds the line
 // search's records and both then serve the owner's cone-block jobs (solver_reg.h).  A generic-nv kernel has no jobs for them.
 template <int NVT, int K>
-DEV void solver_helper_loop(Ctx &c, int seq) {
+DEV void solver_helper_loop(KP Kc, Ctx &c, int seq) {
   if (K == MJPC_NH - 1 && c.nefc > 0) {            // the last helper prices the unconstrained acceleration for the warm-start choice
     double cs = cost_at_smooth<NVT>(c);
     if (LANE == 0) c.red[2] = cs;
@@ -461,7 +461,7 @@ DEV void solver_helper_loop(Ctx &c, int seq) {
   }
   if constexpr (NVT > 0) {
     if (K == 0 && c.nefc > 0) { ls_records_build<NVT>(c); flag_set(c.misc + HX_LSREC, seq / 256 + 1); }     // the line search's per-step constants
-    worker_loop<NVT>(c, K, seq);
+    worker_loop<NVT>(Kc, c, K, seq);
   }
 }
 #endif

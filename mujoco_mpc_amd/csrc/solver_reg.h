@@ -141,14 +141,150 @@ static_assert(HX_WDONE + MJPC_NH <= HX_WDONE_END, "one done slot per worker");
 #define CONE_ITEMS(c) ((unsigned short *)(CONE_BASE(c) + ((c).M->nconmax * NVT + 7) / 8))
 #define CONE_PARTIAL(c, w) (CONE_BASE(c) + ((c).M->nconmax * NVT + 7) / 8 + ((c).M->nconmax * NVT + 3) / 4 + (w) * (NVT * NVP_OF(NVT)))
 
-// the passes p0, p0 + pstep, ... of 64 (contact, row) pairs into the partial `part` (zeroed by the caller)
+// t = B_c ji of a lane's row: P, Q, T as loaded from the contact's CON_H record, ji = J_c[:, dof_a]
+template <int DIMT>
+DEV void cone_row_t(double *P, double *Q, double *T, double *ji, int dim, double *t) {
+  if constexpr (DIMT > 3) {
+#pragma unroll
+    for (int k = 3; k < DIMT; k++) { const bool in = k < dim; P[k] = in ? P[k] : 0.0; Q[k] = in ? Q[k] : 0.0; T[k] = in ? T[k] : 0.0; ji[k] = in ? ji[k] : 0.0; }
+  }
+  double pi = P[0] * ji[0], qi = Q[1] * ji[1];
+#pragma unroll
+  for (int k = 1; k < DIMT; k++) { pi += P[k] * ji[k]; if (k > 1) qi += Q[k] * ji[k]; }
+  t[0] = P[0] * pi + Q[0] * ji[0];                      // Q_0's slot: 0 in the cone zone, D_0 in the quadratic zone
+#pragma unroll
+  for (int k = 1; k < DIMT; k++) t[k] = P[k] * pi - Q[k] * qi + (T[k] * T[k]) * ji[k];
+}
+// one column trip of a lane's row: t . x0 into entry j0 (lanes with on0), t . x1 into entry j1 (lanes with on1) of the partial's row
+template <int DIMT>
+DEV void cone_trip_add(double *prow, const double *t, const double *x0, const double *x1, int j0, int j1, bool on0, bool on1) {
+  double v0 = t[0] * x0[0], v1 = t[0] * x1[0];
+#pragma unroll
+  for (int k = 1; k < DIMT; k++) { v0 += t[k] * x0[k]; v1 += t[k] * x1[k]; }
+  if (on0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)(prow + j0), v0);
+  if (on1) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)(prow + j1), v1);
+}
+// the column trips from column b on with everything read from LDS: the target dofs from the contact's dof list, J_c from efc_J
 template <int NVT, int DIMT>
-DEV void cone_rows(const Ctx &c, double *part, int p0, int pstep) {
+DEV void cone_trips_lds(const unsigned char *dofs, const double *Jr, int dim, double *prow, const double *t, bool active, int a, int b) {
   constexpr int nvp = NVP_OF(NVT);
-  const int nitems = uniform_i(c.misc[HX_NITEMS]), stride = c.M->con_stride;
+  for (; __builtin_amdgcn_ballot_w64(active && b <= a) != 0; b += 2) {
+    const bool on0 = active && b <= a, on1 = active && b + 1 <= a;
+    const int j0 = dofs[on0 ? b : 0], j1 = dofs[on1 ? b + 1 : 0];
+    double x0[DIMT], x1[DIMT];
+#pragma unroll
+    for (int k = 0; k < DIMT; k++) { x0[k] = Jr[(DIMT <= 3 || k < dim ? k : 0) * nvp + j0]; x1[k] = Jr[(DIMT <= 3 || k < dim ? k : 0) * nvp + j1]; }
+    __builtin_amdgcn_sched_barrier(0);
+    cone_trip_add<DIMT>(prow, t, x0, x1, j0, j1, on0, on1);
+  }
+}
+#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
+#define CONE_PROF_COUNT(c, active, first) do { if (MJPC_PROFILE_WAVE != 0 && WAVE_ID() == MJPC_PROFILE_WAVE) { int na_ = __builtin_popcountll(__builtin_amdgcn_ballot_w64(active)); if (LANE == 0) { (c).prof[23] += na_; (c).prof[22] += (first); } } } while (0)      // active rows / jobs of this worker (diagnostics)
+#else
+#define CONE_PROF_COUNT(c, active, first) ((void)0)
+#endif
+
+// What a worker keeps in registers for one step: the item of its FIRST pass (pass W of 64 (contact, row) pairs), decoded once.
+// Between the Newton iterates of a step only the contact's zone, its CON_H record and the zeroed partial change; the item list,
+// the contact's dof list, its first row and dim and every Jacobian entry are fixed once make_contact_rows and ls_records_build have
+// run, so a job does not have to walk items -> record -> dof list -> efc_J (four dependent LDS round trips) and then two more per
+// column trip again.  CAP = the columns b < CAP of the row whose target dof and J_c[:, dof_b] are kept (even: trips take two
+// columns); columns from CAP on and every later pass of the worker read LDS as before.  10 covers the 9 dofs of an
+// A1 foot contact.  DIMT = 6 (the A1's feet are condim 6) costs 12 registers per column: 120 of the 248 the loop then uses, within
+// the budget of a flavour with one workgroup per CU; the two-per-CU flavours (256 registers per wave) keep 4 columns.  No flavour
+// touches scratch inside the loop (worker_phase below saves callee-saved registers at entry and exit).
+template <int DIMT> struct ConeCap {
+#if defined(MJPC_MIN_BLOCKS) && MJPC_MIN_BLOCKS > 1
+  static constexpr int CAP = DIMT <= 3 ? 10 : 4;
+#else
+  static constexpr int CAP = 10;
+#endif
+};
+template <int NVT, int DIMT>
+struct ConePre {
+  static constexpr int CAP = ConeCap<DIMT>::CAP;
+  int nitems;                     // (wave-uniform)
+  int valid, a, r0, dim, ci, poff;          // poff = dof_a * nvp: the lane's row of the partial
+  double ji[DIMT];
+  int j[CAP];
+  double x[CAP][DIMT];
+};
+// decode pass W into registers.  Reads the records helper 0 publishes with HX_LSREC: the caller has seen that flag (or is helper 0).
+// A lane without an item loads nothing (a step without an elliptic contact leaves stale items behind).
+template <int NVT, int DIMT>
+DEV void cone_preload(const Ctx &c, int W, bool built, ConePre<NVT, DIMT> &p) {
+  constexpr int nvp = NVP_OF(NVT), CAP = ConePre<NVT, DIMT>::CAP;
+  p.nitems = built ? uniform_i(c.misc[HX_NITEMS]) : 0;
+  const int it = W * NLANE + LANE;
+  p.valid = it < p.nitems;
+  p.a = 0; p.r0 = 0; p.dim = 0; p.ci = 0; p.poff = 0;
+#pragma unroll
+  for (int k = 0; k < DIMT; k++) p.ji[k] = 0.0;
+#pragma unroll
+  for (int b = 0; b < CAP; b++) {
+    p.j[b] = 0;
+#pragma unroll
+    for (int k = 0; k < DIMT; k++) p.x[b][k] = 0.0;
+  }
+  if (p.valid) {
+    const int item = CONE_ITEMS(c)[it];
+    p.ci = item & 255; p.a = item >> 8;
+    const int info = ((const int *)(LS_CONREC(c) + p.ci * LSC_STRIDE + 14))[0];        // on | dim << 8 | first row << 16
+    p.r0 = info >> 16; p.dim = (info >> 8) & 255;
+    const unsigned char *dofs = CONE_DOFS(c) + p.ci * NVT;
+    const double *Jr = c.efc_J + p.r0 * nvp;
+    const int i = dofs[p.a];
+    p.poff = i * nvp;
+#pragma unroll
+    for (int k = 0; k < DIMT; k++) p.ji[k] = Jr[(DIMT <= 3 || k < p.dim ? k : 0) * nvp + i];
+#pragma unroll
+    for (int b = 0; b < CAP; b++) {
+      // (a trip reads column b + 1 of a lane whose row ends at b as column 0 and does not add it: any value serves)
+      const int jb = dofs[b <= p.a ? b : 0];
+      p.j[b] = jb;
+#pragma unroll
+      for (int k = 0; k < DIMT; k++) p.x[b][k] = Jr[(DIMT <= 3 || k < p.dim ? k : 0) * nvp + jb];
+    }
+  }
+}
+
+// the passes p0, p0 + pstep, ... of 64 (contact, row) pairs into the partial `part` (zeroed by the caller).
+// Determinism: the bits of the partial depend on the sequence of ds_add_f64 instructions the worker issues
+// into it and on what each lane adds.  Pass p0 from the registers issues the same trips in the same order with the same two
+// columns each, the same ballot exit, and forms pi, qi, t[], v0, v1 with the same expressions (cone_row_t, cone_trip_add are
+// shared with the LDS path) from the same values - only where ji, j_b and x_b come from differs.  So the partial is bit-identical.
+template <int NVT, int DIMT>
+DEV void cone_rows(const Ctx &c, double *part, int p0, int pstep, const ConePre<NVT, DIMT> &pre) {
+  constexpr int nvp = NVP_OF(NVT), CAP = ConePre<NVT, DIMT>::CAP;
+  const int nitems = pre.nitems, stride = c.M->con_stride;
   const unsigned short *items = CONE_ITEMS(c);
   const double *crec = LS_CONREC(c);
-  for (int it0 = p0 * NLANE; it0 < nitems; it0 += pstep * NLANE) {
+  int it0 = p0 * NLANE;
+  if (it0 < nitems) {
+    // pass p0: the worker's registers; only the contact's zone and its CON_H record are loaded
+    const int st = c.efc_state[pre.r0];
+    const double *cf = c.contact + pre.ci * stride + CON_H;
+    double P[DIMT], Q[DIMT], T[DIMT], ji[DIMT], t[DIMT];
+#pragma unroll
+    for (int k = 0; k < DIMT; k++) { P[k] = cf[k]; Q[k] = cf[6 + k]; T[k] = cf[12 + k]; ji[k] = pre.ji[k]; }
+    __builtin_amdgcn_sched_barrier(0);
+    const bool active = pre.valid && st == STATE_CONE;
+    const int a = pre.a;
+    CONE_PROF_COUNT(c, active, 1);
+    cone_row_t<DIMT>(P, Q, T, ji, pre.dim, t);
+    double *prow = part + pre.poff;
+    PROFW(c, 16);
+    int b = 0;
+#pragma unroll
+    for (int u = 0; u < CAP; u += 2) {
+      if (__builtin_amdgcn_ballot_w64(active && u <= a) == 0) break;
+      cone_trip_add<DIMT>(prow, t, pre.x[u], pre.x[u + 1], pre.j[u], pre.j[u + 1], active && u <= a, active && u + 1 <= a);
+      b = u + 2;
+    }
+    cone_trips_lds<NVT, DIMT>(CONE_DOFS(c) + pre.ci * NVT, c.efc_J + pre.r0 * nvp, pre.dim, prow, t, active, a, b);
+    it0 += pstep * NLANE;
+  }
+  for (; it0 < nitems; it0 += pstep * NLANE) {
     const int it = it0 + LANE;
     const bool valid = it < nitems;
     const int item = items[valid ? it : 0];
@@ -167,63 +303,37 @@ DEV void cone_rows(const Ctx &c, double *part, int p0, int pstep) {
     for (int k = 0; k < DIMT; k++) ji[k] = Jr[(DIMT <= 3 || k < dim ? k : 0) * nvp + i];
     __builtin_amdgcn_sched_barrier(0);
     const bool active = valid && st == STATE_CONE;
-#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
-    if (MJPC_PROFILE_WAVE != 0 && WAVE_ID() == MJPC_PROFILE_WAVE) { int na_ = __builtin_popcountll(__builtin_amdgcn_ballot_w64(active)); if (LANE == 0) { c.prof[23] += na_; c.prof[22] += (it0 == p0 * NLANE); } }      // active rows / jobs of this worker (diagnostics)
-#endif
-    if constexpr (DIMT > 3) {
-#pragma unroll
-      for (int k = 3; k < DIMT; k++) { const bool in = k < dim; P[k] = in ? P[k] : 0.0; Q[k] = in ? Q[k] : 0.0; T[k] = in ? T[k] : 0.0; ji[k] = in ? ji[k] : 0.0; }
-    }
-    double pi = P[0] * ji[0], qi = Q[1] * ji[1];
-#pragma unroll
-    for (int k = 1; k < DIMT; k++) { pi += P[k] * ji[k]; if (k > 1) qi += Q[k] * ji[k]; }
+    CONE_PROF_COUNT(c, active, 0);
     double t[DIMT];
-    t[0] = P[0] * pi + Q[0] * ji[0];                      // Q_0's slot: 0 in the cone zone, D_0 in the quadratic zone
-#pragma unroll
-    for (int k = 1; k < DIMT; k++) t[k] = P[k] * pi - Q[k] * qi + (T[k] * T[k]) * ji[k];
+    cone_row_t<DIMT>(P, Q, T, ji, dim, t);
     double *prow = part + i * nvp;
     PROFW(c, 16);
     // columns b <= a of the lane's row, two per trip
-    for (int b = 0; __builtin_amdgcn_ballot_w64(active && b <= a) != 0; b += 2) {
-      const bool on0 = active && b <= a, on1 = active && b + 1 <= a;
-      const int j0 = dofs[on0 ? b : 0], j1 = dofs[on1 ? b + 1 : 0];
-      double x0[DIMT], x1[DIMT];
-#pragma unroll
-      for (int k = 0; k < DIMT; k++) { x0[k] = Jr[(DIMT <= 3 || k < dim ? k : 0) * nvp + j0]; x1[k] = Jr[(DIMT <= 3 || k < dim ? k : 0) * nvp + j1]; }
-      __builtin_amdgcn_sched_barrier(0);
-      double v0 = t[0] * x0[0], v1 = t[0] * x1[0];
-#pragma unroll
-      for (int k = 1; k < DIMT; k++) { v0 += t[k] * x0[k]; v1 += t[k] * x1[k]; }
-      if (on0) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)(prow + j0), v0);
-      if (on1) __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)(prow + j1), v1);
-    }
+    cone_trips_lds<NVT, DIMT>(dofs, Jr, dim, prow, t, active, a, 0);
   }
 }
 
 DEV int jobw_load(const Ctx &c) { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(c.misc + HX_JOBW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 // owner: post the job of the iterate whose zones / cone records are in LDS; returns the number of workers it was cut for
 // (always the same workers: the partition of the sums - and with it every rounding - must not depend on timing).
-// side_in is what is left of the side wave as a third worker (measured slower): always 0.  Dropping the
-// argument changes the order of ph_solve's instructions, so it waits for a change that measures the kernel.
-DEV int job_post(Ctx &c, int kind, int &side_in) {
+DEV int job_post(Ctx &c, int kind) {
   if (c.M->cone != 1) return 0;
   const int seq = ++c.hseq;
-  const int np = MJPC_NH + (side_in ? 1 : 0);
-  flag_set(c.misc + HX_JOBW, JOBW(seq, np, kind));
-  return np;
+  flag_set(c.misc + HX_JOBW, JOBW(seq, MJPC_NH, kind));
+  return MJPC_NH;
 }
 DEV void job_wait(Ctx &c, int np) {
   const int seq = c.hseq;
   for (int k = 0; k < np; k++) if (!flag_wait(c.misc + HX_WDONE + k, seq)) c.warning |= WARN_SYNC;
 }
 template <int NVT, int DIMT>
-DEV void worker_job(Ctx &c, int W, int np, int seq) {
+DEV void worker_job(Ctx &c, int W, int np, int seq, const ConePre<NVT, DIMT> &pre) {
   constexpr int nvp = NVP_OF(NVT);
   PROFW(c, 12);
   double *part = CONE_PARTIAL(c, W);
   PFOR(e, NVT * nvp) part[e] = 0;
   PROFW(c, 15);
-  cone_rows<NVT, DIMT>(c, part, W, np);
+  cone_rows<NVT, DIMT>(c, part, W, np, pre);
   PROFW(c, 13);
   flag_set(c.misc + HX_WDONE + W, seq);
   PROFW(c, 14);
@@ -233,6 +343,10 @@ template <int NVT, int DIMT>
 DEV void worker_loop_d(Ctx &c, int W, int last) {
   // the contact records the cone blocks walk are helper 0's first job of the solve phase
   if (W != 0 && c.nefc > 0 && !flag_wait(c.misc + HX_LSREC, (last >> 8) + 1)) return;
+  // the records are up (helper 0 built them itself): the worker's first pass goes to registers while the owner still prices the
+  // warm start.  A step that never posts a job (no contact in its cone zone, nefc == 0) only pays this decode and is released as before.
+  ConePre<NVT, DIMT> pre;
+  cone_preload<NVT, DIMT>(c, W, c.nefc > 0, pre);
   for (;;) {
     int word = 0, ok = 0;
     for (int n = 0; n < (1 << 21); n++) { word = jobw_load(c); if ((word >> 4) > last) { ok = 1; break; } }
@@ -241,13 +355,21 @@ DEV void worker_loop_d(Ctx &c, int W, int last) {
     const int kind = word & 3, np = (word >> 2) & 3;
     if (kind == 0) return;
     last = word >> 4;
-    if (W < np) worker_job<NVT, DIMT>(c, W, np, last);
+    if (W < np) worker_job<NVT, DIMT>(c, W, np, last, pre);
   }
 }
+// The loop is a function of its own: the registers of ConePre reach into the callee-saved ones, and a callable function saves and
+// restores those in scratch at entry and exit.  Here that happens behind the helpers' per-step work (the warm-start price, the
+// line-search records: what the owner waits for first), and a pyramidal model, which has no job, never pays it.
+template <int NVT, int DIMT>
+DEV_NOINLINE void worker_phase(KP Kc, int W, int last) {
+  Ctx c; ctx_open(c, Kc, 1);
+  worker_loop_d<NVT, DIMT>(c, uniform_i(W), uniform_i(last));
+}
 template <int NVT>
-DEV void worker_loop(Ctx &c, int W, int last) {
+DEV void worker_loop(KP Kc, Ctx &c, int W, int last) {
   if (c.M->cone != 1) return;
-  if (c.M->maxdim <= 3) worker_loop_d<NVT, 3>(c, W, last); else worker_loop_d<NVT, 6>(c, W, last);
+  if (c.M->maxdim <= 3) worker_phase<NVT, 3>(Kc, W, last); else worker_phase<NVT, 6>(Kc, W, last);
 }
 
 // qH = hq + diag of the single-entry rows: the owner's part of the Hessian.  The elliptic contacts' blocks are the workers'
@@ -617,7 +739,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     cost = cost_ws;
   }
   PROF(c, 12);
-  int np = 0, side_in = 0;
+  int np = 0;
   // contacts in their cone (middle) zone: only those have an iterate-dependent block (the workers' job); none => no job at all
   int ncone = 0;
   if (c.M->cone == 1) {
@@ -626,7 +748,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     const int stc = c.efc_state[r0c];
     ncone = __builtin_popcountll(__builtin_amdgcn_ballot_w64(LANE < c.ncon && dim > 1 && stc == STATE_CONE));
   }
-  if (ncone) np = job_post(c, 1, side_in);
+  if (ncone) np = job_post(c, 1);
   double hq[CB];
   hblock_init<NVT>(c, hq, hi, j0);
   PROF(c, 15);
@@ -705,7 +827,7 @@ DEV void solve_constraints_reg_d(Ctx &c) {
     PROF(c, 12);
     const double improvement = scale * (oldcost - cost);
     const int stop = improvement < M.tolerance || (c.warning & WARN_SYNC) != 0;
-    np = (stop || !ncone) ? 0 : job_post(c, 1, side_in);
+    np = (stop || !ncone) ? 0 : job_post(c, 1);
     if (!stop) {
 #pragma unroll
       for (int k = 0; k < LS_RPL; k++) { if (k >= d.nslot) break; hblock_add_rows<NVT>(c, hq, chg_mask[k], NLANE * k, chg_w[k], hi, j0); }

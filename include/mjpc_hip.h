@@ -520,6 +520,47 @@ int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const dou
                              const double *mocap, const double *userdata, double eps, int centered, const MjpcHipRiccatiSettings *s,
                              double *regularization, double *regularization_rate, double *k, double *K, double *Vx, double *Vxx, double *Qx,
                              double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status, int *failure);
+/* ---- Rollouts under a feedback policy (iLQG's ActionRollouts / FeedbackRollouts, mjpc/planners/ilqg/planner.cc:618-712) ------------
+ * Candidate i of the batch applies at step t < H-1, with x_t its own state at that step,
+ *   u = clamp( (ubar[t] + action_step[i] * kbar[t]) + feedback_scaling[i] * ( Kbar[t] * StateDiff(xbar[t], x_t) ), ctrlrange )
+ * StateDiff = mj_differentiatePos over the positions (quaternions: body-frame rotation vector of xbar^-1 x) and plain differences
+ * of velocities and activations, tangent order [dq(nv), dv(nv), dact(na)]; nd = 2nv+na, ds = nq+nv+na.
+ *   mode MJPC_FEEDBACK_INDEXED: ubar[t], kbar[t], xbar[t], Kbar[t] are row t of the policy's arrays (T >= H)  - Trajectory::RolloutDiscrete
+ *   mode MJPC_FEEDBACK_TIME:    they are the policy interpolated at the step's time (zero / linear / cubic by `representation`, the
+ *     actions, improvement and gains over the first T-1 knots, the states over all T with their quaternions renormalised; zero-order
+ *     outside the knots): iLQGPolicy::Action.  The step times are in->time + t timesteps, accumulated as the rollout does; the
+ *     tables are resampled once per call on the device, the rollout never interpolates.
+ * use_feedback = 0 skips the feedback term (it is not multiplied by zero); action_improvement = NULL skips the action_step term.
+ * Arithmetic: mjpc_hip::iLQGPolicy::Action's - every row of Kbar dx from 0.0 in ascending index with one rounded product and one rounded
+ * add, each scaled add one product and one add, the clamp last - so the recorded action of a step equals that function at the recorded
+ * state of the step bit for bit (the angle of a quaternion tangent comes from one correctly rounded atan2 that host and device share,
+ * csrc/atan2_cr.h, not from either side's math library).
+ * Of `in` only state, mocap, userdata, time, horizon, num_trajectory and candidate_offset are read: the engine rolls out the candidates
+ * [candidate_offset, num_trajectory).  Full capacity only
+ * (no dense tier): the reference caps the batch at kMaxTrajectory = 128.  Outputs, mjpc_hip_plan_fetch and the mjpc_hip_get_* calls
+ * behave as after mjpc_hip_plan; there are no knots (winner_knots is left untouched, mjpc_hip_get_knots copies nothing).
+ * Errors: a plan in flight, a batch above the engine's max_local (max_samples), horizon out of range, T < 2, indexed mode with T < H, an unknown mode or
+ * representation, null arrays, a NaN in action_step / feedback_scaling, policy->struct_size. */
+enum { MJPC_FEEDBACK_INDEXED = 0, MJPC_FEEDBACK_TIME = 1 };
+typedef struct MjpcHipFeedbackPolicy {
+  int struct_size;                  /* sizeof(MjpcHipFeedbackPolicy) */
+  int mode;                         /* MJPC_FEEDBACK_* */
+  int T;                            /* number of knots */
+  int representation;               /* MJPC_SPLINE_* (0 zero, 1 linear, 2 cubic): read in MJPC_FEEDBACK_TIME mode */
+  const double *times;              /* [T] */
+  const double *states;             /* [T][ds] */
+  const double *actions;            /* [T][nu] */
+  const double *feedback_gain;      /* [T][nu][nd] */
+  const double *action_improvement; /* [T][nu] or NULL */
+  const double *action_step;        /* [num_trajectory] alpha_i (global indexing) */
+  const double *feedback_scaling;   /* [num_trajectory] s_i (global indexing) */
+  int use_feedback;                 /* 0: no feedback term (the reference's state == NULL) */
+} MjpcHipFeedbackPolicy;
+int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, const MjpcHipFeedbackPolicy *policy);
+int mjpc_hip_plan_feedback(MjpcHipEngine *e, const MjpcHipPlanInput *in, const MjpcHipFeedbackPolicy *policy, MjpcHipPlanOutput *out);
+/* Device time of the last call's resampling kernel in microseconds (0 in indexed mode); valid after the fetch. */
+double mjpc_hip_feedback_resample_time_us(MjpcHipEngine *e);
+int mjpc_hip_sizeof_feedback_policy(void);
 /* Bytes of the backward-pass kernel's work image at (nd, nu), and where it lies: *in_lds = 1 in the workgroup's LDS (up to 160 KiB),
  * 0 in a global-memory scratch of the same layout.  Host only, no GPU needed. */
 int mjpc_hip_riccati_layout_bytes(int nd, int nu, int *in_lds);

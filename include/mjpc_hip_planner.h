@@ -523,8 +523,8 @@ class GradientPlanner {
   mutable std::shared_mutex mtx_;
 };
 
-// ---- the iLQG backward pass (mjpc/planners/ilqg/): boxqp.h, settings.h, policy.{h,cc}, backward_pass.{h,cc}.  The planner around it
-// (feedback rollouts, line search) is not built; these are the reference's public components, which its iLQS drives as well.
+// ---- iLQG (mjpc/planners/ilqg/): boxqp.h, settings.h, policy.{h,cc}, backward_pass.{h,cc}, and the planner (iLQGPlanner, at the end of
+// this header).  The components are the reference's public ones, which its iLQS drives as well.
 // ilqg/boxqp.h: storage of the box-constrained control solve
 class BoxQP {
  public:
@@ -579,6 +579,7 @@ class iLQGPolicy {
   mutable std::vector<double> state_scratch, action_scratch, feedback_gain_scratch, state_interp;
 };
 // utilities.cc:525-535 over the joint tables above: ds [2nv+na] = (s2 (-) s1) / h
+// (the angle of a quaternion tangent comes from csrc/atan2_cr.h, a correctly rounded atan2 the feedback rollout kernel shares: DESIGN 8h)
 void StateDiff(const iLQGPolicy& dims, double* ds, const double* s1, const double* s2, double h);
 
 // ilqg/backward_pass.{h,cc}.  RiccatiStep and Riccati run on the host by the summation rule of csrc/riccati.h, bit-equal to the device's
@@ -614,6 +615,71 @@ class iLQGBackwardPass {
   std::vector<double> Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, Q_scratch;
   double dV[2] = {0.0, 0.0};
   double regularization = 1.0, regularization_rate = 1.0, regularization_factor = 2.0;
+};
+
+// ilqg/planner.{h,cc}:156-223, 377-712 on one engine.  OptimizePolicy = NominalTrajectory + Iteration.
+//  - NominalTrajectory: ONE mjpc_hip_plan_feedback in time mode over `policy` (FeedbackRollouts): candidate i has feedback scale
+//    linesearch_steps[i] (LogScale(1, min_linesearch_step) with the last 0), no action step; the best rollout becomes candidate.trajectory
+//    and feedback_scaling its step.  All candidates failed: candidate.trajectory = policy.trajectory, feedback_scaling = 0.
+//  - Iteration: derivatives and backward pass of candidate.trajectory (fused: one mjpc_hip_trajectory_ilqg; composed: ModelDerivatives,
+//    CostDerivatives, iLQGBackwardPass::Compute) into candidate's gains and improvement; a failed pass returns early, the policy unchanged.
+//    ONE mjpc_hip_plan_feedback in indexed mode (ActionRollouts): action step linesearch_steps[i], feedback scale 1.  The winner is
+//    picked on the host by BestRollout (from the last index down, strict <: the highest index wins a tie).  The adopted policy is the
+//    reference's candidate_policy[winner]: gains and improvement of the pass, the NOMINAL's states, actions ubar + step k (unclamped) -
+//    except for winner 0, whose slot the reference has by then overwritten with the winning rollout itself (planner.cc:561 before :596).
+//    previous_policy = policy; policy.feedback_scaling = 1.
+constexpr int kMaxiLQGTrajectory = 128;        // kMaxTrajectory (planners/planner.h:28): the reference's cap on the batch
+class iLQGPlanner {
+ public:
+  iLQGPlanner() = default;
+  ~iLQGPlanner();
+  iLQGPlanner(const iLQGPlanner&) = delete;
+  iLQGPlanner& operator=(const iLQGPlanner&) = delete;
+
+  void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
+  void Allocate();
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void SetTask(const MjpcHipTask* task);
+  void OptimizePolicy(int horizon);
+  bool NominalTrajectory(int horizon);                 // false: refused (horizon out of range, engine error); nothing was changed
+  void Iteration(int horizon);                         // only behind a NominalTrajectory of the same horizon that returned true
+  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
+  const Trajectory* BestTrajectory() { return winner >= 0 ? &trajectory_winner : nullptr; }
+  // planner.cc:715-729: -1 when every candidate failed
+  static int BestRollout(const double* returns, const int* failures, int n);
+  static void LogScale(double* values, double max_value, double min_value, int steps);
+
+  iLQGPolicy policy, previous_policy, candidate;       // candidate: candidate_policy[0]
+  iLQGSettings settings;
+  iLQGBackwardPass backward_pass;
+  ModelDerivatives model_derivative;
+  CostDerivatives cost_derivative;
+  std::vector<double> state, mocap, userdata;
+  double time = 0;
+  std::vector<double> returns, linesearch_steps;       // of the last batch of rollouts
+  std::vector<int> failures;
+  Trajectory trajectory_winner;                        // the winning rollout of the last ActionRollouts
+  int num_trajectory = 10;                             // ilqg_num_rollouts
+  int representation = kLinearSpline;                  // ilqg_representation
+  int winner = -1, derivative_skip_ = 0;
+  bool fused = true;                                   // derivatives + backward pass in one device call (derivative_skip == 0 only)
+  bool backward_pass_failed = false, all_failed = false;    // of the last OptimizePolicy
+  int backward_pass_status[3] = {0, 0, 0};
+  double feedback_scaling = 1.0, action_step = 0, expected = 0, improvement = 0, surprise = 0;
+  double nominal_compute_time = 0, derivative_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;   // microseconds
+  double resample_kernel_time = 0, rollout_kernel_time = 0;       // device times of the last NominalTrajectory's resampling / last rollouts
+
+ private:
+  bool Rollouts(const iLQGPolicy& p, int mode, int horizon, const double* action_step, const double* feedback_scaling, bool use_feedback, bool improvement);
+  bool Fetch(int index, int horizon, Trajectory& tr);
+  MjpcHipEngine* engine_ = nullptr;
+  Numerics numerics_;
+  int ns_ = 0, nd_ = 0, nu_ = 0, nr_ = 0, ntrace_ = 0, nmocap_ = 0, nuserdata_ = 0;
+  std::vector<double> ctrlrange_, zeros_, ones_;
+  std::vector<int> fail_;
+  bool nominal_ok_ = false; int nominal_horizon_ = 0;  // the last NominalTrajectory went through, at this horizon
+  mutable std::shared_mutex mtx_;
 };
 
 }  // namespace mjpc_hip

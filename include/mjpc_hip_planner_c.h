@@ -174,6 +174,32 @@ void mjpc_gd_timings(void *planner, double *out);
 void mjpc_gd_returns(void *planner, double *out, int n);          /* the last line search's returns */
 int mjpc_gd_linesearch_steps(void *planner, double *out /* NULL: size only */);
 int mjpc_gd_parameter_update(void *planner, double *out /* NULL: size only */);   /* M' k of the last iteration */
+/* iLQGPlanner (mjpc/planners/ilqg/planner.h): create = Initialize + Allocate.  settings[9] = {min_linesearch_step, fd_tolerance, fd_mode,
+ * min_regularization, max_regularization, regularization_type, max_regularization_iterations, action_limits, nominal_feedback_scaling}
+ * (NULL: the reference's defaults); fused != 0: derivatives and backward pass in one device call.  values out[12] = {action_step, expected,
+ * improvement, surprise, winner, backward pass failed, feedback_scaling, regularization, regularization_rate, all nominal rollouts failed,
+ * dV[0], dV[1]}; timings out[6] = {nominal, derivatives + backward pass, rollouts, policy update (host, microseconds), resampling kernel,
+ * rollout kernel (device, microseconds)}.  get_policy: which 0 policy, 1 previous_policy, 2 the nominal candidate; returns its horizon. */
+void *mjpc_ilqg_create(const MjpcHipModel *model, const MjpcHipTask *task, int num_trajectory, int representation, int derivative_skip, int fused,
+                       const double *settings, int max_samples, int max_horizon, int device);
+void mjpc_ilqg_destroy(void *planner);
+void mjpc_ilqg_reset(void *planner, int horizon, const double *initial_repeated_action);
+void mjpc_ilqg_set_state(void *planner, const double *state, const double *mocap, const double *userdata, double time);
+void mjpc_ilqg_set_task(void *planner, const MjpcHipTask *task);
+void mjpc_ilqg_set_num_trajectory(void *planner, int num_trajectory);
+void mjpc_ilqg_optimize_policy(void *planner, int horizon);
+void mjpc_ilqg_nominal_trajectory(void *planner, int horizon);
+void mjpc_ilqg_iteration(void *planner, int horizon);      /* only behind a nominal trajectory of the same horizon: refused otherwise */
+void mjpc_ilqg_action_from_policy(void *planner, double *action, const double *state /* or NULL */, double time, int use_previous);
+double mjpc_ilqg_improvement(void *planner);
+int mjpc_ilqg_best_trajectory(void *planner, double *states, double *actions, double *costs, double *total_return);   /* returns H */
+void mjpc_ilqg_values(void *planner, double *out);
+void mjpc_ilqg_timings(void *planner, double *out);
+void mjpc_ilqg_returns(void *planner, double *out, int n);
+int mjpc_ilqg_linesearch_steps(void *planner, double *out /* NULL: size only */);
+int mjpc_ilqg_get_policy(void *planner, int which, double *times, double *states, double *actions, double *feedback_gain, double *action_improvement,
+                         double *feedback_scaling);
+int mjpc_ilqg_best_rollout(const double *returns, const int *failures, int n);      /* iLQGPlanner::BestRollout, host only */
 /* host closed forms without a planner (no GPU needed): a spline mapping [(dim num_output)][(dim num_input)], GradientPolicy::Action */
 void mjpc_gd_spline_mapping(int representation, int dim, const double *input_times, int num_input, const double *output_times, int num_output,
                             double *mapping);
@@ -220,7 +246,7 @@ void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int
                              const double *feedback_gain, double feedback_scaling, const double *state, double time, double *action);
 
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
- * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create.  state / mocap are in-out;
+ * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create, 4 = handle from mjpc_ilqg_create (its policy is evaluated at the simulator's state).  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,
  * plan_steps, failure}.  Returns the total cost. */
 double mjpc_testspeed_run(const MjpcHipModel *model, const MjpcHipTask *task, void *planner, int planner_kind, double *state,

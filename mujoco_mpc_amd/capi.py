@@ -248,6 +248,37 @@ def riccati_settings(regularization_type=0, action_limits_on=1, max_regularizati
     return s
 
 
+class MjpcHipFeedbackPolicy(C.Structure):
+    """include/mjpc_hip.h: the feedback policy of mjpc_hip_plan_feedback (iLQG's ActionRollouts / FeedbackRollouts)"""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("T", C.c_int), ("representation", C.c_int),
+                ("times", c_double_p), ("states", c_double_p), ("actions", c_double_p), ("feedback_gain", c_double_p),
+                ("action_improvement", c_double_p), ("action_step", c_double_p), ("feedback_scaling", c_double_p), ("use_feedback", C.c_int)]
+
+
+FEEDBACK_INDEXED, FEEDBACK_TIME = 0, 1
+
+
+def make_feedback_policy(times, states, actions, feedback_gain, action_step, feedback_scaling, action_improvement=None, mode=FEEDBACK_INDEXED,
+                         representation=1, use_feedback=True):
+    """MjpcHipFeedbackPolicy over contiguous copies of the arrays (kept alive on the struct)."""
+    keep = []
+
+    def arr(x):
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+        keep.append(a)
+        return _dp(a)
+    p = MjpcHipFeedbackPolicy()
+    p.struct_size = C.sizeof(MjpcHipFeedbackPolicy)
+    p.mode = int(mode); p.T = int(len(np.asarray(times).ravel())); p.representation = int(representation)
+    p.times = arr(times); p.states = arr(states); p.actions = arr(actions); p.feedback_gain = arr(feedback_gain)
+    if action_improvement is not None:
+        p.action_improvement = arr(action_improvement)
+    p.action_step = arr(action_step); p.feedback_scaling = arr(feedback_scaling)
+    p.use_feedback = 1 if use_feedback else 0
+    p._keep = keep
+    return p
+
+
 _engine = None
 
 
@@ -271,6 +302,9 @@ def load_engine():
     lib.mjpc_hip_plan_mixed_async.argtypes = [C.c_void_p, C.POINTER(MjpcHipPlanInput), C.c_int]
     lib.mjpc_hip_plan_mixed.argtypes = [C.c_void_p, C.POINTER(MjpcHipPlanInput), C.c_int, C.POINTER(MjpcHipPlanOutput)]
     lib.mjpc_hip_noise_history_reset.argtypes = [C.c_void_p]
+    lib.mjpc_hip_plan_feedback_async.argtypes = [C.c_void_p, C.POINTER(MjpcHipPlanInput), C.POINTER(MjpcHipFeedbackPolicy)]
+    lib.mjpc_hip_plan_feedback.argtypes = [C.c_void_p, C.POINTER(MjpcHipPlanInput), C.POINTER(MjpcHipFeedbackPolicy), C.POINTER(MjpcHipPlanOutput)]
+    lib.mjpc_hip_feedback_resample_time_us.argtypes = [C.c_void_p]; lib.mjpc_hip_feedback_resample_time_us.restype = C.c_double
     lib.mjpc_hip_sample_gradient.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p, c_double_p]
     lib.mjpc_hip_step_batch.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [c_double_p, c_double_p, c_int_p]
     lib.mjpc_hip_transition_fd.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [C.c_double, C.c_int, C.c_int] + [c_double_p] * 4 + [c_int_p]
@@ -310,7 +344,8 @@ def load_engine():
     # a stale library next to a newer ctypes layout must not get as far as reading pointers out of the wrong offsets
     if lib.mjpc_hip_version() != ABI_VERSION:
         raise RuntimeError(f"{ENGINE_PATH}: ABI revision {lib.mjpc_hip_version()}, these bindings are revision {ABI_VERSION}: rebuild the engine")
-    for what, ctype in (("model", MjpcHipModel), ("task", MjpcHipTask), ("plan_input", MjpcHipPlanInput), ("plan_output", MjpcHipPlanOutput)):
+    for what, ctype in (("model", MjpcHipModel), ("task", MjpcHipTask), ("plan_input", MjpcHipPlanInput), ("plan_output", MjpcHipPlanOutput),
+                        ("feedback_policy", MjpcHipFeedbackPolicy)):
         n = getattr(lib, "mjpc_hip_sizeof_" + what)()
         if n != C.sizeof(ctype):
             raise RuntimeError(f"{ENGINE_PATH}: sizeof {what} struct is {n} in the library, {C.sizeof(ctype)} in capi.py: rebuild the engine")
@@ -335,6 +370,7 @@ EXPORTED_SYMBOLS = [
     "mjpc_hip_get_traces", "mjpc_hip_get_all_candidates", "mjpc_hip_lds_bytes", "mjpc_hip_layout_bytes", "mjpc_hip_set_fetch_mode", "mjpc_hip_dense_tier", "mjpc_hip_debug_dense_capacity",
     "mjpc_hip_debug_spill", "mjpc_hip_debug_spill_layout",
     "mjpc_hip_plan_mixed_async", "mjpc_hip_plan_mixed", "mjpc_hip_noise_history_reset", "mjpc_hip_sample_gradient",
+    "mjpc_hip_plan_feedback_async", "mjpc_hip_plan_feedback", "mjpc_hip_feedback_resample_time_us", "mjpc_hip_sizeof_feedback_policy",
     "mjpc_hip_step_batch", "mjpc_hip_transition_fd", "mjpc_hip_cost_derivatives", "mjpc_hip_trajectory_gradient",
     "mjpc_hip_ilqg_backward_pass", "mjpc_hip_trajectory_ilqg", "mjpc_hip_riccati_layout_bytes",
     "mjpc_hip_multi_create", "mjpc_hip_multi_destroy", "mjpc_hip_multi_set_task", "mjpc_hip_multi_plan", "mjpc_hip_multi_get_candidate",

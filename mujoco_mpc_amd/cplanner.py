@@ -135,6 +135,17 @@ def lib():
         "mjpc_gd_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
         "mjpc_gd_values": (None, [vp, c_double_p]), "mjpc_gd_timings": (None, [vp, c_double_p]), "mjpc_gd_returns": (None, [vp, c_double_p, i]),
         "mjpc_gd_linesearch_steps": (i, [vp, c_double_p]), "mjpc_gd_parameter_update": (i, [vp, c_double_p]),
+        "mjpc_ilqg_create": (vp, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), i, i, i, i, c_double_p, i, i, i]),
+        "mjpc_ilqg_destroy": (None, [vp]), "mjpc_ilqg_reset": (None, [vp, i, c_double_p]),
+        "mjpc_ilqg_set_state": (None, [vp, c_double_p, c_double_p, c_double_p, d]),
+        "mjpc_ilqg_set_task": (None, [vp, C.POINTER(capi.MjpcHipTask)]), "mjpc_ilqg_set_num_trajectory": (None, [vp, i]),
+        "mjpc_ilqg_optimize_policy": (None, [vp, i]), "mjpc_ilqg_nominal_trajectory": (None, [vp, i]), "mjpc_ilqg_iteration": (None, [vp, i]),
+        "mjpc_ilqg_action_from_policy": (None, [vp, c_double_p, c_double_p, d, i]), "mjpc_ilqg_improvement": (d, [vp]),
+        "mjpc_ilqg_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_ilqg_values": (None, [vp, c_double_p]), "mjpc_ilqg_timings": (None, [vp, c_double_p]), "mjpc_ilqg_returns": (None, [vp, c_double_p, i]),
+        "mjpc_ilqg_linesearch_steps": (i, [vp, c_double_p]),
+        "mjpc_ilqg_get_policy": (i, [vp, i, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_ilqg_best_rollout": (i, [c_double_p, c_int_p, i]),
         "mjpc_gd_spline_mapping": (None, [i, i, c_double_p, i, c_double_p, i, c_double_p]),
         "mjpc_gd_policy_action": (None, [i, i, c_double_p, c_double_p, c_double_p, i, d, c_double_p]),
         "mjpc_testspeed_run": (d, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), vp, i, c_double_p, c_double_p, d, i, i, d, i,
@@ -451,6 +462,68 @@ class GradientPlanner(_Planner):
     def parameter_update(self):
         out = np.zeros(max(self._L.mjpc_gd_parameter_update(self._h, None), 1)); n = self._L.mjpc_gd_parameter_update(self._h, _dp(out))
         return out[:n].reshape(-1, self.nu)
+
+
+class iLQGPlanner(_Planner):
+    """mjpc_hip::iLQGPlanner (C++) driven from Python; names follow planners/ilqg/planner.h."""
+    _prefix = "mjpc_ilqg_"
+    SETTINGS = ("min_linesearch_step", "fd_tolerance", "fd_mode", "min_regularization", "max_regularization", "regularization_type",
+                "max_regularization_iterations", "action_limits", "nominal_feedback_scaling")
+    DEFAULTS = (1.0e-3, 1.0e-6, 0, 1.0e-6, 1.0e6, 0, 5, 1, 1)
+
+    def Initialize(self, model: dict, task: dict, numerics: dict | None = None, settings: dict | None = None, max_samples=128, max_horizon=512, device=0):
+        numerics = numerics or {}; settings = settings or {}
+        self.cm = capi.CModel(model, task)
+        self.nu = int(model["nu"]); self.ns = int(model["nq"] + model["nv"] + model["na"]); self.nd = int(2 * model["nv"] + model["na"])
+        self.max_samples, self.max_horizon = int(max_samples), int(max_horizon)
+        s = np.array([float(settings.get(k, v)) for k, v in zip(self.SETTINGS, self.DEFAULTS)])
+        self.close()
+        h = self._L.mjpc_ilqg_create(C.byref(self.cm.c_model), C.byref(self.cm.c_task), int(numerics.get("ilqg_num_rollouts", 10)),
+                                     int(numerics.get("ilqg_representation", 1)), int(numerics.get("derivative_skip", 0)),
+                                     int(bool(settings.get("fused", True))), _dp(s), self.max_samples, self.max_horizon, int(device))
+        self._h = C.c_void_p(h)
+        _check()
+
+    def set_num_trajectory(self, n): self._L.mjpc_ilqg_set_num_trajectory(self._h, int(n))
+
+    def Iteration(self, horizon): self._L.mjpc_ilqg_iteration(self._h, int(horizon)); _check()
+
+    def ActionFromPolicy(self, time, use_previous=False, state=None):
+        a = np.zeros(self.nu)
+        st = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
+        self._L.mjpc_ilqg_action_from_policy(self._h, _dp(a), _dp(st), float(time), int(bool(use_previous))); _check()
+        return a
+
+    def values(self):
+        o = np.zeros(12); self._L.mjpc_ilqg_values(self._h, _dp(o))
+        return dict(action_step=o[0], expected=o[1], improvement=o[2], surprise=o[3], winner=int(o[4]), backward_pass_failed=bool(o[5]),
+                    feedback_scaling=o[6], regularization=o[7], regularization_rate=o[8], all_failed=bool(o[9]), dV=o[10:12].copy())
+
+    def timings(self):
+        o = np.zeros(6); self._L.mjpc_ilqg_timings(self._h, _dp(o))
+        return dict(nominal_us=o[0], derivative_us=o[1], rollouts_us=o[2], policy_update_us=o[3], resample_kernel_us=o[4], rollout_kernel_us=o[5])
+
+    def linesearch_steps(self):
+        out = np.zeros(max(self._L.mjpc_ilqg_linesearch_steps(self._h, None), 1)); n = self._L.mjpc_ilqg_linesearch_steps(self._h, _dp(out)); return out[:n]
+
+    def get_policy(self, which=0):
+        """which: 0 policy, 1 previous_policy, 2 the nominal candidate -> dict of its first `horizon` knots"""
+        H = self._L.mjpc_ilqg_get_policy(self._h, int(which), None, None, None, None, None, None)
+        Hn = max(H, 1)
+        o = dict(times=np.zeros(Hn), states=np.zeros((Hn, self.ns)), actions=np.zeros((Hn, self.nu)), feedback_gain=np.zeros((Hn, self.nu, self.nd)),
+                 action_improvement=np.zeros((Hn, self.nu)))
+        fs = C.c_double()
+        self._L.mjpc_ilqg_get_policy(self._h, int(which), _dp(o["times"]), _dp(o["states"]), _dp(o["actions"]), _dp(o["feedback_gain"]),
+                                     _dp(o["action_improvement"]), C.cast(C.byref(fs), c_double_p))
+        o = {k: v[:H] for k, v in o.items()}
+        o["feedback_scaling"] = fs.value; o["horizon"] = H
+        return o
+
+
+def ilqg_best_rollout(returns, failures):
+    """iLQGPlanner::BestRollout (host closed form, no GPU needed): from the last index down, strict <; -1 when every candidate failed"""
+    r = np.ascontiguousarray(returns, dtype=np.float64); f = np.ascontiguousarray(failures, dtype=np.int32)
+    return lib().mjpc_ilqg_best_rollout(_dp(r), f.ctypes.data_as(c_int_p), int(r.size))
 
 
 def gradient_spline_mapping(representation, dim, input_times, output_times):

@@ -17,6 +17,9 @@
 //                   every knot from the residual and its Jacobian, and the gradient planner's backward recursion
 //   rc_backward_kernel  (riccati.h)  mjpc_hip_ilqg_backward_pass / mjpc_hip_trajectory_ilqg: iLQG's backward pass, one workgroup: Riccati
 //                   recursion, box-QP controls and the regularisation loop
+//   fb_kernel / fb_resample_kernel  (rollout_fb_cached / _direct / _spill.hip, feedback.h; feedback_resample.h)  mjpc_hip_plan_feedback: the
+//                   rollout kernel under a feedback policy read at the candidate's own state (iLQG's rollouts), and the policy resampled
+//                   at the step times once per call
 //   argmin_kernel   wavefront (value, index) min-reduction, lowest index wins ties
 //                   (planner.cc:168-181 partial_sort -> trajectory_order[0]).
 //   pack_kernel     the plan's result in one contiguous buffer for one D2H copy
@@ -34,6 +37,7 @@
 #include "transition_fd.h"
 #include "cost_derivatives.h"
 #include "riccati.h"
+#include "feedback_resample.h"
 #include "host.h"
 #include "devbuf.h"
 #include "../../include/mjpc_hip_debug.h"
@@ -54,6 +58,13 @@ typedef void (*StepLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_
   extern "C" void mjpc_launch_step_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, double *, double *, int *);
 MJPC_STEP_DECL(cached) MJPC_STEP_DECL(direct) MJPC_STEP_DECL(spill)
 #undef MJPC_STEP_DECL
+// the feedback-policy rollout kernels (rollout_fb_*.hip, feedback_tu.h): opaque here as well
+typedef void (*FbLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *xbar, const double *ubar,
+                           const double *kbar, const double *Kbar, const double *alpha, const double *scale);
+#define MJPC_FB_DECL(tu) extern "C" const void *mjpc_pick_fb_##tu(int nv); \
+  extern "C" void mjpc_launch_fb_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, const double *, const double *, const double *);
+MJPC_FB_DECL(cached) MJPC_FB_DECL(direct) MJPC_FB_DECL(spill)
+#undef MJPC_FB_DECL
 
 // Capacity tiers.  One candidate per CU leaves every SIMD with a single, mostly stalled wave; two resident workgroups per CU
 // raise throughput ~1.6x once a shard has more candidates than CUs, but need <= 80 KiB of LDS each.  The dense tier gets
@@ -239,6 +250,14 @@ extern "C" __global__ void __launch_bounds__(RC_THREADS) rc_backward_kernel(cons
   else rc_backward(a, rc_work(a.nd, a.nu, a.scratch), (int)threadIdx.x, RC_THREADS);
 }
 
+// mjpc_hip_plan_feedback, time mode: workgroup t fills row t of the [H] tables (feedback_resample.h), then renormalises the row's quaternions
+extern "C" __global__ void __launch_bounds__(256) fb_resample_kernel(const FbResampleArgs a) {
+  const int t = (int)blockIdx.x, n = fb_resample_elements(a);
+  for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) fb_resample(a, t, e);
+  __syncthreads();
+  for (int j = (int)threadIdx.x; j < a.njnt; j += (int)blockDim.x) fb_resample_normalize(a, t, j);
+}
+
 // winner[0] = local index of the first minimum of returns[0..n), winner_val[0] = its value
 extern "C" __global__ void __launch_bounds__(64) argmin_kernel(const double *returns, int n, int *winner, double *winner_val) {
   int lane = threadIdx.x;
@@ -300,6 +319,7 @@ enum Buf {
   B_CKPT,                                                            // dense-tier checkpoints for the retry launch
   B_SLAB,                                                            // spill flavour: per-candidate HBM slab
   B_HIST, B_SLOT, B_SCALE, B_GRAD,                                   // Sample-Gradient planner: noise history [max_local][P_max * nu], gradient inputs / output
+  B_FBP,                                                             // feedback rollouts: the call's policy arrays, steps and [H] tables, grown on demand
   B_FD,                                                              // one-step calls: the call's tables (inputs, stepped rows, matrices), grown on demand
   B_PACK,                                                            // packed plan result, grown on demand
   H_PACK, H_SMALL, H_TASK0, H_TASK1,                                 // pinned: packed plan result | small plan inputs (Staging) | set_task staging
@@ -340,6 +360,9 @@ struct MjpcHipEngine {
   bool cost_rows_ok = false;   // cost_rows_tile of the current task
   // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour
   const void *step_kernel = nullptr; StepLaunchFn step_launch = nullptr;
+  // feedback rollout kernel (mjpc_hip_plan_feedback): picked at the first call, in the full-capacity rollout's flavour
+  const void *fb_kernel = nullptr; FbLaunchFn fb_launch = nullptr;
+  hipEvent_t ev_fb[2] = {nullptr, nullptr}; int fb_resampled = 0; double fb_resample_us = 0;
   DenseTier tierB; int num_cu = 256, force_tier = 0;
   MjpcHipEngine() { for (int b = H_PACK; b < B_COUNT; b++) buf[b].kind = DevBuf::PINNED; }
 };
@@ -497,6 +520,7 @@ int mjpc_hip_sizeof_model(void) { return (int)sizeof(MjpcHipModel); }
 int mjpc_hip_sizeof_task(void) { return (int)sizeof(MjpcHipTask); }
 int mjpc_hip_sizeof_plan_input(void) { return (int)sizeof(MjpcHipPlanInput); }
 int mjpc_hip_sizeof_plan_output(void) { return (int)sizeof(MjpcHipPlanOutput); }
+int mjpc_hip_sizeof_feedback_policy(void) { return (int)sizeof(MjpcHipFeedbackPolicy); }
 
 MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *task, int max_local, int max_horizon, int device) {
   // arguments
@@ -561,6 +585,7 @@ void mjpc_hip_destroy(MjpcHipEngine *e) {
   for (DevBuf &b : e->buf) b.release();
   for (int i = 0; i < 2; i++) if (e->ev_task[i]) hipEventDestroy(e->ev_task[i]);
   for (int i = 0; i < 4; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
+  for (int i = 0; i < 2; i++) if (e->ev_fb[i]) hipEventDestroy(e->ev_fb[i]);
   if (e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -601,6 +626,7 @@ static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int fir
   if (nl < 1 || nl > e->max_local || in->candidate_offset < 0 || in->candidate_offset + nl > in->num_trajectory) { set_error("mjpc_hip_plan: candidate range out of bounds"); return -1; }
   if (in->interpolation < 0 || in->interpolation > 2) { set_error("mjpc_hip_plan: unknown interpolation"); return -1; }
   if (!in->state || !in->knot_times || !in->knot_values || (e->nmocap > 0 && !in->mocap)) { set_error("mjpc_hip_plan: null input"); return -1; }
+  e->fb_resampled = 0; e->fb_resample_us = 0;      // (mjpc_hip_feedback_resample_time_us speaks of the last call: this one resamples nothing)
   const bool mixed = first_explicit >= 0;
   if (mixed) {
     if (first_explicit > in->num_trajectory) { set_error("mjpc_hip_plan_mixed: first_explicit out of range (0..num_trajectory)"); return -1; }
@@ -708,6 +734,7 @@ int mjpc_hip_plan_fetch(MjpcHipEngine *e, MjpcHipPlanOutput *out) {
   const int was_pending = e->pending;
   e->pending = 0;
   if (sync_rc != hipSuccess) { set_error(std::string("mjpc_hip_plan_fetch: hipStreamSynchronize: ") + hipGetErrorString(sync_rc)); return -2; }
+  if (was_pending && e->fb_resampled) { float tr = 0; hipEventElapsedTime(&tr, e->ev_fb[0], e->ev_fb[1]); e->fb_resample_us = 1e3 * tr; }
   if (was_pending) {
     float t01 = 0, t12 = 0, t03 = 0;
     hipEventElapsedTime(&t01, e->ev[0], e->ev[1]); hipEventElapsedTime(&t12, e->ev[1], e->ev[2]); hipEventElapsedTime(&t03, e->ev[0], e->ev[3]);
@@ -744,6 +771,106 @@ int mjpc_hip_plan(MjpcHipEngine *e, const MjpcHipPlanInput *in, MjpcHipPlanOutpu
   if (rc != 0) return rc;
   return mjpc_hip_plan_fetch(e, out);
 }
+
+// ------------------------------------------------------------------------------ rollouts under a feedback policy (feedback.h)
+int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, const MjpcHipFeedbackPolicy *p) {
+  const char *who = "mjpc_hip_plan_feedback";
+  auto bad = [&](const std::string &m) { set_error(std::string(who) + ": " + m); return -1; };
+  if (!e || !in || !p) return bad("invalid argument");
+  if (p->struct_size != (int)sizeof(MjpcHipFeedbackPolicy)) return bad("MjpcHipFeedbackPolicy.struct_size does not match this library");
+  if (e->pending) return bad("the previous plan step has not been fetched (one plan in flight per engine)");
+  const int H = in->horizon, nl = in->num_trajectory - in->candidate_offset, nu = e->nu, ds = e->ds, nv = e->nv, nd = 2 * nv + (ds - e->nq - nv), T = p->T;
+  if (nu < 1) return bad("the model has no actuators");
+  if (H < 1 || H > e->max_horizon) return bad("horizon out of range");
+  if (in->candidate_offset < 0 || nl < 1) return bad("candidate range out of bounds");
+  if (nl > e->max_local) return bad("the batch exceeds max_samples (" + std::to_string(e->max_local) + ")");
+  if (p->mode != MJPC_FEEDBACK_INDEXED && p->mode != MJPC_FEEDBACK_TIME) return bad("unknown mode");
+  if (T < 2) return bad("T < 2");
+  if (p->mode == MJPC_FEEDBACK_INDEXED && T < H) return bad("indexed mode needs T >= horizon");
+  if (p->mode == MJPC_FEEDBACK_TIME && (p->representation < 0 || p->representation > 2)) return bad("unknown representation");
+  if (!in->state || (e->nmocap > 0 && !in->mocap) || !p->times || !p->states || !p->actions || !p->feedback_gain || !p->action_step || !p->feedback_scaling) return bad("null input");
+  for (int i = 0; i < nl; i++) {
+    const double a = p->action_step[in->candidate_offset + i], s = p->feedback_scaling[in->candidate_offset + i];
+    if (a != a || s != s) return bad("NaN in action_step / feedback_scaling of candidate " + std::to_string(in->candidate_offset + i));
+  }
+  if (nd > FB_DX_CAPACITY(nv)) return bad("2 nv + na exceeds the state-difference scratch of the kernel");
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->fb_kernel) {
+    const void *k = e->spill ? mjpc_pick_fb_spill(e->nv) : e->cached ? mjpc_pick_fb_cached(e->nv) : mjpc_pick_fb_direct(e->nv);
+    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
+    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&e->ev_fb[i]));
+    e->fb_kernel = k;
+    e->fb_launch = e->spill ? mjpc_launch_fb_spill : e->cached ? mjpc_launch_fb_cached : mjpc_launch_fb_direct;
+  }
+  // the call's device block: the policy [T], the steps [nl] and, in time mode, the resampled tables [H]
+  const size_t Tz = (size_t)T, Hz = (size_t)H, row = (size_t)ds + 2 * nu + (size_t)nu * nd;
+  const bool timed = p->mode == MJPC_FEEDBACK_TIME;
+  size_t need_pack = 2 + 2 * (size_t)nl;
+  for (int k = 1; k < (e->summary_only ? 1 : NROWS); k++) need_pack += row_doubles(e, k, H, 0);
+  HIPCHK(e->buf[B_FBP].reserve(sizeof(double) * (Tz * (row + 1) + 2 * (size_t)nl + (timed ? Hz * row : 0) + 8)));
+  HIPCHK(reserve_knots(e, 1));
+  HIPCHK(e->buf[B_PACK].reserve(sizeof(double) * need_pack));
+  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * need_pack));
+  double *d_times = e->at(B_FBP), *d_states = d_times + Tz, *d_actions = d_states + Tz * ds, *d_impr = d_actions + Tz * nu, *d_gain = d_impr + Tz * nu;
+  double *d_alpha = d_gain + Tz * nu * nd, *d_scale = d_alpha + nl, *d_tab = d_scale + nl;
+  const Staging &s = e->hs;
+  HIPCHK(stage(e, s.state, in->state, ds, B_STATE));
+  if (e->nmocap) HIPCHK(stage(e, s.mocap, in->mocap, 7 * e->nmocap, B_MOCAP));
+  if (e->nuserdata) HIPCHK(stage(e, s.userdata, in->userdata, e->nuserdata, B_USERDATA));
+  HIPCHK(hipEventRecord(e->ev[0], e->stream));
+  const size_t D = sizeof(double);
+  HIPCHK(hipMemcpyAsync(d_times, p->times, D * Tz, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_states, p->states, D * Tz * ds, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_actions, p->actions, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
+  if (p->action_improvement) HIPCHK(hipMemcpyAsync(d_impr, p->action_improvement, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_gain, p->feedback_gain, D * Tz * nu * nd, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_alpha, p->action_step + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_scale, p->feedback_scaling + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
+  const double *xbar = d_states, *ubar = d_actions, *kbar = p->action_improvement ? d_impr : nullptr, *Kbar = d_gain;
+  e->fb_resampled = 0; e->fb_resample_us = 0;
+  if (timed) {
+    FbResampleArgs ra;
+    ra.times = d_times; ra.states = d_states; ra.actions = d_actions; ra.gains = d_gain; ra.improvement = p->action_improvement ? d_impr : nullptr;
+    ra.jnt_type = e->K.M.jnt_type; ra.jnt_qposadr = e->K.M.jnt_qposadr;
+    ra.T = T; ra.H = H; ra.ds = ds; ra.nu = nu; ra.nd = nd; ra.njnt = e->K.M.njnt; ra.representation = p->representation;
+    ra.time0 = in->time; ra.timestep = e->K.M.timestep;
+    ra.xbar = d_tab; ra.ubar = ra.xbar + Hz * ds; ra.kbar = ra.ubar + Hz * nu; ra.Kbar = ra.kbar + Hz * nu;
+    HIPCHK(hipEventRecord(e->ev_fb[0], e->stream));
+    hipLaunchKernelGGL(fb_resample_kernel, dim3(H), dim3(256), 0, e->stream, ra);
+    HIPCHK(hipEventRecord(e->ev_fb[1], e->stream));
+    e->fb_resampled = 1;
+    xbar = ra.xbar; ubar = ra.ubar; kbar = p->action_improvement ? ra.kbar : nullptr; Kbar = ra.Kbar;
+  }
+  if (!p->use_feedback) xbar = nullptr;
+  // a copy of the engine's parameters: no spline, no noise, no candidate table, no force noise, full capacity
+  KParams K = e->K;
+  K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  K.time = in->time; K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0;
+  K.P = 0; K.interp = 0; K.H = H; K.N = in->num_trajectory; K.offset = in->candidate_offset; K.nlocal = nl; K.use_device_noise = 0; K.nominal_index = 0;
+  K.xfrc_std = 0; K.xfrc_rate = 0; K.retry = 0; K.tier = 0;
+  HIPCHK(hipEventRecord(e->ev[1], e->stream));
+  e->fb_launch(e->fb_kernel, nl, e->lds_bytes, e->stream, &K, xbar, ubar, kbar, Kbar, d_alpha, d_scale);
+  e->last_dense = 0;
+  HIPCHK(hipEventRecord(e->ev[2], e->stream));
+  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
+  HIPCHK(hipEventRecord(e->ev[3], e->stream));
+  PackArgs pa{e->at<int>(B_WINNER), e->at(B_WINNER_VAL), e->at(B_RETURNS), e->at<int>(B_FAILURE), e->at(B_KNOTS + 1), e->at(B_KNOTS + 2), e->at(B_KNOTS + 3),
+              e->at(B_KNOTS + 4), e->at(B_KNOTS + 5), e->at(B_KNOTS + 6), e->at(B_KNOTS), nl, H, 0, ds, nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->at(B_PACK)};
+  e->last_summary = e->summary_only;
+  hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
+  HIPCHK(hipMemcpyAsync(e->at(H_PACK), e->at(B_PACK), sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipGetLastError());
+  e->last_H = H; e->last_P = 0; e->last_nlocal = nl; e->last_offset = in->candidate_offset; e->pending = 1;
+  return 0;
+}
+
+int mjpc_hip_plan_feedback(MjpcHipEngine *e, const MjpcHipPlanInput *in, const MjpcHipFeedbackPolicy *p, MjpcHipPlanOutput *out) {
+  int rc = mjpc_hip_plan_feedback_async(e, in, p);
+  if (rc != 0) return rc;
+  return mjpc_hip_plan_fetch(e, out);
+}
+
+double mjpc_hip_feedback_resample_time_us(MjpcHipEngine *e) { return e ? e->fb_resample_us : 0.0; }
 
 int mjpc_hip_plan_mixed_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, int first_explicit) {
   if (first_explicit < 0) { set_error("mjpc_hip_plan_mixed: first_explicit out of range (0..num_trajectory)"); return -1; }

@@ -8,6 +8,7 @@
 //   mjpc/planners/ilqg/backward_pass.cc, policy.cc, planner.cc:429-520   BoxQP, iLQGPolicy, iLQGBackwardPass (host, and the engine's kernel)
 #include "../../include/mjpc_hip_planner.h"
 #include "../../include/mjpc_hip_planner_c.h"
+#include "atan2_cr.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1258,7 +1259,7 @@ void StateDiff(const iLQGPolicy& p, double* ds, const double* s1, const double* 
     const double sn = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
     if (sn < 1e-15) { axis[0] = 1.0; axis[1] = 0.0; axis[2] = 0.0; }        // mju_normalize3 of a zero vector
     else for (double& a : axis) a /= sn;
-    double speed = 2 * std::atan2(sn, d[0]);
+    double speed = 2 * atan2_cr(sn, d[0]);        // csrc/atan2_cr.h: the function the feedback rollout kernel evaluates (a library atan2 is a last place off between host and device)
     if (speed > M_PI) speed -= 2 * M_PI;
     for (int k = 0; k < 3; k++) res[k] = axis[k] * speed / h;
   };
@@ -1559,6 +1560,217 @@ void iLQGBackwardPass::UpdateRegularization(double reg_min, double reg_max, doub
   if (bad(z) || bad(s)) ScaleRegularization(regularization_factor * regularization_factor, reg_min, reg_max);
   else if (z > 0.5 || s > 0.3) ScaleRegularization(1.0 / regularization_factor, reg_min, reg_max);
   else if (z < 0.1 || s < 0.06) ScaleRegularization(regularization_factor, reg_min, reg_max);
+}
+
+// ------------------------------------------------------------------ iLQGPlanner (ilqg/planner.cc:40-729)
+iLQGPlanner::~iLQGPlanner() { if (engine_) mjpc_hip_destroy(engine_); }
+
+void iLQGPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
+  numerics_ = numerics;
+  ns_ = model->nq + model->nv + model->na; nd_ = 2 * model->nv + model->na; nu_ = model->nu; nr_ = task->num_residual; ntrace_ = task->num_trace;
+  nmocap_ = model->nmocap; nuserdata_ = model->nuserdata;
+  derivative_skip_ = numerics.derivative_skip;
+  if (representation < kZeroSpline || representation > kCubicSpline) { Fatal("Unknown ilqg_representation"); return; }
+  if (num_trajectory < 1 || num_trajectory > kMaxiLQGTrajectory) { Fatal("Too many trajectories."); return; }
+  if (engine_) { mjpc_hip_destroy(engine_); engine_ = nullptr; }
+  engine_ = mjpc_hip_create(model, task, std::max(numerics.max_samples, num_trajectory), std::max(numerics.max_horizon, 2), numerics.device);
+  if (!engine_) { Fatal(mjpc_hip_last_error()); return; }
+  ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
+  for (iLQGPolicy* p : {&policy, &previous_policy, &candidate}) p->Allocate(model, nr_, ntrace_, numerics.max_horizon, representation);
+}
+
+void iLQGPlanner::Allocate() {
+  if (!engine_) return;
+  const size_t Hm = (size_t)numerics_.max_horizon;
+  state.assign(ns_, 0.0); mocap.assign(7 * nmocap_, 0.0); userdata.assign(nuserdata_, 0.0);
+  Trajectory* tr = &trajectory_winner;
+  tr->dim_state = ns_; tr->dim_action = nu_; tr->dim_residual = nr_; tr->dim_trace = 3 * ntrace_;
+  tr->states.assign(Hm * ns_, 0.0); tr->actions.assign(Hm * nu_, 0.0); tr->times.assign(Hm, 0.0); tr->residual.assign(Hm * nr_, 0.0);
+  tr->costs.assign(Hm, 0.0); tr->trace.assign(Hm * 3 * std::max(ntrace_, 1), 0.0);
+  // (the policies' trajectories were sized by iLQGPolicy::Allocate with dim_trace = 3 ntrace: give the trace row one element at least)
+  for (iLQGPolicy* p : {&policy, &previous_policy, &candidate}) if (p->trajectory.trace.empty()) p->trajectory.trace.assign(Hm, 0.0);
+  model_derivative.Allocate(nd_, nu_, nr_, (int)Hm, ns_);
+  cost_derivative.Allocate(nd_, nu_, nr_, (int)Hm);
+  backward_pass.Allocate(nd_, nu_, (int)Hm);
+  const size_t N = (size_t)std::max(numerics_.max_samples, num_trajectory);
+  zeros_.assign(N, 0.0); ones_.assign(N, 1.0); fail_.assign(Hm, 0);
+  winner = -1;
+}
+
+void iLQGPlanner::Reset(int horizon, const double* initial_repeated_action) {
+  std::fill(state.begin(), state.end(), 0.0); std::fill(mocap.begin(), mocap.end(), 0.0); std::fill(userdata.begin(), userdata.end(), 0.0);
+  time = 0.0;
+  const int h = horizon > 0 ? std::min(horizon, numerics_.max_horizon) : numerics_.max_horizon;
+  model_derivative.Reset(nd_, nu_, nr_, h); cost_derivative.Reset(nd_, nu_, nr_, h); backward_pass.Reset(nd_, nu_, h);
+  for (iLQGPolicy* p : {&policy, &previous_policy, &candidate}) { p->Reset(h, initial_repeated_action); p->representation = representation; }
+  feedback_scaling = 1.0; action_step = 0.0; expected = 0.0; improvement = 0.0; surprise = 0.0;
+  winner = -1; backward_pass_failed = false; all_failed = false;
+  derivative_skip_ = numerics_.derivative_skip;
+}
+
+void iLQGPlanner::SetState(const double* s, const double* m, const double* u, double t) {
+  std::copy(s, s + ns_, state.begin());
+  if (m) std::copy(m, m + 7 * nmocap_, mocap.begin());
+  if (u) std::copy(u, u + nuserdata_, userdata.begin());
+  time = t;
+}
+
+void iLQGPlanner::SetTask(const MjpcHipTask* task) { if (mjpc_hip_set_task(engine_, task) != 0) Fatal(mjpc_hip_last_error()); }
+
+void iLQGPlanner::ActionFromPolicy(double* action, const double* s, double t, bool use_previous) {
+  const std::shared_lock<std::shared_mutex> lock(mtx_);
+  (use_previous ? previous_policy : policy).Action(action, s, t);
+}
+
+int iLQGPlanner::BestRollout(const double* ret, const int* fail, int n) {
+  double best_return = 0; int best_rollout = -1;
+  for (int j = n - 1; j >= 0; j--) {
+    if (fail[j]) continue;
+    if (best_rollout == -1 || ret[j] < best_return) { best_return = ret[j]; best_rollout = j; }
+  }
+  return best_rollout;
+}
+
+void iLQGPlanner::LogScale(double* values, double max_value, double min_value, int steps) {   // utilities.cc:802-808
+  const double step = (std::log(max_value) - std::log(min_value)) / std::max((steps - 1), 1);
+  for (int i = 0; i < steps; i++) values[i] = std::exp(std::log(min_value) + i * step);       // ascending, as the reference spells it: no pinned value
+}
+
+bool iLQGPlanner::Rollouts(const iLQGPolicy& p, int mode, int horizon, const double* alpha, const double* scale, bool use_feedback, bool improvement_term) {
+  const int N = num_trajectory;
+  returns.assign(N, 0.0); failures.assign(N, 0);
+  MjpcHipPlanInput in;
+  std::memset(&in, 0, sizeof(in));
+  in.state = state.data(); in.mocap = mocap.data(); in.userdata = userdata.data(); in.time = time;
+  in.num_trajectory = N; in.num_local = N; in.horizon = horizon;
+  MjpcHipFeedbackPolicy fp;
+  std::memset(&fp, 0, sizeof(fp));
+  fp.struct_size = (int)sizeof(fp); fp.mode = mode; fp.T = horizon; fp.representation = p.representation;
+  fp.times = p.trajectory.times.data(); fp.states = p.trajectory.states.data(); fp.actions = p.trajectory.actions.data();
+  fp.feedback_gain = p.feedback_gain.data(); fp.action_improvement = improvement_term ? p.action_improvement.data() : nullptr;
+  fp.action_step = alpha; fp.feedback_scaling = scale; fp.use_feedback = use_feedback ? 1 : 0;
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.returns = returns.data(); out.failure = failures.data();
+  const int rc = mjpc_hip_plan_feedback(engine_, &in, &fp, &out);
+  if (rc != 0 && rc != -3) { Fatal(mjpc_hip_last_error()); return false; }               // -3: no finite return; returns[] / failure[] are valid
+  rollout_kernel_time = out.rollouts_compute_time_us;
+  return true;
+}
+
+bool iLQGPlanner::Fetch(int index, int horizon, Trajectory& tr) {
+  MjpcHipPlanOutput out;
+  std::memset(&out, 0, sizeof(out));
+  out.states = tr.states.data(); out.actions = tr.actions.data(); out.times = tr.times.data();
+  out.residual = tr.residual.data(); out.costs = tr.costs.data(); out.trace = tr.trace.data();
+  if (mjpc_hip_get_candidate(engine_, index, &out) != 0) { Fatal(mjpc_hip_last_error()); return false; }
+  // trajectory.cc: the last action repeats the one before it (the kernel applies none at the terminal step)
+  if (horizon > 1) std::copy(tr.actions.begin() + (size_t)(horizon - 2) * nu_, tr.actions.begin() + (size_t)(horizon - 1) * nu_, tr.actions.begin() + (size_t)(horizon - 1) * nu_);
+  tr.horizon = horizon; tr.total_return = returns[index]; tr.failure = failures[index] != 0;
+  return true;
+}
+
+bool iLQGPlanner::NominalTrajectory(int horizon) {   // planner.cc:167-223
+  using clock = std::chrono::steady_clock;
+  nominal_ok_ = false;
+  if (!engine_ || num_trajectory == 0) return false;
+  if (horizon < 2 || horizon > numerics_.max_horizon) { Fatal("iLQGPlanner: horizon out of range (2 .. max_horizon)"); return false; }
+  auto t0 = clock::now();
+  num_trajectory = std::max(1, std::min(num_trajectory, std::min(numerics_.max_samples, kMaxiLQGTrajectory)));
+  const int N = num_trajectory;
+  policy.trajectory.horizon = horizon;
+  linesearch_steps.assign(N, 0.0);
+  if (N > 1) LogScale(linesearch_steps.data(), 1.0, settings.min_linesearch_step, N - 1);
+  linesearch_steps[N - 1] = 0.0;
+  { const std::shared_lock<std::shared_mutex> lock(mtx_); candidate.CopyFrom(policy, horizon); candidate.representation = policy.representation; }
+  // FeedbackRollouts: the policy interpolated at the step's time, feedback scale = the step
+  if (!Rollouts(candidate, MJPC_FEEDBACK_TIME, horizon, zeros_.data(), linesearch_steps.data(), settings.nominal_feedback_scaling != 0, false)) return false;
+  resample_kernel_time = mjpc_hip_feedback_resample_time_us(engine_);
+  const int best = BestRollout(returns.data(), failures.data(), N);
+  all_failed = best == -1;
+  if (best == -1) {
+    const std::shared_lock<std::shared_mutex> lock(mtx_);
+    candidate.trajectory = policy.trajectory;
+    feedback_scaling = 0.0;
+  } else {
+    Fetch(best, horizon, candidate.trajectory);
+    feedback_scaling = linesearch_steps[best];
+  }
+  nominal_compute_time = std::chrono::duration<double, std::micro>(clock::now() - t0).count();
+  nominal_ok_ = true; nominal_horizon_ = horizon;
+  return true;
+}
+
+void iLQGPlanner::Iteration(int horizon) {   // planner.cc:377-615
+  using clock = std::chrono::steady_clock;
+  auto us = [](clock::time_point t0) { return std::chrono::duration<double, std::micro>(clock::now() - t0).count(); };
+  // only behind a NominalTrajectory of the same horizon and batch that went through: it sized linesearch_steps and filled `candidate`
+  if (!engine_ || !nominal_ok_ || horizon != nominal_horizon_ || num_trajectory < 1 || (int)linesearch_steps.size() != num_trajectory) {
+    if (engine_) Fatal("iLQGPlanner::Iteration: no nominal trajectory of this horizon and batch (call NominalTrajectory first)");
+    return;
+  }
+  const int N = num_trajectory;
+  const double previous_return = candidate.trajectory.total_return;
+  if (N > 1) LogScale(linesearch_steps.data(), 1.0, settings.min_linesearch_step, N - 1);
+  linesearch_steps[N - 1] = 0.0;
+  derivative_compute_time = rollouts_compute_time = policy_update_compute_time = 0.0;
+  backward_pass_failed = false;
+
+  // ----- derivatives and backward pass of the nominal -----
+  auto t0 = clock::now();
+  const Trajectory& tr = candidate.trajectory;
+  std::fill(fail_.begin(), fail_.end(), 0);
+  bool ok;
+  if (fused && derivative_skip_ <= 0) {
+    ok = backward_pass.ComputeFused(engine_, &candidate, tr.states.data(), tr.actions.data(), tr.times.data(), tr.residual.data(), nd_, nu_, horizon, settings,
+                                    backward_pass_status, fail_.data(), mocap.data(), userdata.data());
+  } else {
+    ok = model_derivative.Compute(engine_, tr.states.data(), tr.actions.data(), tr.times.data(), horizon, settings.fd_tolerance, settings.fd_mode != 0 ? 1 : 0,
+                                  derivative_skip_, mocap.data(), userdata.data()) &&
+         cost_derivative.Compute(engine_, tr.residual.data(), model_derivative.C.data(), model_derivative.D.data(), nd_, nu_, nr_, horizon, true);
+    if (ok) {
+      std::copy(model_derivative.failure.begin(), model_derivative.failure.begin() + horizon, fail_.begin());
+      ok = backward_pass.Compute(engine_, &candidate, &model_derivative, &cost_derivative, nd_, nu_, horizon, tr.actions.data(), ctrlrange_.data(), settings,
+                                 backward_pass_status);
+    }
+  }
+  derivative_compute_time = us(t0);
+  if (!ok) { Fatal(mjpc_hip_last_error()); backward_pass_failed = true; return; }
+  for (int t = 0; t < horizon; t++) if (fail_[t]) { backward_pass_failed = true; return; }     // a failed derivative evaluation: as a failed pass
+  if (backward_pass_status[0] == 0) { backward_pass_failed = true; return; }                    // planner.cc:524-532: the policy stays as it was
+
+  // ----- ActionRollouts: one batch, action step = the line-search step, full feedback -----
+  t0 = clock::now();
+  if (!Rollouts(candidate, MJPC_FEEDBACK_INDEXED, horizon, linesearch_steps.data(), ones_.data(), true, true)) return;
+  const int best = BestRollout(returns.data(), failures.data(), N);
+  if (best == -1) return;
+  winner = best;
+  if (!Fetch(winner, horizon, trajectory_winner)) return;
+  // candidate_policy[winner] as the reference leaves it: the nominal with actions ubar + step k (mju_addScl over nu * horizon); slot 0
+  // is the winning rollout itself by the time the policy is copied
+  action_step = linesearch_steps[winner];
+  if (winner == 0) candidate.trajectory = trajectory_winner;
+  else for (size_t e = 0; e < (size_t)nu_ * horizon; e++) candidate.trajectory.actions[e] = candidate.trajectory.actions[e] + candidate.action_improvement[e] * action_step;
+  expected = -1.0 * action_step * (backward_pass.dV[0] + action_step * backward_pass.dV[1]) + 1.0e-16;
+  improvement = previous_return - trajectory_winner.total_return;
+  surprise = std::min(std::max(0.0, improvement / expected), 2.0);
+  backward_pass.UpdateRegularization(settings.min_regularization, settings.max_regularization, surprise, action_step);
+  rollouts_compute_time = us(t0);
+
+  // ----- policy update -----
+  t0 = clock::now();
+  {
+    const std::unique_lock<std::shared_mutex> lock(mtx_);
+    previous_policy = policy;
+    policy.CopyFrom(candidate, horizon);
+    policy.feedback_scaling = 1.0;
+  }
+  policy_update_compute_time = us(t0);
+}
+
+void iLQGPlanner::OptimizePolicy(int horizon) {
+  if (!NominalTrajectory(horizon)) return;        // refused (horizon, engine error): the policy stays as it was
+  Iteration(horizon);
 }
 
 // ------------------------------------------------------------------ spline mappings (gradient/spline_mapping.cc)
@@ -2105,6 +2317,66 @@ void mjpc_gd_policy_action(int representation, int nu, const double* ctrlrange, 
   pol.times.assign(times, times + num_spline_points); pol.parameters.assign(parameters, parameters + (size_t)num_spline_points * nu);
   pol.Action(action, nullptr, time);
 }
+
+// ---- iLQGPlanner
+#define ILQ(p) ((mjpc_hip::iLQGPlanner*)(p))
+void* mjpc_ilqg_create(const MjpcHipModel* model, const MjpcHipTask* task, int num_trajectory, int representation, int derivative_skip, int fused,
+                       const double* settings, int max_samples, int max_horizon, int device) {
+  auto* p = new mjpc_hip::iLQGPlanner();
+  mjpc_hip::Numerics n;
+  n.derivative_skip = derivative_skip; n.max_samples = max_samples; n.max_horizon = max_horizon; n.device = device;
+  p->num_trajectory = num_trajectory; p->representation = representation; p->fused = fused != 0;
+  if (settings) {
+    mjpc_hip::iLQGSettings& s = p->settings;
+    s.min_linesearch_step = settings[0]; s.fd_tolerance = settings[1]; s.fd_mode = settings[2]; s.min_regularization = settings[3];
+    s.max_regularization = settings[4]; s.regularization_type = (int)settings[5]; s.max_regularization_iterations = (int)settings[6];
+    s.action_limits = (int)settings[7]; s.nominal_feedback_scaling = (int)settings[8];
+  }
+  p->Initialize(model, task, n);
+  p->Allocate();
+  return p;
+}
+void mjpc_ilqg_destroy(void* p) { delete ILQ(p); }
+void mjpc_ilqg_reset(void* p, int horizon, const double* a) { ILQ(p)->Reset(horizon, a); }
+void mjpc_ilqg_set_state(void* p, const double* s, const double* m, const double* u, double t) { ILQ(p)->SetState(s, m, u, t); }
+void mjpc_ilqg_set_task(void* p, const MjpcHipTask* task) { ILQ(p)->SetTask(task); }
+void mjpc_ilqg_set_num_trajectory(void* p, int n) { ILQ(p)->num_trajectory = n; }
+void mjpc_ilqg_optimize_policy(void* p, int horizon) { ILQ(p)->OptimizePolicy(horizon); }
+void mjpc_ilqg_nominal_trajectory(void* p, int horizon) { ILQ(p)->NominalTrajectory(horizon); }
+void mjpc_ilqg_iteration(void* p, int horizon) { ILQ(p)->Iteration(horizon); }
+void mjpc_ilqg_action_from_policy(void* p, double* a, const double* state, double t, int prev) { ILQ(p)->ActionFromPolicy(a, state, t, prev != 0); }
+double mjpc_ilqg_improvement(void* p) { return ILQ(p)->improvement; }
+int mjpc_ilqg_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
+  return CopyTrajectory(ILQ(p)->BestTrajectory(), states, actions, nullptr, nullptr, costs, nullptr, total_return, nullptr);
+}
+void mjpc_ilqg_values(void* p, double* out) {
+  auto* g = ILQ(p);
+  out[0] = g->action_step; out[1] = g->expected; out[2] = g->improvement; out[3] = g->surprise; out[4] = g->winner; out[5] = g->backward_pass_failed ? 1 : 0;
+  out[6] = g->feedback_scaling; out[7] = g->backward_pass.regularization; out[8] = g->backward_pass.regularization_rate; out[9] = g->all_failed ? 1 : 0;
+  out[10] = g->backward_pass.dV[0]; out[11] = g->backward_pass.dV[1];
+}
+void mjpc_ilqg_timings(void* p, double* out) {
+  auto* g = ILQ(p);
+  out[0] = g->nominal_compute_time; out[1] = g->derivative_compute_time; out[2] = g->rollouts_compute_time; out[3] = g->policy_update_compute_time;
+  out[4] = g->resample_kernel_time; out[5] = g->rollout_kernel_time;
+}
+void mjpc_ilqg_returns(void* p, double* out, int n) { std::copy(ILQ(p)->returns.begin(), ILQ(p)->returns.begin() + std::min(n, (int)ILQ(p)->returns.size()), out); }
+int mjpc_ilqg_linesearch_steps(void* p, double* out) { auto& w = ILQ(p)->linesearch_steps; if (out) std::copy(w.begin(), w.end(), out); return (int)w.size(); }
+// which: 0 policy, 1 previous_policy, 2 candidate.  Arrays of `horizon` knots (any may be NULL); returns the policy's trajectory.horizon
+int mjpc_ilqg_get_policy(void* p, int which, double* times, double* states, double* actions, double* feedback_gain, double* action_improvement,
+                         double* feedback_scaling) {
+  auto* g = ILQ(p);
+  const mjpc_hip::iLQGPolicy& pol = which == 0 ? g->policy : which == 1 ? g->previous_policy : g->candidate;
+  const size_t H = pol.trajectory.horizon, ds = pol.nq + pol.nv + pol.na, nd = 2 * pol.nv + pol.na, nu = pol.nu;
+  if (times) std::copy(pol.trajectory.times.begin(), pol.trajectory.times.begin() + H, times);
+  if (states) std::copy(pol.trajectory.states.begin(), pol.trajectory.states.begin() + H * ds, states);
+  if (actions) std::copy(pol.trajectory.actions.begin(), pol.trajectory.actions.begin() + H * nu, actions);
+  if (feedback_gain) std::copy(pol.feedback_gain.begin(), pol.feedback_gain.begin() + H * nu * nd, feedback_gain);
+  if (action_improvement) std::copy(pol.action_improvement.begin(), pol.action_improvement.begin() + H * nu, action_improvement);
+  if (feedback_scaling) *feedback_scaling = pol.feedback_scaling;
+  return (int)H;
+}
+int mjpc_ilqg_best_rollout(const double* returns, const int* failures, int n) { return mjpc_hip::iLQGPlanner::BestRollout(returns, failures, n); }
 
 // ---- iLQGBackwardPass, BoxQP, iLQGPolicy
 namespace {

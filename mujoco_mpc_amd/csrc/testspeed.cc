@@ -473,7 +473,7 @@ TestspeedResult SynchronousPlanningCost(const MjpcHipModel& model, HostTask& tas
 // ====================================================================== flat C view (ctypes tests / Python front end)
 extern "C" {
 // planner_kind: 0 = SamplingPlanner handle (mjpc_planner_create), 1 = CrossEntropyPlanner handle (mjpc_cem_create),
-// 2 = SampleGradientPlanner handle (mjpc_sg_create), 3 = GradientPlanner handle (mjpc_gd_create).
+// 2 = SampleGradientPlanner handle (mjpc_sg_create), 3 = GradientPlanner handle (mjpc_gd_create), 4 = iLQGPlanner handle (mjpc_ilqg_create).
 // state/mocap are in-out (final simulator state); cost_per_step[total_steps] optional.  Returns the total cost
 // (testspeed.cc:128) and fills out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds, plan_steps, failure}.
 double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, void* planner, int planner_kind, double* state, double* mocap,
@@ -488,8 +488,16 @@ double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, vo
   if (mocap) std::copy(mocap, mocap + 7 * model->nmocap, s.mocap.begin());
   s.userdata.assign((size_t)std::max(model->nuserdata, 1), 0.0);
   s.time = time0;
-  PlannerOps ops = planner_kind == 0 ? Ops(*(SamplingPlanner*)planner) : planner_kind == 2 ? Ops(*(SampleGradientPlanner*)planner)
-                   : planner_kind == 3 ? Ops(*(GradientPlanner*)planner) : Ops(*(CrossEntropyPlanner*)planner);
+  PlannerOps ops;
+  if (planner_kind == 4) {     // iLQGPlanner handle (mjpc_ilqg_create): a feedback policy, evaluated at the simulator's current state (testspeed.cc:96)
+    iLQGPlanner* ip = (iLQGPlanner*)planner;
+    ops = Ops(*ip);
+    const SimState* live = &s;
+    ops.ActionFromPolicy = [ip, live](double* a, double t) { ip->ActionFromPolicy(a, live->state.data(), t, false); };
+  } else {
+    ops = planner_kind == 0 ? Ops(*(SamplingPlanner*)planner) : planner_kind == 2 ? Ops(*(SampleGradientPlanner*)planner)
+          : planner_kind == 3 ? Ops(*(GradientPlanner*)planner) : Ops(*(CrossEntropyPlanner*)planner);
+  }
   TestspeedResult r = SynchronousPlanningCost(*model, ht, ops, sim, s, horizon, steps_per_planning_iteration, total_time,
                                               TransitionForTask(task->task_id, mode, mode_time));
   if (task_parameters_io) std::copy(ht.parameters.begin(), ht.parameters.end(), task_parameters_io);   // what Transition left behind

@@ -109,6 +109,28 @@ class HipBackend:
         self._last_PN = inp.num_spline_points * self.model["nu"]
         return o
 
+    def plan_feedback(self, state, time, horizon, times, states, actions, feedback_gain, action_step, feedback_scaling, action_improvement=None,
+                      mode=capi.FEEDBACK_INDEXED, representation=1, use_feedback=True, mocap=None, userdata=None, candidate_offset=0):
+        """Rollouts under a feedback policy (mjpc_hip_plan_feedback): candidate i applies
+        clamp((actions[t] + action_step[i] * action_improvement[t]) + feedback_scaling[i] * (feedback_gain[t] * StateDiff(states[t], x_t)))
+        with the tables indexed by the step (FEEDBACK_INDEXED) or interpolated at the step's time (FEEDBACK_TIME).  The winner's
+        rows come back as after plan(); fetch_all(N, H, 0) gives every candidate's."""
+        N = int(len(np.asarray(action_step).ravel()))
+        inp = self.make_input(state=state, mocap=mocap, time=time, knot_times=np.zeros(1), knot_values=np.zeros(self.model["nu"]), interpolation=0,
+                              num_trajectory=N, horizon=horizon, userdata=userdata, candidate_offset=candidate_offset,
+                              num_local=N - int(candidate_offset))
+        pol = capi.make_feedback_policy(times, states, actions, feedback_gain, action_step, feedback_scaling, action_improvement=action_improvement,
+                                        mode=mode, representation=representation, use_feedback=use_feedback)
+        o, c, ntr = self._alloc_out(max(N - int(candidate_offset), 1), horizon, 1)
+        if self.lib.mjpc_hip_plan_feedback(self.h, C.byref(inp), C.byref(pol), C.byref(c)) != 0:
+            raise RuntimeError("mjpc_hip_plan_feedback failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["winner"] = c.winner; o["winner_return"] = c.winner_return
+        o["rollouts_compute_time_us"] = c.rollouts_compute_time_us
+        o["resample_time_us"] = self.lib.mjpc_hip_feedback_resample_time_us(self.h)
+        o["trace"] = o["trace"][:, :ntr]
+        del o["winner_knots"]
+        return o
+
     def sample_gradient(self, slot, scale):
         """gradient[k] = sum_i history[slot[i]][k] * scale[i] over the noise history, k < P * nu of the last plan
         (mjpc_hip_sample_gradient): products rounded, added in ascending i."""

@@ -11,6 +11,7 @@
 //   mjpc/planners/sample_gradient/planner.h:35-175 SampleGradientPlanner (mixed batch; gradient reduced on the device)
 //   mjpc/planners/model_derivatives.h:30-70  ModelDerivatives (finite-difference A, B, C, D along a trajectory, on the device)
 //   mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h  CostDerivatives (on the device), Gradient (backward recursion, host)
+//   mjpc/planners/ilqs/planner.h             iLQSPlanner (a SamplingPlanner and an iLQGPlanner taking turns on one plan)
 // Differences forced by the boundary: `mjModel*` / `const Task&` become the ABI's MjpcHipModel / MjpcHipTask views
 // plus the planner's <custom><numeric> settings (Numerics); `ThreadPool&` arguments are gone (the GPU is the pool);
 // `State` is passed as its raw arrays (State::CopyTo, mjpc/states/state.cc:128-135).
@@ -524,7 +525,7 @@ class GradientPlanner {
 };
 
 // ---- iLQG (mjpc/planners/ilqg/): boxqp.h, settings.h, policy.{h,cc}, backward_pass.{h,cc}, and the planner (iLQGPlanner, at the end of
-// this header).  The components are the reference's public ones, which its iLQS drives as well.
+// this header).  The components are the reference's public ones, which its iLQS (iLQSPlanner, below) drives as well.
 // ilqg/boxqp.h: storage of the box-constrained control solve
 class BoxQP {
  public:
@@ -644,6 +645,11 @@ class iLQGPlanner {
   void OptimizePolicy(int horizon);
   bool NominalTrajectory(int horizon);                 // false: refused (horizon out of range, engine error); nothing was changed
   void Iteration(int horizon);                         // only behind a NominalTrajectory of the same horizon that returned true
+  // iLQS's `candidate_policy[0].trajectory = sampling.trajectory[0]` (ilqs/planner.cc:198): the first `horizon` rows of `trajectory`
+  // (states, actions, times, residual, costs), its return and failure flag become candidate.trajectory, the last action row repeating
+  // the one before it as every rollout leaves it; linesearch_steps is sized for num_trajectory and Iteration(horizon) may follow.
+  // false: refused (horizon out of range, dimensions that are not this planner's); nothing was changed
+  bool SetNominal(const Trajectory& trajectory, int horizon);
   void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);
   const Trajectory* BestTrajectory() { return winner >= 0 ? &trajectory_winner : nullptr; }
   // planner.cc:715-729: -1 when every candidate failed
@@ -665,6 +671,7 @@ class iLQGPlanner {
   int winner = -1, derivative_skip_ = 0;
   bool fused = true;                                   // derivatives + backward pass in one device call (derivative_skip == 0 only)
   bool backward_pass_failed = false, all_failed = false;    // of the last OptimizePolicy
+  bool adopted = false;                                // the last Iteration replaced `policy` (false: failed pass, every rollout failed, refusal)
   int backward_pass_status[3] = {0, 0, 0};
   double feedback_scaling = 1.0, action_step = 0, expected = 0, improvement = 0, surprise = 0;
   double nominal_compute_time = 0, derivative_compute_time = 0, rollouts_compute_time = 0, policy_update_compute_time = 0;   // microseconds
@@ -680,6 +687,89 @@ class iLQGPlanner {
   std::vector<int> fail_;
   bool nominal_ok_ = false; int nominal_horizon_ = 0;  // the last NominalTrajectory went through, at this horizon
   mutable std::shared_mutex mtx_;
+};
+
+// ---- iLQS (mjpc/planners/ilqs/planner.{h,cc}): sampling and iLQG taking turns on one plan.  A composition, as in the reference; each
+// member keeps its own engine.  OptimizePolicy(horizon), ilqs/planner.cc:87-214:
+//  1. previous_active_policy = active_policy;
+//  2. if that is iLQG: ilqg.NominalTrajectory, then sampling.policy.plan becomes the P-knot spline fitted (SplineFit below) to the first
+//     horizon - 1 actions of ilqg.candidate.trajectory, each knot clamped to the ctrlrange, at the times sampling.time + p time_shift
+//     (repeated addition), time_shift = max((horizon - 1) timestep / (P - 1), 1e-5);
+//  3. sampling.OptimizePolicy.  Kept from the reference: without sampling_sliding_plan its UpdateNominalPolicy rebuilds policy.plan from
+//     the knots of sampling's own last winner, so the fitted plan of step 2 reaches the rollouts only with a sliding plan;
+//  4. sampling improved when winner > 0 and returns[winner] < (previous was sampling ? returns[0] : ilqg.candidate's return), strictly:
+//     active_policy = kSampling, iLQG's derivative / rollout / update timers are zeroed (the nominal one only when the active policy was
+//     sampling already), return;
+//  5. else, when the previous active policy was sampling, sampling's batch member 0 becomes iLQG's nominal (iLQGPlanner::SetNominal;
+//     sampling.BestTrajectory() is its winner's again afterwards);
+//  6. ilqg.Iteration;
+//  7. if it adopted a policy and ilqg.trajectory_winner's return < (previous was sampling ? sampling.returns[winner] : ilqg.returns[0], the
+//     full-step rollout of this iteration's batch), strictly: active_policy = kiLQG.
+// Deliberate differences, where the reference is undefined:
+//  - Initialize refuses sampling_spline_points < 2 (the reference divides by P - 1), > kMaxGradientSplinePoints (the mapping's capacity)
+//    and sampling_representation == kZeroSpline (the last knot lies one step behind the last action: its column of the mapping is zero and
+//    the normal matrix singular for every horizon and P);
+//  - a fit whose normal matrix has a Cholesky pivot that is not positive and finite (linear with P >= horizon, for one) is refused,
+//    "iLQS: spline fit is singular": the sampling plan stays as it was and OptimizePolicy returns;
+//  - when ilqg.Iteration adopted nothing (failed backward pass, every rollout failed) active_policy stays: the reference would compare
+//    returns left over from an earlier call.
+// The mappings are allocated with dim = 1: the reference's [nu (H-1)][nu P] matrix is kron(M, I_nu), so the scalar M [H-1][P] is computed
+// once and its pseudo-inverse W applied per actuator.  As in the reference, W is recomputed only when (H - 1, P) changed since the last
+// conversion (here: or the representation); until then it belongs to the times of the conversion that filled it.
+enum iLQSActivePolicy : int { kSampling = 0, kiLQG = 1 };
+
+// W = (M'M)^-1 M' [P][H1] of M = mapping->Compute(knot_times, P, action_times, H1) [H1][P] (mapping->dim == 1): G = M'M, its lower
+// Cholesky factor L (left-looking, row by row), then per column t of M' forward and back substitution.  Every sum starts at 0.0 and takes
+// its index ascending, one rounded product and one rounded add per term (this library is compiled without contraction).  scratch is
+// resized to P (P + 2).  Returns 0, or -1 when a pivot is not positive and finite (W is then unspecified).
+int SplineFitOperator(SplineMapping* mapping, const std::vector<double>& knot_times, int P, const double* action_times, int H1, double* W,
+                      std::vector<double>& scratch);
+// knots [P][nu]: theta[p][j] = sum_t W[p][t] actions[t][j], by the same summation rule
+void SplineFitApply(const double* W, int P, int H1, int nu, const double* actions, double* knots);
+// both, without a cache: the least-squares knots of a `representation` spline over knot_times [P] through actions [H1][nu] at
+// action_times [H1].  0, or -1: singular, representation not 0 .. 2, P not 1 .. kMaxGradientSplinePoints, H1 not 1 .. kMaxTrajectoryHorizon
+int SplineFit(int representation, int P, const double* knot_times, int H1, const double* action_times, int nu, const double* actions,
+              double* knots);
+
+class iLQSPlanner {
+ public:
+  // whose Action ActionFromPolicy returns (ilqs/planner.cc:228-253)
+  enum PolicySource : int { kSamplingCurrent = 0, kSamplingPrevious, kiLQGCurrent, kiLQGPrevious };
+  iLQSPlanner();
+  iLQSPlanner(const iLQSPlanner&) = delete;
+  iLQSPlanner& operator=(const iLQSPlanner&) = delete;
+
+  // ilqg.num_trajectory / representation / settings / fused are set on the member before Initialize, as for an iLQGPlanner
+  void Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics);
+  void Allocate();
+  void Reset(int horizon, const double* initial_repeated_action = nullptr);
+  void SetState(const double* state, const double* mocap, const double* userdata, double time);
+  void SetTask(const MjpcHipTask* task);
+  void OptimizePolicy(int horizon);
+  void NominalTrajectory(int horizon);
+  void ActionFromPolicy(double* action, const double* state, double time, bool use_previous = false);   // state reaches iLQG only
+  const Trajectory* BestTrajectory();
+  // the four cases of use_previous: sampling's previous policy when it was active before; iLQG's CURRENT policy when iLQG was active
+  // before and sampling returned early since (iLQG was not updated); iLQG's previous policy when it was updated
+  static int ActionSource(int previous_active_policy, int active_policy, bool use_previous);
+
+  SamplingPlanner sampling;
+  iLQGPlanner ilqg;
+  int active_policy = kSampling, previous_active_policy = kSampling;
+  std::unique_ptr<SplineMapping> mappings[3];          // dim = 1
+  std::vector<double> spline_times_cache, spline_parameters_cache;     // knot times [P], fitted and clamped knots [P][nu] of the last conversion
+  std::vector<double> inversemapping;                  // W [P][H - 1]
+  int dim_actions = 0, dim_parameters = 0, mapping_representation = -1;      // the cache key: H - 1, P, representation
+  bool converted = false, returned_early = false, iterated = false;   // of the last OptimizePolicy
+  bool fit_cache_miss = false;                         // the last conversion recomputed W
+  double fit_compute_time = 0;                         // microseconds: mapping, factor and W when recomputed, and the product
+
+ private:
+  bool Convert(int horizon);                           // step 2 behind ilqg.NominalTrajectory; false: singular, the plan was left as it was
+  bool initialized_ = false;
+  int nu_ = 0;
+  double timestep_ = 0;
+  std::vector<double> ctrlrange_, fit_scratch_;
 };
 
 }  // namespace mjpc_hip

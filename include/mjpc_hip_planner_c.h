@@ -7,6 +7,7 @@
  *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
  *   mjpc_md_*       -> mjpc::ModelDerivatives                 (mjpc/planners/model_derivatives.h:30-70)
  *   mjpc_cd_* / mjpc_gd_* -> mjpc::CostDerivatives, mjpc::Gradient (mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h)
+ *   mjpc_ilqg_* / mjpc_ilqs_* -> mjpc::iLQGPlanner, mjpc::iLQSPlanner (mjpc/planners/ilqg/planner.h, planners/ilqs/planner.h)
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
  */
 #ifndef MJPC_HIP_PLANNER_C_H_
@@ -200,6 +201,39 @@ int mjpc_ilqg_linesearch_steps(void *planner, double *out /* NULL: size only */)
 int mjpc_ilqg_get_policy(void *planner, int which, double *times, double *states, double *actions, double *feedback_gain, double *action_improvement,
                          double *feedback_scaling);
 int mjpc_ilqg_best_rollout(const double *returns, const int *failures, int n);      /* iLQGPlanner::BestRollout, host only */
+/* iLQSPlanner (mjpc/planners/ilqs/planner.h): create = Initialize + Allocate of a SamplingPlanner (exploration .. spline_points as for
+ * mjpc_planner_create) and an iLQGPlanner (ilqg_num_trajectory .. settings as for mjpc_ilqg_create), each on its own engine.  Refused through
+ * the error handler: spline_points < 2 or > 25, representation 0 (zero-order); the handle is then inert and only to be destroyed.
+ * values out[6] = {active_policy, previous_active_policy (0 sampling, 1 iLQG), and of the last optimize_policy: converted iLQG's nominal to
+ * a spline, returned early on sampling's improvement, ran an iLQG iteration, that iteration adopted a policy}; timings out[2] = {spline fit
+ * of the last conversion (host, microseconds), 1 when it recomputed the cached operator}.  mjpc_ilqs_sampling / mjpc_ilqs_ilqg return BORROWED
+ * handles for the mjpc_planner_* / mjpc_ilqg_* calls, owned by the iLQS planner: never destroy them. */
+void *mjpc_ilqs_create(const MjpcHipModel *model, const MjpcHipTask *task, const double *exploration /* [2] */, int trajectories, int representation,
+                       int sliding_plan, int spline_points, int ilqg_num_trajectory, int ilqg_representation, int derivative_skip, int fused,
+                       const double *settings, int max_samples, int max_horizon, int device);
+void mjpc_ilqs_destroy(void *planner);
+void mjpc_ilqs_reset(void *planner, int horizon, const double *initial_repeated_action);
+void mjpc_ilqs_set_state(void *planner, const double *state, const double *mocap, const double *userdata, double time);
+void mjpc_ilqs_set_task(void *planner, const MjpcHipTask *task);
+void mjpc_ilqs_optimize_policy(void *planner, int horizon);
+void mjpc_ilqs_nominal_trajectory(void *planner, int horizon);
+void mjpc_ilqs_action_from_policy(void *planner, double *action, const double *state /* or NULL; reaches iLQG only */, double time, int use_previous);
+int mjpc_ilqs_best_trajectory(void *planner, double *states, double *actions, double *costs, double *total_return);   /* the active member's; returns H */
+void mjpc_ilqs_values(void *planner, int *out);
+void mjpc_ilqs_timings(void *planner, double *out);
+void mjpc_ilqs_set_noise_exploration(void *planner, double first, double second);   /* sampling's GUI sliders noise_exploration[2] */
+void *mjpc_ilqs_sampling(void *planner);
+void *mjpc_ilqs_ilqg(void *planner);
+int mjpc_ilqs_fitted_knots(void *planner, double *times, double *values);      /* the last conversion's knots, clamped: [P], [P][nu]; returns P */
+/* sampling's batch member `index` of the last plan step (the reference's sampling.trajectory[index]); the planner's best trajectory is its
+ * winner's again afterwards.  Any pointer may be NULL; returns H */
+int mjpc_ilqs_sampling_member(void *planner, int index, double *states, double *actions, double *times, double *residual, double *total_return);
+/* host closed forms without a planner (no GPU needed).  action_source: whose policy ActionFromPolicy evaluates, 0 sampling's current,
+ * 1 sampling's previous, 2 iLQG's current, 3 iLQG's previous.  spline_fit: the least-squares knots out_knots [P][nu] of a spline
+ * (representation 0 .. 2) over knot_times [P] through actions [H1][nu] at action_times [H1]; 0, or -1 when singular or out of range */
+int mjpc_ilqs_action_source(int previous_active_policy, int active_policy, int use_previous);
+int mjpc_ilqs_spline_fit(int representation, int P, const double *knot_times, int H1, const double *action_times, int nu, const double *actions,
+                         double *out_knots);
 /* host closed forms without a planner (no GPU needed): a spline mapping [(dim num_output)][(dim num_input)], GradientPolicy::Action */
 void mjpc_gd_spline_mapping(int representation, int dim, const double *input_times, int num_input, const double *output_times, int num_output,
                             double *mapping);
@@ -246,7 +280,7 @@ void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int
                              const double *feedback_gain, double feedback_scaling, const double *state, double time, double *action);
 
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
- * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create, 4 = handle from mjpc_ilqg_create (its policy is evaluated at the simulator's state).  state / mocap are in-out;
+ * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create, 4 = handle from mjpc_ilqg_create, 5 = handle from mjpc_ilqs_create (4 and 5: the policy is evaluated at the simulator's state).  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,
  * plan_steps, failure}.  Returns the total cost. */
 double mjpc_testspeed_run(const MjpcHipModel *model, const MjpcHipTask *task, void *planner, int planner_kind, double *state,

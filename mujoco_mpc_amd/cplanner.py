@@ -146,6 +146,20 @@ def lib():
         "mjpc_ilqg_linesearch_steps": (i, [vp, c_double_p]),
         "mjpc_ilqg_get_policy": (i, [vp, i, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
         "mjpc_ilqg_best_rollout": (i, [c_double_p, c_int_p, i]),
+        "mjpc_ilqs_create": (vp, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), c_double_p, i, i, i, i, i, i, i, i, c_double_p, i, i, i]),
+        "mjpc_ilqs_set_noise_exploration": (None, [vp, d, d]),
+        "mjpc_ilqs_destroy": (None, [vp]), "mjpc_ilqs_reset": (None, [vp, i, c_double_p]),
+        "mjpc_ilqs_set_state": (None, [vp, c_double_p, c_double_p, c_double_p, d]),
+        "mjpc_ilqs_set_task": (None, [vp, C.POINTER(capi.MjpcHipTask)]),
+        "mjpc_ilqs_optimize_policy": (None, [vp, i]), "mjpc_ilqs_nominal_trajectory": (None, [vp, i]),
+        "mjpc_ilqs_action_from_policy": (None, [vp, c_double_p, c_double_p, d, i]),
+        "mjpc_ilqs_best_trajectory": (i, [vp, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_ilqs_values": (None, [vp, c_int_p]), "mjpc_ilqs_timings": (None, [vp, c_double_p]),
+        "mjpc_ilqs_sampling": (vp, [vp]), "mjpc_ilqs_ilqg": (vp, [vp]),
+        "mjpc_ilqs_fitted_knots": (i, [vp, c_double_p, c_double_p]),
+        "mjpc_ilqs_sampling_member": (i, [vp, i, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "mjpc_ilqs_action_source": (i, [i, i, i]),
+        "mjpc_ilqs_spline_fit": (i, [i, i, c_double_p, i, c_double_p, i, c_double_p, c_double_p]),
         "mjpc_gd_spline_mapping": (None, [i, i, c_double_p, i, c_double_p, i, c_double_p]),
         "mjpc_gd_policy_action": (None, [i, i, c_double_p, c_double_p, c_double_p, i, d, c_double_p]),
         "mjpc_testspeed_run": (d, [C.POINTER(capi.MjpcHipModel), C.POINTER(capi.MjpcHipTask), vp, i, c_double_p, c_double_p, d, i, i, d, i,
@@ -520,6 +534,92 @@ class iLQGPlanner(_Planner):
         return o
 
 
+class iLQSPlanner(_Planner):
+    """mjpc_hip::iLQSPlanner (C++) driven from Python; names follow planners/ilqs/planner.h.  `.sampling` and `.ilqg` are ordinary
+    SamplingPlanner / iLQGPlanner views of its two members over borrowed handles: they never destroy them."""
+    _prefix = "mjpc_ilqs_"
+    kSampling, kiLQG = 0, 1
+    kMaxSplinePoints = 25
+
+    def Initialize(self, model: dict, task: dict, numerics: dict | None = None, settings: dict | None = None, max_samples=128, max_horizon=512, device=0):
+        numerics = numerics or {}; settings = settings or {}
+        self.cm = capi.CModel(model, task)
+        se = numerics.get("sampling_exploration", 0.1)
+        se = list(se) if isinstance(se, (list, tuple)) else [se]
+        self._expl = np.array([float(se[0]), float(se[1]) if len(se) > 1 else 0.0])
+        self.nu = int(model["nu"]); self.ns = int(model["nq"] + model["nv"] + model["na"]); self.nd = int(2 * model["nv"] + model["na"])
+        self.nr = int(task["num_residual"])
+        self.max_samples, self.max_horizon = int(max_samples), int(max_horizon)
+        s = np.array([float(settings.get(k, v)) for k, v in zip(iLQGPlanner.SETTINGS, iLQGPlanner.DEFAULTS)])
+        self.close()
+        h = self._L.mjpc_ilqs_create(C.byref(self.cm.c_model), C.byref(self.cm.c_task), _dp(self._expl), int(numerics.get("sampling_trajectories", 10)),
+                                     int(numerics.get("sampling_representation", 2)), int(numerics.get("sampling_sliding_plan", 0)),
+                                     int(numerics.get("sampling_spline_points", 10)), int(numerics.get("ilqg_num_rollouts", 10)),
+                                     int(numerics.get("ilqg_representation", 1)), int(numerics.get("derivative_skip", 0)),
+                                     int(bool(settings.get("fused", True))), _dp(s), self.max_samples, self.max_horizon, int(device))
+        self._h = C.c_void_p(h)
+        self.sampling = self._view(SamplingPlanner, self._L.mjpc_ilqs_sampling(self._h), task)
+        self.ilqg = self._view(iLQGPlanner, self._L.mjpc_ilqs_ilqg(self._h), task)
+        _check()
+
+    def _view(self, cls, handle, task):
+        v = cls.__new__(cls)
+        v._L = self._L; v._h = C.c_void_p(handle); v._noise = None
+        v.cm = self.cm; v.nu = self.nu; v.ns = self.ns; v.nd = self.nd; v.nr = self.nr; v.ntrace = int(task["num_trace"])
+        v.max_samples = self.max_samples; v.max_horizon = self.max_horizon
+        v.close = lambda: None
+        return v
+
+    def ActionFromPolicy(self, time, use_previous=False, state=None):
+        a = np.zeros(self.nu)
+        st = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
+        self._L.mjpc_ilqs_action_from_policy(self._h, _dp(a), _dp(st), float(time), int(bool(use_previous))); _check()
+        return a
+
+    def set_noise_exploration(self, first, second=0.0):
+        """sampling's noise_exploration sliders"""
+        self._L.mjpc_ilqs_set_noise_exploration(self._h, float(first), float(second))
+
+    def values(self):
+        o = np.zeros(6, np.int32); self._L.mjpc_ilqs_values(self._h, o.ctypes.data_as(c_int_p))
+        return dict(active_policy=int(o[0]), previous_active_policy=int(o[1]), converted=bool(o[2]), returned_early=bool(o[3]), iterated=bool(o[4]),
+                    adopted=bool(o[5]))
+
+    def timings(self):
+        o = np.zeros(2); self._L.mjpc_ilqs_timings(self._h, _dp(o))
+        return dict(fit_us=o[0], fit_cache_miss=bool(o[1]), sampling=self.sampling.timings(), ilqg=self.ilqg.timings())
+
+    def fitted_knots(self):
+        """the knots of the last conversion of iLQG's nominal to sampling's spline, clamped: times [P], values [P, nu]"""
+        return self._knots("fitted_knots")
+
+    def sampling_member(self, index, horizon):
+        """sampling.trajectory[index] of the last plan step (batch index, not rank)"""
+        H = int(horizon)
+        o = dict(states=np.zeros((H, self.ns)), actions=np.zeros((H, self.nu)), times=np.zeros(H), residual=np.zeros((H, max(self.nr, 1))))
+        tot = C.c_double()
+        n = self._L.mjpc_ilqs_sampling_member(self._h, int(index), _dp(o["states"]), _dp(o["actions"]), _dp(o["times"]), _dp(o["residual"]),
+                                              C.cast(C.byref(tot), c_double_p)); _check()
+        assert n == H, (n, H)
+        o["residual"] = o["residual"].ravel()[:H * self.nr].reshape(H, self.nr); o["total_return"] = tot.value
+        return o
+
+
+def ilqs_action_source(previous_active_policy, active_policy, use_previous):
+    """iLQSPlanner::ActionSource (host closed form, no GPU needed): 0 sampling's current policy, 1 sampling's previous, 2 iLQG's current, 3 iLQG's previous"""
+    return lib().mjpc_ilqs_action_source(int(previous_active_policy), int(active_policy), int(bool(use_previous)))
+
+
+def ilqs_spline_fit(representation, knot_times, action_times, actions):
+    """SplineFit (host closed form, no GPU needed): the least-squares knots [P, nu] of a spline over knot_times through actions [H1, nu] at
+    action_times, or None when the normal matrix is singular"""
+    kt = np.ascontiguousarray(knot_times, dtype=np.float64); at = np.ascontiguousarray(action_times, dtype=np.float64)
+    u = np.ascontiguousarray(actions, dtype=np.float64).reshape(at.size, -1)
+    out = np.zeros((kt.size, u.shape[1]))
+    rc = lib().mjpc_ilqs_spline_fit(int(representation), int(kt.size), _dp(kt), int(at.size), _dp(at), int(u.shape[1]), _dp(u), _dp(out))
+    return out if rc == 0 else None
+
+
 def ilqg_best_rollout(returns, failures):
     """iLQGPlanner::BestRollout (host closed form, no GPU needed): from the last index down, strict <; -1 when every candidate failed"""
     r = np.ascontiguousarray(returns, dtype=np.float64); f = np.ascontiguousarray(failures, dtype=np.int32)
@@ -560,7 +660,7 @@ def sample_gradient_step_sizes(steps, max_value=2.0, min_value=1.0e-3):
 
 def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_planning_iteration=1, total_time=1.0, device=0, mode=0, mode_time=0.0):
     """mjpc/testspeed.cc:44-129 (`SynchronousPlanningCost`) through the C++ harness: `planner` is a cplanner.SamplingPlanner or
-    cplanner.CrossEntropyPlanner / cplanner.SampleGradientPlanner / cplanner.GradientPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
+    cplanner.CrossEntropyPlanner / cplanner.SampleGradientPlanner / cplanner.GradientPlanner / cplanner.iLQGPlanner / cplanner.iLQSPlanner that has been Initialize()d / Reset(); the world is stepped on the HIP engine as well."""
     L = lib()
     cm = planner.cm
     m = cm.model
@@ -568,7 +668,8 @@ def testspeed(planner, state, mocap=None, time0=0.0, horizon=None, steps_per_pla
     st = np.ascontiguousarray(state, dtype=np.float64).copy()
     mc = None if (mocap is None or m["nmocap"] == 0) else np.ascontiguousarray(mocap, dtype=np.float64).copy()
     costs = np.zeros(nsteps); out = np.zeros(6); params = np.zeros(max(int(cm.task["num_parameter"]), 1))
-    kind = 1 if isinstance(planner, CrossEntropyPlanner) else 2 if isinstance(planner, SampleGradientPlanner) else 3 if isinstance(planner, GradientPlanner) else 0
+    kind = (1 if isinstance(planner, CrossEntropyPlanner) else 2 if isinstance(planner, SampleGradientPlanner) else 3 if isinstance(planner, GradientPlanner)
+            else 4 if isinstance(planner, iLQGPlanner) else 5 if isinstance(planner, iLQSPlanner) else 0)
     total = L.mjpc_testspeed_run(C.byref(cm.c_model), C.byref(cm.c_task), planner._h, kind, _dp(st), _dp(mc), float(time0), int(horizon),
                                  int(steps_per_planning_iteration), float(total_time), int(device), _dp(costs), _dp(out), int(mode), float(mode_time), _dp(params))
     _check()

@@ -6,6 +6,7 @@
 //   mjpc/planners/sample_gradient/planner.cc:43-493    SampleGradientPlanner host logic (batch + gradient sum on the engine)
 //   mjpc/planners/model_derivatives.cc:24-165          ModelDerivatives (evaluations on the engine, interpolation on the host)
 //   mjpc/planners/ilqg/backward_pass.cc, policy.cc, planner.cc:429-520   BoxQP, iLQGPolicy, iLQGBackwardPass (host, and the engine's kernel)
+//   mjpc/planners/ilqs/planner.cc:33-263               iLQSPlanner (host; its spline fit is defined here, not MuJoCo's)
 #include "../../include/mjpc_hip_planner.h"
 #include "../../include/mjpc_hip_planner_c.h"
 #include "atan2_cr.h"
@@ -1604,7 +1605,7 @@ void iLQGPlanner::Reset(int horizon, const double* initial_repeated_action) {
   model_derivative.Reset(nd_, nu_, nr_, h); cost_derivative.Reset(nd_, nu_, nr_, h); backward_pass.Reset(nd_, nu_, h);
   for (iLQGPolicy* p : {&policy, &previous_policy, &candidate}) { p->Reset(h, initial_repeated_action); p->representation = representation; }
   feedback_scaling = 1.0; action_step = 0.0; expected = 0.0; improvement = 0.0; surprise = 0.0;
-  winner = -1; backward_pass_failed = false; all_failed = false;
+  winner = -1; backward_pass_failed = false; all_failed = false; adopted = false;
   derivative_skip_ = numerics_.derivative_skip;
 }
 
@@ -1704,7 +1705,8 @@ bool iLQGPlanner::NominalTrajectory(int horizon) {   // planner.cc:167-223
 void iLQGPlanner::Iteration(int horizon) {   // planner.cc:377-615
   using clock = std::chrono::steady_clock;
   auto us = [](clock::time_point t0) { return std::chrono::duration<double, std::micro>(clock::now() - t0).count(); };
-  // only behind a NominalTrajectory of the same horizon and batch that went through: it sized linesearch_steps and filled `candidate`
+  adopted = false;
+  // only behind a NominalTrajectory (or SetNominal) of the same horizon and batch that went through: it sized linesearch_steps and filled `candidate`
   if (!engine_ || !nominal_ok_ || horizon != nominal_horizon_ || num_trajectory < 1 || (int)linesearch_steps.size() != num_trajectory) {
     if (engine_) Fatal("iLQGPlanner::Iteration: no nominal trajectory of this horizon and batch (call NominalTrajectory first)");
     return;
@@ -1714,7 +1716,7 @@ void iLQGPlanner::Iteration(int horizon) {   // planner.cc:377-615
   if (N > 1) LogScale(linesearch_steps.data(), 1.0, settings.min_linesearch_step, N - 1);
   linesearch_steps[N - 1] = 0.0;
   derivative_compute_time = rollouts_compute_time = policy_update_compute_time = 0.0;
-  backward_pass_failed = false;
+  backward_pass_failed = false; adopted = false;
 
   // ----- derivatives and backward pass of the nominal -----
   auto t0 = clock::now();
@@ -1765,12 +1767,38 @@ void iLQGPlanner::Iteration(int horizon) {   // planner.cc:377-615
     policy.CopyFrom(candidate, horizon);
     policy.feedback_scaling = 1.0;
   }
+  adopted = true;
   policy_update_compute_time = us(t0);
 }
 
 void iLQGPlanner::OptimizePolicy(int horizon) {
   if (!NominalTrajectory(horizon)) return;        // refused (horizon, engine error): the policy stays as it was
   Iteration(horizon);
+}
+
+bool iLQGPlanner::SetNominal(const Trajectory& tr, int horizon) {   // ilqs/planner.cc:198
+  if (!engine_ || num_trajectory == 0) return false;
+  if (horizon < 2 || horizon > numerics_.max_horizon) { Fatal("iLQGPlanner: horizon out of range (2 .. max_horizon)"); return false; }
+  const size_t H = (size_t)horizon;
+  if (tr.dim_state != ns_ || tr.dim_action != nu_ || tr.dim_residual != nr_ || tr.states.size() < H * ns_ || tr.actions.size() < H * nu_ ||
+      tr.times.size() < H || tr.residual.size() < H * nr_) { Fatal("iLQGPlanner::SetNominal: the trajectory's dimensions are not this planner's"); return false; }
+  num_trajectory = std::max(1, std::min(num_trajectory, std::min(numerics_.max_samples, kMaxiLQGTrajectory)));
+  const int N = num_trajectory;
+  linesearch_steps.assign(N, 0.0);
+  if (N > 1) LogScale(linesearch_steps.data(), 1.0, settings.min_linesearch_step, N - 1);
+  linesearch_steps[N - 1] = 0.0;
+  Trajectory& c = candidate.trajectory;
+  std::copy(tr.states.begin(), tr.states.begin() + H * ns_, c.states.begin());
+  std::copy(tr.actions.begin(), tr.actions.begin() + H * nu_, c.actions.begin());
+  std::copy(tr.times.begin(), tr.times.begin() + H, c.times.begin());
+  std::copy(tr.residual.begin(), tr.residual.begin() + H * nr_, c.residual.begin());
+  if (tr.costs.size() >= H) std::copy(tr.costs.begin(), tr.costs.begin() + H, c.costs.begin());
+  // trajectory.cc: the last action repeats the one before it
+  std::copy(c.actions.begin() + (H - 2) * nu_, c.actions.begin() + (H - 1) * nu_, c.actions.begin() + (H - 1) * nu_);
+  c.horizon = horizon; c.total_return = tr.total_return; c.failure = tr.failure;
+  policy.trajectory.horizon = horizon;
+  nominal_ok_ = true; nominal_horizon_ = horizon;
+  return true;
 }
 
 // ------------------------------------------------------------------ spline mappings (gradient/spline_mapping.cc)
@@ -1844,6 +1872,242 @@ void CubicSplineMapping::Compute(const std::vector<double>& input_times, int num
       for (size_t q = 0; q < 2 * ni; q++) acc += output_mapping[r * 2 * ni + q] * point_slope_mapping[q * ni + cc];
       mapping[r * ni + cc] = acc;
     }
+}
+
+// ------------------------------------------------------------------ iLQSPlanner (ilqs/planner.cc:33-263)
+// The reference solves (A'A) theta = A'u with mju_cholFactor / mju_cholSolve over A = kron(M, I_nu); MuJoCo is not part of this project, so
+// the arithmetic is defined here (include/mjpc_hip_planner.h), over the scalar M.
+int SplineFitOperator(SplineMapping* mapping, const std::vector<double>& knot_times, int P, const double* action_times, int H1, double* W,
+                      std::vector<double>& scratch) {
+  mapping->Compute(knot_times, P, action_times, H1);
+  const double* M = mapping->Get();                                  // [H1][P]
+  scratch.assign((size_t)P * (P + 2), 0.0);
+  double *L = scratch.data(), *y = L + (size_t)P * P, *x = y + P;    // G = M'M, overwritten by its lower factor
+  for (int i = 0; i < P; i++)
+    for (int j = 0; j <= i; j++) {
+      double acc = 0.0;
+      for (int t = 0; t < H1; t++) acc += M[(size_t)t * P + i] * M[(size_t)t * P + j];
+      L[(size_t)i * P + j] = acc;
+    }
+  for (int i = 0; i < P; i++) {
+    for (int j = 0; j < i; j++) {
+      double acc = 0.0;
+      for (int k = 0; k < j; k++) acc += L[(size_t)i * P + k] * L[(size_t)j * P + k];
+      L[(size_t)i * P + j] = (L[(size_t)i * P + j] - acc) / L[(size_t)j * P + j];
+    }
+    double acc = 0.0;
+    for (int k = 0; k < i; k++) acc += L[(size_t)i * P + k] * L[(size_t)i * P + k];
+    const double pivot = L[(size_t)i * P + i] - acc;
+    if (!(pivot > 0.0) || !std::isfinite(pivot)) return -1;
+    L[(size_t)i * P + i] = std::sqrt(pivot);
+  }
+  for (int t = 0; t < H1; t++) {                                     // column t of W: L L' x = M[t][:]
+    for (int i = 0; i < P; i++) {
+      double acc = 0.0;
+      for (int k = 0; k < i; k++) acc += L[(size_t)i * P + k] * y[k];
+      y[i] = (M[(size_t)t * P + i] - acc) / L[(size_t)i * P + i];
+    }
+    for (int i = P - 1; i >= 0; i--) {
+      double acc = 0.0;
+      for (int k = i + 1; k < P; k++) acc += L[(size_t)k * P + i] * x[k];
+      x[i] = (y[i] - acc) / L[(size_t)i * P + i];
+    }
+    for (int i = 0; i < P; i++) W[(size_t)i * H1 + t] = x[i];
+  }
+  return 0;
+}
+
+void SplineFitApply(const double* W, int P, int H1, int nu, const double* actions, double* knots) {
+  for (int p = 0; p < P; p++)
+    for (int j = 0; j < nu; j++) {
+      double acc = 0.0;
+      for (int t = 0; t < H1; t++) acc += W[(size_t)p * H1 + t] * actions[(size_t)t * nu + j];
+      knots[(size_t)p * nu + j] = acc;
+    }
+}
+
+static std::unique_ptr<SplineMapping> MakeSplineMapping(int representation) {
+  std::unique_ptr<SplineMapping> m;
+  if (representation == kZeroSpline) m.reset(new ZeroSplineMapping());
+  else if (representation == kLinearSpline) m.reset(new LinearSplineMapping());
+  else m.reset(new CubicSplineMapping());
+  m->Allocate(1);
+  return m;
+}
+
+int SplineFit(int representation, int P, const double* knot_times, int H1, const double* action_times, int nu, const double* actions,
+              double* knots) {
+  if (representation < kZeroSpline || representation > kCubicSpline || P < 1 || P > kMaxGradientSplinePoints || H1 < 1 ||
+      H1 > kMaxTrajectoryHorizon || nu < 0) return -1;
+  std::unique_ptr<SplineMapping> mapping = MakeSplineMapping(representation);
+  std::vector<double> W((size_t)P * H1), scratch;
+  if (SplineFitOperator(mapping.get(), std::vector<double>(knot_times, knot_times + P), P, action_times, H1, W.data(), scratch) != 0) return -1;
+  SplineFitApply(W.data(), P, H1, nu, actions, knots);
+  return 0;
+}
+
+iLQSPlanner::iLQSPlanner() {
+  for (int r = 0; r < 3; r++) mappings[r] = MakeSplineMapping(r);
+}
+
+void iLQSPlanner::Initialize(const MjpcHipModel* model, const MjpcHipTask* task, const Numerics& numerics) {
+  initialized_ = false;
+  // where the reference is undefined (header): refuse instead of producing NaN
+  if (numerics.sampling_spline_points < 2) { Fatal("iLQS: sampling_spline_points must be at least 2"); return; }
+  if (numerics.sampling_spline_points > kMaxGradientSplinePoints) { Fatal("iLQS: sampling_spline_points exceeds the spline mapping's capacity (25)"); return; }
+  if (numerics.sampling_representation == kZeroSpline) { Fatal("iLQS: a zero-order sampling_representation has no spline fit (its normal matrix is singular)"); return; }
+  // what the members refuse themselves (their Initialize reports it and leaves them without an engine) leaves this planner inert as well
+  const bool sampling_refuses = numerics.sampling_trajectories > numerics.max_samples;
+  const bool ilqg_refuses = ilqg.representation < kZeroSpline || ilqg.representation > kCubicSpline || ilqg.num_trajectory < 1 ||
+                            ilqg.num_trajectory > kMaxiLQGTrajectory;
+  sampling.Initialize(model, task, numerics);
+  if (sampling_refuses) return;
+  // iLQG's batch is capped at kMaxiLQGTrajectory whatever the sampling batch: its engine needs no more rows than that
+  Numerics ilqg_numerics = numerics;
+  ilqg_numerics.max_samples = std::min(numerics.max_samples, kMaxiLQGTrajectory);
+  ilqg.Initialize(model, task, ilqg_numerics);
+  if (ilqg_refuses) return;
+  nu_ = model->nu; timestep_ = model->timestep;
+  ctrlrange_.assign(model->actuator_ctrlrange, model->actuator_ctrlrange + 2 * nu_);
+  initialized_ = true;
+}
+
+void iLQSPlanner::Allocate() {
+  if (!initialized_) return;
+  sampling.Allocate();
+  ilqg.Allocate();
+  dim_actions = 0; dim_parameters = 0; mapping_representation = -1;
+}
+
+void iLQSPlanner::Reset(int horizon, const double* initial_repeated_action) {
+  if (!initialized_) return;
+  sampling.Reset(horizon, initial_repeated_action);
+  ilqg.Reset(horizon, initial_repeated_action);
+  active_policy = kSampling; previous_active_policy = kSampling;
+  dim_actions = 0; dim_parameters = 0; mapping_representation = -1;
+  converted = returned_early = iterated = false;
+}
+
+void iLQSPlanner::SetState(const double* s, const double* m, const double* u, double t) {
+  if (!initialized_) return;
+  sampling.SetState(s, m, u, t);
+  ilqg.SetState(s, m, u, t);
+}
+
+void iLQSPlanner::SetTask(const MjpcHipTask* task) {
+  if (!initialized_) return;
+  sampling.SetTask(task);
+  ilqg.SetTask(task);
+}
+
+bool iLQSPlanner::Convert(int horizon) {   // ilqs/planner.cc:96-169
+  auto t0 = std::chrono::steady_clock::now();
+  const int P = sampling.policy.num_spline_points, H1 = horizon - 1;
+  const int representation = (int)sampling.policy.plan.Interpolation();
+  double nominal_time = sampling.time;
+  const double time_shift = std::max((horizon - 1) * timestep_ / (P - 1), 1.0e-5);
+  spline_times_cache.clear();
+  for (int t = 0; t < P; t++) {
+    spline_times_cache.push_back(nominal_time);
+    nominal_time += time_shift;                           // repeated addition, like the reference
+  }
+  const Trajectory& nominal = ilqg.candidate.trajectory;
+  fit_cache_miss = dim_actions != H1 || dim_parameters != P || mapping_representation != representation;
+  if (fit_cache_miss) {
+    dim_actions = 0; dim_parameters = 0; mapping_representation = -1;       // nothing valid until the factorisation went through
+    inversemapping.resize((size_t)P * H1);
+    if (SplineFitOperator(mappings[representation].get(), spline_times_cache, P, nominal.times.data(), H1, inversemapping.data(), fit_scratch_) != 0) {
+      fit_compute_time = Micros(t0);
+      Fatal("iLQS: spline fit is singular");
+      return false;
+    }
+    dim_actions = H1; dim_parameters = P; mapping_representation = representation;
+  }
+  spline_parameters_cache.resize((size_t)P * nu_);
+  SplineFitApply(inversemapping.data(), P, H1, nu_, nominal.actions.data(), spline_parameters_cache.data());
+  for (int t = 0; t < P; t++)
+    for (int i = 0; i < nu_; i++) {
+      double& v = spline_parameters_cache[(size_t)t * nu_ + i];
+      v = std::max(ctrlrange_[2 * i], std::min(ctrlrange_[2 * i + 1], v));   // Clamp
+    }
+  fit_compute_time = Micros(t0);
+  sampling.policy.plan.Clear();
+  for (int t = 0; t < P; t++) sampling.policy.plan.AddNode(spline_times_cache[t], spline_parameters_cache.data() + (size_t)t * nu_);
+  return true;
+}
+
+void iLQSPlanner::OptimizePolicy(int horizon) {   // ilqs/planner.cc:87-214
+  if (!initialized_) return;
+  converted = returned_early = iterated = false;
+  previous_active_policy = active_policy;
+  if (previous_active_policy == kiLQG) {
+    // sampling optimises a spline: the trajectory-based policy of iLQG (the previous winner) is converted to one first
+    if (!ilqg.NominalTrajectory(horizon)) return;
+    if (!Convert(horizon)) return;
+    converted = true;
+  }
+
+  sampling.OptimizePolicy(horizon);
+
+  // winner == 0: there was surely no improvement
+  if (sampling.winner > 0 && sampling.returns[sampling.winner] < (previous_active_policy == kSampling ? sampling.returns[0]
+                                                                                                      : ilqg.candidate.trajectory.total_return)) {
+    if (active_policy == kSampling) ilqg.nominal_compute_time = 0.0;
+    ilqg.derivative_compute_time = 0.0;       // model derivatives, cost derivatives and backward pass are one timer here
+    ilqg.rollouts_compute_time = 0.0;
+    ilqg.policy_update_compute_time = 0.0;
+    active_policy = kSampling;
+    returned_early = true;
+    return;                                   // the best rollout is sampling's
+  }
+  if (previous_active_policy == kSampling) {
+    // candidate_policy[0].trajectory = sampling.trajectory[0]; trajectory_winner is sampling's winner again afterwards
+    sampling.FetchCandidateUnranked(0);
+    const bool ok = ilqg.SetNominal(sampling.trajectory_winner, horizon);
+    if (sampling.winner > 0) sampling.FetchCandidateUnranked(sampling.winner);
+    if (!ok) return;
+  }
+
+  ilqg.Iteration(horizon);
+  iterated = true;
+
+  // adopted nothing (failed backward pass, every rollout failed): the returns below would be an earlier call's
+  if (!ilqg.adopted) return;
+  if (ilqg.trajectory_winner.total_return < (previous_active_policy == kSampling ? sampling.returns[sampling.winner] : ilqg.returns[0]))
+    active_policy = kiLQG;
+  // no improvement either way: both policies were updated, active_policy was not
+}
+
+void iLQSPlanner::NominalTrajectory(int horizon) {   // ilqs/planner.cc:217-225
+  if (!initialized_) return;
+  if (active_policy == kSampling) sampling.NominalTrajectory(horizon);
+  else ilqg.NominalTrajectory(horizon);
+}
+
+int iLQSPlanner::ActionSource(int previous_active, int active, bool use_previous) {   // ilqs/planner.cc:228-253
+  if (use_previous) {
+    // sampling.OptimizePolicy runs in every call and always updates sampling's policy: its previous one is wanted
+    if (previous_active == kSampling) return kSamplingPrevious;
+    // the last call returned early: iLQG was not updated, the previous policy is its current one
+    if (active == kSampling) return kiLQGCurrent;
+    return kiLQGPrevious;
+  }
+  return active == kSampling ? kSamplingCurrent : kiLQGCurrent;
+}
+
+void iLQSPlanner::ActionFromPolicy(double* action, const double* state, double time, bool use_previous) {
+  if (!initialized_) return;
+  switch (ActionSource(previous_active_policy, active_policy, use_previous)) {
+    case kSamplingCurrent: sampling.ActionFromPolicy(action, state, time, false); break;
+    case kSamplingPrevious: sampling.ActionFromPolicy(action, state, time, true); break;
+    case kiLQGCurrent: ilqg.ActionFromPolicy(action, state, time, false); break;
+    default: ilqg.ActionFromPolicy(action, state, time, true); break;
+  }
+}
+
+const Trajectory* iLQSPlanner::BestTrajectory() {   // ilqs/planner.cc:256-263
+  if (!initialized_) return nullptr;
+  return active_policy == kSampling ? sampling.BestTrajectory() : ilqg.BestTrajectory();
 }
 
 // ------------------------------------------------------------------ GradientPlanner (gradient/planner.cc:40-415)
@@ -2377,6 +2641,69 @@ int mjpc_ilqg_get_policy(void* p, int which, double* times, double* states, doub
   return (int)H;
 }
 int mjpc_ilqg_best_rollout(const double* returns, const int* failures, int n) { return mjpc_hip::iLQGPlanner::BestRollout(returns, failures, n); }
+
+// ---- iLQSPlanner
+#define ILS(p) ((mjpc_hip::iLQSPlanner*)(p))
+void* mjpc_ilqs_create(const MjpcHipModel* model, const MjpcHipTask* task, const double* exploration, int trajectories, int representation, int sliding_plan,
+                       int spline_points, int ilqg_num_trajectory, int ilqg_representation, int derivative_skip, int fused, const double* settings,
+                       int max_samples, int max_horizon, int device) {
+  auto* p = new mjpc_hip::iLQSPlanner();
+  mjpc_hip::Numerics n;
+  n.sampling_exploration[0] = exploration[0]; n.sampling_exploration[1] = exploration[1];
+  n.sampling_trajectories = trajectories; n.sampling_representation = representation; n.sampling_sliding_plan = sliding_plan;
+  n.sampling_spline_points = spline_points; n.derivative_skip = derivative_skip; n.max_samples = max_samples; n.max_horizon = max_horizon; n.device = device;
+  p->ilqg.num_trajectory = ilqg_num_trajectory; p->ilqg.representation = ilqg_representation; p->ilqg.fused = fused != 0;
+  if (settings) {
+    mjpc_hip::iLQGSettings& s = p->ilqg.settings;
+    s.min_linesearch_step = settings[0]; s.fd_tolerance = settings[1]; s.fd_mode = settings[2]; s.min_regularization = settings[3];
+    s.max_regularization = settings[4]; s.regularization_type = (int)settings[5]; s.max_regularization_iterations = (int)settings[6];
+    s.action_limits = (int)settings[7]; s.nominal_feedback_scaling = (int)settings[8];
+  }
+  p->Initialize(model, task, n);
+  p->Allocate();
+  return p;
+}
+void mjpc_ilqs_destroy(void* p) { delete ILS(p); }
+void mjpc_ilqs_reset(void* p, int horizon, const double* a) { ILS(p)->Reset(horizon, a); }
+void mjpc_ilqs_set_state(void* p, const double* s, const double* m, const double* u, double t) { ILS(p)->SetState(s, m, u, t); }
+void mjpc_ilqs_set_task(void* p, const MjpcHipTask* task) { ILS(p)->SetTask(task); }
+void mjpc_ilqs_optimize_policy(void* p, int horizon) { ILS(p)->OptimizePolicy(horizon); }
+void mjpc_ilqs_nominal_trajectory(void* p, int horizon) { ILS(p)->NominalTrajectory(horizon); }
+void mjpc_ilqs_action_from_policy(void* p, double* a, const double* state, double t, int prev) { ILS(p)->ActionFromPolicy(a, state, t, prev != 0); }
+int mjpc_ilqs_best_trajectory(void* p, double* states, double* actions, double* costs, double* total_return) {
+  return CopyTrajectory(ILS(p)->BestTrajectory(), states, actions, nullptr, nullptr, costs, nullptr, total_return, nullptr);
+}
+void mjpc_ilqs_values(void* p, int* out) {
+  auto* g = ILS(p);
+  out[0] = g->active_policy; out[1] = g->previous_active_policy; out[2] = g->converted ? 1 : 0; out[3] = g->returned_early ? 1 : 0;
+  out[4] = g->iterated ? 1 : 0; out[5] = (g->iterated && g->ilqg.adopted) ? 1 : 0;
+}
+void mjpc_ilqs_timings(void* p, double* out) { out[0] = ILS(p)->fit_compute_time; out[1] = ILS(p)->fit_cache_miss ? 1.0 : 0.0; }
+void mjpc_ilqs_set_noise_exploration(void* p, double first, double second) { ILS(p)->sampling.noise_exploration[0] = first; ILS(p)->sampling.noise_exploration[1] = second; }
+void* mjpc_ilqs_sampling(void* p) { return &ILS(p)->sampling; }
+void* mjpc_ilqs_ilqg(void* p) { return &ILS(p)->ilqg; }
+int mjpc_ilqs_fitted_knots(void* p, double* times, double* values) {
+  auto* g = ILS(p);
+  if (times) std::copy(g->spline_times_cache.begin(), g->spline_times_cache.end(), times);
+  if (values) std::copy(g->spline_parameters_cache.begin(), g->spline_parameters_cache.end(), values);
+  return (int)g->spline_times_cache.size();
+}
+int mjpc_ilqs_sampling_member(void* p, int index, double* states, double* actions, double* times, double* residual, double* total_return) {
+  mjpc_hip::SamplingPlanner& s = ILS(p)->sampling;
+  if (index < 0 || index >= s.num_trajectory_ || s.winner < 0) return 0;
+  s.FetchCandidateUnranked(index);
+  const int H = CopyTrajectory(&s.trajectory_winner, states, actions, times, residual, nullptr, nullptr, total_return, nullptr);
+  if (s.winner != index) s.FetchCandidateUnranked(s.winner);
+  return H;
+}
+int mjpc_ilqs_action_source(int previous_active_policy, int active_policy, int use_previous) {
+  return mjpc_hip::iLQSPlanner::ActionSource(previous_active_policy, active_policy, use_previous != 0);
+}
+int mjpc_ilqs_spline_fit(int representation, int P, const double* knot_times, int H1, const double* action_times, int nu, const double* actions,
+                         double* out_knots) {
+  return mjpc_hip::SplineFit(representation, P, knot_times, H1, action_times, nu, actions, out_knots);
+}
+#undef ILS
 
 // ---- iLQGBackwardPass, BoxQP, iLQGPolicy
 namespace {

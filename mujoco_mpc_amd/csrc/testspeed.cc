@@ -473,7 +473,7 @@ TestspeedResult SynchronousPlanningCost(const MjpcHipModel& model, HostTask& tas
 // ====================================================================== flat C view (ctypes tests / Python front end)
 extern "C" {
 // planner_kind: 0 = SamplingPlanner handle (mjpc_planner_create), 1 = CrossEntropyPlanner handle (mjpc_cem_create),
-// 2 = SampleGradientPlanner handle (mjpc_sg_create), 3 = GradientPlanner handle (mjpc_gd_create), 4 = iLQGPlanner handle (mjpc_ilqg_create).
+// 2 = SampleGradientPlanner handle (mjpc_sg_create), 3 = GradientPlanner handle (mjpc_gd_create), 4 = iLQGPlanner handle (mjpc_ilqg_create), 5 = iLQSPlanner handle (mjpc_ilqs_create).
 // state/mocap are in-out (final simulator state); cost_per_step[total_steps] optional.  Returns the total cost
 // (testspeed.cc:128) and fills out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds, plan_steps, failure}.
 double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, void* planner, int planner_kind, double* state, double* mocap,
@@ -491,6 +491,11 @@ double mjpc_testspeed_run(const MjpcHipModel* model, const MjpcHipTask* task, vo
   PlannerOps ops;
   if (planner_kind == 4) {     // iLQGPlanner handle (mjpc_ilqg_create): a feedback policy, evaluated at the simulator's current state (testspeed.cc:96)
     iLQGPlanner* ip = (iLQGPlanner*)planner;
+    ops = Ops(*ip);
+    const SimState* live = &s;
+    ops.ActionFromPolicy = [ip, live](double* a, double t) { ip->ActionFromPolicy(a, live->state.data(), t, false); };
+  } else if (planner_kind == 5) {     // iLQSPlanner handle (mjpc_ilqs_create): the state reaches its iLQG member only
+    iLQSPlanner* ip = (iLQSPlanner*)planner;
     ops = Ops(*ip);
     const SimState* live = &s;
     ops.ActionFromPolicy = [ip, live](double* a, double t) { ip->ActionFromPolicy(a, live->state.data(), t, false); };

@@ -449,6 +449,39 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
 int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
                            const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
                            double *D, int *failure);
+/* ---- State estimators: the device half of an unscented and an extended Kalman filter update ---------------------------------
+ * mjpc/estimators/unscented.cc, kalman.cc.  nd = 2nv+na, ds = nq+nv+na.  The measurement is rows [sensor_first_row,
+ * sensor_first_row + ns) of the engine's residual as mjpc_hip_step_batch reports it (the reference's estimator_sensor_start: one
+ * task can carry cost rows and sensor rows).  Host pointers in and out, row-major.  Both calls are blocking.
+ *
+ * mjpc_hip_unscented_moments: the 2nd+1 sigma points around `state`, one step of each, and their weighted moments, in four stages
+ * on the device with one upload and one download.  `factor` is a lower Cholesky factor L[nd][nd] of the covariance (entries above
+ * the diagonal are not read); with c_i = sigma_step * L[:, i], row i < nd is state (+) c_i, row nd + i is state (-) c_i, row 2nd is
+ * `state`, where (+) is the engine's position integration of the velocity c[0:nv] over time +-1 (a plain add on hinge, slide and
+ * free-translation coordinates, on qvel and on act; quaternions are right-multiplied by exp(+-c) and normalised).  ctrl and time
+ * are the same for every row.  weights = {mean0, cov0, sigma}: the nominal row's weight in the means, in the covariances, and
+ * every other row's weight in both.
+ *   state_mean[ds], sensor_mean[ns]   sum_j w_j y_j over the ascending row index j, one rounded product and one rounded add per step;
+ *                     a quaternion's four numbers are instead the principal eigenvector of sum_j 4 w_j q_j q_j' - (sum_j w_j) I with the
+ *                     covariance weights, its sign chosen so that its dot product with the nominal row's next quaternion is >= 0
+ *   cov_ss[nd][nd], cov_sy[nd][ns], cov_yy[ns][ns]   noise_diag + sum_j (d_a[j] d_b[j]) w_j over ascending j, each operation rounded
+ *                     separately, with d_j the difference of row j to the means (state part in tangent order: quaternion coordinates
+ *                     the body-frame rotation vector of mean^-1 * q_j, everything else a plain difference); noise_process[nd] is the
+ *                     diagonal added to ss, noise_sensor[ns] the one added to yy
+ *   sigma_next[2nd+1][ds]   the next state of every row (may be NULL)
+ *   *failure         OR of the rows' MJPC_WARN_* bits.  A failed row is not an error of the call.
+ * Errors: a plan in flight, null inputs, max_horizon < 2, ns < 1, a row range outside num_residual.
+ *
+ * mjpc_hip_linearize_step: mjpc_hip_transition_fd at T = 1, last_is_terminal = 0, which also hands back the base evaluation it is
+ * built around: next_state[ds] and residual[num_residual] are mjpc_hip_step_batch's of (state, ctrl, time), A[nd][nd] and
+ * C[num_residual][nd] are transition_fd's.  Any output may be NULL.  One half-step of an extended Kalman filter is one call.
+ * Errors: a plan in flight, null inputs, max_horizon < 2, eps <= 0. */
+int mjpc_hip_unscented_moments(MjpcHipEngine *e, const double *state, const double *factor, double sigma_step, const double *weights,
+                               const double *ctrl, double time, const double *mocap, const double *userdata, const double *noise_process,
+                               const double *noise_sensor, int sensor_first_row, int ns, double *state_mean, double *sensor_mean,
+                               double *cov_ss, double *cov_sy, double *cov_yy, double *sigma_next, int *failure);
+int mjpc_hip_linearize_step(MjpcHipEngine *e, const double *state, const double *ctrl, double time, const double *mocap, const double *userdata,
+                            double eps, int centered, double *next_state, double *residual, double *A, double *C, int *failure);
 /* ---- Cost derivatives and the gradient planner's backward pass --------------------------------------------------------------
  * The other half of a derivative-based planner's iteration (mjpc/planners/cost_derivatives.cc, planners/gradient/gradient.cc),
  * on the device.  nd = 2nv+na, nr = num_residual; the cost table (norms, parameters, weights) and risk are the engine's current

@@ -772,5 +772,93 @@ class iLQSPlanner {
   std::vector<double> ctrlrange_, fit_scratch_;
 };
 
+// ---- State estimators (mjpc/estimators/kalman.h, unscented.h) on the one-step engine -------------------------------------------
+// The filter algebra is on the host, the model evaluations on the device: one mjpc_hip_linearize_step per EKF half-step, one
+// mjpc_hip_unscented_moments per UKF update.  nd = 2nv+na.  The measurement is rows [sensor_first_row, sensor_first_row + ns) of the
+// engine's residual (the reference's estimator_sensor_start); `sensor` arguments hold those ns numbers only.
+//
+// Failure policy, a deliberate deviation: the reference calls mju_error on a rank-deficient factor.  Here a rank-deficient covariance
+// or sensor covariance, or a step the engine flagged, makes the update RETURN a status and leave state, covariance and time untouched.
+enum EstimatorStatus : int {
+  kEstimatorOk = 0,
+  kEstimatorCovarianceRank = 1,    // the covariance has no Cholesky factor (a pivot is not > 0)
+  kEstimatorSensorRank = 2,        // the sensor covariance C P C' + R, or cov_yy, has none
+  kEstimatorStepFlagged = 3,       // the engine flagged an evaluation (MJPC_WARN_* bits in last_failure)
+  kEstimatorEngineError = 4,       // the engine refused the call (mjpc_hip_last_error)
+};
+
+// The algebra as pure functions over row-major matrices.  Every contraction starts at 0.0 and runs over the ascending index with a
+// rounded product and a rounded add per step; mju_symmetrize's rule is 0.5 * (m[i][j] + m[j][i]) for both entries.  A function that
+// returns a status other than kEstimatorOk has written none of its outputs.
+// lower Cholesky factor L [n][n] of P (zeros above the diagonal); false: a pivot is not > 0
+bool CovarianceFactor(int n, const double* P, double* L);
+// PCt [nd][ns] = P C', factor [ns][ns] = chol(C P C' + diag(R)), gain [nd][ns] with row i = (C P C' + R) \ PCt[i]  (kalman.cc:209-262)
+int KalmanGain(int nd, int ns, const double* P, const double* C, const double* R, double* PCt, double* factor, double* gain);
+// correction [nd] = PCt ((C P C' + R) \ sensor_error); P <- sym(P - PCt gain')  (kalman.cc:238-272)
+void KalmanCorrect(int nd, int ns, const double* PCt, const double* factor, const double* gain, const double* sensor_error, double* correction,
+                   double* P);
+// P <- sym(A (P A') + diag(Q))  (kalman.cc:303-319)
+void CovariancePredict(int nd, const double* A, const double* Q, double* P);
+// correction [nd] = cov_sy (cov_yy \ sensor_error); P [nd][nd] = sym(cov_ss - cov_sy (cov_yy \ cov_sy')')  (unscented.cc:509-567)
+int UnscentedCorrect(int nd, int ns, const double* cov_ss, const double* cov_sy, const double* cov_yy, const double* sensor_error,
+                     double* correction, double* P);
+
+struct EstimatorSettings {
+  double epsilon = 1.0e-6;       // Kalman: finite-difference step
+  bool flg_centered = false;     // Kalman: centred differences
+  double alpha = 1.0, beta = 2.0;        // Unscented: sigma-point spread and prior knowledge (unscented.h defaults)
+  // the reference's estimator_covariance_initial_scale, estimator_process_noise_scale, estimator_sensor_noise_scale numerics
+  double covariance_initial_scale = 1.0e-4, process_noise_scale = 1.0e-4, sensor_noise_scale = 1.0e-4;
+};
+
+// what the two filters share: dimensions, the model's joint tables, the engine and the public estimate
+class Estimator {
+ public:
+  // engine: created by the caller from the same model and task, with max_horizon >= 2; it stays the caller's.  0, or -1 when the
+  // sensor rows are not inside the task's residual
+  int Initialize(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                 const EstimatorSettings& settings = EstimatorSettings());
+  // covariance = scale I, the noises filled with their scales
+  void Reset(const double* state, double time);
+  void SetShared(const double* mocap, const double* userdata);      // what every evaluation sees beside state, ctrl and time
+  // state <- state (+) correction: position integration over time 1 of correction[0:nv], a plain add on qvel and act
+  void IntegrateState(double* state, const double* correction) const;
+
+  std::vector<double> state, covariance, noise_process, noise_sensor;
+  double time = 0.0;
+  EstimatorSettings settings;
+  int last_failure = 0;            // the engine's warning bits of the last update
+
+  int nq = 0, nv = 0, na = 0, nu = 0, nr = 0, nd = 0, ns = 0, first = 0;
+  double timestep = 0.0;
+
+ protected:
+  MjpcHipEngine* engine_ = nullptr;
+  std::vector<int> jnt_type_, jnt_qposadr_, jnt_dofadr_;
+  std::vector<double> mocap_, userdata_, ctrl_;
+};
+
+// mjpc/estimators/kalman.cc:188-330
+class Kalman : public Estimator {
+ public:
+  int UpdateMeasurement(const double* ctrl, const double* sensor);     // EstimatorStatus
+  int UpdatePrediction();                                              // under the last UpdateMeasurement's ctrl; advances time
+  int Update(const double* ctrl, const double* sensor);                // both; a failed second half undoes the first
+ private:
+  std::vector<double> next_, residual_, A_, C_, PCt_, factor_, gain_, error_, correction_;
+};
+
+// mjpc/estimators/unscented.cc:484-574, weights :134-143
+class Unscented : public Estimator {
+ public:
+  int Initialize(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                 const EstimatorSettings& settings = EstimatorSettings());
+  int Update(const double* ctrl, const double* sensor);                // EstimatorStatus; advances time
+  double sigma_step = 0.0, weight_mean0 = 0.0, weight_covariance0 = 0.0, weight_sigma = 0.0;
+  std::vector<double> sigma_next;      // [2nd+1][nq+nv+na]: the stepped sigma points of the last update
+ private:
+  std::vector<double> factor_, state_mean_, sensor_mean_, cov_ss_, cov_sy_, cov_yy_, error_, correction_, P_;
+};
+
 }  // namespace mjpc_hip
 #endif  // MJPC_HIP_PLANNER_H_

@@ -279,6 +279,40 @@ void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int
                              const double *ctrlrange, int representation, int horizon, const double *times, const double *states, const double *actions,
                              const double *feedback_gain, double feedback_scaling, const double *state, double time, double *action);
 
+/* Kalman, Unscented (mjpc/estimators/; mjpc_hip::Kalman, mjpc_hip::Unscented of mjpc_hip_planner.h).  The engine is the caller's (created from the
+ * same model and task with max_horizon >= 2) and outlives the estimator.  The measurement is residual rows [sensor_first_row, sensor_first_row +
+ * num_sensor); `sensor` holds those num_sensor numbers.  settings[7] = {epsilon, flg_centered, alpha, beta, covariance_initial_scale,
+ * process_noise_scale, sensor_noise_scale} or NULL for the defaults (1e-6, 0, 1, 2, 1e-4, 1e-4, 1e-4).  create returns NULL when the rows are not
+ * inside the task's residual.  An update returns an EstimatorStatus: 0 ok, 1 covariance rank, 2 sensor-covariance rank, 3 a flagged step, 4 the
+ * engine refused (mjpc_hip_last_error); on anything but 0 the state, covariance and time are what they were. */
+void *mjpc_kalman_create(MjpcHipEngine *engine, const MjpcHipModel *model, const MjpcHipTask *task, int sensor_first_row, int num_sensor,
+                         const double *settings);
+void mjpc_kalman_destroy(void *estimator);
+int mjpc_kalman_update_measurement(void *estimator, const double *ctrl, const double *sensor);
+int mjpc_kalman_update_prediction(void *estimator);
+int mjpc_kalman_update(void *estimator, const double *ctrl, const double *sensor);
+void *mjpc_unscented_create(MjpcHipEngine *engine, const MjpcHipModel *model, const MjpcHipTask *task, int sensor_first_row, int num_sensor,
+                            const double *settings);
+void mjpc_unscented_destroy(void *estimator);
+int mjpc_unscented_update(void *estimator, const double *ctrl, const double *sensor);
+void mjpc_unscented_weights(void *estimator, double *out /* {sigma_step, weight_mean0, weight_covariance0, weight_sigma} */);
+/* either kind.  dims out[4] = {nq+nv+na, nd, num_sensor, the engine's warning bits of the last update}; time: set from *set when not NULL, returned;
+ * access: which 0 state [nq+nv+na], 1 covariance [nd][nd], 2 noise_process [nd], 3 noise_sensor [num_sensor]: set from `set` when not NULL, then
+ * read into `out` when not NULL */
+void mjpc_estimator_reset(void *estimator, const double *state, double time);
+void mjpc_estimator_set_shared(void *estimator, const double *mocap, const double *userdata);
+void mjpc_estimator_dims(void *estimator, int *out);
+double mjpc_estimator_time(void *estimator, const double *set);
+void mjpc_estimator_access(void *estimator, int which, const double *set, double *out);
+/* the filter algebra as pure functions (host, no GPU; mjpc_hip_planner.h): row-major, a status other than 0 leaves the outputs untouched */
+int mjpc_estimator_covariance_factor(int n, const double *P, double *L);
+int mjpc_estimator_kalman_gain(int nd, int ns, const double *P, const double *C, const double *R, double *PCt, double *factor, double *gain);
+void mjpc_estimator_kalman_correct(int nd, int ns, const double *PCt, const double *factor, const double *gain, const double *sensor_error,
+                                   double *correction, double *P);
+void mjpc_estimator_covariance_predict(int nd, const double *A, const double *Q, double *P);
+int mjpc_estimator_unscented_correct(int nd, int ns, const double *cov_ss, const double *cov_sy, const double *cov_yy, const double *sensor_error,
+                                     double *correction, double *P);
+
 /* Closed-loop harness (include/mjpc_hip_testspeed.h; mjpc/testspeed.cc:44-129 `SynchronousPlanningCost`): world and planner on the
  * HIP engine.  planner_kind 0 = handle from mjpc_planner_create, 1 = handle from mjpc_cem_create, 2 = handle from mjpc_sg_create, 3 = handle from mjpc_gd_create, 4 = handle from mjpc_ilqg_create, 5 = handle from mjpc_ilqs_create (4 and 5: the policy is evaluated at the simulator's state).  state / mocap are in-out;
  * cost_per_step[ceil(total_time/timestep)] optional; out[6] = {average_cost, wall_seconds, realtime_factor, plan_seconds,

@@ -13,6 +13,8 @@
 //                   rollout kernel's phases from that row's own state, control and time (mjpc_hip_step_batch)
 //   fd_assemble_kernel / fd_difference_kernel  (transition_fd.h)  mjpc_hip_transition_fd: the perturbed table around the nominal
 //                   knots, and the A / B / C / D entries from the stepped rows
+//   ukf_sigma_kernel / ukf_mean_kernel / ukf_cov_kernel  (estimator.h)  mjpc_hip_unscented_moments: the sigma-point table around a mean
+//                   state, and the weighted means, difference table and covariance blocks of the stepped rows
 //   cd_kernel / gd_backward_kernel  (cost_derivatives.h)  mjpc_hip_cost_derivatives / mjpc_hip_trajectory_gradient: the cost derivatives of
 //                   every knot from the residual and its Jacobian, and the gradient planner's backward recursion
 //   rc_backward_kernel  (riccati.h)  mjpc_hip_ilqg_backward_pass / mjpc_hip_trajectory_ilqg: iLQG's backward pass, one workgroup: Riccati
@@ -35,6 +37,7 @@
 #include "philox.h"
 #include "gradient.h"
 #include "transition_fd.h"
+#include "estimator.h"
 #include "cost_derivatives.h"
 #include "riccati.h"
 #include "feedback_resample.h"
@@ -150,6 +153,57 @@ extern "C" __global__ void __launch_bounds__(FD_TILE * FD_TILE) fd_difference_ke
     int w = wave_or_i(fd_failure(a, t, (int)threadIdx.x, 64));
     if (threadIdx.x == 0) a.failure[t] = w;
   }
+}
+
+// mjpc_hip_unscented_moments, sigma-point table: one wave per table row, its lanes walk the row's ds + nu + 1 elements
+extern "C" __global__ void __launch_bounds__(256) ukf_sigma_kernel(const UkfArgs a) {
+  const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (g >= ukf_rows(a)) return;
+  const int n = a.nq + a.nv + a.na + a.nu + 1;
+  for (int i = threadIdx.x & 63; i < n; i += 64) ukf_sigma(a, g, i);
+}
+
+// mjpc_hip_unscented_moments, means and differences: ONE workgroup.  One lane per mean component (a serial sum over the sigma rows);
+// then the lane that owns a quaternion's w replaces its four numbers; then the difference table against the means just stored
+// (the workgroup barrier orders the global stores before the loads) and the OR of the rows' warning bits
+extern "C" __global__ void __launch_bounds__(256) ukf_mean_kernel(const UkfArgs a) {
+  const int ds = a.nq + a.nv + a.na, nd = ukf_nd(a), n = nd + a.ns, R = ukf_rows(a);
+  for (int i = threadIdx.x; i < ds + a.ns; i += 256) {
+    const double v = ukf_mean_component(a, i);
+    if (i < ds) a.state_mean[i] = v; else a.sensor_mean[i - ds] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < a.nq; i += 256)
+    if (a.qmap[2 * i + 1] == 0) {
+      double q[4]; ukf_quat_mean(a, i, q);
+      a.state_mean[i] = q[0]; a.state_mean[i + 1] = q[1]; a.state_mean[i + 2] = q[2]; a.state_mean[i + 3] = q[3];
+    }
+  __syncthreads();
+  for (int e = threadIdx.x; e < R * n; e += 256) a.diff[e] = ukf_diff(a, e / n, e % n);
+  if (threadIdx.x < 64) {
+    int w = wave_or_i(ukf_failure(a, (int)threadIdx.x, 64));
+    if (threadIdx.x == 0) *a.failure = w;
+  }
+}
+
+// mjpc_hip_unscented_moments, covariances: block (x, y) owns the UKF_TILE x UKF_TILE tile of the combined matrix [[ss, sy], [sy', yy]]
+// at rows y * UKF_TILE, columns x * UKF_TILE.  The difference rows go through LDS 16 sigma points at a time (estimator.h): the
+// global reads run along the rows of the table, the LDS reads are a broadcast (ta) and 16 consecutive doubles (tb).  No f64 MFMA:
+// the sum over sigma points is the serial, separately rounded one of the host restatement.
+extern "C" __global__ void __launch_bounds__(UKF_TILE * UKF_TILE) ukf_cov_kernel(const UkfArgs a) {
+  __shared__ double ta[UKF_TILE * UKF_TILE], tb[UKF_TILE * UKF_TILE];
+  const int r0 = blockIdx.y * UKF_TILE, c0 = blockIdx.x * UKF_TILE, nd = ukf_nd(a), R = ukf_rows(a);
+  if (r0 >= nd && c0 + UKF_TILE <= nd) return;          // a tile inside the lower-left block (sy'): nothing to store
+  const int ri = threadIdx.x / UKF_TILE, ci = threadIdx.x % UKF_TILE;
+  double acc = ukf_cov_init(a, r0 + ri, c0 + ci);
+  for (int j0 = 0; j0 < R; j0 += UKF_TILE) {
+    ukf_cov_stage(a, j0, r0, c0, (int)threadIdx.x, ta, tb);
+    __syncthreads();
+    acc = ukf_cov_accum(a, j0, ri, ci, ta, tb, acc);
+    __syncthreads();
+  }
+  double *d = ukf_cov_dest(a, r0 + ri, c0 + ci);
+  if (d) *d = acc;
 }
 
 // mjpc_hip_cost_derivatives: block (x, y, z) owns the CD_TILE x CD_TILE tile of knot z's (nd + nu)^2 Gauss-Newton matrix at rows
@@ -1061,6 +1115,111 @@ int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const doubl
     HIPCHK(hipMemcpyAsync(failure + t0, a.failure, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ estimators: unscented moments, one-knot linearisation
+// position coordinate -> (dof, quaternion component or -1): the inverse of fd_dofmap
+static std::vector<int> ukf_qmap(const MjpcHipEngine *e) {
+  std::vector<int> qmap(2 * e->nq + 2, -1);
+  const DevModel hm = mjpc_host::relocate(e->pm, e->pm.ib.data(), e->pm.db.data());
+  for (int j = 0; j < hm.njnt; j++) {
+    const int type = hm.jnt_type[j], qa = hm.jnt_qposadr[j], da = hm.jnt_dofadr[j];
+    if (type == 0) { for (int k = 0; k < 3; k++) { qmap[2 * (qa + k)] = da + k; qmap[2 * (qa + k) + 1] = -1; }
+                     for (int k = 0; k < 4; k++) { qmap[2 * (qa + 3 + k)] = da + 3; qmap[2 * (qa + 3 + k) + 1] = k; } }
+    else if (type == 1) { for (int k = 0; k < 4; k++) { qmap[2 * (qa + k)] = da; qmap[2 * (qa + k) + 1] = k; } }
+    else { qmap[2 * qa] = da; qmap[2 * qa + 1] = -1; }
+  }
+  return qmap;
+}
+
+int mjpc_hip_unscented_moments(MjpcHipEngine *e, const double *state, const double *factor, double sigma_step, const double *weights,
+                               const double *ctrl, double time, const double *mocap, const double *userdata, const double *noise_process,
+                               const double *noise_sensor, int sensor_first_row, int ns, double *state_mean, double *sensor_mean,
+                               double *cov_ss, double *cov_sy, double *cov_yy, double *sigma_next, int *failure) {
+  if (!e) { set_error("mjpc_hip_unscented_moments: invalid argument"); return -1; }
+  if (ns < 1) { set_error("mjpc_hip_unscented_moments: ns < 1"); return -1; }
+  if (sensor_first_row < 0 || (long long)sensor_first_row + ns > e->nr) {
+    set_error("mjpc_hip_unscented_moments: sensor rows [" + std::to_string(sensor_first_row) + ", " + std::to_string((long long)sensor_first_row + ns) +
+              ") are outside the task's " + std::to_string(e->nr) + " residual rows");
+    return -1;
+  }
+  if (!state || !factor || !weights || (e->nu > 0 && !ctrl) || !noise_process || !noise_sensor || !state_mean || !sensor_mean || !cov_ss || !cov_sy ||
+      !cov_yy || !failure) { set_error("mjpc_hip_unscented_moments: null input"); return -1; }
+  KParams K;
+  int rc = step_prepare(e, "mjpc_hip_unscented_moments", mocap, userdata, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, nq = e->nq, na = ds - nq - nv, nd = 2 * nv + na, nsz = (size_t)ns, R = 2 * nd + 1;
+  // B_FD, in doubles.  One block goes up, one comes back:
+  //   up    x [ds] | L [nd][nd] | u [nu] | noise_process [nd] | noise_sensor [ns] | dofmap, qmap (ints, two to a double)
+  //   tables the kernels write and read: state, ctrl, time rows | residual rows | difference table | the rows' warning bits (ints)
+  //   back  next-state rows [R][ds] (only when the caller asks for them) | state_mean | sensor_mean | ss | sy | yy | failure (an int)
+  const size_t n_map = 2 * nv + 2 + 2 * nq + 2, n_in = ds + nd * nd + nu + nd + nsz + (n_map + 1) / 2;
+  const size_t n_mom = ds + nsz + nd * nd + nd * nsz + nsz * nsz + 1, n_back = R * ds + n_mom;
+  const size_t n_tab = R * (ds + nu + 1) + R * nr + R * (nd + nsz) + (R + 1) / 2;
+  HIPCHK(e->buf[B_FD].reserve((n_in + n_tab + n_back + 8) * sizeof(double)));
+  HIPCHK(e->buf[H_PACK].reserve((n_in + n_back) * sizeof(double)));
+  double *h = e->at(H_PACK), *hp = h;
+  memcpy(hp, state, sizeof(double) * ds); hp += ds;
+  memcpy(hp, factor, sizeof(double) * nd * nd); hp += nd * nd;
+  if (nu) memcpy(hp, ctrl, sizeof(double) * nu);
+  hp += nu;
+  memcpy(hp, noise_process, sizeof(double) * nd); hp += nd;
+  memcpy(hp, noise_sensor, sizeof(double) * nsz); hp += nsz;
+  const std::vector<int> dofmap = fd_dofmap(e), qmap = ukf_qmap(e);
+  memcpy(hp, dofmap.data(), sizeof(int) * (2 * nv + 2));
+  memcpy((int *)hp + 2 * nv + 2, qmap.data(), sizeof(int) * (2 * nq + 2));
+  double *d_in = e->at(B_FD);
+  HIPCHK(hipMemcpyAsync(d_in, h, sizeof(double) * n_in, hipMemcpyHostToDevice, e->stream));
+  UkfArgs a;
+  a.x = d_in; a.L = a.x + ds; a.u = a.L + nd * nd; a.noise_process = a.u + nu; a.noise_sensor = a.noise_process + nd;
+  a.dofmap = (const int *)(a.noise_sensor + nsz); a.qmap = a.dofmap + 2 * nv + 2;
+  a.nq = (int)nq; a.nv = (int)nv; a.na = (int)na; a.nu = (int)nu; a.nr = (int)nr; a.ns = ns; a.first = sensor_first_row;
+  a.sigma_step = sigma_step; a.time = time; a.w_mean0 = weights[0]; a.w_cov0 = weights[1]; a.w_sigma = weights[2];
+  double *st = d_in + n_in, *ct = st + R * ds, *tt = ct + R * nu, *rs = tt + R, *df = rs + R * nr;
+  int *fl = (int *)(df + R * (nd + nsz));
+  double *nx = d_in + n_in + n_tab, *mom = nx + R * ds;
+  a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = nx; a.residual = rs; a.fail = fl; a.diff = df;
+  a.state_mean = mom; a.sensor_mean = a.state_mean + ds; a.cov_ss = a.sensor_mean + nsz; a.cov_sy = a.cov_ss + nd * nd; a.cov_yy = a.cov_sy + nd * nsz;
+  a.failure = (int *)(a.cov_yy + nsz * nsz);
+  hipLaunchKernelGGL(ukf_sigma_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a);
+  step_rows(e, K, R, st, ct, tt, nx, rs, fl);
+  hipLaunchKernelGGL(ukf_mean_kernel, dim3(1), dim3(256), 0, e->stream, a);
+  const unsigned tiles = (unsigned)((nd + nsz + UKF_TILE - 1) / UKF_TILE);
+  hipLaunchKernelGGL(ukf_cov_kernel, dim3(tiles, tiles), dim3(UKF_TILE * UKF_TILE), 0, e->stream, a);
+  HIPCHK(hipGetLastError());
+  double *hb = h + n_in;
+  if (sigma_next) HIPCHK(hipMemcpyAsync(hb, nx, sizeof(double) * n_back, hipMemcpyDeviceToHost, e->stream));
+  else HIPCHK(hipMemcpyAsync(hb + R * ds, mom, sizeof(double) * n_mom, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (sigma_next) memcpy(sigma_next, hb, sizeof(double) * R * ds);
+  hb += R * ds;
+  const struct { double *dst; size_t n; } outs[] = {{state_mean, ds}, {sensor_mean, nsz}, {cov_ss, nd * nd}, {cov_sy, nd * nsz}, {cov_yy, nsz * nsz}};
+  for (const auto &o : outs) { memcpy(o.dst, hb, sizeof(double) * o.n); hb += o.n; }
+  memcpy(failure, hb, sizeof(int));
+  return 0;
+}
+
+int mjpc_hip_linearize_step(MjpcHipEngine *e, const double *state, const double *ctrl, double time, const double *mocap, const double *userdata,
+                            double eps, int centered, double *next_state, double *residual, double *A, double *C, int *failure) {
+  if (!e) { set_error("mjpc_hip_linearize_step: invalid argument"); return -1; }
+  if (!(eps > 0)) { set_error("mjpc_hip_linearize_step: eps <= 0"); return -1; }
+  if (!state || (e->nu > 0 && !ctrl)) { set_error("mjpc_hip_linearize_step: null input"); return -1; }
+  KParams K;
+  int rc = step_prepare(e, "mjpc_hip_linearize_step", mocap, userdata, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv);
+  const std::vector<int> dofmap = fd_dofmap(e);
+  FdArgs a;
+  rc = fd_pass(e, K, dofmap, 0, 1, 0, state, ctrl, &time, eps, centered ? 1 : 0, 0, &a, nullptr);
+  if (rc != 0) return rc;
+  // the base row (slot 0) of the table is the step from `state` itself
+  if (next_state) HIPCHK(hipMemcpyAsync(next_state, a.next_state, sizeof(double) * ds, hipMemcpyDeviceToHost, e->stream));
+  if (residual && nr) HIPCHK(hipMemcpyAsync(residual, a.residual, sizeof(double) * nr, hipMemcpyDeviceToHost, e->stream));
+  if (A && nd) HIPCHK(hipMemcpyAsync(A, a.A, sizeof(double) * nd * nd, hipMemcpyDeviceToHost, e->stream));
+  if (C && nr * nd) HIPCHK(hipMemcpyAsync(C, a.C, sizeof(double) * nr * nd, hipMemcpyDeviceToHost, e->stream));
+  if (failure) HIPCHK(hipMemcpyAsync(failure, a.failure, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
 

@@ -2312,6 +2312,236 @@ void GradientPlanner::OptimizePolicy(int horizon) {
   policy_update_compute_time = us(t0);
 }
 
+// ------------------------------------------------------------------ Estimators: Kalman, Unscented (mjpc/estimators/)
+// The algebra by the summation rule of this file: ascending contraction index from 0.0, a rounded product and a rounded add per step.
+namespace {
+void Symmetrize(double* P, int n) {            // mju_symmetrize
+  for (int i = 0; i < n; i++)
+    for (int j = i + 1; j < n; j++) {
+      const double v = 0.5 * (P[(size_t)i * n + j] + P[(size_t)j * n + i]);
+      P[(size_t)i * n + j] = v; P[(size_t)j * n + i] = v;
+    }
+}
+// res [r1][r2] = A B', A [r1][c], B [r2][c]
+void MulMatMatT(double* res, const double* A, const double* B, int r1, int c, int r2) {
+  for (int i = 0; i < r1; i++)
+    for (int j = 0; j < r2; j++) {
+      double s = 0.0;
+      for (int k = 0; k < c; k++) s += A[(size_t)i * c + k] * B[(size_t)j * c + k];
+      res[(size_t)i * r2 + j] = s;
+    }
+}
+bool CholFactorFull(double* L, const double* H, int n) {
+  std::vector<int> identity(n);
+  for (int i = 0; i < n; i++) identity[i] = i;
+  return n == 0 || CholFactorSub(L, H, n, identity.data(), n);
+}
+// ukf_sincos / ukf_quatintegrate of csrc/estimator.h, operation for operation (this file is compiled without contraction): the same bits
+// as the sigma-point kernel's and the emulation's
+void SinCosRn(double x, double* sn, double* cs) {
+  if (!(std::fabs(x) < 64.0)) { *sn = std::sin(x); *cs = std::cos(x); return; }
+  const double k = std::rint(x * 0.63661977236758134308);
+  const double r = (x + -(k * 1.57079632673412561417e+00)) + -(k * 6.07710050650619224932e-11);
+  const double z = r * r;
+  double ps = 1.58969099521155010221e-10, pc = -1.13596475577881948265e-11;
+  const double S[5] = {-2.50507602534068634195e-08, 2.75573137070700676789e-06, -1.98412698298579493134e-04, 8.33333333332248946124e-03, -1.66666666666666324348e-01};
+  const double C[5] = {2.08757232129817482790e-09, -2.75573143513906633035e-07, 2.48015872894767294178e-05, -1.38888888888741095749e-03, 4.16666666666666019037e-02};
+  for (int i = 0; i < 5; i++) { ps = S[i] + z * ps; pc = C[i] + z * pc; }
+  const double s = r + (r * z) * ps;
+  const double c = (1.0 + -(0.5 * z)) + (z * z) * pc;
+  const int q = ((int)k) & 3;
+  const double s1 = (q & 1) ? c : s, c1 = (q & 1) ? s : c;
+  *sn = (q & 2) ? -s1 : s1;
+  *cs = ((q + 1) & 2) ? -c1 : c1;
+}
+void Normalize4(double* q) {
+  const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+  const double n = std::sqrt(n2);
+  if (n < 1e-15) { q[0] = 1; q[1] = 0; q[2] = 0; q[3] = 0; }
+  else if (std::fabs(n - 1) > 1e-15) { q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n; }
+}
+void QuatIntegrate(double* q, const double* vel, double scale) {
+  double ax[3] = {vel[0], vel[1], vel[2]};
+  const double n = std::sqrt((ax[0] * ax[0] + ax[1] * ax[1]) + ax[2] * ax[2]);
+  if (n < 1e-15) { ax[0] = 1; ax[1] = 0; ax[2] = 0; }
+  else { ax[0] = ax[0] / n; ax[1] = ax[1] / n; ax[2] = ax[2] / n; }
+  const double angle = scale * n;
+  double b[4] = {1, 0, 0, 0};
+  if (angle != 0) {
+    double sn, cs;
+    SinCosRn(angle * 0.5, &sn, &cs);
+    b[0] = cs; b[1] = ax[0] * sn; b[2] = ax[1] * sn; b[3] = ax[2] * sn;
+  }
+  Normalize4(q);
+  const double a[4] = {q[0], q[1], q[2], q[3]};
+  q[0] = ((a[0] * b[0] + -(a[1] * b[1])) + -(a[2] * b[2])) + -(a[3] * b[3]);
+  q[1] = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) + -(a[3] * b[2]);
+  q[2] = ((a[0] * b[2] + -(a[1] * b[3])) + a[2] * b[0]) + a[3] * b[1];
+  q[3] = ((a[0] * b[3] + a[1] * b[2]) + -(a[2] * b[1])) + a[3] * b[0];
+  Normalize4(q);
+}
+}  // namespace
+
+bool CovarianceFactor(int n, const double* P, double* L) {
+  std::vector<double> tmp((size_t)n * n, 0.0);
+  if (!CholFactorFull(tmp.data(), P, n)) return false;
+  std::copy(tmp.begin(), tmp.end(), L);
+  return true;
+}
+
+int KalmanGain(int nd, int ns, const double* P, const double* C, const double* R, double* PCt, double* factor, double* gain) {
+  std::vector<double> pct((size_t)nd * ns), S((size_t)ns * ns), F((size_t)ns * ns, 0.0);
+  MulMatMatT(pct.data(), P, C, nd, nd, ns);                 // P C'
+  MulMatMat(S.data(), C, pct.data(), ns, nd, ns);           // C (P C')
+  for (int i = 0; i < ns; i++) S[(size_t)i * ns + i] += R[i];
+  if (!CholFactorFull(F.data(), S.data(), ns)) return kEstimatorSensorRank;
+  std::copy(pct.begin(), pct.end(), PCt);
+  std::copy(F.begin(), F.end(), factor);
+  for (int i = 0; i < nd; i++) CholSolveSub(gain + (size_t)i * ns, F.data(), ns, PCt + (size_t)i * ns);     // column by column of the gain's transpose
+  return kEstimatorOk;
+}
+
+void KalmanCorrect(int nd, int ns, const double* PCt, const double* factor, const double* gain, const double* sensor_error, double* correction,
+                   double* P) {
+  std::vector<double> y(ns), D((size_t)nd * nd);
+  CholSolveSub(y.data(), factor, ns, sensor_error);
+  MulMatMat(correction, PCt, y.data(), nd, ns, 1);
+  MulMatMatT(D.data(), PCt, gain, nd, ns, nd);
+  for (size_t e = 0; e < (size_t)nd * nd; e++) P[e] = P[e] - D[e];
+  Symmetrize(P, nd);
+}
+
+void CovariancePredict(int nd, const double* A, const double* Q, double* P) {
+  std::vector<double> PAt((size_t)nd * nd), N((size_t)nd * nd);
+  MulMatMatT(PAt.data(), P, A, nd, nd, nd);
+  MulMatMat(N.data(), A, PAt.data(), nd, nd, nd);
+  for (int i = 0; i < nd; i++) N[(size_t)i * nd + i] += Q[i];
+  std::copy(N.begin(), N.end(), P);
+  Symmetrize(P, nd);
+}
+
+int UnscentedCorrect(int nd, int ns, const double* cov_ss, const double* cov_sy, const double* cov_yy, const double* sensor_error,
+                     double* correction, double* P) {
+  std::vector<double> F((size_t)ns * ns, 0.0), y(ns), G((size_t)nd * ns), D((size_t)nd * nd);
+  if (!CholFactorFull(F.data(), cov_yy, ns)) return kEstimatorSensorRank;
+  CholSolveSub(y.data(), F.data(), ns, sensor_error);
+  MulMatMat(correction, cov_sy, y.data(), nd, ns, 1);
+  for (int i = 0; i < nd; i++) CholSolveSub(G.data() + (size_t)i * ns, F.data(), ns, cov_sy + (size_t)i * ns);
+  MulMatMatT(D.data(), cov_sy, G.data(), nd, ns, nd);
+  for (size_t e = 0; e < (size_t)nd * nd; e++) P[e] = cov_ss[e] - D[e];
+  Symmetrize(P, nd);
+  return kEstimatorOk;
+}
+
+int Estimator::Initialize(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                          const EstimatorSettings& s) {
+  engine_ = engine; settings = s;
+  nq = model->nq; nv = model->nv; na = model->na; nu = model->nu; nr = task->num_residual; nd = 2 * nv + na;
+  ns = num_sensor; first = sensor_first_row; timestep = model->timestep;
+  if (!engine || ns < 1 || first < 0 || first + ns > nr) return -1;
+  jnt_type_.assign(model->jnt_type, model->jnt_type + model->njnt);
+  jnt_qposadr_.assign(model->jnt_qposadr, model->jnt_qposadr + model->njnt);
+  jnt_dofadr_.assign(model->jnt_dofadr, model->jnt_dofadr + model->njnt);
+  state.assign(nq + nv + na, 0.0); covariance.assign((size_t)nd * nd, 0.0); noise_process.assign(nd, 0.0); noise_sensor.assign(ns, 0.0);
+  mocap_.assign(7 * (size_t)model->nmocap, 0.0); userdata_.assign(model->nuserdata, 0.0); ctrl_.assign(nu, 0.0);
+  for (int i = 0; i < model->nmocap; i++) mocap_[7 * i + 3] = 1.0;
+  Reset(state.data(), 0.0);
+  return 0;
+}
+
+void Estimator::Reset(const double* st, double t) {
+  if (st != state.data()) std::copy(st, st + nq + nv + na, state.begin());
+  time = t;
+  std::fill(covariance.begin(), covariance.end(), 0.0);
+  for (int i = 0; i < nd; i++) covariance[(size_t)i * nd + i] = settings.covariance_initial_scale;
+  std::fill(noise_process.begin(), noise_process.end(), settings.process_noise_scale);
+  std::fill(noise_sensor.begin(), noise_sensor.end(), settings.sensor_noise_scale);
+  last_failure = 0;
+}
+
+void Estimator::SetShared(const double* mocap, const double* userdata) {
+  if (mocap) std::copy(mocap, mocap + mocap_.size(), mocap_.begin());
+  if (userdata) std::copy(userdata, userdata + userdata_.size(), userdata_.begin());
+}
+
+void Estimator::IntegrateState(double* x, const double* c) const {
+  for (size_t j = 0; j < jnt_type_.size(); j++) {
+    const int qa = jnt_qposadr_[j], da = jnt_dofadr_[j];
+    if (jnt_type_[j] == 0) { for (int k = 0; k < 3; k++) x[qa + k] = x[qa + k] + c[da + k]; QuatIntegrate(x + qa + 3, c + da + 3, 1.0); }
+    else if (jnt_type_[j] == 1) QuatIntegrate(x + qa, c + da, 1.0);
+    else x[qa] = x[qa] + c[da];
+  }
+  for (int i = 0; i < nv + na; i++) x[nq + i] = x[nq + i] + c[nv + i];
+}
+
+int Kalman::UpdateMeasurement(const double* ctrl, const double* sensor) {
+  next_.resize(state.size()); residual_.resize(nr); A_.resize((size_t)nd * nd); C_.resize((size_t)nr * nd);
+  PCt_.resize((size_t)nd * ns); factor_.resize((size_t)ns * ns); gain_.resize((size_t)nd * ns); error_.resize(ns); correction_.resize(nd);
+  if (nu) std::copy(ctrl, ctrl + nu, ctrl_.begin());
+  if (mjpc_hip_linearize_step(engine_, state.data(), ctrl_.data(), time, mocap_.data(), userdata_.data(), settings.epsilon, settings.flg_centered ? 1 : 0,
+                              nullptr, residual_.data(), nullptr, C_.data(), &last_failure) != 0) return kEstimatorEngineError;
+  if (last_failure) return kEstimatorStepFlagged;
+  const double* C = C_.data() + (size_t)first * nd;
+  const int rc = KalmanGain(nd, ns, covariance.data(), C, noise_sensor.data(), PCt_.data(), factor_.data(), gain_.data());
+  if (rc != kEstimatorOk) return rc;
+  for (int i = 0; i < ns; i++) error_[i] = sensor[i] - residual_[first + i];
+  KalmanCorrect(nd, ns, PCt_.data(), factor_.data(), gain_.data(), error_.data(), correction_.data(), covariance.data());
+  IntegrateState(state.data(), correction_.data());
+  return kEstimatorOk;
+}
+
+int Kalman::UpdatePrediction() {
+  next_.resize(state.size()); A_.resize((size_t)nd * nd);
+  if (mjpc_hip_linearize_step(engine_, state.data(), ctrl_.data(), time, mocap_.data(), userdata_.data(), settings.epsilon, settings.flg_centered ? 1 : 0,
+                              next_.data(), nullptr, A_.data(), nullptr, &last_failure) != 0) return kEstimatorEngineError;
+  if (last_failure) return kEstimatorStepFlagged;
+  state = next_;
+  CovariancePredict(nd, A_.data(), noise_process.data(), covariance.data());
+  time += timestep;
+  return kEstimatorOk;
+}
+
+int Kalman::Update(const double* ctrl, const double* sensor) {
+  const std::vector<double> state0 = state, covariance0 = covariance;
+  int rc = UpdateMeasurement(ctrl, sensor);
+  if (rc != kEstimatorOk) return rc;
+  rc = UpdatePrediction();
+  if (rc != kEstimatorOk) { state = state0; covariance = covariance0; }
+  return rc;
+}
+
+int Unscented::Initialize(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                          const EstimatorSettings& s) {
+  const int rc = Estimator::Initialize(engine, model, task, sensor_first_row, num_sensor, s);
+  const double lambda = nd * (s.alpha * s.alpha - 1.0);
+  sigma_step = std::sqrt(nd + lambda);
+  weight_mean0 = lambda / (nd + lambda);
+  weight_covariance0 = weight_mean0 + 1.0 - s.alpha * s.alpha + s.beta;
+  weight_sigma = 1.0 / (2.0 * (nd + lambda));
+  return rc;
+}
+
+int Unscented::Update(const double* ctrl, const double* sensor) {
+  const size_t ds = state.size(), n = nd, m = ns;
+  factor_.resize(n * n); state_mean_.resize(ds); sensor_mean_.resize(m); cov_ss_.resize(n * n); cov_sy_.resize(n * m); cov_yy_.resize(m * m);
+  error_.resize(m); correction_.resize(n); P_.resize(n * n); sigma_next.resize((2 * n + 1) * ds);
+  if (nu) std::copy(ctrl, ctrl + nu, ctrl_.begin());
+  if (!CovarianceFactor(nd, covariance.data(), factor_.data())) return kEstimatorCovarianceRank;
+  const double w[3] = {weight_mean0, weight_covariance0, weight_sigma};
+  if (mjpc_hip_unscented_moments(engine_, state.data(), factor_.data(), sigma_step, w, ctrl_.data(), time, mocap_.data(), userdata_.data(),
+                                 noise_process.data(), noise_sensor.data(), first, ns, state_mean_.data(), sensor_mean_.data(), cov_ss_.data(),
+                                 cov_sy_.data(), cov_yy_.data(), sigma_next.data(), &last_failure) != 0) return kEstimatorEngineError;
+  if (last_failure) return kEstimatorStepFlagged;
+  for (int i = 0; i < ns; i++) error_[i] = sensor[i] - sensor_mean_[i];
+  const int rc = UnscentedCorrect(nd, ns, cov_ss_.data(), cov_sy_.data(), cov_yy_.data(), error_.data(), correction_.data(), P_.data());
+  if (rc != kEstimatorOk) return rc;
+  state = state_mean_;
+  IntegrateState(state.data(), correction_.data());
+  covariance = P_;
+  time += timestep;
+  return kEstimatorOk;
+}
+
 }  // namespace mjpc_hip
 
 // ====================================================================== flat C wrapper (tests / ctypes)
@@ -2704,6 +2934,65 @@ int mjpc_ilqs_spline_fit(int representation, int P, const double* knot_times, in
   return mjpc_hip::SplineFit(representation, P, knot_times, H1, action_times, nu, actions, out_knots);
 }
 #undef ILS
+
+// ---- Kalman, Unscented
+namespace {
+void EstimatorSettingsFrom(mjpc_hip::EstimatorSettings& s, const double* v) {
+  if (!v) return;
+  s.epsilon = v[0]; s.flg_centered = v[1] != 0; s.alpha = v[2]; s.beta = v[3];
+  s.covariance_initial_scale = v[4]; s.process_noise_scale = v[5]; s.sensor_noise_scale = v[6];
+}
+}  // namespace
+#define EST(p) ((mjpc_hip::Estimator*)(p))
+void* mjpc_kalman_create(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                         const double* settings) {
+  auto* k = new mjpc_hip::Kalman();
+  mjpc_hip::EstimatorSettings s; EstimatorSettingsFrom(s, settings);
+  if (k->Initialize(engine, model, task, sensor_first_row, num_sensor, s) != 0) { delete k; return nullptr; }
+  return (mjpc_hip::Estimator*)k;
+}
+void mjpc_kalman_destroy(void* p) { delete (mjpc_hip::Kalman*)EST(p); }
+int mjpc_kalman_update_measurement(void* p, const double* ctrl, const double* sensor) { return ((mjpc_hip::Kalman*)EST(p))->UpdateMeasurement(ctrl, sensor); }
+int mjpc_kalman_update_prediction(void* p) { return ((mjpc_hip::Kalman*)EST(p))->UpdatePrediction(); }
+int mjpc_kalman_update(void* p, const double* ctrl, const double* sensor) { return ((mjpc_hip::Kalman*)EST(p))->Update(ctrl, sensor); }
+void* mjpc_unscented_create(MjpcHipEngine* engine, const MjpcHipModel* model, const MjpcHipTask* task, int sensor_first_row, int num_sensor,
+                            const double* settings) {
+  auto* u = new mjpc_hip::Unscented();
+  mjpc_hip::EstimatorSettings s; EstimatorSettingsFrom(s, settings);
+  if (u->Initialize(engine, model, task, sensor_first_row, num_sensor, s) != 0) { delete u; return nullptr; }
+  return (mjpc_hip::Estimator*)u;
+}
+void mjpc_unscented_destroy(void* p) { delete (mjpc_hip::Unscented*)EST(p); }
+int mjpc_unscented_update(void* p, const double* ctrl, const double* sensor) { return ((mjpc_hip::Unscented*)EST(p))->Update(ctrl, sensor); }
+void mjpc_unscented_weights(void* p, double* out) {
+  auto* u = (mjpc_hip::Unscented*)EST(p);
+  out[0] = u->sigma_step; out[1] = u->weight_mean0; out[2] = u->weight_covariance0; out[3] = u->weight_sigma;
+}
+void mjpc_estimator_reset(void* p, const double* state, double time) { EST(p)->Reset(state, time); }
+void mjpc_estimator_set_shared(void* p, const double* mocap, const double* userdata) { EST(p)->SetShared(mocap, userdata); }
+void mjpc_estimator_dims(void* p, int* out) { auto* e = EST(p); out[0] = e->nq + e->nv + e->na; out[1] = e->nd; out[2] = e->ns; out[3] = e->last_failure; }
+double mjpc_estimator_time(void* p, const double* set) { if (set) EST(p)->time = *set; return EST(p)->time; }
+void mjpc_estimator_access(void* p, int which, const double* set, double* out) {
+  auto* e = EST(p);
+  std::vector<double>* v[4] = {&e->state, &e->covariance, &e->noise_process, &e->noise_sensor};
+  if (which < 0 || which > 3) return;
+  if (set) std::copy(set, set + v[which]->size(), v[which]->begin());
+  if (out) std::copy(v[which]->begin(), v[which]->end(), out);
+}
+#undef EST
+int mjpc_estimator_covariance_factor(int n, const double* P, double* L) { return mjpc_hip::CovarianceFactor(n, P, L) ? 0 : mjpc_hip::kEstimatorCovarianceRank; }
+int mjpc_estimator_kalman_gain(int nd, int ns, const double* P, const double* C, const double* R, double* PCt, double* factor, double* gain) {
+  return mjpc_hip::KalmanGain(nd, ns, P, C, R, PCt, factor, gain);
+}
+void mjpc_estimator_kalman_correct(int nd, int ns, const double* PCt, const double* factor, const double* gain, const double* sensor_error,
+                                   double* correction, double* P) {
+  mjpc_hip::KalmanCorrect(nd, ns, PCt, factor, gain, sensor_error, correction, P);
+}
+void mjpc_estimator_covariance_predict(int nd, const double* A, const double* Q, double* P) { mjpc_hip::CovariancePredict(nd, A, Q, P); }
+int mjpc_estimator_unscented_correct(int nd, int ns, const double* cov_ss, const double* cov_sy, const double* cov_yy, const double* sensor_error,
+                                     double* correction, double* P) {
+  return mjpc_hip::UnscentedCorrect(nd, ns, cov_ss, cov_sy, cov_yy, sensor_error, correction, P);
+}
 
 // ---- iLQGBackwardPass, BoxQP, iLQGPolicy
 namespace {

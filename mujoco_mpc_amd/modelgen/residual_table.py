@@ -227,6 +227,11 @@ class ResidualTable:
         ints, dbls = self.encode(len(parameters))
         return make_task(TASK_TABLE, terms, parameters=parameters, risk=risk, traces=traces, int_data=list(ints), dbl_data=list(dbls))
 
+    def measurement(self, parameters=(), traces=()):
+        """a task whose rows are only sensors (the estimators' measurement model, mujoco_mpc_amd/estimators.py): the cost table is one
+        quadratic term of weight 0 over all rows"""
+        return self.task([(self.rows, 0, 0.0, [])], parameters=parameters, traces=traces)
+
 
 # ---------------------------------------------------------------------------------------- registry tasks restated as tables
 def _cost_of(task):

@@ -195,6 +195,50 @@ class HipBackend:
             raise RuntimeError("mjpc_hip_transition_fd failed: " + self.lib.mjpc_hip_last_error().decode())
         return o
 
+    def unscented_moments(self, state, factor, sigma_step, weights, ctrl, time, noise_process, noise_sensor, sensor_first_row=0, num_sensor=None,
+                          mocap=None, userdata=None, sigma_next=True):
+        """The device half of an unscented filter update (mjpc_hip_unscented_moments): the 2nd+1 sigma points around `state` from the lower
+        Cholesky factor [nd, nd], one step of each, and dict(state_mean [ds], sensor_mean [ns], cov_ss [nd, nd], cov_sy [nd, ns],
+        cov_yy [ns, ns], sigma_next [2nd+1, ds] or None, failure: OR of the rows' MJPC_WARN_* bits).  weights = (mean0, cov0, sigma); the
+        measurement is residual rows [sensor_first_row, sensor_first_row + num_sensor) (default: all rows from sensor_first_row)."""
+        ds, nd, nu, nr = self._dims()
+        ns = nr - int(sensor_first_row) if num_sensor is None else int(num_sensor)
+        arr = lambda a, n: np.ascontiguousarray(a, dtype=np.float64).reshape(n)      # noqa: E731
+        x = arr(state, ds); L = arr(factor, (nd, nd)); w = arr(weights, 3); u = arr(ctrl, nu) if nu else np.zeros(1)
+        qp = arr(noise_process, nd); qs = arr(noise_sensor, max(ns, 0))
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        m = max(ns, 0)
+        o = dict(state_mean=np.zeros(ds), sensor_mean=np.zeros(m), cov_ss=np.zeros((nd, nd)), cov_sy=np.zeros((nd, m)), cov_yy=np.zeros((m, m)),
+                 sigma_next=np.zeros((2 * nd + 1, ds)) if sigma_next else None)
+        fail = np.zeros(1, np.int32)
+        dp = capi.c_double_p
+        ptr = lambda a: None if a is None else (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_unscented_moments(self.h, ptr(x), ptr(L), float(sigma_step), ptr(w), ptr(u), float(time), pmo, pud, ptr(qp), ptr(qs),
+                                                 int(sensor_first_row), ns, ptr(o["state_mean"]), ptr(o["sensor_mean"]), ptr(o["cov_ss"]),
+                                                 ptr(o["cov_sy"]), ptr(o["cov_yy"]), ptr(o["sigma_next"]), fail.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_unscented_moments failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["failure"] = int(fail[0])
+        return o
+
+    def linearize_step(self, state, ctrl, time, mocap=None, userdata=None, eps=1e-6, centered=False):
+        """One knot's step and its state derivatives (mjpc_hip_linearize_step): dict(next_state [ds], residual [nr], A [nd, nd], C [nr, nd],
+        failure).  next_state / residual are step_batch's of the knot, A / C are transition_fd's at T = 1."""
+        ds, nd, nu, nr = self._dims()
+        x = np.ascontiguousarray(state, dtype=np.float64).reshape(ds)
+        u = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(nu) if nu else np.zeros(1)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(next_state=np.zeros(ds), residual=np.zeros(nr), A=np.zeros((nd, nd)), C=np.zeros((nr, nd)))
+        fail = np.zeros(1, np.int32)
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_linearize_step(self.h, ptr(x), ptr(u), float(time), pmo, pud, float(eps), int(bool(centered)), ptr(o["next_state"]),
+                                              ptr(o["residual"]), ptr(o["A"]), ptr(o["C"]), fail.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_linearize_step failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["failure"] = int(fail[0])
+        return o
+
     def cost_derivatives(self, residual, C_, D, last_is_terminal=False, hessians=True, fill=0.0):
         """Cost derivatives of T knots from the residual [T, nr] and its Jacobian C [T, nr, nd], D [T, nr, nu] under the engine's current
         cost table and risk (mjpc_hip_cost_derivatives): dict(cr [T, nr], cx [T, nd], cu [T, nu], and with hessians cxx [T, nd, nd],

@@ -98,7 +98,9 @@ DEV double dpp_xchg(double v, const int ctrl_sel) {
     case 0: lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true); break;   // quad_perm [1,0,3,2]
     case 1: lo = __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true); break;   // quad_perm [2,3,0,1]
     case 2: lo = __builtin_amdgcn_update_dpp(0, lo, 0x141, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x141, 0xF, 0xF, true); break; // row_half_mirror
-    default: lo = __builtin_amdgcn_update_dpp(0, lo, 0x140, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x140, 0xF, 0xF, true); break; // row_mirror
+    case 3: lo = __builtin_amdgcn_update_dpp(0, lo, 0x140, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x140, 0xF, 0xF, true); break; // row_mirror
+    case 4: lo = __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xF, 0xF, true); break; // row_ror:4
+    default: lo = __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xF, 0xF, true); break; // row_ror:8
   }
   return __hiloint2double(hi, lo);
 }
@@ -122,23 +124,60 @@ DEV double wave_sum(double v) {
   // every lane of a row now holds that row's sum (the butterflies are symmetric => identical bits in all lanes)
   return row_total(v);
 }
-// several reductions in lock-step: the butterfly steps of independent sums interleave, which hides the DPP / add latency of
-// each chain behind the others (one after the other they are a serial chain of ~30 dependent instructions each)
+// Several reductions at once, TRANSPOSED: the sums share one register from the second tree level on, so a level costs one
+// exchange and one add whatever the number of sums (one butterfly chain per sum costs 26 instructions per sum).
+// The tree of every sum is wave_sum's, add for add; only the LANE that performs an add differs, and a + b == b + a in every bit
+// (IEEE 754; a NaN result may carry either operand's payload), so no bit of a finite or infinite result moves:
+//   level 1 (xor 1)  even lanes keep a and get the neighbour's a, odd lanes keep b and get the neighbour's b: one exchange of
+//                    the value NOT kept, one add; lane l then holds the PAIR sum a[l] + a[l^1] (l even) or b[l] + b[l^1] (l odd),
+//                    the pair sums wave_sum forms in both lanes of the pair.  The third (and fourth) value pair up likewise;
+//   level 2 (xor 2)  the same one level up, pair register against pair register: lanes 0, 1 of a quad keep x, lanes 2, 3 keep y.
+//                    Lane j of quad q now holds sum number j's QUAD sum Q_j[q] (three sums: lanes 2 and 3 both hold the third's);
+//   levels 3, 4      wave_sum adds the two quads of an octet (row_half_mirror), then the two octets of a row (row_mirror); either
+//                    mirror would move lane j to lane 3 - j of its quad.  row_ror:4 / row_ror:8 (lane l reads lane l - 4 / l - 8
+//                    of its row, mod 16) keep j.  After ror:4 quad q holds Q[q] + Q[q-1]: an octet sum of the tree for q = 1
+//                    (Q1 + Q0) and q = 3 (Q3 + Q2), a sum the tree never forms for q = 0, 2.  After ror:8 quad q adds quad q - 2:
+//                    quads 1 and 3 hold (Q1 + Q0) + (Q3 + Q2) resp. (Q3 + Q2) + (Q1 + Q0), the row sum R of the tree, quads 0
+//                    and 2 a differently associated one.  From here on ONLY lanes 4..7 and 12..15 of each row count;
+//   levels 5, 6      v_permlane16_swap of (v, v) leaves rows {0, 0, 2, 2} of v in one result and rows {1, 1, 3, 3} in the other
+//                    (rows of 16 lanes, lane positions kept): their sum is R0 + R1 in rows 0, 1 and R2 + R3 in rows 2, 3, the two
+//                    adds of row_bcast:15.  v_permlane32_swap does the same with the halves: (R0 + R1) + (R2 + R3) in every
+//                    row, the add of row_bcast:31.  Neither needs the zero-filled `old` operand of a row_bcast;
+//   result           sum j from lane 12 + j (the lanes 4 + j and 12 + j of every row hold it).
+// Requires full EXEC, as wave_sum does.
+DEV double swap_add16(double v) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+}
+DEV double swap_add32(double v) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+}
+DEV double lane_value(double v, const int lane) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+// levels 3 .. 6 on the shared register
+DEV double wave_sum_upper(double v) {
+  v += dpp_xchg(v, 4);
+  v += dpp_xchg(v, 5);
+  v = swap_add16(v);
+  return swap_add32(v);
+}
 DEV void wave_sum3(double &a, double &b, double &c) {
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    double ta = dpp_xchg(a, s), tb = dpp_xchg(b, s), tc = dpp_xchg(c, s);
-    a += ta; b += tb; c += tc;
-  }
-  a = row_total(a); b = row_total(b); c = row_total(c);
+  const bool e1 = !(LANE & 1), e2 = !(LANE & 2);
+  const double x = (e1 ? a : b) + dpp_xchg(e1 ? b : a, 0);
+  const double y = c + dpp_xchg(c, 0);
+  const double v = wave_sum_upper((e2 ? x : y) + dpp_xchg(e2 ? y : x, 1));
+  a = lane_value(v, 12); b = lane_value(v, 13); c = lane_value(v, 14);
 }
 DEV void wave_sum4(double &a, double &b, double &c, double &d) {
-#pragma unroll
-  for (int s = 0; s < 4; s++) {
-    double ta = dpp_xchg(a, s), tb = dpp_xchg(b, s), tc = dpp_xchg(c, s), td = dpp_xchg(d, s);
-    a += ta; b += tb; c += tc; d += td;
-  }
-  a = row_total(a); b = row_total(b); c = row_total(c); d = row_total(d);
+  const bool e1 = !(LANE & 1), e2 = !(LANE & 2);
+  const double x = (e1 ? a : b) + dpp_xchg(e1 ? b : a, 0);
+  const double y = (e1 ? c : d) + dpp_xchg(e1 ? d : c, 0);
+  const double v = wave_sum_upper((e2 ? x : y) + dpp_xchg(e2 ? y : x, 1));
+  a = lane_value(v, 12); b = lane_value(v, 13); c = lane_value(v, 14); d = lane_value(v, 15);
 }
 DEV double wave_min(double v) {
 #pragma unroll
@@ -150,10 +189,16 @@ DEV int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// OR over the 64 lanes on the VALU (the shuffle form is six dependent LDS round trips): butterflies inside each row, then the
+// row_bcast steps of row_total; lane 63 has seen every lane.  Requires full EXEC.
 DEV int wave_or_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
+  v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+  return __builtin_amdgcn_readlane(v, 63);
 }
 DEV int wave_any(int flag) { return __builtin_amdgcn_ballot_w64(flag != 0) != 0; }
 // point-to-point hand-shake between two waves of the workgroup through a sequence number in LDS: the setter publishes all

@@ -924,14 +924,15 @@ template <bool HEAVY>
 DEV int narrow_batch(Ctx &c, int base, int nactive, int *used_heavy = nullptr) {
   const DevModel &M = *c.M;
   int a = base + LANE, n = 0, g1 = 0, g2 = 0;
-  double margin = 0, gap = 0;
+  double margin = 0;
   NPCon con[4] = {};
   BBPend pend; pend.refA = 0;
   if (a < nactive) {
     const int gg = c.active[a];           // (the broad phase leaves the pair's two geoms in the list, not its index)
     g1 = gg & 0xffff; g2 = (int)((unsigned)gg >> 16);
-    margin = fmax(MD(geom_margin)[g1], MD(geom_margin)[g2]);
-    gap = fmax(MD(geom_gap)[g1], MD(geom_gap)[g2]);
+    // a contact in the gap zone (margin - gap <= dist < margin) is inactive: the solver never sees it (mjContact.exclude), so the
+    // colliders are asked for the contacts inside margin - gap only, which is each kept contact's includemargin
+    margin = fmax(MD(geom_margin)[g1], MD(geom_margin)[g2]) - fmax(MD(geom_gap)[g1], MD(geom_gap)[g2]);
     n = narrow_phase(c, g1, g2, margin, con);
 #if defined(MJPC_PROFILE_COLLISION) && MJPC_PROFILE_COLLISION == 2
     if constexpr (HEAVY) PROF(c, 10);
@@ -996,7 +997,7 @@ DEV int narrow_batch(Ctx &c, int base, int nactive, int *used_heavy = nullptr) {
     cc[CON_DIST] = cur.dist;
     d_copy3(cc + CON_POS, cur.pos);
     for (int q = 0; q < 9; q++) cc[CON_FRAME + q] = fr[q];
-    cc[CON_INCLUDEMARGIN] = margin - gap;
+    cc[CON_INCLUDEMARGIN] = margin;
     cc[CON_MU] = 0;
     int *ci_ = c.con_i + ci * CONI_STRIDE;
     ci_[0] = dim; ci_[1] = g1; ci_[2] = g2; ci_[3] = 0;

@@ -329,7 +329,8 @@ static void collision(const OModel *om, OData *d) {
     }
     OContact con[8];
     int before = d->unsupported;
-    int n = oracle_collide_pair(om, d, g1, g2, margin, con, &d->unsupported);
+    /* the gap zone (margin - gap <= dist < margin) holds inactive contacts, which the solver never sees: only the contacts inside margin - gap are asked for */
+    int n = oracle_collide_pair(om, d, g1, g2, margin - gap, con, &d->unsupported);
     if (d->unsupported != before) d->warning |= MJPC_WARN_UNSUPPORTED;   /* a pair without a collider came within reach: fail loudly */
     for (int k = 0; k < n; k++) {
       if (d->ncon >= om->nconmax) { d->warning |= MJPC_WARN_CONTACTFULL; return; }   /* contact buffer full */

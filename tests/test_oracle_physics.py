@@ -108,7 +108,23 @@ def test_sphere_rests_on_plane_with_weight_as_contact_force():
     q, v, _, _, w = o.step(q, v, nstep=1500)
     r = o.forward(q, v)
     assert w == 0 and r["ncon"] == 1 and r["nefc"] == 1
-    assert abs(v[2]) < 1e-6 and 0.09 < q[2] < 0.1          # small static penetration
+    # the rest penetration of the documented soft-contact model: at rest jar = K d(r) r and the force -jar / R with
+    # R = (1 - d(r)) / d(r) * body_invweight0 carries the weight, so r < 0 is the root of m g = K d(r)^2 (-r) / ((1 - d(r)) invweight)
+    from con_ref import impedance, stiffness_damping
+    solimp, iw = m["geom_solimp"][1], m["body_invweight0"][1][0]
+    K, _ = stiffness_damping(m["geom_solref"][1], solimp, m["timestep"])
+
+    def excess(r):
+        d = impedance(solimp, abs(r))
+        return K * d * d * (-r) / ((1 - d) * iw) - 9.81 * m["body_mass"][1]
+    lo, hi = -0.01, 0.0
+    assert excess(lo) > 0 > excess(hi)
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if excess(mid) > 0 else (lo, mid)
+    rest = 0.5 * (lo + hi)
+    assert -1e-3 < rest < -1e-4
+    assert abs(v[2]) < 1e-6 and abs(q[2] - (0.1 + rest)) < 1e-8, (q[2] - 0.1, rest)
     assert r["efc_force"][0] == pytest.approx(9.81, rel=1e-4)
     assert np.abs(r["qacc"]).max() < 1e-4
 

@@ -111,8 +111,30 @@ enum {
  *   MJPC_TBL_LINVEL / ANGVEL      3           object         MJPC_OBJ_GEOM or MJPC_OBJ_SITE, in the world frame: what the framepos / framequat /
  *                                                            frame?axis / framelinvel / frameangvel sensors give (MAT row-major; a quaternion
  *                                                            of a site / geom / inertial frame is xquat[body] * the local quaternion)
- * Only position- and velocity-stage quantities exist when the residual runs (beside the constraint solve): accelerations, constraint
- * forces and the time are not sources.
+ * The sources above are position- and velocity-stage quantities: the residual runs beside the constraint solve.  The time is not a
+ * source.  Accelerations and contact forces are LATE sources, evaluated after the solve by the one-step calls only:
+ *   MJPC_TBL_QACC                 nv          -              qacc of the converged solve (after the noslip pass where the model has one):
+ *                                                            the acceleration mj_forward reports, not the integrator's damped one
+ *   MJPC_TBL_LINACC / ANGACC      3           object         world-frame linear / angular acceleration of the object's frame (objtype as for
+ *                                                            LINVEL), as framelinacc / frameangacc: the linear one carries -gravity (a body at
+ *                                                            rest reads +9.81 z) and the omega x v term of a moving point
+ *   MJPC_TBL_ACCELEROMETER        3           site           LINACC of the site in the site's frame (objtype = MJPC_OBJ_SITE)
+ *   MJPC_TBL_GYRO / VELOCIMETER   3           site           ANGVEL / LINVEL of the site in the site's frame (objtype = MJPC_OBJ_SITE)
+ *   MJPC_TBL_TOUCH                1           site           objtype = the zone's shape MJPC_ZONE_*, off = index into dbl_data of the zone's
+ *                                                            size[3] (MuJoCo's size conventions; the component offset is 0): the sum of the
+ *                                                            normal forces of the contacts that took part in the solve, have a geom on the
+ *                                                            site's body, a positive normal force and their position p (site coordinates)
+ *                                                            inside the zone: sphere |p| <= r; box |p_i| <= s_i; ellipsoid sum (p_i / s_i)^2
+ *                                                            <= 1; cylinder p_x^2 + p_y^2 <= r^2 and |p_z| <= h; capsule: distance to the
+ *                                                            segment +-h z at most r.  Normal force: the first row's force (frictionless /
+ *                                                            elliptic), the sum of the 2 (dim - 1) edge forces (pyramidal).  (MuJoCo also
+ *                                                            counts a contact outside the zone whose normal ray crosses it: not done here.)
+ * Late rules.  A block with a late term is a LATE BLOCK: its other terms may only be late kinds, CONST or PARAM, and its operation is
+ * SUM or NORM.  TOUCH names a site, a known shape, positive sizes and a dbl_data range in bounds; ACCELEROMETER / GYRO / VELOCIMETER
+ * name a site.  Late rows exist in the one-step calls only (mjpc_hip_step_batch, mjpc_hip_transition_fd, mjpc_hip_linearize_step,
+ * mjpc_hip_unscented_moments and what is built on them).  In a rollout (mjpc_hip_plan*) late rows are written as 0.0: the cost term
+ * that covers them should carry weight 0 (the reference's estimator sensors sit outside the cost as well).  Sums run in ascending
+ * dof index and ascending contact index.
  * Encoding.  int_data = [MJPC_TBL_VERSION, nblock, nterm,  nblock x {op, row, dim, ncomp, first term, number of terms},
  *                        nterm x {kind, objtype (CONST: count; 0 where the kind has none), id (0 where the kind has none), off}];
  * a block's terms are consecutive and the blocks use the terms in order.  dbl_data = [coef_0 .. coef_{nterm-1}, constants ...].
@@ -128,7 +150,11 @@ enum { MJPC_TBL_OP_SUM = 0, MJPC_TBL_OP_NORM = 1, MJPC_TBL_OP_SUBQUAT = 2 };
 enum { MJPC_TBL_CONST = 0, MJPC_TBL_PARAM = 1, MJPC_TBL_QPOS = 2, MJPC_TBL_QVEL = 3, MJPC_TBL_ACT = 4, MJPC_TBL_CTRL = 5,
        MJPC_TBL_ACTUATOR_FORCE = 6, MJPC_TBL_KEY_QPOS = 7, MJPC_TBL_MOCAP_POS = 8, MJPC_TBL_MOCAP_QUAT = 9, MJPC_TBL_MOCAP_MAT = 10,
        MJPC_TBL_SUBTREE_COM = 11, MJPC_TBL_SUBTREE_LINVEL = 12, MJPC_TBL_POS = 13, MJPC_TBL_QUAT = 14, MJPC_TBL_MAT = 15,
-       MJPC_TBL_XAXIS = 16, MJPC_TBL_YAXIS = 17, MJPC_TBL_ZAXIS = 18, MJPC_TBL_LINVEL = 19, MJPC_TBL_ANGVEL = 20 };
+       MJPC_TBL_XAXIS = 16, MJPC_TBL_YAXIS = 17, MJPC_TBL_ZAXIS = 18, MJPC_TBL_LINVEL = 19, MJPC_TBL_ANGVEL = 20,
+       /* late kinds (one-step calls only) */
+       MJPC_TBL_QACC = 21, MJPC_TBL_LINACC = 22, MJPC_TBL_ANGACC = 23, MJPC_TBL_ACCELEROMETER = 24, MJPC_TBL_GYRO = 25,
+       MJPC_TBL_VELOCIMETER = 26, MJPC_TBL_TOUCH = 27 };
+enum { MJPC_ZONE_SPHERE = 2, MJPC_ZONE_CAPSULE = 3, MJPC_ZONE_ELLIPSOID = 4, MJPC_ZONE_CYLINDER = 5, MJPC_ZONE_BOX = 6 };   /* mjtGeom values */
 #define MJPC_TBL_VERSION 1
 #define MJPC_TBL_MAX_BLOCKS 64
 #define MJPC_TBL_MAX_TERMS 256

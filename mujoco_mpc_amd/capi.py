@@ -365,6 +365,10 @@ def debug_set(name: str, value=None):
 
 ABI_VERSION = 4            # MJPC_HIP_ABI_VERSION of include/mjpc_hip.h
 
+# late table sources and touch zone shapes of MJPC_TASK_TABLE (include/mjpc_hip.h; modelgen.ResidualTable builds them)
+(MJPC_TBL_QACC, MJPC_TBL_LINACC, MJPC_TBL_ANGACC, MJPC_TBL_ACCELEROMETER, MJPC_TBL_GYRO, MJPC_TBL_VELOCIMETER, MJPC_TBL_TOUCH) = range(21, 28)
+MJPC_ZONE_SPHERE, MJPC_ZONE_CAPSULE, MJPC_ZONE_ELLIPSOID, MJPC_ZONE_CYLINDER, MJPC_ZONE_BOX = 2, 3, 4, 5, 6
+
 EXPORTED_SYMBOLS = [
     "mjpc_hip_sizeof_model", "mjpc_hip_sizeof_task", "mjpc_hip_sizeof_plan_input", "mjpc_hip_sizeof_plan_output", "mjpc_hip_debug_set",
     "mjpc_hip_create", "mjpc_hip_destroy", "mjpc_hip_set_task", "mjpc_hip_plan", "mjpc_hip_plan_async",

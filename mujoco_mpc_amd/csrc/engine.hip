@@ -56,9 +56,9 @@ extern "C" RolloutFn mjpc_pick_rollout_spill(int nv, int *exact);
 extern "C" int mjpc_rollout_threads_cached(void);
 // the one-step kernels (rollout_step_*.hip, step_tu.h): opaque here, their parameter block needs core.h
 typedef void (*StepLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *state_tab, const double *ctrl_tab,
-                             const double *time_tab, double *next_state, double *residual_out, int *failure_out);
+                             const double *time_tab, double *next_state, double *residual_out, int *failure_out, const int *late_tab);
 #define MJPC_STEP_DECL(tu) extern "C" const void *mjpc_pick_step_##tu(int nv); \
-  extern "C" void mjpc_launch_step_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, double *, double *, int *);
+  extern "C" void mjpc_launch_step_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, double *, double *, int *, const int *);
 MJPC_STEP_DECL(cached) MJPC_STEP_DECL(direct) MJPC_STEP_DECL(spill)
 #undef MJPC_STEP_DECL
 // the feedback-policy rollout kernels (rollout_fb_*.hip, feedback_tu.h): opaque here as well
@@ -655,16 +655,18 @@ int mjpc_hip_set_task(MjpcHipEngine *e, const MjpcHipTask *task) {
   // only the task block changes (cost table, residual parameters, frozen ResidualFn state): one small stream-ordered copy per
   // buffer out of the engine's own packed image, ahead of the next plan's kernels; the model and key-frame tables stay put
   const PackedModel &pm = e->pm;
-  size_t bi = pm.task_i_cap * sizeof(int), bd = pm.task_d_cap * sizeof(double);
+  size_t bi = pm.task_i_cap * sizeof(int), bd = pm.task_d_cap * sizeof(double), bl = pm.late_cap * sizeof(int);
   int slot = e->task_slot ^= 1;                       // two pinned staging slots: the copy of the previous call may still be in flight
-  HIPCHK(e->buf[H_TASK0 + slot].reserve(bi + bd + 16));
+  HIPCHK(e->buf[H_TASK0 + slot].reserve(bi + bd + bl + 16));
   if (!e->ev_task[slot]) HIPCHK(hipEventCreateWithFlags(&e->ev_task[slot], hipEventDisableTiming));
   else HIPCHK(hipEventSynchronize(e->ev_task[slot]));
   char *h = e->at<char>(H_TASK0 + slot);
   memcpy(h, pm.db.data() + pm.task_d0, bd);
   memcpy(h + bd, pm.ib.data() + pm.task_i0, bi);
+  if (bl) memcpy(h + bd + bi, pm.ib.data() + pm.late_i0, bl);
   HIPCHK(hipMemcpyAsync(e->at(B_DB) + pm.task_d0, h, bd, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemcpyAsync(e->at<int>(B_IB) + pm.task_i0, h + bd, bi, hipMemcpyHostToDevice, e->stream));
+  if (bl) HIPCHK(hipMemcpyAsync(e->at<int>(B_IB) + pm.late_i0, h + bd + bi, bl, hipMemcpyHostToDevice, e->stream));      // the late table (host.h)
   HIPCHK(hipEventRecord(e->ev_task[slot], e->stream));
   e->K.M = mjpc_host::relocate(e->pm, e->at<int>(B_IB), e->at(B_DB));
   return 0;
@@ -998,9 +1000,11 @@ static int step_prepare(MjpcHipEngine *e, const char *who, const double *mocap, 
 // rows [0, rows) of the tables through the step kernel, at most max_local workgroups per launch (stream-ordered: a launch reuses
 // the row buffers, the slab and the CU's LDS of the one before it)
 static void step_rows(MjpcHipEngine *e, const KParams &K, size_t rows, const double *st, const double *ct, const double *tt, double *ns, double *rs, int *fl) {
+  // the task's late table (host.h): null without late rows, and the step kernel then has no late phase
+  const int *late = e->pm.late_blocks ? e->at<int>(B_IB) + e->pm.late_i0 : nullptr;
   for (size_t r0 = 0; r0 < rows; r0 += (size_t)e->max_local) {
     const int nl = (int)(rows - r0 < (size_t)e->max_local ? rows - r0 : (size_t)e->max_local);
-    e->step_launch(e->step_kernel, nl, e->lds_bytes, e->stream, &K, st + r0 * e->ds, ct + r0 * e->nu, tt + r0, ns + r0 * e->ds, rs + r0 * e->nr, fl + r0);
+    e->step_launch(e->step_kernel, nl, e->lds_bytes, e->stream, &K, st + r0 * e->ds, ct + r0 * e->nu, tt + r0, ns + r0 * e->ds, rs + r0 * e->nr, fl + r0, late);
   }
 }
 

@@ -24,6 +24,8 @@ struct PackedModel {
   size_t cache_i, cache_d;                           // prefix of ib/db copied into LDS by every workgroup
   size_t hot_i = 0, hot_d = 0;                       // the shorter prefix the hot-tables-only flavour copies
   int slab_doubles = 0;                              // per-candidate HBM slab of the spill flavour (make_layout), 0 without one
+  size_t late_i0 = 0, late_cap = 0;                  // the late table (model.h) at the end of ib: outside the LDS copy and the task region
+  int late_blocks = 0;                               // 0: the task has no late rows (the step kernels get a null table)
   std::string error;
 };
 
@@ -60,6 +62,31 @@ static inline size_t put_d(PackedModel &p, const double *src, size_t n) {
   return o;
 }
 
+// MJPC_TASK_TABLE, a checked table: block b has a term of a late kind (model.h)
+static inline bool block_is_late(const int *I, int b) {
+  const int *B = I + TBL_HEADER + TBL_BLOCK_INTS * b, *T = I + TBL_HEADER + TBL_BLOCK_INTS * I[1];
+  for (int j = B[4]; j < B[4] + B[5]; j++) if (T[TBL_TERM_INTS * j] >= TBL_QACC) return true;
+  return false;
+}
+// the late table of a checked task (model.h: the late blocks and their terms); empty when the task has none
+static inline std::vector<int> late_table(const MjpcHipTask *t, int *nblock) {
+  std::vector<int> blocks, terms;
+  *nblock = 0;
+  if (t->task_id != MJPC_TASK_TABLE) return blocks;
+  const int *I = t->int_data, *T = I + TBL_HEADER + TBL_BLOCK_INTS * I[1];
+  for (int b = 0; b < I[1]; b++) if (block_is_late(I, b)) {
+    const int *B = I + TBL_HEADER + TBL_BLOCK_INTS * b;
+    for (int k = 0; k < 4; k++) blocks.push_back(B[k]);
+    blocks.push_back((int)terms.size() / LATE_TERM_INTS); blocks.push_back(B[5]);
+    for (int j = B[4]; j < B[4] + B[5]; j++) { for (int k = 0; k < TBL_TERM_INTS; k++) terms.push_back(T[TBL_TERM_INTS * j + k]); terms.push_back(j); }
+    (*nblock)++;
+  }
+  if (*nblock == 0) return blocks;
+  std::vector<int> out = {*nblock, (int)terms.size() / LATE_TERM_INTS};
+  out.insert(out.end(), blocks.begin(), blocks.end()); out.insert(out.end(), terms.begin(), terms.end());
+  return out;
+}
+
 // pack the task tables at the current end of ib/db and fill M.task with offsets
 static inline void pack_task(PackedModel &p, const MjpcHipTask *t) {
   DevTask &T = p.M.task;
@@ -77,6 +104,11 @@ static inline void pack_task(PackedModel &p, const MjpcHipTask *t) {
   T.norm_parameter = as_off<double>(put_d(p, t->norm_parameter, np));
   T.parameters = as_off<double>(put_d(p, t->parameters, t->num_parameter));
   T.dbl_data = as_off<double>(put_d(p, t->dbl_data, t->num_dbl));
+  // what residuals.h reads of a table shows every late block as a term-less SUM block ("writes zeros"); late_table() keeps the original
+  if (t->task_id == MJPC_TASK_TABLE) {
+    int *I = p.ib.data() + (reinterpret_cast<size_t>(T.int_data) - 1) / sizeof(int);
+    for (int b = 0; b < I[1]; b++) if (block_is_late(t->int_data, b)) { int *B = I + TBL_HEADER + TBL_BLOCK_INTS * b; B[0] = TBL_OP_SUM; B[3] = B[2]; B[5] = 0; }
+  }
 }
 
 // MJPC_TASK_TABLE: the table is input from outside the program and the kernel trusts every index in it, so everything is checked
@@ -88,6 +120,10 @@ static_assert(TBL_CONST == MJPC_TBL_CONST && TBL_PARAM == MJPC_TBL_PARAM && TBL_
               TBL_SUBTREE_LINVEL == MJPC_TBL_SUBTREE_LINVEL && TBL_POS == MJPC_TBL_POS && TBL_QUAT == MJPC_TBL_QUAT && TBL_MAT == MJPC_TBL_MAT &&
               TBL_XAXIS == MJPC_TBL_XAXIS && TBL_YAXIS == MJPC_TBL_YAXIS && TBL_ZAXIS == MJPC_TBL_ZAXIS && TBL_LINVEL == MJPC_TBL_LINVEL && TBL_ANGVEL == MJPC_TBL_ANGVEL,
               "table source kinds");
+static_assert(TBL_QACC == MJPC_TBL_QACC && TBL_LINACC == MJPC_TBL_LINACC && TBL_ANGACC == MJPC_TBL_ANGACC && TBL_ACCELEROMETER == MJPC_TBL_ACCELEROMETER &&
+              TBL_GYRO == MJPC_TBL_GYRO && TBL_VELOCIMETER == MJPC_TBL_VELOCIMETER && TBL_TOUCH == MJPC_TBL_TOUCH && TBL_QACC == TBL_NKIND, "late source kinds");
+static_assert(ZONE_SPHERE == MJPC_ZONE_SPHERE && ZONE_CAPSULE == MJPC_ZONE_CAPSULE && ZONE_ELLIPSOID == MJPC_ZONE_ELLIPSOID && ZONE_CYLINDER == MJPC_ZONE_CYLINDER &&
+              ZONE_BOX == MJPC_ZONE_BOX, "touch zone shapes");
 static_assert(TBL_VERSION == MJPC_TBL_VERSION && TBL_MAX_BLOCKS == MJPC_TBL_MAX_BLOCKS && TBL_MAX_TERMS == MJPC_TBL_MAX_TERMS && TBL_MAX_NORM == MJPC_TBL_MAX_NORM, "table caps");
 static inline bool table_check(const DevModel &M, const MjpcHipTask *t, std::string &err) {
   if (t->task_id != MJPC_TASK_TABLE) return true;
@@ -115,6 +151,16 @@ static inline bool table_check(const DevModel &M, const MjpcHipTask *t, std::str
     if (op == TBL_OP_SUM && ncomp != dim) return fail(blk + ": SUM needs ncomp = dim");
     if (op == TBL_OP_NORM && (dim != 1 || ncomp < 1 || ncomp > TBL_MAX_NORM || n < 1)) return fail(blk + ": NORM needs dim = 1, 1 <= ncomp <= " + std::to_string(TBL_MAX_NORM) + " and at least one term");
     if (op == TBL_OP_SUBQUAT && (dim != 3 || ncomp != 4 || n != 2)) return fail(blk + ": SUBQUAT needs dim = 3, ncomp = 4 and exactly two terms");
+    // a block with a late term is a late block (evaluated after the solve, by the one-step kernels only)
+    bool late = false;
+    for (int j = t0; j < t0 + n; j++) if (T[TBL_TERM_INTS * j] >= TBL_QACC && T[TBL_TERM_INTS * j] < TBL_NKIND_LATE) late = true;
+    if (late && op == TBL_OP_SUBQUAT) return fail(blk + ": a late block (one with an acceleration / touch source) is a SUM or a NORM");
+    if (late) {      // named at the block's first late term: it is what makes the block late
+      int jl = -1, je = -1;
+      for (int j = t0 + n - 1; j >= t0; j--) { const int k = T[TBL_TERM_INTS * j]; if (k >= TBL_QACC) jl = j; else if (k != TBL_CONST && k != TBL_PARAM) je = j; }
+      if (je >= 0) return fail(blk + " term " + std::to_string(jl) + ": late source kind " + std::to_string(T[TBL_TERM_INTS * jl]) + " beside source kind " + std::to_string(T[TBL_TERM_INTS * je]) +
+                               " of term " + std::to_string(je) + " (a late block holds late kinds, CONST and PARAM only)");
+    }
     for (int j = t0; j < t0 + n; j++) {
       const std::string trm = blk + " term " + std::to_string(j);
       const int *R = T + TBL_TERM_INTS * j, kind = R[0], ty = R[1], id = R[2], off = R[3];
@@ -140,6 +186,26 @@ static inline bool table_check(const DevModel &M, const MjpcHipTask *t, std::str
           else if (ty == MJPC_OBJ_SITE) { if (!obj(M.nsite, "site")) return false; }
           else return fail(trm + ": unknown object type " + std::to_string(ty));
           len = kind == TBL_QUAT ? 4 : (kind == TBL_MAT ? 9 : 3); break;
+        case TBL_QACC: len = M.nv; break;
+        case TBL_LINACC: case TBL_ANGACC:
+          if (ty == MJPC_OBJ_BODY || ty == MJPC_OBJ_XBODY) { if (!obj(M.nbody, "body")) return false; }
+          else if (ty == MJPC_OBJ_GEOM) { if (!obj(M.ngeom, "geom")) return false; }
+          else if (ty == MJPC_OBJ_SITE) { if (!obj(M.nsite, "site")) return false; }
+          else return fail(trm + ": unknown object type " + std::to_string(ty));
+          len = 3; break;
+        case TBL_ACCELEROMETER: case TBL_GYRO: case TBL_VELOCIMETER:
+          if (ty != MJPC_OBJ_SITE) return fail(trm + ": ACCELEROMETER / GYRO / VELOCIMETER sit on a site (object type " + std::to_string(ty) + ")");
+          if (!obj(M.nsite, "site")) return false;
+          len = 3; break;
+        case TBL_TOUCH: {
+          if (!obj(M.nsite, "site")) return false;
+          if (ty != ZONE_SPHERE && ty != ZONE_CAPSULE && ty != ZONE_ELLIPSOID && ty != ZONE_CYLINDER && ty != ZONE_BOX) return fail(trm + ": unknown touch zone shape " + std::to_string(ty));
+          if (off < 0 || off > t->num_dbl - 3) return fail(trm + ": zone size dbl_data[" + std::to_string(off) + " .. +3) out of range (num_dbl = " + std::to_string(t->num_dbl) + ")");
+          const int need = ty == ZONE_SPHERE ? 1 : ((ty == ZONE_CAPSULE || ty == ZONE_CYLINDER) ? 2 : 3);
+          for (int k = 0; k < need; k++) if (!(t->dbl_data[off + k] > 0)) return fail(trm + ": touch zone size " + std::to_string(k) + " is not positive");
+          if (ncomp != 1) return fail(trm + ": TOUCH has one component");
+          len = 1 + off; break;      // (off is the zone's address, not a component offset: the test below passes)
+        }
         default: return fail(trm + ": unknown source kind " + std::to_string(kind));
       }
       if (op == TBL_OP_SUBQUAT && ((kind != TBL_QUAT && kind != TBL_MOCAP_QUAT) || off != 0)) return fail(trm + ": SUBQUAT takes two quaternion sources (QUAT / MOCAP_QUAT) at offset 0");
@@ -675,6 +741,10 @@ static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTas
     M.hfield_nrow = as_off<int>(put_i(p, m->hfield_nrow, nh)); M.hfield_ncol = as_off<int>(put_i(p, m->hfield_ncol, nh));
     M.hfield_adr = as_off<int>(put_i(p, m->hfield_adr, nh)); M.hfield_size = as_off<double>(put_d(p, m->hfield_size, 4 * nh));
     M.hfield_data = as_off<double>(put_d(p, m->hfield_data, (size_t)(m->nhfielddata > 0 ? m->nhfielddata : 0))); }
+  // the late table: behind everything the kernels' model view names, read from HBM by the late-row phase of the step kernels
+  { std::vector<int> lt = late_table(t, &p.late_blocks);
+    p.late_i0 = p.ib.size(); p.late_cap = lt.size();
+    p.ib.insert(p.ib.end(), lt.begin(), lt.end()); }
   // ---- LDS layout
   if (!use_cache) { p.cache_i = hot_only ? p.hot_i : 0; p.cache_d = hot_only ? p.hot_d : 0; }      // the kernel reads (the rest of) the tables from HBM / L2
   make_layout(p, p.L, m, t, P_max, p.cache_d, p.cache_i, lean, reg_solver);
@@ -736,6 +806,9 @@ static inline DevModel relocate(const PackedModel &p, const int *ibase, const do
 // re-pack the task into the reserved region (sizes must not exceed the initial ones)
 static inline bool repack_task(PackedModel &p, const MjpcHipTask *t) {
   if (!table_check(p.M, t, p.error)) return false;      // before anything is touched: the engine keeps its task
+  int late_nb = 0;
+  const std::vector<int> lt = late_table(t, &late_nb);      // goes into the room the created task's late table reserved
+  if (lt.size() > p.late_cap) { p.error = "task grew beyond the size given at create() (late rows)"; return false; }
   std::vector<int> ib_tail(p.ib.begin() + p.task_i0 + p.task_i_cap, p.ib.end());       // keyframe tables behind the task region
   std::vector<double> db_tail(p.db.begin() + p.task_d0 + p.task_d_cap, p.db.end());
   const std::vector<int> ib_old(p.ib.begin() + p.task_i0, p.ib.begin() + p.task_i0 + p.task_i_cap);      // a refused task leaves the old one in place
@@ -752,6 +825,7 @@ static inline bool repack_task(PackedModel &p, const MjpcHipTask *t) {
   }
   p.ib.resize(p.task_i0 + p.task_i_cap, 0); p.db.resize(p.task_d0 + p.task_d_cap, 0.0);
   p.ib.insert(p.ib.end(), ib_tail.begin(), ib_tail.end()); p.db.insert(p.db.end(), db_tail.begin(), db_tail.end());
+  if (ok) { p.late_blocks = late_nb; for (size_t k = 0; k < lt.size(); k++) p.ib[p.late_i0 + k] = lt[k]; }
   return ok;
 }
 

@@ -81,6 +81,13 @@ enum { WARN_BADQPOS = 1, WARN_BADQVEL = 2, WARN_BADQACC = 4, WARN_CONTACTFULL = 
 enum { TBL_CONST = 0, TBL_PARAM = 1, TBL_QPOS = 2, TBL_QVEL = 3, TBL_ACT = 4, TBL_CTRL = 5, TBL_ACTUATOR_FORCE = 6, TBL_KEY_QPOS = 7,
        TBL_MOCAP_POS = 8, TBL_MOCAP_QUAT = 9, TBL_MOCAP_MAT = 10, TBL_SUBTREE_COM = 11, TBL_SUBTREE_LINVEL = 12, TBL_POS = 13,
        TBL_QUAT = 14, TBL_MAT = 15, TBL_XAXIS = 16, TBL_YAXIS = 17, TBL_ZAXIS = 18, TBL_LINVEL = 19, TBL_ANGVEL = 20, TBL_NKIND = 21 };
+// late kinds: evaluated after the solve by the one-step kernels only (late_rows.h); residuals.h never sees them (host.h shows it a
+// late block as a term-less SUM block).  The late table of a packed model, ints:
+//   [number of late blocks, number of late terms,  blocks x {op, row, dim, ncomp, first late term, number of terms},
+//    terms x {kind, objtype, id, off, index of the coefficient in dbl_data}]
+enum { TBL_QACC = 21, TBL_LINACC = 22, TBL_ANGACC = 23, TBL_ACCELEROMETER = 24, TBL_GYRO = 25, TBL_VELOCIMETER = 26, TBL_TOUCH = 27, TBL_NKIND_LATE = 28 };
+enum { ZONE_SPHERE = 2, ZONE_CAPSULE = 3, ZONE_ELLIPSOID = 4, ZONE_CYLINDER = 5, ZONE_BOX = 6 };
+enum { LATE_HEADER = 2, LATE_BLOCK_INTS = 6, LATE_TERM_INTS = 5 };
 enum { TBL_OP_SUM = 0, TBL_OP_NORM = 1, TBL_OP_SUBQUAT = 2 };
 enum { TBL_VERSION = 1, TBL_HEADER = 3, TBL_BLOCK_INTS = 6, TBL_TERM_INTS = 4, TBL_MAX_BLOCKS = 64, TBL_MAX_TERMS = 256, TBL_MAX_NORM = 16 };
 

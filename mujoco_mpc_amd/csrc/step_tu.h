@@ -24,9 +24,10 @@ extern "C" const void *MJPC_CAT(mjpc_pick_step_, MJPC_TU)(int nv) {
   return (const void *)MJPC_CAT(step_kernel_, MJPC_TU)<0>;
 }
 extern "C" void MJPC_CAT(mjpc_launch_step_, MJPC_TU)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *state_tab,
-                                                     const double *ctrl_tab, const double *time_tab, double *next_state, double *residual_out, int *failure_out) {
+                                                     const double *ctrl_tab, const double *time_tab, double *next_state, double *residual_out, int *failure_out,
+                                                     const int *late_tab) {
   StepParams S;
   S.K = *K; S.K.nlocal = n;
-  S.state_tab = state_tab; S.ctrl_tab = ctrl_tab; S.time_tab = time_tab; S.next_state = next_state; S.residual_out = residual_out; S.failure_out = failure_out;
+  S.state_tab = state_tab; S.ctrl_tab = ctrl_tab; S.time_tab = time_tab; S.next_state = next_state; S.residual_out = residual_out; S.failure_out = failure_out; S.late_tab = late_tab;
   hipLaunchKernelGGL((StepFn)fn, dim3(n), dim3(64 * MJPC_WAVES), lds_bytes, stream, S);
 }

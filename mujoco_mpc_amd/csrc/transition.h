@@ -19,6 +19,7 @@ struct StepParams {
   double *next_state;         // [nlocal][nq+nv+na]
   double *residual_out;       // [nlocal][num_residual]
   int *failure_out;           // [nlocal]           MJPC_WARN_* bits, 0 = the step succeeded
+  const int *late_tab;        // the task's late table (model.h) in device memory, or null: no late rows, no late phase
 };
 #ifdef MJPC_EMU
 typedef const StepParams *SP;
@@ -26,6 +27,7 @@ typedef const StepParams *SP;
 typedef const __attribute__((address_space(4))) StepParams *SP;
 #endif
 DEV const StepParams *sp_generic(SP s) { return (const StepParams *)kp_generic((KP)s); }
+#include "late_rows.h"
 
 // sibling of ph_init: the same LDS model-cache copy and zeroing; state, time and the one-knot policy come from row r of the tables
 DEV_NOINLINE void ph_init_step(SP Sc) {
@@ -132,6 +134,11 @@ DEV void transition(SP Sc) {
     }
     XBAR();
     have_residual = 1;
+    // late rows (accelerations, touch): the side wave, idle here, between the solve and the integration; uniform from the kernel arguments
+    if (Sc->late_tab) {
+      if (r1) ph_late_rows(Sc);
+      XBAR();
+    }
     if (uniform_i(misc[MISC_WARNING]) | uniform_i(misc[MISC_WARN_OTHERS])) { failure = 1; break; }
     if (r0) ph_integrate<NVT>(Kc, t);
   } while (0);

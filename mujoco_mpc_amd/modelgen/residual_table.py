@@ -30,10 +30,15 @@ OP_SUM, OP_NORM, OP_SUBQUAT = 0, 1, 2
 (SRC_CONST, SRC_PARAM, SRC_QPOS, SRC_QVEL, SRC_ACT, SRC_CTRL, SRC_ACTUATOR_FORCE, SRC_KEY_QPOS, SRC_MOCAP_POS, SRC_MOCAP_QUAT,
  SRC_MOCAP_MAT, SRC_SUBTREE_COM, SRC_SUBTREE_LINVEL, SRC_POS, SRC_QUAT, SRC_MAT, SRC_XAXIS, SRC_YAXIS, SRC_ZAXIS, SRC_LINVEL,
  SRC_ANGVEL) = range(21)
+# late kinds (include/mjpc_hip.h): they need the converged solve and exist in the one-step calls only; a rollout writes their rows as 0.0
+SRC_QACC, SRC_LINACC, SRC_ANGACC, SRC_ACCELEROMETER, SRC_GYRO, SRC_VELOCIMETER, SRC_TOUCH = range(21, 28)
+ZONES = {"sphere": 2, "capsule": 3, "ellipsoid": 4, "cylinder": 5, "box": 6}
+_ZONE_SIZES = {2: 1, 3: 2, 4: 3, 5: 2, 6: 3}          # how many of size[3] the shape reads (MuJoCo's size conventions)
 MAX_BLOCKS, MAX_TERMS, MAX_NORM = 64, 256, 16
 _OBJ = {"body": OBJ_BODY, "xbody": OBJ_XBODY, "geom": OBJ_GEOM, "site": OBJ_SITE}
 _OBJ_NAMES = {OBJ_BODY: "body", OBJ_XBODY: "body", OBJ_GEOM: "geom", OBJ_SITE: "site"}
-_FRAME_LEN = {SRC_POS: 3, SRC_QUAT: 4, SRC_MAT: 9, SRC_XAXIS: 3, SRC_YAXIS: 3, SRC_ZAXIS: 3, SRC_LINVEL: 3, SRC_ANGVEL: 3}
+_FRAME_LEN = {SRC_POS: 3, SRC_QUAT: 4, SRC_MAT: 9, SRC_XAXIS: 3, SRC_YAXIS: 3, SRC_ZAXIS: 3, SRC_LINVEL: 3, SRC_ANGVEL: 3, SRC_LINACC: 3, SRC_ANGACC: 3,
+              SRC_ACCELEROMETER: 3, SRC_GYRO: 3, SRC_VELOCIMETER: 3}
 
 
 class Expr:
@@ -158,6 +163,29 @@ class ResidualTable:
     def linvel(self, objtype, name): return self._frame(SRC_LINVEL, objtype, name)
     def angvel(self, objtype, name): return self._frame(SRC_ANGVEL, objtype, name)
 
+    # ---- late sources: a block that uses one may otherwise only hold late sources, constants and parameters, and is a sum or a norm
+    def qacc(self): return self._src(SRC_QACC, self.m["nv"])
+    def linacc(self, objtype, name): return self._frame(SRC_LINACC, objtype, name)
+    def angacc(self, objtype, name): return self._frame(SRC_ANGACC, objtype, name)
+    def accelerometer(self, site): return self._frame(SRC_ACCELEROMETER, "site", site)
+    def gyro(self, site): return self._frame(SRC_GYRO, "site", site)
+    def velocimeter(self, site): return self._frame(SRC_VELOCIMETER, "site", site)
+
+    def touch(self, site, shape, size):
+        """sum of the normal forces of the contacts of the site's body inside the zone `shape` ("sphere", "capsule", "ellipsoid",
+        "cylinder", "box") of MuJoCo's `size` around the site"""
+        ty, i = self._id("site", site)
+        z = ZONES[shape] if isinstance(shape, str) else int(shape)
+        if z not in _ZONE_SIZES:
+            raise ValueError(f"unknown touch zone shape {shape}")
+        v = np.zeros(3); sz = np.asarray(size, float).ravel()
+        if sz.size < _ZONE_SIZES[z] or sz.size > 3:
+            raise ValueError(f"a {shape} zone reads {_ZONE_SIZES[z]} sizes, got {sz.size}")
+        v[:sz.size] = sz
+        if not np.all(v[:_ZONE_SIZES[z]] > 0):
+            raise ValueError("touch zone sizes must be positive")
+        return Expr([(1.0, SRC_TOUCH, z, i, 0, v)], 1)
+
     # ---- blocks (each appends rows behind the ones before it)
     def _cut(self, expr, dim):
         if not isinstance(expr, Expr):
@@ -169,6 +197,9 @@ class ResidualTable:
         return expr
 
     def _add(self, op, dim, ncomp, terms):
+        if any(t[1] >= SRC_QACC for t in terms):
+            if op == OP_SUBQUAT or any(t[1] < SRC_QACC and t[1] not in (SRC_CONST, SRC_PARAM) for t in terms):
+                raise ValueError("a late block (acceleration / touch sources) is a sum or a norm of late sources, constants and parameters only")
         self.blocks.append((op, int(dim), int(ncomp), list(terms)))
         self.rows += int(dim)
         return self
@@ -214,6 +245,9 @@ class ResidualTable:
                 need = 4 if op == OP_SUBQUAT else ncomp
                 if kind == SRC_CONST:
                     ty, i = int(v.size), nterm + len(pool)
+                    pool += [float(x) for x in v]
+                if kind == SRC_TOUCH:      # the zone's size[3] goes to the constant pool, the record's off is its address
+                    off = nterm + len(pool)
                     pool += [float(x) for x in v]
                 if kind == SRC_PARAM and off + need > num_parameter:
                     raise IndexError(f"parameters [{off}, {off + need}) of {num_parameter}")

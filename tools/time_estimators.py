@@ -5,7 +5,9 @@ calls the engine had before them - step_batch over a sigma table built on the ho
 plus step_batch per half-step - with the host part in vectorised numpy.  The paths alternate in one process.
 
 usage: tools/time_estimators.py [--model quadruped|humanoid_track] [--calls 5] [--passes 2] [--only unscented|kalman|unscented_composed|kalman_composed]
-The measurement is the trunk's (root body's) position plus the joint positions behind the free joint.  Prints one line per pass and
+                                [--imu-site torso] [--touch-sites FR,FL,RR,RL]
+The measurement is the trunk's (root body's) position plus the joint positions behind the free joint; --imu-site / --touch-sites add
+an IMU (gyro + accelerometer, 6 rows) and touch rows, which the step kernel fills in its late phase.  Prints one line per pass and
 path: median (min - max) in ms.  With --only one path runs alone, for a profiler run of its own, e.g.
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/time_estimators.py --only unscented
 whose kernel statistics hold ukf_sigma_kernel, the step kernel, ukf_mean_kernel and ukf_cov_kernel.  DESIGN section 8j holds the
@@ -62,6 +64,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="quadruped"); ap.add_argument("--calls", type=int, default=5); ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--only", default="")
+    ap.add_argument("--imu-site", default="", help="add late rows to the measurement: gyro and accelerometer of this site (6 rows) and one touch row per --touch-site")
+    ap.add_argument("--touch-sites", default="", help="comma-separated sites, each with a spherical touch zone of radius 0.03")
     a = ap.parse_args()
     m, _, d = REGISTRY[a.model]()
     nq, nv, na, nu = m["nq"], m["nv"], m["na"], m["nu"]
@@ -69,6 +73,10 @@ def main():
     nd = 2 * nv
     t = ResidualTable(m)
     t.sum(t.pos("xbody", int(m["jnt_bodyid"][0]))); t.sum(t.qpos()[7:])
+    if a.imu_site:                                                    # late rows: the step kernel runs its late phase
+        t.sum(t.gyro(a.imu_site)); t.sum(t.accelerometer(a.imu_site))
+    for s_ in filter(None, a.touch_sites.split(",")):
+        t.sum(t.touch(s_, "sphere", (0.03,)))
     task = t.measurement(); ns = task["num_residual"]
     be = HipBackend(m, task, max_samples=256, max_horizon=2)
     mocap = np.asarray(d["mocap"], float) if len(d["mocap"]) else None

@@ -112,17 +112,33 @@ DEV void static_for(F &&f) {
 // every index below is a compile-time constant (static_for, not `#pragma unroll`: with N = 33 the nested pragma loops exceeded
 // the unroller's budget, the row array stayed in scratch memory and the kernel wrote gigabytes of spills per launch)
 // row i of the symmetric matrix (only its lower triangle is valid in LDS) and its diagonal entry, partial matrices added
+//
+// Where lane i finds its row depends on the lane alone: entry j at (max(i, j), min(i, j)) of the lower triangle, the diagonal at
+// (i, i).  The offsets are formed once and serve A and every partial (same layout, same stride).  The lane index is clamped once
+// (an inactive lane, i >= N, walks column 0: entries (j, 0), inside the block and in the lower triangle), every lane loads and
+// adds without a select, and ONE mask at the end gives the inactive lanes a[j] = +0.0 and dg = 1.0: what the row-local
+// broadcasts of the factorisations need (finite operands beside their exact zeros, see above the dense routines; an inactive
+// lane's sums are discarded by the select whatever they are).  An active lane forms ((A + X0) + X1) + X2 as before.
+template <int N>
+struct LDLRowOff { int e[N], d; };
+template <int N>
+DEV void ldl_row_offsets(int nvp, LDLRowOff<N> &o) {
+  const int ic = LANE < N ? LANE : 0;
+  static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; o.e[j] = (j <= ic) ? ic * nvp + j : j * nvp + ic; });
+  o.d = ic * nvp + ic;
+}
 template <int N>
 DEV void ldl_load_row(const double *A, int nvp, const LDLExtra *ex, double *a, double &dg) {
   const int i = LANE;
   const bool act = i < N;
+  LDLRowOff<N> o;
+  ldl_row_offsets<N>(nvp, o);
   if (ex && ex->row) {
-    double d0 = 1.0;
-    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] = act ? ex->row[j] : 0.0; d0 = (j == i) ? ex->row[j] : d0; });
-    dg = act ? d0 : 1.0;
+    dg = 1.0;
+    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] = ex->row[j]; dg = (j == i) ? ex->row[j] : dg; });
   } else {
-    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] = act ? A[(j <= i) ? i * nvp + j : j * nvp + i] : 0.0; });
-    dg = act ? A[i * nvp + i] : 1.0;
+    static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] = A[o.e[j]]; });
+    dg = A[o.d];
   }
   if (ex && ex->n > 0) {
     const int nx = ex->n;
@@ -130,27 +146,27 @@ DEV void ldl_load_row(const double *A, int nvp, const LDLExtra *ex, double *a, d
 #pragma unroll
     for (int w = 0; w < 3; w++) {
       const double *X = ex->x[w < nx ? w : 0];
-      static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; t[w][j] = X[(j <= i && act) ? i * nvp + j : (act ? j * nvp + i : 0)]; });
-      td[w] = X[act ? i * nvp + i : 0];
+      static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; t[w][j] = X[o.e[j]]; });
+      td[w] = X[o.d];
       if (w + 1 >= nx) break;
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int w = 0; w < 3; w++) {
       if (w >= nx) break;
-      static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] += act ? t[w][j] : 0.0; });
-      dg += act ? td[w] : 0.0;
+      static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] += t[w][j]; });
+      dg += td[w];
     }
   }
+  static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; a[j] = act ? a[j] : 0.0; });
+  dg = act ? dg : 1.0;
 }
+// the elimination proper, from the row (and diagonal entry) ldl_load_row left in the lane's registers; a[] is consumed
 template <int N>
-DEV void ldl_factor_regs(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
+DEV void ldl_eliminate_regs(double *a, double dg, LDLRegs<N> &f) {
   static_assert(N >= 1 && N <= 64, "one matrix row per lane");
   const int i = LANE;
   const bool act = i < N;
-  double a[N];
-  double dg;
-  ldl_load_row<N>(A, nvp, ex, a, dg);
   static_for<1, N>([&](auto kc) {
     constexpr int k = N - decltype(kc)::value;                                 // N-1 ... 1
     constexpr bool loc = dense_up_local<N>(k);
@@ -175,6 +191,13 @@ DEV void ldl_factor_regs(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
   if (dg < D_MINVAL) dg = D_MINVAL;
   f.rinv = fast_rcp(dg);
   static_for<0, N>([&](auto jc) { constexpr int j = decltype(jc)::value; f.lo[j] = (act && j < i) ? a[j] * f.rinv : 0.0; });
+}
+template <int N>
+DEV void ldl_factor_regs(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
+  double a[N];
+  double dg;
+  ldl_load_row<N>(A, nvp, ex, a, dg);
+  ldl_eliminate_regs<N>(a, dg, f);
 }
 template <int N>
 DEV double ldl_solve_regs(const LDLRegs<N> &f, double xi) {
@@ -222,13 +245,10 @@ static_assert(tree_nup_local<18>() == 15 && !tree_up_local<18>(16) && !tree_up_l
 static_assert(tree_ndown<18>(false) == 14 && tree_ndown<18>(true) == 7, "DofTree<18>: row-local steps of L x = v");
 #define TREE_BAR() __builtin_amdgcn_sched_barrier(0)
 template <int N>
-DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
+DEV void ldl_eliminate_tree(double *a, double dg, LDLRegs<N> &f) {
   static_assert(DofTree<N>::known && N <= 64, "one matrix row per lane");
   const int i = LANE;
   const bool act = i < N;
-  double a[N];
-  double dg;
-  ldl_load_row<N>(A, nvp, ex, a, dg);
   static_for<0, tree_nlevel<N>()>([&](auto hc) {
     constexpr int H = decltype(hc)::value;
     // 1/d in the vector domain (every lane inverts its own diagonal: one reciprocal chain per LEVEL, no scalar clamp
@@ -277,6 +297,13 @@ DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra
   for (int j = 0; j < N; j++) f.lo[j] = (act && j < i) ? a[j] * f.rinv : 0.0;
 }
 template <int N>
+DEV void ldl_factor_tree(const double *A, int nvp, LDLRegs<N> &f, const LDLExtra *ex = nullptr) {
+  double a[N];
+  double dg;
+  ldl_load_row<N>(A, nvp, ex, a, dg);
+  ldl_eliminate_tree<N>(a, dg, f);
+}
+template <int N>
 DEV double ldl_solve_tree(const LDLRegs<N> &f, double xi) {
   static_for<0, tree_nlevel<N>()>([&](auto hc) {          // L^T u = b, leaves first
     constexpr int H = decltype(hc)::value;
@@ -321,24 +348,30 @@ DEV void chol_solve_reg(const double *L, const double *Dinv, double *x, int nvp,
   const bool act = i < N;
   LDLRegs<N> f;
   f.rinv = act ? Dinv[i] : 0.0;
+  // lo[k] and up[k] are never both set: one load per k, entry (max(i, k), min(i, k)) as in ldl_load_row (k == i reads the diagonal
+  // slot, which the factor leaves alone, and drops it)
+  LDLRowOff<N> o;
+  ldl_row_offsets<N>(nvp, o);
   static_for<0, N>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
-    f.lo[k] = (act && k < i) ? L[i * nvp + k] : 0.0;
-    f.up[k] = (act && k > i) ? L[k * nvp + i] : 0.0;
+    const double v = L[o.e[k]];
+    f.lo[k] = (act && k < i) ? v : 0.0;
+    f.up[k] = (act && k > i) ? v : 0.0;
   });
   double xi = ldl_solve_any<N>(f, act ? x[i] : 0.0, tree);
   if (act) x[i] = xi;
   SYNC();
 }
-// fused factor + solve (the factor never leaves the registers): Newton direction, implicit-damping solve
+// fused factor + solve (the factor never leaves the registers): Newton direction, implicit-damping solve.
+// negx: also receives -x (the Newton solver's search direction, from the lane that holds the solution entry)
 template <int N>
-DEV void chol_factor_solve_reg(const double *A, double *x, int nvp, int tree, const LDLExtra *ex = nullptr) {
+DEV void chol_factor_solve_reg(const double *A, double *x, int nvp, int tree, const LDLExtra *ex = nullptr, double *negx = nullptr) {
   SYNC();
   LDLRegs<N> f;
   ldl_factor_any<N>(A, nvp, f, tree, ex);
   const int i = LANE;
   double xi = ldl_solve_any<N>(f, i < N ? x[i] : 0.0, tree);
-  if (i < N) x[i] = xi;
+  if (i < N) { x[i] = xi; if (negx) negx[i] = -xi; }
   SYNC();
 }
 #endif

@@ -471,14 +471,6 @@ DEV void newton_direction(Ctx &c) {
   chol_factor_solve<NVT>(c.qH, c.Hinv, c.vtmp, c.Mgrad, nv, nvp, c.M->tree_ok && !c.cross);
   PROF(c, 17);
 }
-#ifndef MJPC_EMU
-// the same with the Hessian given as qH + partial matrices (the worker waves' cone blocks): summed while the rows are loaded
-template <int NVT>
-DEV void newton_direction_sum(Ctx &c, const LDLExtra &ex) {
-  chol_factor_solve_reg<NVT>(c.qH, c.Mgrad, NVP_OF(NVT), c.M->tree_ok && !c.cross, &ex);
-  PROF(c, 17);
-}
-#endif
 
 // ---- the generic solver's exact line search: phi(alpha) = Gauss(alpha) + sum_i s_i(jar + alpha*jv), data in registers
 // Row costs in one branch-free form: with xc = clamp(x, lo, hi),

@@ -84,14 +84,34 @@ DEV void hblock_init(const Ctx &c, double *hq, int hi, int j0) {
   }
 }
 
-// grad = Ma - qfrc_smooth - J^T force (also copied to Mgrad for the solve); single-entry rows through their per-dof folds (sgl)
+// grad = Ma - qfrc_smooth - J^T force (also copied to Mgrad for the solve); single-entry rows through their per-dof folds (sgl).
+// Returns grad[LANE] to the lane that formed it, 0.0 to the others (the gradient norm needs no read-back).
+// Several column groups (G > 1): a batch of 8 trips that lies wholly inside the general rows ((t0 + 8) * G <= n, so rr < n on
+// every lane and the select of the clamped form would pass every product through) walks from one per-lane base each for efc_force
+// and efc_J: the trips are compile-time offsets (u * G rows).  Only the last, partial batch clamps its rows; no batch reads a row
+// beyond the n general ones.  The product stays a rounded product there (mul_rn): behind the select the compiler cannot contract it
+// with the add, and the sums must keep those bits.  With ONE column group (the hand) every lane walks the same rows, the select
+// is wave-uniform, the compiler makes it a branch and contracts product and add to an FMA: that form is left exactly as it is.
 template <int NVT>
-DEV void newton_grad_reg(Ctx &c, int hi, int hg, bool hact) {
+DEV double newton_grad_reg(Ctx &c, int hi, int hg, bool hact) {
   constexpr int nvp = NVP_OF(NVT), G = HLay<NVT>::G;
   const int ns = c.nsingle, n = c.nefc - ns;
   double part = 0;
   const int trips = (n + G - 1) / G;
-  for (int t0 = 0; t0 < trips; t0 += 8) {
+  int t0 = 0;
+  if constexpr (G > 1) {
+    const double *fb = c.efc_force + ns + hg, *jb = c.efc_J + (ns + hg) * nvp + hi;
+    for (; (t0 + 8) * G <= n; t0 += 8, fb += 8 * G, jb += 8 * G * nvp) {
+      double f[8], j[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) { f[u] = fb[u * G]; j[u] = jb[u * G * nvp]; }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 8; u++) part += mul_rn(j[u], f[u]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  for (; t0 < trips; t0 += 8) {
     double f[8], j[8];
 #pragma unroll
     for (int u = 0; u < 8; u++) {
@@ -107,16 +127,18 @@ DEV void newton_grad_reg(Ctx &c, int hi, int hg, bool hact) {
   double *sc = c.efc_JA;                   // dead during this solve: the scaled-row tables belong to the generic path
   if (hact) sc[hg * NVT + hi] = part;
   SYNC();
+  double gr = 0.0;
   if (LANE < NVT) {
     int i = LANE;
     double jtf = 0;
 #pragma unroll
     for (int g = 0; g < G; g++) jtf += sc[g * NVT + i];
-    double gr = c.Ma[i] - c.qfrc_smooth[i] - (c.sgl[i] + c.sgl[2 * NVT + i]) - jtf;
+    gr = c.Ma[i] - c.qfrc_smooth[i] - (c.sgl[i] + c.sgl[2 * NVT + i]) - jtf;
     c.grad[i] = gr;
     c.Mgrad[i] = gr;
   }
   SYNC();
+  return gr;
 }
 
 // ---- the worker waves' job on an iterate (elliptic models): the contacts' cone blocks ---------------------------------------
@@ -387,17 +409,20 @@ DEV void newton_assemble(Ctx &c, const double *hq, int hi, int hg, int j0, bool 
   }
   SYNC();
 }
-// Newton direction from qH (+ the workers' partials): Mgrad <- H^-1 grad
+// Newton direction from qH (+ the workers' partials): Mgrad <- H^-1 grad, search <- -Mgrad (written by the lane that holds the
+// entry, under the solve's closing SYNC)
 template <int NVT>
 DEV void newton_direction_np(Ctx &c, int np) {
+  const int tree = c.M->tree_ok && !c.cross;
   if (np > 0) {
     LDLExtra ex;
     ex.row = nullptr;
     ex.n = np;
 #pragma unroll
     for (int w = 0; w < 3; w++) ex.x[w] = CONE_PARTIAL(c, w < np ? w : 0);
-    newton_direction_sum<NVT>(c, ex);
-  } else newton_direction<NVT>(c);
+    chol_factor_solve_reg<NVT>(c.qH, c.Mgrad, NVP_OF(NVT), tree, &ex, c.search);
+  } else chol_factor_solve_reg<NVT>(c.qH, c.Mgrad, NVP_OF(NVT), tree, nullptr, c.search);
+  PROF(c, 17);
 }
 
 // One column group (nv > 32: the hand): lane i's Hessian block IS row i, the layout the register factorisation works in - the
@@ -414,7 +439,7 @@ DEV void newton_direction_rows(Ctx &c, const double *hq, int hi, bool hact, int 
   ex.n = np;
 #pragma unroll
   for (int w = 0; w < 3; w++) ex.x[w] = CONE_PARTIAL(c, w < np ? w : 0);
-  chol_factor_solve_reg<NVT>(c.qH, c.Mgrad, NVP_OF(NVT), c.M->tree_ok && !c.cross, &ex);
+  chol_factor_solve_reg<NVT>(c.qH, c.Mgrad, NVP_OF(NVT), c.M->tree_ok && !c.cross, &ex, c.search);
   PROF(c, 17);
 }
 
@@ -757,8 +782,6 @@ DEV void solve_constraints_reg_d(Ctx &c) {
   if constexpr (!ROWS) { newton_assemble<NVT>(c, hq, hi, hg, j0, hact); PROF(c, 19); }
   if (np) { job_wait(c, np); PROF(c, 16); }
   if constexpr (!ROWS) newton_direction_np<NVT>(c, np); else newton_direction_rows<NVT>(c, hq, hi, hact, np);
-  PFOR(i, nv) c.search[i] = -c.Mgrad[i];
-  SYNC();
   const double scale = 1.0 / (M.meaninertia * (nv > 1 ? nv : 1));
   for (int iter = 0; iter < M.iterations; iter++) {
     PROF(c, 13);
@@ -833,19 +856,15 @@ DEV void solve_constraints_reg_d(Ctx &c) {
       for (int k = 0; k < LS_RPL; k++) { if (k >= d.nslot) break; hblock_add_rows<NVT>(c, hq, chg_mask[k], NLANE * k, chg_w[k], hi, j0); }
     }
     PROF(c, 15);
-    newton_grad_reg<NVT>(c, hi, hg, hact);
+    const double gr = newton_grad_reg<NVT>(c, hi, hg, hact);
     PROF(c, 9);
     c.solver_iter++;
-    double pg = 0;
-    PFOR(i, nv) pg += c.grad[i] * c.grad[i];
-    const double gradient = scale * sqrt(wave_sum(pg));
+    const double gradient = scale * sqrt(wave_sum(mul_rn(gr, gr)));          // (the rounded square the read-back summed: no FMA with the tree's first add)
     const int done = stop || gradient < M.tolerance;
     if constexpr (!ROWS) { if (!done) { newton_assemble<NVT>(c, hq, hi, hg, j0, hact); PROF(c, 19); } }
     if (np) { job_wait(c, np); PROF(c, 16); }           // (also when the gradient says stop: no job is left behind unfinished)
     if (done) break;
     if constexpr (!ROWS) newton_direction_np<NVT>(c, np); else newton_direction_rows<NVT>(c, hq, hi, hact, np);
-    PFOR(i, nv) c.search[i] = -c.Mgrad[i];
-    SYNC();
   }
   if (LANE == 0) { c.misc[MISC_SUM_ITER] += c.solver_iter; if (c.ncon > c.misc[MISC_MAX_NCON]) c.misc[MISC_MAX_NCON] = c.ncon; if (c.nefc > c.misc[MISC_MAX_NEFC]) c.misc[MISC_MAX_NEFC] = c.nefc; }
   PFOR(i, nv) c.qfrc_constraint[i] = (c.Ma[i] - c.qfrc_smooth[i]) - c.grad[i];

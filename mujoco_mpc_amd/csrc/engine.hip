@@ -43,6 +43,7 @@
 #include "feedback_resample.h"
 #include "host.h"
 #include "devbuf.h"
+#include "carve.h"
 #include "../../include/mjpc_hip_debug.h"
 
 // ------------------------------------------------------------------------------ kernels
@@ -360,6 +361,8 @@ static void set_error(const std::string &s) { g_error = s; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return -2; } } while (0)
 // inside mjpc_hip_create only: `e` (when already allocated) and everything it owns are released on the error path
 #define HIPCHKP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(e_)); mjpc_hip_destroy(e); return nullptr; } } while (0)
+// layout L (carve.h) in buffer b of engine `e`: lay() once on a null base for the bytes to reserve, once on the buffer for the pointers
+#define PLACE(b, L, ...) do { Carve n_; lay(n_, L, __VA_ARGS__); HIPCHK(e->buf[b].reserve(n_.bytes())); Carve p_(e->buf[b].p); lay(p_, L, __VA_ARGS__); } while (0)
 
 // Every device and pinned buffer of an engine is a DevBuf (devbuf.h) in MjpcHipEngine::buf, named by this enum: mjpc_hip_destroy walks
 // the array, so a buffer added here cannot be forgotten there.  The seven per-candidate row arrays stand together, in the packed
@@ -394,6 +397,8 @@ struct MjpcHipEngine {
   KParams K;
   int max_local = 0, max_horizon = 0, P_max = 0;
   int nq = 0, nv = 0, nu = 0, nmocap = 0, nr = 0, ntr = 0, ds = 0, nuserdata = 0;
+  int na = 0, nd = 0;          // activations; tangent state 2 nv + na
+  Dims dims() const { return Dims{(size_t)nq, (size_t)nv, (size_t)na, (size_t)nu, (size_t)nr, (size_t)ds, (size_t)nd}; }   // for the layouts of carve.h
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int nbody = 0, nsite = 0;
@@ -592,6 +597,7 @@ MjpcHipEngine *mjpc_hip_create(const MjpcHipModel *model, const MjpcHipTask *tas
   e->max_local = max_local; e->max_horizon = max_horizon;
   e->nq = model->nq; e->nv = model->nv; e->nu = model->nu; e->nmocap = model->nmocap; e->nuserdata = model->nuserdata;
   e->nr = task->num_residual; e->ntr = 3 * task->num_trace; e->ds = model->nq + model->nv + model->na;
+  e->na = model->na; e->nd = 2 * model->nv + model->na;
   e->nbody = model->nbody; e->nsite = model->nsite;
   // flavour of the full-capacity launch, dense tier
   if (!pick_flavour(model, task, e->P_max, e->pm, &e->kernel, &e->cached, &e->spill, "mjpc_hip_create")) { mjpc_hip_destroy(e); return nullptr; }
@@ -835,7 +841,7 @@ int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, c
   if (!e || !in || !p) return bad("invalid argument");
   if (p->struct_size != (int)sizeof(MjpcHipFeedbackPolicy)) return bad("MjpcHipFeedbackPolicy.struct_size does not match this library");
   if (e->pending) return bad("the previous plan step has not been fetched (one plan in flight per engine)");
-  const int H = in->horizon, nl = in->num_trajectory - in->candidate_offset, nu = e->nu, ds = e->ds, nv = e->nv, nd = 2 * nv + (ds - e->nq - nv), T = p->T;
+  const int H = in->horizon, nl = in->num_trajectory - in->candidate_offset, nu = e->nu, ds = e->ds, nv = e->nv, nd = e->nd, T = p->T;
   if (nu < 1) return bad("the model has no actuators");
   if (H < 1 || H > e->max_horizon) return bad("horizon out of range");
   if (in->candidate_offset < 0 || nl < 1) return bad("candidate range out of bounds");
@@ -858,44 +864,44 @@ int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, c
     e->fb_kernel = k;
     e->fb_launch = e->spill ? mjpc_launch_fb_spill : e->cached ? mjpc_launch_fb_cached : mjpc_launch_fb_direct;
   }
-  // the call's device block: the policy [T], the steps [nl] and, in time mode, the resampled tables [H]
-  const size_t Tz = (size_t)T, Hz = (size_t)H, row = (size_t)ds + 2 * nu + (size_t)nu * nd;
+  // the call's device block (FbLay, carve.h)
+  const size_t Tz = (size_t)T;
   const bool timed = p->mode == MJPC_FEEDBACK_TIME;
   size_t need_pack = 2 + 2 * (size_t)nl;
   for (int k = 1; k < (e->summary_only ? 1 : NROWS); k++) need_pack += row_doubles(e, k, H, 0);
-  HIPCHK(e->buf[B_FBP].reserve(sizeof(double) * (Tz * (row + 1) + 2 * (size_t)nl + (timed ? Hz * row : 0) + 8)));
+  FbLay L;
+  PLACE(B_FBP, L, e->dims(), Tz, H, nl, timed);
   HIPCHK(reserve_knots(e, 1));
   HIPCHK(e->buf[B_PACK].reserve(sizeof(double) * need_pack));
   HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * need_pack));
-  double *d_times = e->at(B_FBP), *d_states = d_times + Tz, *d_actions = d_states + Tz * ds, *d_impr = d_actions + Tz * nu, *d_gain = d_impr + Tz * nu;
-  double *d_alpha = d_gain + Tz * nu * nd, *d_scale = d_alpha + nl, *d_tab = d_scale + nl;
+  double *d_impr = p->action_improvement ? L.improvement : nullptr;
   const Staging &s = e->hs;
   HIPCHK(stage(e, s.state, in->state, ds, B_STATE));
   if (e->nmocap) HIPCHK(stage(e, s.mocap, in->mocap, 7 * e->nmocap, B_MOCAP));
   if (e->nuserdata) HIPCHK(stage(e, s.userdata, in->userdata, e->nuserdata, B_USERDATA));
   HIPCHK(hipEventRecord(e->ev[0], e->stream));
   const size_t D = sizeof(double);
-  HIPCHK(hipMemcpyAsync(d_times, p->times, D * Tz, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_states, p->states, D * Tz * ds, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_actions, p->actions, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
-  if (p->action_improvement) HIPCHK(hipMemcpyAsync(d_impr, p->action_improvement, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_gain, p->feedback_gain, D * Tz * nu * nd, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_alpha, p->action_step + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_scale, p->feedback_scaling + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
-  const double *xbar = d_states, *ubar = d_actions, *kbar = p->action_improvement ? d_impr : nullptr, *Kbar = d_gain;
+  HIPCHK(hipMemcpyAsync(L.times, p->times, D * Tz, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.states, p->states, D * Tz * ds, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.actions, p->actions, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
+  if (d_impr) HIPCHK(hipMemcpyAsync(d_impr, p->action_improvement, D * Tz * nu, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.gain, p->feedback_gain, D * Tz * nu * nd, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.alpha, p->action_step + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.scale, p->feedback_scaling + in->candidate_offset, D * nl, hipMemcpyHostToDevice, e->stream));
+  const double *xbar = L.states, *ubar = L.actions, *kbar = d_impr, *Kbar = L.gain;
   e->fb_resampled = 0; e->fb_resample_us = 0;
   if (timed) {
     FbResampleArgs ra;
-    ra.times = d_times; ra.states = d_states; ra.actions = d_actions; ra.gains = d_gain; ra.improvement = p->action_improvement ? d_impr : nullptr;
+    ra.times = L.times; ra.states = L.states; ra.actions = L.actions; ra.gains = L.gain; ra.improvement = d_impr;
     ra.jnt_type = e->K.M.jnt_type; ra.jnt_qposadr = e->K.M.jnt_qposadr;
     ra.T = T; ra.H = H; ra.ds = ds; ra.nu = nu; ra.nd = nd; ra.njnt = e->K.M.njnt; ra.representation = p->representation;
     ra.time0 = in->time; ra.timestep = e->K.M.timestep;
-    ra.xbar = d_tab; ra.ubar = ra.xbar + Hz * ds; ra.kbar = ra.ubar + Hz * nu; ra.Kbar = ra.kbar + Hz * nu;
+    ra.xbar = L.xbar; ra.ubar = L.ubar; ra.kbar = L.kbar; ra.Kbar = L.Kbar;
     HIPCHK(hipEventRecord(e->ev_fb[0], e->stream));
     hipLaunchKernelGGL(fb_resample_kernel, dim3(H), dim3(256), 0, e->stream, ra);
     HIPCHK(hipEventRecord(e->ev_fb[1], e->stream));
     e->fb_resampled = 1;
-    xbar = ra.xbar; ubar = ra.ubar; kbar = p->action_improvement ? ra.kbar : nullptr; Kbar = ra.Kbar;
+    xbar = ra.xbar; ubar = ra.ubar; kbar = d_impr ? ra.kbar : nullptr; Kbar = ra.Kbar;
   }
   if (!p->use_feedback) xbar = nullptr;
   // a copy of the engine's parameters: no spline, no noise, no candidate table, no force noise, full capacity
@@ -905,7 +911,7 @@ int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, c
   K.P = 0; K.interp = 0; K.H = H; K.N = in->num_trajectory; K.offset = in->candidate_offset; K.nlocal = nl; K.use_device_noise = 0; K.nominal_index = 0;
   K.xfrc_std = 0; K.xfrc_rate = 0; K.retry = 0; K.tier = 0;
   HIPCHK(hipEventRecord(e->ev[1], e->stream));
-  e->fb_launch(e->fb_kernel, nl, e->lds_bytes, e->stream, &K, xbar, ubar, kbar, Kbar, d_alpha, d_scale);
+  e->fb_launch(e->fb_kernel, nl, e->lds_bytes, e->stream, &K, xbar, ubar, kbar, Kbar, L.alpha, L.scale);
   e->last_dense = 0;
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
   hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
@@ -999,12 +1005,13 @@ static int step_prepare(MjpcHipEngine *e, const char *who, const double *mocap, 
 
 // rows [0, rows) of the tables through the step kernel, at most max_local workgroups per launch (stream-ordered: a launch reuses
 // the row buffers, the slab and the CU's LDS of the one before it)
-static void step_rows(MjpcHipEngine *e, const KParams &K, size_t rows, const double *st, const double *ct, const double *tt, double *ns, double *rs, int *fl) {
+static void step_rows(MjpcHipEngine *e, const KParams &K, size_t rows, const StepTab &t) {
   // the task's late table (host.h): null without late rows, and the step kernel then has no late phase
   const int *late = e->pm.late_blocks ? e->at<int>(B_IB) + e->pm.late_i0 : nullptr;
   for (size_t r0 = 0; r0 < rows; r0 += (size_t)e->max_local) {
     const int nl = (int)(rows - r0 < (size_t)e->max_local ? rows - r0 : (size_t)e->max_local);
-    e->step_launch(e->step_kernel, nl, e->lds_bytes, e->stream, &K, st + r0 * e->ds, ct + r0 * e->nu, tt + r0, ns + r0 * e->ds, rs + r0 * e->nr, fl + r0, late);
+    e->step_launch(e->step_kernel, nl, e->lds_bytes, e->stream, &K, t.state + r0 * e->ds, t.ctrl + r0 * e->nu, t.time + r0, t.next + r0 * e->ds,
+                   t.residual + r0 * e->nr, t.fail + r0, late);
   }
 }
 
@@ -1022,18 +1029,16 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
   const size_t ds = e->ds, nu = e->nu, nr = e->nr;
   for (size_t p0 = 0; p0 < (size_t)n; p0 += STEP_PASS_ROWS) {
     const size_t R = (size_t)n - p0 < STEP_PASS_ROWS ? (size_t)n - p0 : STEP_PASS_ROWS;
-    const size_t nd_ = R * (2 * ds + nu + 1 + nr) + 8;
-    HIPCHK(e->buf[B_FD].reserve(nd_ * sizeof(double) + R * sizeof(int)));
-    double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
-    int *fl = (int *)(st + nd_);
-    HIPCHK(hipMemcpyAsync(st, states + p0 * ds, sizeof(double) * R * ds, hipMemcpyHostToDevice, e->stream));
-    if (nu) HIPCHK(hipMemcpyAsync(ct, ctrl + p0 * nu, sizeof(double) * R * nu, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(tt, time + p0, sizeof(double) * R, hipMemcpyHostToDevice, e->stream));
-    step_rows(e, K, R, st, ct, tt, ns, rs, fl);
+    StepTab t;
+    PLACE(B_FD, t, e->dims(), R);
+    HIPCHK(hipMemcpyAsync(t.state, states + p0 * ds, sizeof(double) * R * ds, hipMemcpyHostToDevice, e->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(t.ctrl, ctrl + p0 * nu, sizeof(double) * R * nu, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(t.time, time + p0, sizeof(double) * R, hipMemcpyHostToDevice, e->stream));
+    step_rows(e, K, R, t);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(next_states + p0 * ds, ns, sizeof(double) * R * ds, hipMemcpyDeviceToHost, e->stream));
-    if (nr) HIPCHK(hipMemcpyAsync(residual + p0 * nr, rs, sizeof(double) * R * nr, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(failure + p0, fl, sizeof(int) * R, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(next_states + p0 * ds, t.next, sizeof(double) * R * ds, hipMemcpyDeviceToHost, e->stream));
+    if (nr) HIPCHK(hipMemcpyAsync(residual + p0 * nr, t.residual, sizeof(double) * R * nr, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(failure + p0, t.fail, sizeof(int) * R, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   return 0;
@@ -1054,40 +1059,32 @@ static std::vector<int> fd_dofmap(const MjpcHipEngine *e) {
 }
 
 // one pass of mjpc_hip_transition_fd over the Tg knots from t0 on, everything stream-ordered and nothing downloaded: the nominal rows
-// go up, the table is assembled, stepped and differenced; the matrices and failure[] stay in B_FD where `a` points.  extra: doubles
-// the caller wants behind the pass's own (B_FD is reserved once, here), returned in *extra_out
-static int fd_pass(MjpcHipEngine *e, const KParams &K, const std::vector<int> &dofmap, size_t t0, size_t Tg, int term, const double *x, const double *u,
-                   const double *time, double eps, int centered, size_t extra, FdArgs *out, double **extra_out) {
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, na = ds - e->nq - e->nv, nd = 2 * nv + na;
-  const size_t E = centered ? 1 + 2 * (nd + nu) : 1 + nd + nu, R = Tg * E;
-  const size_t per_t = ds + nu + 1 + nd * nd + nd * nu + nr * nd + nr * nu;
-  const size_t nd_ = R * (2 * ds + nu + 1 + nr) + Tg * per_t + 8;
-  HIPCHK(e->buf[B_FD].reserve((nd_ + extra) * sizeof(double) + (R + Tg + 2 * nv + 2) * sizeof(int)));
-  double *st = e->at(B_FD), *ct = st + R * ds, *tt = ct + R * nu, *ns = tt + R, *rs = ns + R * ds;
-  double *dx = rs + R * nr, *du = dx + Tg * ds, *dt = du + Tg * nu, *dA = dt + Tg, *dB = dA + Tg * nd * nd, *dC = dB + Tg * nd * nu, *dD = dC + Tg * nr * nd;
-  int *fl = (int *)(st + nd_ + extra), *flT = fl + R, *dmap = flT + Tg;
-  HIPCHK(hipMemcpyAsync(dx, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
-  if (nu) HIPCHK(hipMemcpyAsync(du, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(dt, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(dmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+// go up, the table is assembled, stepped and differenced; the matrices and failure[] stay in B_FD where `a` points.  L: the pass's
+// layout, placed by the caller (alone, or inside the layout of a call that keeps more behind the pass's doubles)
+static int fd_pass(MjpcHipEngine *e, const KParams &K, const std::vector<int> &dofmap, const FdLay &L, size_t t0, size_t Tg, int term, const double *x,
+                   const double *u, const double *time, double eps, int centered, FdArgs *out) {
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, nd = e->nd, R = L.R;
+  HIPCHK(hipMemcpyAsync(L.x, x + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
+  if (nu) HIPCHK(hipMemcpyAsync(L.u, u + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.time, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(L.dofmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
   FdArgs a;
-  a.x = dx; a.u = du; a.time = dt; a.dofmap = dmap; a.ctrllimited = e->K.M.actuator_ctrllimited; a.ctrlrange = e->K.M.actuator_ctrlrange;
-  a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = (int)na; a.nu = e->nu; a.nr = e->nr; a.centered = centered; a.last_is_terminal = term;
+  a.x = L.x; a.u = L.u; a.time = L.time; a.dofmap = L.dofmap; a.ctrllimited = e->K.M.actuator_ctrllimited; a.ctrlrange = e->K.M.actuator_ctrlrange;
+  a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = e->na; a.nu = e->nu; a.nr = e->nr; a.centered = centered; a.last_is_terminal = term;
   a.eps = eps; a.cs = cos(0.5 * eps); a.sn = sin(0.5 * eps);
-  a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = ns; a.residual = rs; a.fail = fl;
-  a.A = dA; a.B = dB; a.C = dC; a.D = dD; a.failure = flT;
+  a.state_tab = L.t.state; a.ctrl_tab = L.t.ctrl; a.time_tab = L.t.time; a.next_state = L.t.next; a.residual = L.t.residual; a.fail = L.t.fail;
+  a.A = L.A; a.B = L.B; a.C = L.C; a.D = L.D; a.failure = L.failure;
   hipLaunchKernelGGL(fd_assemble_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a, (unsigned)R);
-  step_rows(e, K, R, st, ct, tt, ns, rs, fl);
+  step_rows(e, K, R, L.t);
   hipLaunchKernelGGL(fd_difference_kernel, dim3((unsigned)((nd + nu + FD_TILE - 1) / FD_TILE), (unsigned)((nd + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tg),
                      dim3(FD_TILE * FD_TILE), 0, e->stream, a);
   HIPCHK(hipGetLastError());
   *out = a;
-  if (extra_out) *extra_out = st + nd_;
   return 0;
 }
 // knots of one pass: its table stays below STEP_PASS_ROWS rows
 static size_t fd_pass_knots(const MjpcHipEngine *e, int centered) {
-  const size_t nc = 2 * (size_t)e->nv + (e->ds - e->nq - e->nv) + e->nu, E = centered ? 1 + 2 * nc : 1 + nc;
+  const size_t E = fd_rows_per_knot(e->dims(), centered);
   return STEP_PASS_ROWS / E < 1 ? 1 : STEP_PASS_ROWS / E;
 }
 
@@ -1102,14 +1099,16 @@ int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const doubl
   int rc = step_prepare(e, "mjpc_hip_transition_fd", mocap, userdata, &K);
   if (rc != 0) return rc;
   centered = centered ? 1 : 0; last_is_terminal = last_is_terminal ? 1 : 0;
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, na = ds - e->nq - e->nv, nd = 2 * nv + na;
+  const size_t nu = e->nu, nr = e->nr, nd = e->nd;
   const std::vector<int> dofmap = fd_dofmap(e);
   const size_t Tg_max = fd_pass_knots(e, centered);
   for (size_t t0 = 0; t0 < (size_t)T; t0 += Tg_max) {
     const size_t Tg = (size_t)T - t0 < Tg_max ? (size_t)T - t0 : Tg_max;
     const int term = last_is_terminal && t0 + Tg == (size_t)T;
+    FdLay L;
+    PLACE(B_FD, L, e->dims(), Tg, centered);
     FdArgs a;
-    rc = fd_pass(e, K, dofmap, t0, Tg, term, x, u, time, eps, centered, 0, &a, nullptr);
+    rc = fd_pass(e, K, dofmap, L, t0, Tg, term, x, u, time, eps, centered, &a);
     if (rc != 0) return rc;
     const size_t Tw = Tg - (term ? 1 : 0);            // a terminal knot's A / B / D blocks stay the caller's
     if (Tw && nd) HIPCHK(hipMemcpyAsync(A + t0 * nd * nd, a.A, sizeof(double) * Tw * nd * nd, hipMemcpyDeviceToHost, e->stream));
@@ -1153,54 +1152,48 @@ int mjpc_hip_unscented_moments(MjpcHipEngine *e, const double *state, const doub
   KParams K;
   int rc = step_prepare(e, "mjpc_hip_unscented_moments", mocap, userdata, &K);
   if (rc != 0) return rc;
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv, nq = e->nq, na = ds - nq - nv, nd = 2 * nv + na, nsz = (size_t)ns, R = 2 * nd + 1;
-  // B_FD, in doubles.  One block goes up, one comes back:
-  //   up    x [ds] | L [nd][nd] | u [nu] | noise_process [nd] | noise_sensor [ns] | dofmap, qmap (ints, two to a double)
-  //   tables the kernels write and read: state, ctrl, time rows | residual rows | difference table | the rows' warning bits (ints)
-  //   back  next-state rows [R][ds] (only when the caller asks for them) | state_mean | sensor_mean | ss | sy | yy | failure (an int)
-  const size_t n_map = 2 * nv + 2 + 2 * nq + 2, n_in = ds + nd * nd + nu + nd + nsz + (n_map + 1) / 2;
-  const size_t n_mom = ds + nsz + nd * nd + nd * nsz + nsz * nsz + 1, n_back = R * ds + n_mom;
-  const size_t n_tab = R * (ds + nu + 1) + R * nr + R * (nd + nsz) + (R + 1) / 2;
-  HIPCHK(e->buf[B_FD].reserve((n_in + n_tab + n_back + 8) * sizeof(double)));
-  HIPCHK(e->buf[H_PACK].reserve((n_in + n_back) * sizeof(double)));
-  double *h = e->at(H_PACK), *hp = h;
-  memcpy(hp, state, sizeof(double) * ds); hp += ds;
-  memcpy(hp, factor, sizeof(double) * nd * nd); hp += nd * nd;
-  if (nu) memcpy(hp, ctrl, sizeof(double) * nu);
-  hp += nu;
-  memcpy(hp, noise_process, sizeof(double) * nd); hp += nd;
-  memcpy(hp, noise_sensor, sizeof(double) * nsz); hp += nsz;
+  const size_t ds = e->ds, nu = e->nu, nv = e->nv, nq = e->nq, nd = e->nd, nsz = (size_t)ns, R = 2 * nd + 1, D = sizeof(double);
+  // B_FD: the block that goes up, the tables the kernels write and read, the block that comes back (UkfLay, carve.h); H_PACK mirrors
+  // the two blocks that travel
+  UkfLay L;
+  UkfHost h;
+  PLACE(B_FD, L, e->dims(), nsz);
+  PLACE(H_PACK, h, e->dims(), nsz);
+  memcpy(h.in.x, state, D * ds);
+  memcpy(h.in.L, factor, D * nd * nd);
+  if (nu) memcpy(h.in.u, ctrl, D * nu);
+  memcpy(h.in.noise_process, noise_process, D * nd);
+  memcpy(h.in.noise_sensor, noise_sensor, D * nsz);
   const std::vector<int> dofmap = fd_dofmap(e), qmap = ukf_qmap(e);
-  memcpy(hp, dofmap.data(), sizeof(int) * (2 * nv + 2));
-  memcpy((int *)hp + 2 * nv + 2, qmap.data(), sizeof(int) * (2 * nq + 2));
-  double *d_in = e->at(B_FD);
-  HIPCHK(hipMemcpyAsync(d_in, h, sizeof(double) * n_in, hipMemcpyHostToDevice, e->stream));
+  memcpy(h.in.dofmap, dofmap.data(), sizeof(int) * (2 * nv + 2));
+  memcpy(h.in.qmap, qmap.data(), sizeof(int) * (2 * nq + 2));
+  // each block travels in one copy: the mirror's second begins where its first ends; the moments are the second without the rows
+  const size_t in_bytes = (char *)h.back.next - (char *)h.in.x, mom_bytes = (char *)h.back.end - (char *)h.back.state_mean;
+  HIPCHK(hipMemcpyAsync(L.in.x, h.in.x, in_bytes, hipMemcpyHostToDevice, e->stream));
   UkfArgs a;
-  a.x = d_in; a.L = a.x + ds; a.u = a.L + nd * nd; a.noise_process = a.u + nu; a.noise_sensor = a.noise_process + nd;
-  a.dofmap = (const int *)(a.noise_sensor + nsz); a.qmap = a.dofmap + 2 * nv + 2;
-  a.nq = (int)nq; a.nv = (int)nv; a.na = (int)na; a.nu = (int)nu; a.nr = (int)nr; a.ns = ns; a.first = sensor_first_row;
+  a.x = L.in.x; a.L = L.in.L; a.u = L.in.u; a.noise_process = L.in.noise_process; a.noise_sensor = L.in.noise_sensor;
+  a.dofmap = L.in.dofmap; a.qmap = L.in.qmap;
+  a.nq = e->nq; a.nv = e->nv; a.na = e->na; a.nu = e->nu; a.nr = e->nr; a.ns = ns; a.first = sensor_first_row;
   a.sigma_step = sigma_step; a.time = time; a.w_mean0 = weights[0]; a.w_cov0 = weights[1]; a.w_sigma = weights[2];
-  double *st = d_in + n_in, *ct = st + R * ds, *tt = ct + R * nu, *rs = tt + R, *df = rs + R * nr;
-  int *fl = (int *)(df + R * (nd + nsz));
-  double *nx = d_in + n_in + n_tab, *mom = nx + R * ds;
-  a.state_tab = st; a.ctrl_tab = ct; a.time_tab = tt; a.next_state = nx; a.residual = rs; a.fail = fl; a.diff = df;
-  a.state_mean = mom; a.sensor_mean = a.state_mean + ds; a.cov_ss = a.sensor_mean + nsz; a.cov_sy = a.cov_ss + nd * nd; a.cov_yy = a.cov_sy + nd * nsz;
-  a.failure = (int *)(a.cov_yy + nsz * nsz);
+  a.state_tab = L.t.state; a.ctrl_tab = L.t.ctrl; a.time_tab = L.t.time; a.next_state = L.t.next; a.residual = L.t.residual; a.fail = L.t.fail; a.diff = L.diff;
+  a.state_mean = L.back.state_mean; a.sensor_mean = L.back.sensor_mean; a.cov_ss = L.back.cov_ss; a.cov_sy = L.back.cov_sy; a.cov_yy = L.back.cov_yy;
+  a.failure = L.back.failure;
   hipLaunchKernelGGL(ukf_sigma_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, a);
-  step_rows(e, K, R, st, ct, tt, nx, rs, fl);
+  step_rows(e, K, R, L.t);
   hipLaunchKernelGGL(ukf_mean_kernel, dim3(1), dim3(256), 0, e->stream, a);
   const unsigned tiles = (unsigned)((nd + nsz + UKF_TILE - 1) / UKF_TILE);
   hipLaunchKernelGGL(ukf_cov_kernel, dim3(tiles, tiles), dim3(UKF_TILE * UKF_TILE), 0, e->stream, a);
   HIPCHK(hipGetLastError());
-  double *hb = h + n_in;
-  if (sigma_next) HIPCHK(hipMemcpyAsync(hb, nx, sizeof(double) * n_back, hipMemcpyDeviceToHost, e->stream));
-  else HIPCHK(hipMemcpyAsync(hb + R * ds, mom, sizeof(double) * n_mom, hipMemcpyDeviceToHost, e->stream));
+  if (sigma_next) HIPCHK(hipMemcpyAsync(h.back.next, L.back.next, D * R * ds + mom_bytes, hipMemcpyDeviceToHost, e->stream));
+  else HIPCHK(hipMemcpyAsync(h.back.state_mean, L.back.state_mean, mom_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (sigma_next) memcpy(sigma_next, hb, sizeof(double) * R * ds);
-  hb += R * ds;
-  const struct { double *dst; size_t n; } outs[] = {{state_mean, ds}, {sensor_mean, nsz}, {cov_ss, nd * nd}, {cov_sy, nd * nsz}, {cov_yy, nsz * nsz}};
-  for (const auto &o : outs) { memcpy(o.dst, hb, sizeof(double) * o.n); hb += o.n; }
-  memcpy(failure, hb, sizeof(int));
+  if (sigma_next) memcpy(sigma_next, h.back.next, D * R * ds);
+  memcpy(state_mean, h.back.state_mean, D * ds);
+  memcpy(sensor_mean, h.back.sensor_mean, D * nsz);
+  memcpy(cov_ss, h.back.cov_ss, D * nd * nd);
+  memcpy(cov_sy, h.back.cov_sy, D * nd * nsz);
+  memcpy(cov_yy, h.back.cov_yy, D * nsz * nsz);
+  memcpy(failure, h.back.failure, sizeof(int));
   return 0;
 }
 
@@ -1212,10 +1205,12 @@ int mjpc_hip_linearize_step(MjpcHipEngine *e, const double *state, const double 
   KParams K;
   int rc = step_prepare(e, "mjpc_hip_linearize_step", mocap, userdata, &K);
   if (rc != 0) return rc;
-  const size_t ds = e->ds, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv);
+  const size_t ds = e->ds, nr = e->nr, nd = e->nd;
   const std::vector<int> dofmap = fd_dofmap(e);
+  FdLay L;
+  PLACE(B_FD, L, e->dims(), 1, centered ? 1 : 0);
   FdArgs a;
-  rc = fd_pass(e, K, dofmap, 0, 1, 0, state, ctrl, &time, eps, centered ? 1 : 0, 0, &a, nullptr);
+  rc = fd_pass(e, K, dofmap, L, 0, 1, 0, state, ctrl, &time, eps, centered ? 1 : 0, &a);
   if (rc != 0) return rc;
   // the base row (slot 0) of the table is the step from `state` itself
   if (next_state) HIPCHK(hipMemcpyAsync(next_state, a.next_state, sizeof(double) * ds, hipMemcpyDeviceToHost, e->stream));
@@ -1228,7 +1223,15 @@ int mjpc_hip_linearize_step(MjpcHipEngine *e, const double *state, const double 
 }
 
 // ------------------------------------------------------------------------------ cost derivatives, trajectory gradient
-// the cost-derivative kernel over T knots whose inputs and outputs are on the device already (a.residual .. a.cxu set by the caller)
+// the cost-derivative kernel's arguments over T knots whose inputs and outputs are on the device already
+static CdArgs cd_args(const MjpcHipEngine *e, const double *residual, const double *C, const double *D, const CdOut &o, int T, int last_is_terminal, int hessians) {
+  CdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.residual = residual; a.C = C; a.D = D; a.T = T; a.nd = e->nd; a.nu = e->nu; a.nr = e->nr; a.last_is_terminal = last_is_terminal; a.hessians = hessians;
+  a.cr = o.cr; a.cx = o.cx; a.cu = o.cu; a.cxx = o.cxx; a.cuu = o.cuu; a.cxu = o.cxu;
+  return a;
+}
+// the kernel itself (the engine's cost table goes into `a` here)
 static int cd_launch(MjpcHipEngine *e, CdArgs a, const char *who) {
   const DevTask &tk = e->K.M.task;
   a.dim_norm_residual = tk.dim_norm_residual; a.norm = tk.norm; a.num_norm_parameter = tk.num_norm_parameter;
@@ -1247,32 +1250,29 @@ int mjpc_hip_cost_derivatives(MjpcHipEngine *e, int T, const double *residual, c
   if (T < 1) { set_error("mjpc_hip_cost_derivatives: T < 1"); return -1; }
   if (e->pending) { set_error("mjpc_hip_cost_derivatives: a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
   last_is_terminal = last_is_terminal ? 1 : 0; hessians = hessians ? 1 : 0;
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv);
-  const size_t Td = (size_t)T - last_is_terminal;          // knots that have a D
+  const size_t nu = e->nu, nr = e->nr, nd = e->nd, Tz = (size_t)T;
+  const size_t Td = Tz - last_is_terminal;          // knots that have a D
   if ((nr && !residual) || (nr * nd && !C) || (nr * nu * Td && !D)) { set_error("mjpc_hip_cost_derivatives: null input"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  const size_t n_in = (size_t)T * (nr + nr * nd + nr * nu), n_g = (size_t)T * (nr + nd + nu), n_h = hessians ? (size_t)T * (nd * nd + nu * nu + nd * nu) : 0;
-  HIPCHK(e->buf[B_FD].reserve((n_in + n_g + n_h + 8) * sizeof(double)));
-  double *dr = e->at(B_FD), *dC = dr + (size_t)T * nr, *dD = dC + (size_t)T * nr * nd, *o = dD + (size_t)T * nr * nu;
-  CdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.residual = dr; a.C = dC; a.D = dD; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = last_is_terminal; a.hessians = hessians;
-  a.cr = o; a.cx = a.cr + (size_t)T * nr; a.cu = a.cx + (size_t)T * nd;
-  if (hessians) { a.cxx = a.cu + (size_t)T * nu; a.cuu = a.cxx + (size_t)T * nd * nd; a.cxu = a.cuu + (size_t)T * nu * nu; }
-  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * T * nr, hipMemcpyHostToDevice, e->stream));
-  if (nr * nd) HIPCHK(hipMemcpyAsync(dC, C, sizeof(double) * T * nr * nd, hipMemcpyHostToDevice, e->stream));
-  if (nr * nu * Td) HIPCHK(hipMemcpyAsync(dD, D, sizeof(double) * Td * nr * nu, hipMemcpyHostToDevice, e->stream));
+  CdLay L;
+  PLACE(B_FD, L, e->dims(), Tz, hessians);
+  CdArgs a = cd_args(e, L.residual, L.C, L.D, L.out, T, last_is_terminal, hessians);
+  if (nr) HIPCHK(hipMemcpyAsync(L.residual, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
+  if (nr * nd) HIPCHK(hipMemcpyAsync(L.C, C, sizeof(double) * Tz * nr * nd, hipMemcpyHostToDevice, e->stream));
+  if (nr * nu * Td) HIPCHK(hipMemcpyAsync(L.D, D, sizeof(double) * Td * nr * nu, hipMemcpyHostToDevice, e->stream));
   int rc = cd_launch(e, a, "mjpc_hip_cost_derivatives");
   if (rc != 0) return rc;
   HIPCHK(hipGetLastError());
-  const struct { double *dst; const double *src; size_t n; } outs[] = {
-    {cr, a.cr, (size_t)T * nr}, {cx, a.cx, (size_t)T * nd}, {cu, a.cu, (size_t)T * nu},
-    {cxx, a.cxx, (size_t)T * nd * nd}, {cuu, a.cuu, (size_t)T * nu * nu}, {cxu, a.cxu, (size_t)T * nd * nu}};
-  for (int k = 0; k < (hessians ? 6 : 3); k++)
-    if (outs[k].dst && outs[k].n) HIPCHK(hipMemcpyAsync(outs[k].dst, outs[k].src, sizeof(double) * outs[k].n, hipMemcpyDeviceToHost, e->stream));
+  // (without Hessians their fields are null, and nothing comes back for them)
+  auto down = [&](double *dst, const double *src, size_t n) { return dst && src && n ? hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
+  HIPCHK(down(cr, L.out.cr, Tz * nr)); HIPCHK(down(cx, L.out.cx, Tz * nd)); HIPCHK(down(cu, L.out.cu, Tz * nu));
+  HIPCHK(down(cxx, L.out.cxx, Tz * nd * nd)); HIPCHK(down(cuu, L.out.cuu, Tz * nu * nu)); HIPCHK(down(cxu, L.out.cxu, Tz * nd * nu));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
+
+// hand-out of one field of a pinned mirror to the caller's array (which may be null)
+static void give(double *dst, const double *src, size_t n) { if (dst && n) memcpy(dst, src, sizeof(double) * n); }
 
 int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *residual, const double *mocap,
                                  const double *userdata, double eps, int centered, double *k, double *Vx, double *Qx, double *Qu, double *dV, int *failure) {
@@ -1285,88 +1285,69 @@ int mjpc_hip_trajectory_gradient(MjpcHipEngine *e, int T, const double *x, const
   KParams K;
   int rc = step_prepare(e, "mjpc_hip_trajectory_gradient", mocap, userdata, &K);
   if (rc != 0) return rc;
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv), Tz = (size_t)T;
-  // behind the pass's tables: the residual rows, cr / cx / cu, and the block that goes back in one copy:
-  //   k [T][nu] | Vx [T][nd] | Qx [T-1][nd] | Qu [T-1][nu] | dV [2] | failure [T] (ints, two to a double)
-  const size_t n_out = Tz * nu + Tz * nd + (Tz - 1) * nd + (Tz - 1) * nu + 2, n_fail = (Tz + 1) / 2;
-  const size_t extra = Tz * (2 * nr + nd + nu) + n_out + n_fail;
-  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * (n_out + n_fail)));
-  FdArgs f;
-  double *x0 = nullptr;
+  const size_t nu = e->nu, nr = e->nr, nd = e->nd, Tz = (size_t)T;
+  // B_FD: behind the pass's doubles the residual rows, cr / cx / cu and the block that goes back in one copy (GradLay, carve.h)
+  GradLay L;
+  GradOut h;
+  PLACE(H_PACK, h, e->dims(), Tz);
   const std::vector<int> dofmap = fd_dofmap(e);          // (outlives the stream's copy of it)
-  rc = fd_pass(e, K, dofmap, 0, Tz, 1, x, u, time, eps, centered, extra, &f, &x0);
+  PLACE(B_FD, L, e->dims(), Tz, centered);
+  FdArgs f;
+  rc = fd_pass(e, K, dofmap, L.fd, 0, Tz, 1, x, u, time, eps, centered, &f);
   if (rc != 0) return rc;
-  double *dr = x0, *dcr = dr + Tz * nr, *dcx = dcr + Tz * nr, *dcu = dcx + Tz * nd, *ob = dcu + Tz * nu;
-  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
-  CdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.residual = dr; a.C = f.C; a.D = f.D; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = 1; a.hessians = 0;
-  a.cr = dcr; a.cx = dcx; a.cu = dcu;
-  rc = cd_launch(e, a, "mjpc_hip_trajectory_gradient");
+  if (nr) HIPCHK(hipMemcpyAsync(L.residual, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
+  rc = cd_launch(e, cd_args(e, L.residual, f.C, f.D, L.cd, T, 1, 0), "mjpc_hip_trajectory_gradient");
   if (rc != 0) return rc;
   GdArgs g;
-  g.A = f.A; g.B = f.B; g.cx = dcx; g.cu = dcu; g.T = T; g.nd = (int)nd; g.nu = (int)nu;
-  g.k = ob; g.Vx = g.k + Tz * nu; g.Qx = g.Vx + Tz * nd; g.Qu = g.Qx + (Tz - 1) * nd; g.dV = g.Qu + (Tz - 1) * nu;
+  g.A = f.A; g.B = f.B; g.cx = L.cd.cx; g.cu = L.cd.cu; g.T = T; g.nd = (int)nd; g.nu = (int)nu;
+  g.k = L.out.k; g.Vx = L.out.Vx; g.Qx = L.out.Qx; g.Qu = L.out.Qu; g.dV = L.out.dV;
   const size_t gd_lds = sizeof(double) * (2 * (nd + nu) + (nd * (nd + nu) <= (size_t)GD_THREADS * GD_R ? nd * (nd + nu) : 0));
   if (gd_lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)gd_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gd_lds));
   hipLaunchKernelGGL(gd_backward_kernel, dim3(1), dim3(GD_THREADS), gd_lds, e->stream, g);
   HIPCHK(hipGetLastError());
-  int *dfail = (int *)(ob + n_out);
-  HIPCHK(hipMemcpyAsync(dfail, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
-  double *h = e->at(H_PACK);
-  HIPCHK(hipMemcpyAsync(h, ob, sizeof(double) * (n_out + n_fail), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(L.out.failure, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(h.k, L.out.k, (char *)h.end - (char *)h.k, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  const struct { double *dst; size_t n; } outs[] = {{k, Tz * nu}, {Vx, Tz * nd}, {Qx, (Tz - 1) * nd}, {Qu, (Tz - 1) * nu}, {dV, 2}};
-  for (const auto &o : outs) { if (o.dst && o.n) memcpy(o.dst, h, sizeof(double) * o.n); h += o.n; }
-  memcpy(failure, h, sizeof(int) * Tz);
+  give(k, h.k, Tz * nu); give(Vx, h.Vx, Tz * nd); give(Qx, h.Qx, (Tz - 1) * nd); give(Qu, h.Qu, (Tz - 1) * nu); give(dV, h.dV, 2);
+  memcpy(failure, h.failure, sizeof(int) * Tz);
   return 0;
 }
 
 // ------------------------------------------------------------------------------ iLQG backward pass
-// the block that comes back in one copy (doubles): k [T][nu] | K [T][nu][nd] | Vx [T][nd] | Vxx [T][nd][nd] | Qx | Qu | Qxx | Qxu | Quu
-// ([T-1] each) | dV [2] | regularization, rate [2] | status [3] (ints, in two doubles)
-static size_t rc_out_doubles(size_t T, size_t n, size_t m) {
-  return T * (m + m * n + n + n * n) + (T - 1) * (n + m + n * n + n * m + m * m) + 6;
-}
-static void rc_point(RcArgs &g, double *ob, size_t T, size_t n, size_t m) {
-  g.k = ob; g.K = g.k + T * m; g.Vx = g.K + T * m * n; g.Vxx = g.Vx + T * n;
-  g.Qx = g.Vxx + T * n * n; g.Qu = g.Qx + (T - 1) * n; g.Qxx = g.Qu + (T - 1) * m; g.Qxu = g.Qxx + (T - 1) * n * n; g.Quu = g.Qxu + (T - 1) * n * m;
-  g.dV = g.Quu + (T - 1) * m * m; g.reg = g.dV + 2; g.status = (int *)(g.reg + 2);
-}
 static int rc_settings(RcArgs &g, const MjpcHipRiccatiSettings *s, const char *who) {
   if (!s || s->struct_size != (int)sizeof(MjpcHipRiccatiSettings)) { set_error(std::string(who) + ": MjpcHipRiccatiSettings.struct_size does not match this library"); return -1; }
   g.reg_type = s->regularization_type; g.action_limits = s->action_limits ? 1 : 0; g.max_iter = s->max_regularization_iterations;
   g.reg_min = s->min_regularization; g.reg_max = s->max_regularization; g.reg_factor = s->regularization_factor;
   return 0;
 }
-// zero the outputs, hand in the regularisation, run the kernel, bring the block back (pinned) and hand it out.  ob: the block on the
-// device (rc_out_doubles + tail doubles the caller copies back with it); scratch: RC_WORK_DOUBLES behind it when the image is not in LDS
-static int rc_run(MjpcHipEngine *e, RcArgs g, double *ob, size_t tail, double *scratch, double *regularization, double *rate, double **host_tail) {
-  const size_t T = g.T, n = g.nd, m = g.nu, n_out = rc_out_doubles(T, n, m);
-  HIPCHK(e->buf[H_PACK].reserve(sizeof(double) * (n_out + tail)));
-  rc_point(g, ob, T, n, m);
+// doubles of rc_backward_kernel's work image where it has to lie in global memory, 0 where it fits the workgroup's LDS
+static size_t rc_work_doubles(size_t n, size_t m) { return RC_WORK_DOUBLES(n, m) * sizeof(double) <= RC_LDS_LIMIT ? 0 : RC_WORK_DOUBLES(n, m); }
+// zero the outputs, hand in the regularisation, run the kernel, bring the block back and hand it out.  o: the block on the device (the
+// nfail failure ints behind it are the caller's and come back with it, into failure[]); scratch: the work image when it is not in LDS
+static int rc_run(MjpcHipEngine *e, RcArgs g, const RcOut &o, size_t nfail, double *scratch, double *regularization, double *rate, double *k, double *K,
+                  double *Vx, double *Vxx, double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status, int *failure) {
+  const size_t T = g.T, n = g.nd, m = g.nu;
+  RcOut h;
+  PLACE(H_PACK, h, T, n, m, nfail);
+  g.k = o.k; g.K = o.K; g.Vx = o.Vx; g.Vxx = o.Vxx; g.Qx = o.Qx; g.Qu = o.Qu; g.Qxx = o.Qxx; g.Qxu = o.Qxu; g.Quu = o.Quu; g.dV = o.dV; g.reg = o.reg;
+  g.status = o.status;
   g.scratch = scratch;
-  double *h = e->at(H_PACK);
-  h[0] = *regularization; h[1] = *rate;
-  HIPCHK(hipMemsetAsync(ob, 0, sizeof(double) * n_out, e->stream));
-  HIPCHK(hipMemcpyAsync(g.reg, h, sizeof(double) * 2, hipMemcpyHostToDevice, e->stream));
-  const bool fits = RC_WORK_DOUBLES(n, m) * sizeof(double) <= RC_LDS_LIMIT;
-  const size_t lds = fits ? RC_WORK_DOUBLES(n, m) * sizeof(double) : 0;
+  h.reg[0] = *regularization; h.reg[1] = *rate;          // (staged in the mirror's own field: the block overwrites it on its way back)
+  HIPCHK(hipMemsetAsync(o.k, 0, (char *)o.tail - (char *)o.k, e->stream));
+  HIPCHK(hipMemcpyAsync(o.reg, h.reg, sizeof(double) * 2, hipMemcpyHostToDevice, e->stream));
+  const size_t lds = rc_work_doubles(n, m) ? 0 : RC_WORK_DOUBLES(n, m) * sizeof(double);
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)rc_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(rc_backward_kernel, dim3(1), dim3(RC_THREADS), lds, e->stream, g);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h, ob, sizeof(double) * (n_out + tail), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(h.k, o.k, (char *)o.end - (char *)o.k, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  *host_tail = h + n_out;
+  give(k, h.k, T * m); give(K, h.K, T * m * n); give(Vx, h.Vx, T * n); give(Vxx, h.Vxx, T * n * n);
+  give(Qx, h.Qx, (T - 1) * n); give(Qu, h.Qu, (T - 1) * m); give(Qxx, h.Qxx, (T - 1) * n * n); give(Qxu, h.Qxu, (T - 1) * n * m);
+  give(Quu, h.Quu, (T - 1) * m * m); give(dV, h.dV, 2);
+  *regularization = h.reg[0]; *rate = h.reg[1];
+  if (status) memcpy(status, h.status, sizeof(int) * 3);
+  if (nfail) memcpy(failure, h.failure, sizeof(int) * nfail);
   return 0;
-}
-static void rc_hand_out(const double *h, size_t T, size_t n, size_t m, double *regularization, double *rate, double *k, double *K, double *Vx, double *Vxx,
-                        double *Qx, double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status) {
-  const struct { double *dst; size_t n; } outs[] = {{k, T * m}, {K, T * m * n}, {Vx, T * n}, {Vxx, T * n * n}, {Qx, (T - 1) * n}, {Qu, (T - 1) * m},
-                                                    {Qxx, (T - 1) * n * n}, {Qxu, (T - 1) * n * m}, {Quu, (T - 1) * m * m}, {dV, 2}};
-  for (const auto &o : outs) { if (o.dst && o.n) memcpy(o.dst, h, sizeof(double) * o.n); h += o.n; }
-  *regularization = h[0]; *rate = h[1];
-  if (status) memcpy(status, h + 2, sizeof(int) * 3);
 }
 
 int mjpc_hip_ilqg_backward_pass(MjpcHipEngine *e, int T, int nd, int nu, const double *A, const double *B, const double *cx, const double *cu,
@@ -1384,27 +1365,16 @@ int mjpc_hip_ilqg_backward_pass(MjpcHipEngine *e, int T, int nd, int nu, const d
   if (!A || !B || !cx || !cu || !cxx || !cxu || !cuu || !regularization || !regularization_rate || (g.action_limits && (!actions || !action_limits))) {
     set_error(std::string(who) + ": null input"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  const size_t Tz = T, n = nd, m = nu, nn = n * n, nm = n * m, mm = m * m;
-  const size_t cnt[9] = {(Tz - 1) * nn, (Tz - 1) * nm, Tz * n, (Tz - 1) * m, Tz * nn, (Tz - 1) * nm, (Tz - 1) * mm, g.action_limits ? (Tz - 1) * m : 0, g.action_limits ? 2 * m : 0};
-  const double *src[9] = {A, B, cx, cu, cxx, cxu, cuu, actions, action_limits};
-  size_t n_in = 0;
-  for (size_t c : cnt) n_in += c;
-  const bool fits = RC_WORK_DOUBLES(n, m) * sizeof(double) <= RC_LDS_LIMIT;
-  HIPCHK(e->buf[B_FD].reserve((n_in + rc_out_doubles(Tz, n, m) + (fits ? 0 : RC_WORK_DOUBLES(n, m)) + 8) * sizeof(double)));
-  double *d = e->at(B_FD);
-  const double *dev[9];
-  for (int i = 0; i < 9; i++) {
-    dev[i] = d;
-    if (cnt[i]) HIPCHK(hipMemcpyAsync(d, src[i], sizeof(double) * cnt[i], hipMemcpyHostToDevice, e->stream));
-    d += cnt[i];
-  }
-  g.A = dev[0]; g.B = dev[1]; g.cx = dev[2]; g.cu = dev[3]; g.cxx = dev[4]; g.cxu = dev[5]; g.cuu = dev[6]; g.actions = dev[7]; g.limits = dev[8];
+  const size_t Tz = T, n = nd, m = nu;
+  RcLay L;
+  PLACE(B_FD, L, Tz, n, m, g.action_limits, rc_work_doubles(n, m));
+  auto up = [&](double *dst, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  HIPCHK(up(L.A, A, (Tz - 1) * n * n)); HIPCHK(up(L.B, B, (Tz - 1) * n * m)); HIPCHK(up(L.cx, cx, Tz * n)); HIPCHK(up(L.cu, cu, (Tz - 1) * m));
+  HIPCHK(up(L.cxx, cxx, Tz * n * n)); HIPCHK(up(L.cxu, cxu, (Tz - 1) * n * m)); HIPCHK(up(L.cuu, cuu, (Tz - 1) * m * m));
+  if (g.action_limits) { HIPCHK(up(L.actions, actions, (Tz - 1) * m)); HIPCHK(up(L.limits, action_limits, 2 * m)); }
+  g.A = L.A; g.B = L.B; g.cx = L.cx; g.cu = L.cu; g.cxx = L.cxx; g.cxu = L.cxu; g.cuu = L.cuu; g.actions = L.actions; g.limits = L.limits;
   g.T = T; g.nd = nd; g.nu = nu;
-  double *ht = nullptr;
-  const int rc = rc_run(e, g, d, 0, d + rc_out_doubles(Tz, n, m), regularization, regularization_rate, &ht);
-  if (rc != 0) return rc;
-  rc_hand_out(e->at(H_PACK), Tz, n, m, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status);
-  return 0;
+  return rc_run(e, g, L.out, 0, L.scratch, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status, nullptr);
 }
 
 int mjpc_hip_riccati_layout_bytes(int nd, int nu, int *in_lds) {
@@ -1432,24 +1402,15 @@ int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const dou
   KParams K_;
   int rc = step_prepare(e, who, mocap, userdata, &K_);
   if (rc != 0) return rc;
-  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nd = 2 * (size_t)e->nv + (ds - e->nq - e->nv), Tz = (size_t)T;
-  const size_t n_out = rc_out_doubles(Tz, nd, nu), n_fail = (Tz + 1) / 2;
-  const bool fits = RC_WORK_DOUBLES(nd, nu) * sizeof(double) <= RC_LDS_LIMIT;
-  // behind the pass's tables: the residual rows, cr, cx, cu, cxx, cuu, cxu, the limits, the block that goes back, the scratch
-  const size_t n_cd = Tz * (2 * nr + nd + nu + nd * nd + nu * nu + nd * nu);
-  const size_t extra = n_cd + 2 * nu + n_out + n_fail + (fits ? 0 : RC_WORK_DOUBLES(nd, nu));
-  FdArgs f;
-  double *x0 = nullptr;
+  const size_t nu = e->nu, nr = e->nr, Tz = (size_t)T;
+  // B_FD: behind the pass's doubles the residual rows, the cost derivatives, the limits, the block that goes back, the scratch (IlqgLay)
+  IlqgLay L;
   const std::vector<int> dofmap = fd_dofmap(e);
-  rc = fd_pass(e, K_, dofmap, 0, Tz, 1, x, u, time, eps, centered, extra, &f, &x0);
+  PLACE(B_FD, L, e->dims(), Tz, centered, rc_work_doubles(e->nd, nu));
+  FdArgs f;
+  rc = fd_pass(e, K_, dofmap, L.fd, 0, Tz, 1, x, u, time, eps, centered, &f);
   if (rc != 0) return rc;
-  CdArgs a;
-  memset(&a, 0, sizeof(a));
-  double *dr = x0;
-  a.residual = dr; a.C = f.C; a.D = f.D; a.T = T; a.nd = (int)nd; a.nu = (int)nu; a.nr = (int)nr; a.last_is_terminal = 1; a.hessians = 1;
-  a.cr = dr + Tz * nr; a.cx = a.cr + Tz * nr; a.cu = a.cx + Tz * nd; a.cxx = a.cu + Tz * nu; a.cuu = a.cxx + Tz * nd * nd; a.cxu = a.cuu + Tz * nu * nu;
-  double *dlim = x0 + n_cd, *ob = dlim + 2 * nu;
-  if (nr) HIPCHK(hipMemcpyAsync(dr, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
+  if (nr) HIPCHK(hipMemcpyAsync(L.residual, residual, sizeof(double) * Tz * nr, hipMemcpyHostToDevice, e->stream));
   // the model's ctrlrange; an unlimited actuator gets -inf, +inf (kept alive until the stream has been synchronised in rc_run)
   std::vector<double> lim(2 * nu);
   {
@@ -1460,19 +1421,14 @@ int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const dou
       lim[2 * i + 1] = limited ? hm.actuator_ctrlrange[2 * i + 1] : HUGE_VAL;
     }
   }
-  HIPCHK(hipMemcpyAsync(dlim, lim.data(), sizeof(double) * 2 * nu, hipMemcpyHostToDevice, e->stream));
-  rc = cd_launch(e, a, who);
+  HIPCHK(hipMemcpyAsync(L.limits, lim.data(), sizeof(double) * 2 * nu, hipMemcpyHostToDevice, e->stream));
+  rc = cd_launch(e, cd_args(e, L.residual, f.C, f.D, L.cd, T, 1, 1), who);
   if (rc != 0) return rc;
-  g.A = f.A; g.B = f.B; g.cx = a.cx; g.cu = a.cu; g.cxx = a.cxx; g.cxu = a.cxu; g.cuu = a.cuu; g.actions = f.u; g.limits = dlim;
-  g.T = T; g.nd = (int)nd; g.nu = (int)nu;
+  g.A = f.A; g.B = f.B; g.cx = L.cd.cx; g.cu = L.cd.cu; g.cxx = L.cd.cxx; g.cxu = L.cd.cxu; g.cuu = L.cd.cuu; g.actions = f.u; g.limits = L.limits;
+  g.T = T; g.nd = e->nd; g.nu = e->nu;
   // failure[] travels behind the block; rc_run zeroes the block alone, so this copy may be queued first
-  HIPCHK(hipMemcpyAsync(ob + n_out, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
-  double *ht = nullptr;
-  rc = rc_run(e, g, ob, n_fail, ob + n_out + n_fail, regularization, regularization_rate, &ht);
-  if (rc != 0) return rc;
-  rc_hand_out(e->at(H_PACK), Tz, nd, nu, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status);
-  memcpy(failure, ht, sizeof(int) * Tz);
-  return 0;
+  HIPCHK(hipMemcpyAsync(L.out.failure, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
+  return rc_run(e, g, L.out, Tz, L.scratch, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status, failure);
 }
 
 int mjpc_hip_get_frame(MjpcHipEngine *e, double *xpos, double *xmat, double *site_xpos, double *subtree_com, double *subtree_linvel) {

@@ -1,10 +1,12 @@
 """GPU tier of the engine's host-side buffers: one long-lived engine runs a sequence of calls that makes every buffer grown on demand
-(noise, knots, candidate table, packed result, the step / finite-difference tables) grow, then serves smaller requests out of the larger
-allocation, and every call's complete output is bit for bit that of the same call on a fresh engine with the same limits."""
+(noise, knots, candidate table, packed result, the scratch of every one-step call and of the feedback rollouts) grow, then serves smaller
+requests out of the larger allocation, and every call's complete output is bit for bit that of the same call on a fresh engine with the
+same limits."""
 import numpy as np
 import pytest
 
 import transition_cases as tc
+from mujoco_mpc_amd import capi
 from mujoco_mpc_amd.planner import HipBackend
 
 pytestmark = pytest.mark.gpu
@@ -69,8 +71,61 @@ def _calls(name, m, task, d):
     def fd(be):
         return be.transition_fd(X3, U3, T3, mocap=mocap, userdata=ud, eps=1e-6)
 
+    # the other calls that lay their scratch out in the one-step and feedback buffers (csrc/carve.h): each at a larger shape first and at a
+    # smaller one later, so that the second is served out of an allocation another layout has grown and written
+    nq, nv, na, nr = m["nq"], m["nv"], m["na"], task["num_residual"]
+    nd = 2 * nv + na
+    X6, U6, T6 = X[:6], U[:6], T[:6]
+    res6 = 0.1 * rng.standard_normal((6, nr)); C6 = rng.standard_normal((6, nr, nd)); D6 = rng.standard_normal((6, nr, nu))
+    factor = 1e-2 * (np.eye(nd) + 0.1 * np.tril(rng.standard_normal((nd, nd))))
+    weights = (0.1, 0.2, 0.45 / nd); q = np.full(nd, 1e-4); r = 1e-4 * (1 + 0.2 * np.arange(nr))
+    gain = 0.05 * rng.standard_normal((6, nu, nd)); impr = 0.1 * rng.standard_normal((6, nu)); ptimes = 0.01 * np.arange(6)
+    alpha = np.linspace(0.0, 1.0, 8); fscale = np.linspace(1.0, 0.3, 8)
+
+    def known(out):
+        return {k: v for k, v in out.items() if v is not None}
+
+    def ukf(ns, sigma_next):
+        return lambda be: known(be.unscented_moments(X[1], factor, 1.0, weights, U[1], T[1], q, r[:ns], num_sensor=ns, mocap=mocap, userdata=ud,
+                                                     sigma_next=sigma_next))
+
+    def lin(centered):
+        return lambda be: be.linearize_step(X[2], U[2], T[2], mocap=mocap, userdata=ud, centered=centered)
+
+    def cd(n, hessians):
+        return lambda be: be.cost_derivatives(res6[:n], C6[:n], D6[:n], last_is_terminal=True, hessians=hessians, fill=7.0)
+
+    def grad(n, centered):
+        return lambda be: be.trajectory_gradient(X6[:n], U6[:n], T6[:n], res6[:n], mocap=mocap, userdata=ud, centered=centered)
+
+    def riccati(n, a, b, limits):
+        """the backward pass at its own dimensions a x b: a = 80, b = 10 keeps the kernel's work image out of LDS, behind the block"""
+        g = np.random.default_rng(100 * a + b)
+        A = np.eye(a) + 0.1 * g.standard_normal((n - 1, a, a)); B = g.standard_normal((n - 1, a, b))
+        cxx = np.tile(np.eye(a), (n, 1, 1)); cuu = np.tile(np.eye(b), (n, 1, 1)); cxu = 0.01 * g.standard_normal((n, a, b))
+        cx = g.standard_normal((n, a)); cu = g.standard_normal((n, b)); act = 0.1 * g.standard_normal((n, b)); lim = np.tile([-1.0, 1.0], (b, 1))
+        return lambda be: be.ilqg_backward_pass(A, B, cx, cu, cxx, cxu, cuu, actions=act if limits else None, action_limits=lim if limits else None,
+                                                action_limits_on=limits)
+
+    def ilqg(n, centered):
+        return lambda be: be.trajectory_ilqg(X6[:n], U6[:n], T6[:n], res6[:n], mocap=mocap, userdata=ud, centered=centered)
+
+    def feedback(n, H, N, mode, improvement):
+        def call(be):
+            out = be.plan_feedback(d["state"], 0.0, H, ptimes[:n], X6[:n], U6[:n], gain[:n], alpha[:N], fscale[:N],
+                                   action_improvement=impr[:n] if improvement else None, mode=mode, mocap=mocap, userdata=ud)
+            return with_all(out, be, N, H, 0)
+        return call
+
+    carved = [("unscented_moments", ukf(nr, True)), ("linearize_step", lin(True)), ("cost_derivatives hessians", cd(6, True)),
+              ("trajectory_gradient", grad(6, True)), ("ilqg_backward_pass out of LDS", riccati(3, 80, 10, True)), ("trajectory_ilqg", ilqg(6, True)),
+              ("plan_feedback time", feedback(4, 6, 8, capi.FEEDBACK_TIME, True)), ("plan_feedback indexed", feedback(6, 6, 8, capi.FEEDBACK_INDEXED, True)),
+              ("trajectory_ilqg small", ilqg(2, False)), ("ilqg_backward_pass small", riccati(2, 3, 1, False)), ("trajectory_gradient small", grad(2, False)),
+              ("cost_derivatives small", cd(3, False)), ("linearize_step small", lin(False)), ("unscented_moments small", ukf(1, False)),
+              ("plan_feedback indexed small", feedback(3, 3, 2, capi.FEEDBACK_INDEXED, False)),
+              ("plan_feedback time small", feedback(2, 4, 3, capi.FEEDBACK_TIME, False)), ("step_batch again", steps)]
     return [("plain", plain), ("explicit", explicit), ("summary", summary), ("mixed", mixed), ("step_batch", steps), ("transition_fd", fd),
-            ("plain again", plain)]
+            ("plain again", plain)] + carved
 
 
 def _same(a, b):
@@ -99,3 +154,16 @@ def test_a_long_lived_engine_answers_like_a_fresh_one(name):
     assert not got[2]["states"].any() and got[3]["gradient"].any()
     assert got[4]["next_states"].shape[0] == 40 > MAX_SAMPLES and len({r.tobytes() for r in got[4]["next_states"]}) == 40
     assert np.abs(got[5]["A"]).max() > 0.5
+    # nor are the carved calls: every block that comes back holds numbers, the filled Hessians are absent without Hessians, the feedback
+    # candidates differ, and the steps behind all of them are the steps before all of them
+    by = {what: g for (what, _), g in zip(calls, got)}
+    assert by["unscented_moments"]["sigma_next"].shape[0] == 2 * by["unscented_moments"]["cov_ss"].shape[0] + 1
+    assert "sigma_next" not in by["unscented_moments small"] and by["unscented_moments small"]["cov_yy"].shape == (1, 1)
+    assert all(np.abs(by[w]["cov_sy"]).max() > 0 for w in ("unscented_moments", "unscented_moments small"))
+    assert all(np.abs(by[w]["A"]).max() > 0.5 for w in ("linearize_step", "linearize_step small"))
+    assert np.abs(by["cost_derivatives hessians"]["cxx"]).max() > 0 and "cxx" not in by["cost_derivatives small"]
+    assert all(np.abs(by[w]["cx"]).max() > 0 for w in ("cost_derivatives hessians", "cost_derivatives small"))
+    assert all(np.abs(by[w]["Vx"]).max() > 0 for w in ("trajectory_gradient", "trajectory_gradient small", "trajectory_ilqg", "trajectory_ilqg small"))
+    assert all(np.abs(by[w]["K"]).max() > 0 for w in ("ilqg_backward_pass out of LDS", "ilqg_backward_pass small"))
+    assert all(np.ptp(by[w]["returns"]) > 0 for w in ("plan_feedback time", "plan_feedback indexed"))
+    assert _same(by["step_batch again"], got[4]) == []

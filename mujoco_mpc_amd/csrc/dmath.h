@@ -7,7 +7,12 @@
 #define D_MINVAL 1e-15
 #define D_PI 3.14159265358979323846
 
-// 1/sqrt(x) to full fp64 accuracy without the IEEE sqrt/divide sequences (0 -> 0 so that T = x*rsqrt(x) = 0)
+// The four sequences below are pinned to 200-bit references by tests/test_gpu_math.py (element-wise through tests/hip/math_hooks.hip);
+// the figures are maxima measured on an MI355X over the normal doubles, in ulps of the exact value.  Their DOMAIN is the normal
+// doubles: outside it they differ from the IEEE operations ("Domains of the fast scalar sequences", lists the results
+// and the guard of every call site).  v_rsq_f64 / v_rcp_f64 themselves were measured at 2^-24.4 / 2^-24.5 relative.
+// 1/sqrt(x) without the IEEE sqrt/divide sequences: max 1.71 ulp (asserted 2.21).  !(x > 0) -> 0 so that T = x*rsqrt(x) = 0 (also for
+// NaN and negative x); +inf -> NaN; denormal x loses the bits that 0.5 * x drops
 DEV double fast_rsqrt(double x) {
   if (!(x > 0)) return 0.0;
 #ifdef MJPC_EMU
@@ -19,7 +24,9 @@ DEV double fast_rsqrt(double x) {
   return y;
 #endif
 }
-// 1/x without the IEEE divide sequence (v_rcp_f64 + two Newton steps: ~1 ulp)
+// 1/x without the IEEE divide sequence (v_rcp_f64 + two Newton steps): max 0.50 ulp, correctly rounded on every argument tried
+// (asserted 1.0).  +-0, +-inf and |x| below about 5.6e-309 give NaN (the seed is inf / 0 and the Newton step forms 0 * inf), where
+// 1/x gives inf, 0 and inf
 DEV double fast_rcp(double x) {
 #ifdef MJPC_EMU
   return 1.0 / x;
@@ -31,7 +38,9 @@ DEV double fast_rcp(double x) {
   return __builtin_fma(y, e, y);
 #endif
 }
-// a / b and sqrt(x) without the IEEE sequences (~1 ulp; the emulation build keeps the IEEE operations)
+// a / b and sqrt(x) without the IEEE sequences (the emulation build keeps the IEEE operations).  d_div: max 0.50 ulp (asserted 1.0),
+// NaN wherever fast_rcp(b) is.  d_sqrt: max 0.58 ulp (asserted 1.0; above 0.5 only for x < 2^-969, where x - s*s is denormal);
+// -0 -> +0, +inf -> NaN, and the smallest denormals come out wrong (5e-324 -> -5.0e-162)
 DEV double d_div(double a, double b) {
 #ifdef MJPC_EMU
   return a / b;
@@ -90,7 +99,10 @@ DEV void d_normalize4(double *q) {
   else if (fabs(n - 1) > D_MINVAL) { q[0]*=s; q[1]*=s; q[2]*=s; q[3]*=s; }
 }
 // sin and cos of a joint-sized angle: Cody-Waite reduction by pi/2 (two-term constant) + the fdlibm kernel polynomials
-// (max error 1 ulp at |x| <= 20, checked against libm); large arguments fall back to libm
+// for |x| < 64, the range the callers use; |x| >= 64, inf and NaN fall back to libm.  Against the exact value over |x| < 64:
+// |err| <= 1.47 ulp + 4.2e-25 (measured 1.4636 ulp at x = 57.338.. on the MI355X, the same as a CPU restatement gives with and
+// without fused multiply-adds; asserted 1.97).  The absolute term covers the neighbourhood of the multiples of pi/2, where the
+// relative error of a 1e-14 result is unbounded: 41 x (truncation of the two-term constant + rounding of k * its second term)
 DEV void d_sincos(double x, double *sn, double *cs) {
 #ifdef MJPC_EMU
   *sn = sin(x); *cs = cos(x);
@@ -164,6 +176,12 @@ DEV void d_subquat(double *r, const double *qa, const double *qb) {
   double s = d_normalize3(ax);
   double speed = 2 * atan2(s, qd[0]);
   if (speed > D_PI) speed -= 2 * D_PI;
+#ifndef MJPC_EMU
+  // below D_MINVAL the vector part is rounding residue (conj(q) q contracted into FMAs leaves up to 1e-16 of it) and d_normalize3 has
+  // put (1, 0, 0) in place of an axis: the difference is zero, exactly so for equal quaternions.  The emulation build has no
+  // contraction, gives exact zeros there already and keeps the host mirrors' bits (2 s along x for 0 < s < D_MINVAL, at most 2e-15)
+  if (s < D_MINVAL) speed = 0;
+#endif
   d_scl3(r, ax, speed);
 }
 DEV void d_inertcom(double *r, const double *inert, const double *mat, const double *dif, double mass) {

@@ -329,6 +329,23 @@ static inline bool build(PackedModel &p, const MjpcHipModel *m, const MjpcHipTas
   { const int known = MJPC_DSBL_CONSTRAINT | MJPC_DSBL_EQUALITY | MJPC_DSBL_FRICTIONLOSS | MJPC_DSBL_LIMIT | MJPC_DSBL_CONTACT | MJPC_DSBL_SENSOR | MJPC_DSBL_MIDPHASE;
     if (m->disableflags & ~known) { p.error = "disableflags " + std::to_string(m->disableflags) + ": only constraint / frictionloss / limit / contact can be disabled"; return false; }
     if (m->enableflags & (MJPC_ENBL_OVERRIDE | MJPC_ENBL_MULTICCD)) { p.error = "enableflags: contact override and multiccd are not supported"; return false; } }
+  // A contact of dimension > 1 divides by its friction coefficients (constraint.h: R_k = R_1 mu_0^2 / mu_k^2; solver.h: 1 / (mu^2 (1 + mu^2)),
+  // 1 / fr_j^2) with fast_rcp / d_div, which return NaN at 0 (dmath.h), and nothing here clamps them the way MuJoCo's mjMINMU does:
+  // a pair whose combined coefficients (collide.h contact_param: the higher priority's, else the larger one) are not all positive is refused
+  if (m->geom_friction && m->geom_condim && m->geom_contype && m->geom_conaffinity && m->geom_bodyid)
+    for (int a = 0; a < ng; a++) for (int b = a + 1; b < ng; b++) {
+      if (m->geom_bodyid[a] == m->geom_bodyid[b]) continue;
+      if (!((m->geom_contype[a] & m->geom_conaffinity[b]) | (m->geom_contype[b] & m->geom_conaffinity[a]))) continue;
+      const int pa = m->geom_priority ? m->geom_priority[a] : 0, pb = m->geom_priority ? m->geom_priority[b] : 0;
+      const int g = pa > pb ? a : b;
+      const int dim = pa != pb ? m->geom_condim[g] : (m->geom_condim[a] > m->geom_condim[b] ? m->geom_condim[a] : m->geom_condim[b]);
+      const int used = dim < 3 ? 0 : (dim == 3 ? 1 : (dim == 4 ? 2 : 3));      // sliding | + torsional | + rolling
+      for (int k = 0; k < used; k++) {
+        const double fa = m->geom_friction[3 * a + k], fb = m->geom_friction[3 * b + k];
+        const double f = pa != pb ? m->geom_friction[3 * g + k] : (fa > fb ? fa : fb);
+        if (!(f > 0)) { p.error = "geoms " + std::to_string(a) + " and " + std::to_string(b) + " can collide with condim " + std::to_string(dim) + " and friction coefficient " + std::to_string(k) + " = " + std::to_string(f) + ": a contact of dimension > 1 needs positive friction coefficients (MuJoCo's mjMINMU clamp is not applied here)"; return false; }
+      }
+    }
   if (m->nuserdata < 0) { p.error = "nuserdata < 0"; return false; }
   if (m->nefcmax > 192) { p.error = "nefcmax > 192 not supported (line-search rows per lane)"; return false; }
   if (m->nconmax > 64) { p.error = "nconmax > 64 not supported (one contact per lane in the solver)"; return false; }

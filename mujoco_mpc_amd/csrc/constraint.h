@@ -274,12 +274,12 @@ DEV void make_noncontact_rows(Ctx &c, int *nsingle_out, int *n_nc_out) {
   *nsingle_out = nlim_end; *n_nc_out = ntl_end;
 }
 
-// contact rows [n_nc, nefc): dim rows per contact (2(dim-1) pyramid edges), their Jacobian, the cross-branch flag
-DEV void make_contact_rows(Ctx &c, int n_nc) {
+// contact rows [n_nc, nefc): dim rows per contact (2(dim-1) pyramid edges), their Jacobian, the cross-branch flag.  Three parts, so
+// that the Jacobian can be shared out by contact between two waves (core.h, ph_constraints / ph_inertia):
+// 1. the layout: first row of every contact into con_i[3], c.nefc; rows that do not fit cut c.ncon back (WARN_CNSTRFULL)
+DEV void contact_row_scan(Ctx &c, int n_nc) {
   const DevModel &M = *c.M;
-  int nv = M.nv, nvp = M.nvp;
   int nefc = n_nc;
-  // contacts: dim rows each
   for (int base = 0; base < c.ncon; base += NLANE) {
     int ci = base + LANE, dim = 0;
     if (ci < c.ncon) {
@@ -288,27 +288,37 @@ DEV void make_contact_rows(Ctx &c, int n_nc) {
     }
     int tot, off = wave_excl_scan(dim, &tot);
     if (nefc + tot > M.nefcmax) { c.warning |= WARN_CNSTRFULL; c.ncon = base; break; }
-    if (ci < c.ncon) {
-      int r0 = nefc + off;
-      c.con_i[ci * CONI_STRIDE + 3] = r0;
-      int g1 = c.con_i[ci * CONI_STRIDE + 1], g2 = c.con_i[ci * CONI_STRIDE + 2];
-      int b1 = MI(geom_bodyid)[g1], b2 = MI(geom_bodyid)[g2];
-      double tran = MDH(body_invweight0)[2 * b1] + MDH(body_invweight0)[2 * b2];
-      double rot = MDH(body_invweight0)[2 * b1 + 1] + MDH(body_invweight0)[2 * b2 + 1];
-      const double *cc = c.contact + ci * c.M->con_stride;
-      int cdim = c.con_i[ci * CONI_STRIDE];
-      int pyr = (cdim > 1 && M.cone != 1);
-      for (int k = 0; k < dim; k++) {
-        c.efc_type[r0 + k] = cdim == 1 ? CNSTR_CONTACT_FRICTIONLESS : (pyr ? CNSTR_CONTACT_PYRAMIDAL : CNSTR_CONTACT_ELLIPTIC);
-        c.efc_id[r0 + k] = EFC_CON_ID(ci, cdim, r0);      // contact id, its dim and first row in one word: no dependent con_i hop later
-        c.efc_floss[r0 + k] = 0; c.efc_pos[r0 + k] = cc[CON_DIST]; c.efc_margin[r0 + k] = cc[CON_INCLUDEMARGIN];
-        if (pyr) { double mu = cc[CON_FRICTION + k / 2]; c.efc_diag[r0 + k] = tran + mu * mu * (k < 4 ? tran : rot); }
-        else c.efc_diag[r0 + k] = k < 3 ? tran : rot;
-      }
-    }
+    if (ci < c.ncon) c.con_i[ci * CONI_STRIDE + 3] = nefc + off;
     nefc += tot;
   }
   c.nefc = nefc;
+}
+// 2. the per-row headers of the step's ncon contacts (any wave: reads the layout and the contact records only)
+DEV void contact_row_headers(Ctx &c, int ncon) {
+  const DevModel &M = *c.M;
+  PFOR(ci, ncon) {
+    int r0 = c.con_i[ci * CONI_STRIDE + 3];
+    int g1 = c.con_i[ci * CONI_STRIDE + 1], g2 = c.con_i[ci * CONI_STRIDE + 2];
+    int b1 = MI(geom_bodyid)[g1], b2 = MI(geom_bodyid)[g2];
+    double tran = MDH(body_invweight0)[2 * b1] + MDH(body_invweight0)[2 * b2];
+    double rot = MDH(body_invweight0)[2 * b1 + 1] + MDH(body_invweight0)[2 * b2 + 1];
+    const double *cc = c.contact + ci * c.M->con_stride;
+    int cdim = c.con_i[ci * CONI_STRIDE];
+    int pyr = (cdim > 1 && M.cone != 1);
+    int dim = pyr ? 2 * (cdim - 1) : cdim;
+    for (int k = 0; k < dim; k++) {
+      c.efc_type[r0 + k] = cdim == 1 ? CNSTR_CONTACT_FRICTIONLESS : (pyr ? CNSTR_CONTACT_PYRAMIDAL : CNSTR_CONTACT_ELLIPTIC);
+      c.efc_id[r0 + k] = EFC_CON_ID(ci, cdim, r0);      // contact id, its dim and first row in one word: no dependent con_i hop later
+      c.efc_floss[r0 + k] = 0; c.efc_pos[r0 + k] = cc[CON_DIST]; c.efc_margin[r0 + k] = cc[CON_INCLUDEMARGIN];
+      if (pyr) { double mu = cc[CON_FRICTION + k / 2]; c.efc_diag[r0 + k] = tran + mu * mu * (k < 4 ? tran : rot); }
+      else c.efc_diag[r0 + k] = k < 3 ? tran : rot;
+    }
+  }
+  SYNC();
+}
+// the cross-branch flag, one of the owner's scalars
+DEV void contact_cross_flag(Ctx &c) {
+  const DevModel &M = *c.M;
   // cross-branch contacts (both bodies movable, neither dof chain contains the other) break M's sparsity pattern in H
   int crossflag = 0;
   PFOR(ci, c.ncon) {
@@ -319,15 +329,22 @@ DEV void make_contact_rows(Ctx &c, int n_nc) {
   }
   c.cross = wave_or_i(crossflag) | M.limit_cross;
   SYNC();
-  // Jacobian
-  PFOR(e, (nefc - n_nc) * nvp) c.efc_J[n_nc * nvp + e] = 0;
+}
+// 3. the Jacobian rows of the contacts [ci0, ci1) of the step's ncon (nefc rows in all): zeroed and filled by the calling wave, which
+// touches no row of another contact.  Reads con_i[3] of the layout, nothing of Ctx's per-step scalars
+DEV void contact_jacobian(Ctx &c, int ci0, int ci1, int ncon, int nefc) {
+  const DevModel &M = *c.M;
+  int nv = M.nv, nvp = M.nvp;
+  const int rbeg = ci0 < ncon ? uniform_i(c.con_i[ci0 * CONI_STRIDE + 3]) : nefc;
+  const int rend = ci1 < ncon ? uniform_i(c.con_i[ci1 * CONI_STRIDE + 3]) : nefc;
+  PFOR(e, (rend - rbeg) * nvp) c.efc_J[rbeg * nvp + e] = 0;
   SYNC();
-  // element e = ci * nv + d; the quotient / remainder advance incrementally (one runtime division per lane instead of one per element)
+  // element e = (ci - ci0) * nv + d; the quotient / remainder advance incrementally (one runtime division per lane instead of one per element)
   int je_ci = LANE / nv, je_d = LANE - je_ci * nv;
   const int je_sq = NLANE / nv, je_sr = NLANE - je_sq * nv;
-  for (int e = LANE; e < c.ncon * nv; e += NLANE, je_ci += je_sq, je_d += je_sr) {
+  for (int e = LANE; e < (ci1 - ci0) * nv; e += NLANE, je_ci += je_sq, je_d += je_sr) {
     if (je_d >= nv) { je_d -= nv; je_ci++; }
-    const int ci = je_ci, d = je_d;
+    const int ci = ci0 + je_ci, d = je_d;
     const int *cin = c.con_i + ci * CONI_STRIDE;
     int dim = cin[0], r0 = cin[3];
     int pyr = (dim > 1 && M.cone != 1);

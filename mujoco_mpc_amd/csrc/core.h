@@ -343,6 +343,9 @@ DEV_NOINLINE void ph_head(KP Kc, int t, int last) {
 }
 // role 0: contacts and constraint rows (needs positions + qvel only).  With helper waves the contact-free rows and their
 // impedance are built by the last helper meanwhile (ph_noncontact); it publishes nsingle / n_nc in HX_NC_NSINGLE / HX_NC_ROWS, flag HX_NCROWS.
+// The contact Jacobian is shared by contact with helper 0 (ph_inertia), idle behind its factor of M: the owner publishes the row
+// layout (HX_CR_NCON / HX_CR_NEFC, flag HX_CROWS), fills the rows of the first ncon / 2 contacts and waits for the others (HX_CJAC);
+// the per-row headers are written by helper 1 meanwhile (HX_CHDR).
 DEV_NOINLINE void ph_constraints(KP Kc, int t) {
   Ctx c; ctx_open(c, Kc);
   collision(c); PROF(c, 4);
@@ -352,14 +355,26 @@ DEV_NOINLINE void ph_constraints(KP Kc, int t) {
   if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC;        // cdof / subtree_com for the contact Jacobians (side wave)
 #endif
   if (!flag_wait(c.misc + HX_NCROWS, t + 1)) c.warning |= WARN_SYNC;
+  PROF(c, 10);
   nsingle = uniform_i(c.misc[HX_NC_NSINGLE]); n_nc = uniform_i(c.misc[HX_NC_ROWS]);
   c.nsingle = nsingle;
-  make_contact_rows(c, n_nc); PROF(c, 5);
+  contact_row_scan(c, n_nc);
+  if (LANE == 0) { c.misc[HX_CR_NCON] = c.ncon; c.misc[HX_CR_NEFC] = c.nefc; }     // (ncon as the layout left it: cut back when the rows are full)
+  flag_set(c.misc + HX_CROWS, t + 1);
+  contact_cross_flag(c); PROF(c, 18);
+  contact_jacobian(c, 0, c.ncon / 2, c.ncon, c.nefc);
+  if (!flag_wait(c.misc + HX_CJAC, t + 1)) c.warning |= WARN_SYNC;
+  if (!flag_wait(c.misc + HX_CHDR, t + 1)) c.warning |= WARN_SYNC;
+  PROF(c, 5);
   make_impedance(c, n_nc, c.nefc, 1); PROF(c, 7);
 #else
   make_noncontact_rows(c, &nsingle, &n_nc);
   c.nsingle = nsingle;
-  make_contact_rows(c, n_nc); PROF(c, 5);
+  contact_row_scan(c, n_nc);
+  contact_row_headers(c, c.ncon);
+  contact_cross_flag(c);
+  contact_jacobian(c, 0, c.ncon, c.ncon, c.nefc);
+  PROF(c, 5);
   make_impedance(c, 0, c.nefc, 1); PROF(c, 7);
 #endif
   ctx_close(c);
@@ -372,14 +387,31 @@ DEV_NOINLINE void ph_noncontact(KP Kc, int t) {
   // the anchors' point Jacobians of connect constraints need cdof / subtree_com, which the side wave is producing
   if (c.M->neq_connect) { if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC; }
 #endif
+  // first two things off the side wave's chain, which reads them behind HX_SUBSUM only (velocity_stage): the site positions and the
+  // actuator forces with act_dot: joint and tendon transmissions need ctrl, qpos, qvel and act only.  (With a reference-site
+  // transmission the forces need this step's site positions: both stay with the side wave.)
+  if (c.M->nrsact == 0) {
+#if MJPC_SIDE_COM
+    kin_sites(c);          // (site positions: no com-based quantity reads them; otherwise they are part of the owner's kinematics)
+#endif
+    actuator_forces(c);
+  }
+  PROFW(c, 8);
   make_noncontact_rows(c, &nsingle, &n_nc);
   if (LANE == 0) { c.misc[HX_NC_NSINGLE] = nsingle; c.misc[HX_NC_ROWS] = n_nc; }
   flag_set(c.misc + HX_NCROWS, t + 1);
   PROFW(c, 1);
   make_impedance(c, 0, n_nc, 0);
   PROFW(c, 4);
+  // the per-row headers of the contact rows, as soon as the owner has laid them out (it fills Jacobian rows meanwhile)
+  if (!flag_wait(c.misc + HX_CROWS, t + 1)) c.warning |= WARN_SYNC;
+  PROFW(c, 9);
+  contact_row_headers(c, uniform_i(c.misc[HX_CR_NCON]));
+  flag_set(c.misc + HX_CHDR, t + 1);
+  PROFW(c, 10);
   // then its part of the side wave's subtree sums (velocity_stage)
   if (!flag_wait(c.misc + HX_SWEEP, t + 1)) c.warning |= WARN_SYNC;
+  PROFW(c, 7);
   subtree_sums(c, 1);
   flag_set(c.misc + HX_SUBSUM, t + 1);
   PROFW(c, 5);
@@ -397,6 +429,7 @@ DEV_NOINLINE void ph_smooth(KP Kc, int t) {
   kinematics_rest(c);
   com_pos(c);
   flag_set(c.misc + HX_COM, t + 1);
+  PROFW(c, 17);
 #endif
   velocity_stage<NVT>(c, Kc, t + 1);            // helper 0 builds and factors M meanwhile (ph_inertia)
 #else
@@ -412,9 +445,20 @@ DEV_NOINLINE void ph_inertia(KP Kc, int t) {
   Ctx c; ctx_open(c, Kc, 1);
 #if MJPC_SIDE_COM
   if (!flag_wait(c.misc + HX_COM, t + 1)) c.warning |= WARN_SYNC;
+  PROFW(c, 7);
 #endif
   crb_and_factor<NVT>(c);
   flag_set(c.misc + HX_MFACT, t + 1);
+  // then the Jacobian rows of the second half of the step's contacts (the owner has the first, ph_constraints).  An empty share
+  // (ncon 0 or 1 leaves the owner none, ncon 0 none here either) still posts the flag
+  if (!flag_wait(c.misc + HX_CROWS, t + 1)) c.warning |= WARN_SYNC;
+  PROFW(c, 8);
+  {
+    const int ncon = uniform_i(c.misc[HX_CR_NCON]), nefc = uniform_i(c.misc[HX_CR_NEFC]);
+    contact_jacobian(c, ncon / 2, ncon, ncon, nefc);
+  }
+  flag_set(c.misc + HX_CJAC, t + 1);
+  PROFW(c, 9);
   ctx_close(c);
 }
 #endif

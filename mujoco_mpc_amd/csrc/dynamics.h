@@ -98,25 +98,24 @@ DEV void vel_compose(Ctx &c, int i, double *cvel, double *a, int store) {
   d_scl3(c.bodytmp + 3 * i, v, MDH(body_mass)[i]);
 }
 
-// subtree sums of the body forces / momenta left by the sweep.  part 0: cfrc_sub components 0..2; part 1: components 3..5 and
-// subtree_linvel
+// subtree sums of the body forces / momenta left by the sweep: per body the six components of cfrc_sub and the three of
+// subtree_linvel, nine elements, each summed by one lane in list order.  part 0 / 1: the first / second half of the elements.
+// One loop serves both kinds (source and stride picked per lane), so a wave that holds both does not run two loops in turn
 DEV void subtree_sums(Ctx &c, int part) {
   const DevModel &M = *c.M;
-  int per = part ? 6 : 3;
-  PFOR(e, M.nbody * per) {
-    int b = e / per, k = e - per * b;
-    if (k < 3) {
-      int kc = k + 3 * part;
-      double s = 0;
-      if (b > 0) for (int q = MIH(subtree_adr)[b]; q < MIH(subtree_adr)[b + 1]; q++) s += c.cfrc[6 * MIH(subtree_list)[q] + kc];
-      c.cfrc_sub[6 * b + kc] = s;
-    } else {
-      int kk = k - 3;
-      double s = 0;
-      // (a list starts with the body itself; the world's own entry is skipped: it has no momentum, and bodytmp[0] is residual scratch)
-      for (int q = MIH(subtree_adr)[b] + (b == 0); q < MIH(subtree_adr)[b + 1]; q++) s += c.bodytmp[3 * MIH(subtree_list)[q] + kk];
-      c.subtree_linvel[3 * b + kk] = s / fmax(D_MINVAL, MDH(body_subtreemass)[b]);
-    }
+  const int n = 9 * M.nbody, half = (n + 1) >> 1;
+  const int e1 = part ? n : half;
+  for (int e = (part ? half : 0) + LANE; e < e1; e += NLANE) {
+    const int b = e / 9, k = e - 9 * b, mom = k >= 6;
+    const double *src = mom ? c.bodytmp + (k - 6) : c.cfrc + k;
+    const int stride = mom ? 3 : 6;
+    // (a list starts with the body itself; the world has no force sum, and of its momentum sum its own entry is skipped: it has no
+    // momentum, and bodytmp[0] is residual scratch)
+    const int q0 = MIH(subtree_adr)[b] + (b == 0), q1 = (b == 0 && !mom) ? q0 : MIH(subtree_adr)[b + 1];
+    double s = 0;
+    for (int q = q0; q < q1; q++) s += src[stride * MIH(subtree_list)[q]];
+    if (mom) c.subtree_linvel[3 * b + k - 6] = s / fmax(D_MINVAL, MDH(body_subtreemass)[b]);
+    else c.cfrc_sub[6 * b + k] = s;
   }
 }
 
@@ -299,6 +298,29 @@ DEV_NOINLINE void ph_smooth_extras(KP Kc) {
   }
 }
 
+// actuator forces and, for stateful actuators, act_dot (mj_fwdActuation)
+DEV void actuator_forces(Ctx &c) {
+  const DevModel &M = *c.M;
+  PFOR(i, M.nu) {
+    double ctrl = c.ctrl[i];
+    if (MI(actuator_ctrllimited)[i]) ctrl = d_clip(ctrl, MD(actuator_ctrlrange)[2 * i], MD(actuator_ctrlrange)[2 * i + 1]);
+    c.actuator_force[i] = actuator_force_of(c, i, ctrl);
+  }
+  if (M.na) {        // stateful actuators: act_dot from the clamped control, the force from the current activation instead
+    PFOR(i, M.nu) {
+      int dt = MI(actuator_dyntype)[i];
+      if (dt) {
+        double ctrl = c.ctrl[i];
+        if (MI(actuator_ctrllimited)[i]) ctrl = d_clip(ctrl, MD(actuator_ctrlrange)[2 * i], MD(actuator_ctrlrange)[2 * i + 1]);
+        int a = MI(actuator_actadr)[i];
+        double act = C_ACT(c)[a];
+        C_ACTDOT(c)[a] = dt == DYN_INTEGRATOR ? ctrl : d_div(ctrl - act, fmax(D_MINVAL, MD(actuator_dynprm)[i]));
+        c.actuator_force[i] = actuator_force_of(c, i, act);
+      }
+    }
+  }
+}
+
 // mfact_seq != 0: M's factor is produced by a helper wave; wait for its sequence number (HX_MFACT) before the solve
 template <int NVT>
 DEV void velocity_stage(Ctx &c, KP Kc, int mfact_seq) {
@@ -332,37 +354,24 @@ DEV void velocity_stage(Ctx &c, KP Kc, int mfact_seq) {
   }
   PROFW(c, 1);
 #if MJPC_HELPER
-  // the subtree sums are shared with the last helper wave (idle by now, ph_noncontact): it takes the torque half of cfrc_sub and
-  // the subtree momenta, this wave the force half; every element is summed by one lane in list order, as before
+  // the subtree sums are shared with the last helper wave (idle by now, ph_noncontact): each takes half of the elements; every
+  // element is summed by one lane in list order
   flag_set(c.misc + HX_SWEEP, mfact_seq);
   subtree_sums(c, 0);
 #else
   subtree_sums(c, 0); subtree_sums(c, 1);
 #endif
   PROFW(c, 4);
-  // actuator forces
-  PFOR(i, M.nu) {
-    double ctrl = c.ctrl[i];
-    if (MI(actuator_ctrllimited)[i]) ctrl = d_clip(ctrl, MD(actuator_ctrlrange)[2 * i], MD(actuator_ctrlrange)[2 * i + 1]);
-    c.actuator_force[i] = actuator_force_of(c, i, ctrl);
-  }
-  if (M.na) {        // stateful actuators: act_dot from the clamped control, the force from the current activation instead
-    PFOR(i, M.nu) {
-      int dt = MI(actuator_dyntype)[i];
-      if (dt) {
-        double ctrl = c.ctrl[i];
-        if (MI(actuator_ctrllimited)[i]) ctrl = d_clip(ctrl, MD(actuator_ctrlrange)[2 * i], MD(actuator_ctrlrange)[2 * i + 1]);
-        int a = MI(actuator_actadr)[i];
-        double act = C_ACT(c)[a];
-        C_ACTDOT(c)[a] = dt == DYN_INTEGRATOR ? ctrl : d_div(ctrl - act, fmax(D_MINVAL, MD(actuator_dynprm)[i]));
-        c.actuator_force[i] = actuator_force_of(c, i, act);
-      }
-    }
-  }
+#if MJPC_HELPER
+  if (M.nrsact > 0)          // (otherwise helper 1 has done them at the start of its phase, ph_noncontact; HX_SUBSUM below publishes them)
+#endif
+  actuator_forces(c);
+  PROFW(c, 18);
 #if MJPC_HELPER
   if (!flag_wait(c.misc + HX_SUBSUM, mfact_seq)) c.warning |= WARN_SYNC;
 #endif
   SYNC();
+  PROFW(c, 19);
   PFOR(d, nv) {
     const double *cd = c.cdof + 6 * d, *cf = c.cfrc_sub + 6 * MIH(dof_bodyid)[d];
     double bias = cd[0]*cf[0] + cd[1]*cf[1] + cd[2]*cf[2] + cd[3]*cf[3] + cd[4]*cf[4] + cd[5]*cf[5];

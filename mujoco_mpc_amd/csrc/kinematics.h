@@ -92,8 +92,9 @@ DEV void kin_compose(Ctx &c, int i, const double *jq, const double *ppos, const 
 #else
 #define MJPC_SIDE_COM 0
 #endif
-// the poses nothing in collision detection reads: inertial frames and sites (with MJPC_SIDE_COM they are the side wave's work)
-DEV void kin_frames_sites(Ctx &c) {
+// the poses nothing in collision detection reads: inertial frames and sites (with MJPC_SIDE_COM the frames are the side wave's work
+// and the sites, which no com-based quantity needs, helper 1's: ph_noncontact)
+DEV void kin_frames(Ctx &c) {
   const DevModel &M = *c.M;
   PFOR(i, M.nbody) {
     if (i == 0) continue;
@@ -105,6 +106,9 @@ DEV void kin_frames_sites(Ctx &c) {
     d_quat2mat(xm, q);
     for (int k = 0; k < 9; k++) c.ximat[9 * i + k] = xm[k];
   }
+}
+DEV void kin_sites(Ctx &c) {
+  const DevModel &M = *c.M;
   PFOR(s, M.nsite) {
     int b = MI(site_bodyid)[s];
     double v[3], sp[3];
@@ -113,7 +117,8 @@ DEV void kin_frames_sites(Ctx &c) {
     d_add3(c.site_xpos + 3 * s, v, c.xpos + 3 * b);
   }
 }
-DEV void kinematics_rest(Ctx &c) { kin_frames_sites(c); SYNC(); }
+// the side wave's part: the frames, and the sites where its own actuator forces read them (a transmission with a reference site)
+DEV void kinematics_rest(Ctx &c) { kin_frames(c); if (c.M->nrsact > 0) kin_sites(c); SYNC(); }
 
 DEV void kinematics(Ctx &c) {
   const DevModel &M = *c.M;
@@ -136,7 +141,7 @@ DEV void kinematics(Ctx &c) {
   }
   SYNC();
 #if !MJPC_SIDE_COM
-  kin_frames_sites(c);
+  kin_frames(c); kin_sites(c);
 #endif
   PFOR(g, M.ngeom) {
     int b = MI(geom_bodyid)[g];

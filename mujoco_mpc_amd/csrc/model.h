@@ -201,7 +201,7 @@ enum {
   //                 14 - 16 free
   HX_LSREC = 17,          // line-search records of this step ready: helper 0 -> owner, helper 1
   HX_JOBW = 18,           // the owner's cone-block job, one packed word JOBW(seq, workers, kind) -> helpers (solver_reg.h)
-  HX_SUBSUM = 19,         // helper 1's part of the subtree sums done -> side
+  HX_SUBSUM = 19,         // helper 1's part of the subtree sums done (and, from the start of its phase, site positions and actuator forces) -> side
   //                 20, 21 free
   HX_MFACT = 22,          // factor of M ready: helper 0 -> side
   HX_CSM = 23,            // cost at qacc_smooth in red[2]: helper 1 -> owner
@@ -209,7 +209,12 @@ enum {
   HX_NC_NSINGLE = 25,     //   single-entry rows
   HX_NC_ROWS = 26,        //   contact-free rows
   HX_SWEEP = 27,          // velocity sweep done: side -> helper 1
-  //                 28 - 35 free
+  HX_CROWS = 28,          // layout of the contact rows done (con_i[3]), its counts in the next two slots: owner -> helpers 0, 1
+  HX_CR_NCON = 29,        //   contacts of the step, as the layout left them (cut back on WARN_CNSTRFULL)
+  HX_CR_NEFC = 30,        //   constraint rows of the step
+  HX_CJAC = 31,           // Jacobian rows of the contacts [ncon / 2, ncon) filled: helper 0 -> owner
+  HX_CHDR = 32,           // per-row headers of the contact rows written: helper 1 -> owner
+  //                 33 - 35 free
   HX_WDONE = 36,          // + w: worker w (= helper w) finished job seq -> owner
   HX_WDONE_END = 38,
   //                 38 - 43 free

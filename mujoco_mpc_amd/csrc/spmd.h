@@ -46,10 +46,11 @@ DEV int wave_any(int flag) { return flag != 0; }
 #define DEV_NOINLINE static __device__ __noinline__
 // A candidate is owned by the four wavefronts of one workgroup, one per SIMD of a CU:
 //   owner (wave 0, ROLE0): the serial critical path (kinematics -> collision / contact rows -> Newton solver -> integration);
-//   helper 0 (wave 1): joint-space inertia and its factor while the owner builds the constraints; during the solve the line
-//     search's records, then cone-block jobs of the owner's Newton iterations (elliptic models, solver_reg.h);
-//   helper 1 (wave 2): the contact-free constraint rows and half of the subtree sums; during the solve the price of the
-//     unconstrained acceleration, then cone-block jobs;
+//   helper 0 (wave 1): joint-space inertia and its factor while the owner builds the constraints, then the Jacobian rows of the
+//     second half of the step's contacts (the owner fills the first half); during the solve the line search's records, then
+//     cone-block jobs of the owner's Newton iterations (elliptic models, solver_reg.h);
+//   helper 1 (wave 2): site positions and actuator forces, the contact-free constraint rows and half of the subtree sums; during
+//     the solve the price of the unconstrained acceleration, then cone-block jobs;
 //   side wave (wave 3, ROLE1): work that only hangs off that path (smooth dynamics while the owner builds the constraints;
 //     residual / cost / trajectory record and the integrator's factor while the owner solves).
 // SYNC() orders LDS traffic inside ONE wave (DS operations of a wave execute in order; only the compiler must not

@@ -41,16 +41,16 @@ prof = np.zeros((N, 24), np.int64)
 be.lib.mjpc_hip_debug_fetch_prof.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
 be.lib.mjpc_hip_debug_fetch_prof(be.h, prof.ctypes.data_as(C.POINTER(C.c_longlong)))
 allc = be.fetch_all(N, H, P)
-names = ["(loop overhead/record)", "kinematics", "com_pos + barrier wait after head", "BARRIER WAIT after presolve", "collision", "make_constraint", "BARRIER WAIT after solve", "impedance(+warm)",
-         "solver tail", "gradient (J^T f)", "assemble: hq + diag", "integrate", "warm-start evals / ls commit", "newton misc (search, loop top)", "(alpha pick)", "hq init / rank-1 updates", "wait for the workers", "factor + solve H", "assemble: add cone partials", "assemble: qH store", "ls: Mv,jv", "ls: load", "ls: evals"]
+names = ["(loop overhead/record)", "kinematics", "com_pos + barrier wait after head", "BARRIER WAIT after presolve", "collision", "contact rows: zero + Jacobian (+ wait for the helpers' parts)", "BARRIER WAIT after solve", "impedance(+warm)",
+         "solver tail", "gradient (J^T f)", "presolve: wait for com + contact-free rows (+ heavy colliders)", "integrate", "warm-start evals / ls commit", "newton misc (search, loop top)", "(alpha pick)", "hq init / rank-1 updates", "wait for the workers", "factor + solve H", "presolve: contact-row layout, publish, cross flag (+ heavy colliders)", "assemble: qH store", "ls: Mv,jv", "ls: load", "ls: evals"]
 W = int(os.environ.get("PROFILE_WAVE", "0"))
 if W == 3:      # side wave
-    names = ["(head: idle)", "smooth: com->vel/acc level sweep", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "smooth: subtree sums", "smooth: actuation/bias/springs", "BARRIER WAIT after solve",
-             "smooth: wait for factor(M)", "smooth: solve qacc_smooth", "residual", "cost+record", "prefactor M+hB", "worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)"] + ["-"] * 6
+    names = ["(head: idle)", "smooth: level sweep", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "smooth: subtree sums (its half)", "smooth: bias / qfrc_smooth / springs", "BARRIER WAIT after solve",
+             "smooth: wait for factor(M)", "smooth: solve qacc_smooth", "residual", "cost+record", "prefactor M+hB", "worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)", "smooth: kinematics_rest + com_pos", "smooth: actuator forces", "smooth: wait for helper 1's subtree sums"] + ["-"] * 3
 elif W == 1:    # helper 0
-    names = ["-", "inertia: crb subtree sums", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "inertia: M entries", "inertia: factor M", "BARRIER WAIT after solve (= solver helper loop)"] + ["-"] * 5 + ["worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)"] + ["-"] * 6
+    names = ["-", "inertia: crb subtree sums", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "inertia: M entries", "inertia: factor M", "BARRIER WAIT after solve (= solver helper loop)", "inertia: wait for com (side wave)", "wait for the contact-row layout (owner)", "contact Jacobian (its half)"] + ["-"] * 2 + ["worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)"] + ["-"] * 6
 elif W == 2:    # helper 1
-    names = ["-", "noncontact rows", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "noncontact impedance", "-", "BARRIER WAIT after solve (= cost@smooth + solver helper loop)"] + ["-"] * 5 + ["worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)"] + ["-"] * 6
+    names = ["-", "noncontact rows", "BARRIER WAIT after head", "BARRIER WAIT after presolve", "noncontact impedance", "subtree sums (its half)", "BARRIER WAIT after solve (= cost@smooth + solver helper loop)", "wait for the side wave's sweep", "sites + actuator forces", "wait for the contact-row layout (owner)", "contact-row headers", "-"] + ["worker: wait for a job", "worker: cone rows (column loop)", "worker: flag", "worker: zero the partial", "worker: row setup (t = B J)"] + ["-"] * 6
 tot = prof[:, :(23 if W == 0 else 22)].sum(1).mean()
 print(f"rollout us {out['rollouts_compute_time_us']:.0f}; mean stamped ticks/candidate {tot:.3e} ")
 for i, n in enumerate(names):

@@ -475,6 +475,42 @@ int mjpc_hip_step_batch(MjpcHipEngine *e, int n, const double *states, const dou
 int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const double *u, const double *time, const double *mocap,
                            const double *userdata, double eps, int centered, int last_is_terminal, double *A, double *B, double *C,
                            double *D, int *failure);
+/* ---- Batched inverse dynamics and its finite-difference derivatives ----------------------------------------------------------
+ * What the reference's direct trajectory optimiser and batch estimator spend their time in (mjpc/direct/direct.cc:1545-1576: one
+ * mj_inverse per configuration of a window; :1717-1756: one mjd_inverseFD per configuration, 1 + 3nv independent inverse evaluations
+ * one-sided, 1 + 6nv centred).  ds = nq+nv+na, nr = num_residual.
+ *
+ * mjpc_hip_inverse_batch: row i of `states` / `ctrl` / `qacc` / `time` is ONE inverse evaluation, no solver iteration in it:
+ *   qfrc_constraint[i][nv] = J' f, f the force law of the step's constraint rows at jar = J a - aref (may be NULL)
+ *   qfrc_inverse[i][nv]    = M a + qfrc_bias - qfrc_passive - qfrc_constraint: MuJoCo's meaning, actuator forces are NOT subtracted, so
+ *                            the acceleration of a forward step gives back qfrc_actuator
+ *   residual[i][nr]        the task residual at (qpos, qvel, act, ctrl) as mjpc_hip_step_batch reports it (may be NULL); the late rows
+ *                            (accelerations, accelerometer / gyro / velocimeter, touch) are evaluated at the GIVEN acceleration and the
+ *                            inverse constraint forces, as mj_sensorAcc does behind mj_inverse
+ *   failure[i]             the MJPC_WARN_* bits (0 = ok): bad state, full contact / constraint buffers, and MJPC_WARN_BADQACC when
+ *                            qacc[i] is not finite
+ * discrete != 0 (mjENBL_INVDISCRETE, what direct/ sets): qacc is the discrete-time acceleration (v' - v) / timestep of a step and is first
+ * converted to the continuous one, a = M^-1 (A qacc) with A the matrix the integrator solves with: M + timestep diag(damping) for Euler,
+ * the same plus the tendon-damping / actuator-bias velocity terms for implicitfast (a term is skipped while its actuator's force sits on
+ * its forcerange, as in the step), A = M without damping.  Then inverse_batch(discrete = 1) at (x, u, (v' - v) / timestep) of a forward
+ * step returns that step's qfrc_actuator and qfrc_constraint up to the solver's convergence (models without a noslip pass).  Models with
+ * the dense implicit integrators (MJPC_INT_IMPLICIT, implicitfast with fluid forces) are refused for discrete != 0: an error of the call,
+ * no output is written.  mocap / userdata are shared by the batch.  n is unbounded (launches of at most max_local workgroups).
+ * Blocking.  A failed row is not an error of the call: its failure[i] is set, and its outputs are NaN where the evaluation never got
+ * there.  Errors: a plan in flight, n < 1, null inputs, max_horizon < 2, the refusal above.
+ *
+ * mjpc_hip_inverse_fd: for each configuration t < T, row-major, with f = qfrc_inverse and s = the residual of inverse_batch,
+ *   DfDq[t][nv][nv], DfDv[t][nv][nv], DfDa[t][nv][nv], DsDq[t][nr][nv], DsDv[t][nr][nv], DsDa[t][nr][nv]      (any may be NULL)
+ * entry [i][j] = d out_i / d in_j (mjd_inverseFD stores the transpose).  A position nudge is mjpc_hip_transition_fd's; velocities and
+ * accelerations add eps; activations and controls are not differentiated.  One-sided (y(+eps) - y(base)) / eps, centred
+ * (y(+eps) - y(-eps)) / (2 eps).  failure[t] = OR of the warning bits of every evaluation at t; the columns a failed evaluation feeds
+ * are left as computed.  T is unbounded.  Blocking.  Errors: as above, and eps <= 0. */
+int mjpc_hip_inverse_batch(MjpcHipEngine *e, int n, const double *states, const double *ctrl, const double *qacc, const double *time,
+                           const double *mocap, const double *userdata, int discrete, double *qfrc_inverse, double *qfrc_constraint,
+                           double *residual, int *failure);
+int mjpc_hip_inverse_fd(MjpcHipEngine *e, int T, const double *states, const double *ctrl, const double *qacc, const double *time,
+                        const double *mocap, const double *userdata, int discrete, double eps, int centered, double *DfDq, double *DfDv,
+                        double *DfDa, double *DsDq, double *DsDv, double *DsDa, int *failure);
 /* ---- State estimators: the device half of an unscented and an extended Kalman filter update ---------------------------------
  * mjpc/estimators/unscented.cc, kalman.cc.  nd = 2nv+na, ds = nq+nv+na.  The measurement is rows [sensor_first_row,
  * sensor_first_row + ns) of the engine's residual as mjpc_hip_step_batch reports it (the reference's estimator_sensor_start: one

@@ -379,6 +379,41 @@ class ModelDerivatives {
   std::vector<int> gfail_;
 };
 
+// mjpc/direct/direct.cc:1641-1830 (Direct::InverseDynamicsDerivatives): the Jacobians of the inverse dynamics f = qfrc_inverse and of
+// the sensors s = the task's residual with respect to configuration, velocity and acceleration along a window of T configurations,
+// what the direct optimiser and the batch estimator linearise around.  The reference runs one mjd_inverseFD per configuration on its
+// thread pool; here the window goes to the device in ONE mjpc_hip_inverse_fd call.  Blocks are row-major per configuration and NOT
+// transposed: DfDq[t] is [nv][nv] with entry [i][j] = d f_i / d q_j, DsDq[t] is [nr][nv] (direct.cc transposes mjd_inverseFD's
+// output into this form).  The ends of the window follow the reference:
+//   t = 0      evaluated at zero velocity and acceleration; only DsDq is kept, and of it only the position-stage rows
+//   t = T - 1  evaluated at zero acceleration; only DsDq and DsDv are kept, and of them not the acceleration-stage rows
+// Every other block of the two ends is zero (the device computes all six blocks for every configuration and the ends are zeroed on the
+// host afterwards: the reference passes NULL for the blocks it drops there, so 2 of T configurations do some unused work in exchange for
+// one call).  The stage of a residual row (the reference's sensor_needstage) comes from the task's
+// table (RowStagesFromTable); rows of a task without a table count as acceleration stage.
+class InverseDerivatives {
+ public:
+  enum { kStagePos = 0, kStageVel = 1, kStageAcc = 2 };
+  void Allocate(int dim_state /* nq + nv + na */, int nq, int nv, int dim_action, int dim_sensor, int T);
+  void Reset(int T);                                   // zero the first T blocks
+  void SetRowStages(const int* stage);                 // [dim_sensor] of kStage*; Allocate sets every row to kStageAcc
+  // the stages of a MJPC_TASK_TABLE residual: a block takes the latest stage among its terms (velocities: kStageVel; actuator forces
+  // and every late kind: kStageAcc).  false (and nothing written) when the task is not a table
+  static bool RowStagesFromTable(const MjpcHipTask* task, int* stage);
+  // x [T][dim_state], u [T][dim_action], a [T][nv], h [T] = the configurations' times; tol = the finite-difference eps, mode =
+  // flg_centered, discrete = mjENBL_INVDISCRETE.  T < 1 is an error; false after an engine error (mjpc_hip_last_error)
+  bool Compute(MjpcHipEngine* engine, const double* x, const double* u, const double* a, const double* h, int T, double tol, int mode, int discrete,
+               const double* mocap = nullptr, const double* userdata = nullptr);
+
+  std::vector<double> DfDq, DfDv, DfDa, DsDq, DsDv, DsDa;
+  std::vector<int> failure;                            // [T]: MJPC_WARN_* bits of the evaluations at t
+  std::vector<int> row_stage;                          // [dim_sensor]
+  int dim_state = 0, dim_q = 0, dim_v = 0, dim_action = 0, dim_sensor = 0;
+
+ private:
+  std::vector<double> gx_, ga_;
+};
+
 // mjpc/planners/cost_derivatives.{h,cc}: derivatives of the cost along a trajectory from the residual and its Jacobians.  The
 // reference's third thread-pool fan-out (one task per knot) is ONE mjpc_hip_cost_derivatives call; the cost table and risk are the
 // engine's current task, so Compute takes no norms / weights / parameters.  crr is not materialised (a dense type's Hessian is

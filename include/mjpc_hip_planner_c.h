@@ -6,6 +6,7 @@
  *                                                             mjpc/planners/planner.h:38-101)
  *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
  *   mjpc_md_*       -> mjpc::ModelDerivatives                 (mjpc/planners/model_derivatives.h:30-70)
+ *   mjpc_id_*       -> mjpc::Direct::InverseDynamicsDerivatives (mjpc/direct/direct.cc:1641-1830)
  *   mjpc_cd_* / mjpc_gd_* -> mjpc::CostDerivatives, mjpc::Gradient (mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h)
  *   mjpc_ilqg_* / mjpc_ilqs_* -> mjpc::iLQGPlanner, mjpc::iLQSPlanner (mjpc/planners/ilqg/planner.h, planners/ilqs/planner.h)
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
@@ -138,6 +139,20 @@ void mjpc_md_interpolate(void *md);
 void mjpc_md_indices(void *md, int *evaluate, int *interpolate, int *n);
 /* the first T blocks: store != 0 copies the arrays INTO the object (tests fill the evaluated blocks), else out of it; any pointer may be NULL */
 void mjpc_md_blocks(void *md, int T, int store, double *A, double *B, double *C, double *D, int *failure);
+
+/* InverseDerivatives (mjpc/direct/direct.cc:1641-1830, Direct::InverseDynamicsDerivatives): the six blocks of mjpc_hip_inverse_fd along a
+ * window, with the window's ends as the reference keeps them (include/mjpc_hip_planner.h).  create = Allocate + Reset. */
+void *mjpc_id_create(int dim_state /* nq + nv + na */, int nq, int nv, int dim_action, int dim_sensor, int T);
+void mjpc_id_destroy(void *id);
+/* stage[dim_sensor] of 0 (position), 1 (velocity), 2 (acceleration); from a MJPC_TASK_TABLE task: 0 = ok, -1 = not a table of dim_sensor rows */
+void mjpc_id_set_row_stages(void *id, const int *stage);
+int mjpc_id_row_stages_from_table(void *id, const MjpcHipTask *task);
+void mjpc_id_row_stages(void *id, int *stage);
+/* 0 = ok, -1 = refused (T < 1: through the error handler) or engine error (mjpc_hip_last_error) */
+int mjpc_id_compute(void *id, MjpcHipEngine *engine, const double *x, const double *u, const double *a, const double *h, int T, double tol, int mode,
+                    int discrete, const double *mocap, const double *userdata);
+/* the first T blocks out of the object; any pointer may be NULL */
+void mjpc_id_blocks(void *id, int T, double *DfDq, double *DfDv, double *DfDa, double *DsDq, double *DsDv, double *DsDa, int *failure);
 
 /* CostDerivatives (mjpc/planners/cost_derivatives.h): create = Allocate + Reset; compute on the caller's engine under its current task.
  * 0 = ok, -1 = engine error (mjpc_hip_last_error). */

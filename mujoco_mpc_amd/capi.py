@@ -308,6 +308,8 @@ def load_engine():
     lib.mjpc_hip_sample_gradient.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p, c_double_p]
     lib.mjpc_hip_step_batch.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [c_double_p, c_double_p, c_int_p]
     lib.mjpc_hip_transition_fd.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [C.c_double, C.c_int, C.c_int] + [c_double_p] * 4 + [c_int_p]
+    lib.mjpc_hip_inverse_batch.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 6 + [C.c_int] + [c_double_p] * 3 + [c_int_p]
+    lib.mjpc_hip_inverse_fd.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 6 + [C.c_int, C.c_double, C.c_int] + [c_double_p] * 6 + [c_int_p]
     lib.mjpc_hip_unscented_moments.argtypes = ([C.c_void_p, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, C.c_double] + [c_double_p] * 4
                                                + [C.c_int, C.c_int] + [c_double_p] * 6 + [c_int_p])
     lib.mjpc_hip_linearize_step.argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, C.c_double, C.c_int] + [c_double_p] * 4 + [c_int_p]
@@ -378,7 +380,7 @@ EXPORTED_SYMBOLS = [
     "mjpc_hip_debug_spill", "mjpc_hip_debug_spill_layout",
     "mjpc_hip_plan_mixed_async", "mjpc_hip_plan_mixed", "mjpc_hip_noise_history_reset", "mjpc_hip_sample_gradient",
     "mjpc_hip_plan_feedback_async", "mjpc_hip_plan_feedback", "mjpc_hip_feedback_resample_time_us", "mjpc_hip_sizeof_feedback_policy",
-    "mjpc_hip_step_batch", "mjpc_hip_transition_fd", "mjpc_hip_unscented_moments", "mjpc_hip_linearize_step", "mjpc_hip_cost_derivatives", "mjpc_hip_trajectory_gradient",
+    "mjpc_hip_step_batch", "mjpc_hip_transition_fd", "mjpc_hip_inverse_batch", "mjpc_hip_inverse_fd", "mjpc_hip_unscented_moments", "mjpc_hip_linearize_step", "mjpc_hip_cost_derivatives", "mjpc_hip_trajectory_gradient",
     "mjpc_hip_ilqg_backward_pass", "mjpc_hip_trajectory_ilqg", "mjpc_hip_riccati_layout_bytes",
     "mjpc_hip_multi_create", "mjpc_hip_multi_destroy", "mjpc_hip_multi_set_task", "mjpc_hip_multi_plan", "mjpc_hip_multi_get_candidate",
     "mjpc_hip_multi_get_knots", "mjpc_hip_multi_get_traces", "mjpc_hip_multi_num_devices", "mjpc_hip_multi_engine",

@@ -64,6 +64,31 @@ static inline void lay(Carve &c, FdLay &f, const Dims &d, size_t Tg, int centere
   lay_fd_ints(c, f, d, Tg);
 }
 
+// ------------------------------------------------------------------------------ the inverse kernel's tables, R rows
+struct InvTab { double *state, *ctrl, *time, *qacc, *qfrc, *qfrc_constraint, *residual; int *fail; };
+static inline void lay_inv_rows(Carve &c, InvTab &t, const Dims &d, size_t R) {
+  t.state = c.take<double>(R * d.ds); t.ctrl = c.take<double>(R * d.nu); t.time = c.take<double>(R); t.qacc = c.take<double>(R * d.nv);
+  t.qfrc = c.take<double>(R * d.nv); t.qfrc_constraint = c.take<double>(R * d.nv); t.residual = c.take<double>(R * d.nr);
+}
+// mjpc_hip_inverse_batch
+static inline void lay(Carve &c, InvTab &t, const Dims &d, size_t R) {
+  lay_inv_rows(c, t, d, R);
+  c.take<double>(CARVE_SPARE_DOUBLES);
+  t.fail = c.take<int>(R);
+}
+// mjpc_hip_inverse_fd: one pass over Tg configurations; the six blocks stand in the order DfDq, DfDv, DfDa, DsDq, DsDv, DsDa
+struct InvFdLay { size_t R; InvTab t; double *x, *u, *a, *time, *Df[3], *Ds[3]; int *failure, *dofmap; };
+static inline size_t inv_fd_rows_per_config(const Dims &d, int centered) { return 1 + (centered ? 6 : 3) * d.nv; }
+static inline void lay(Carve &c, InvFdLay &f, const Dims &d, size_t Tg, int centered) {
+  f.R = Tg * inv_fd_rows_per_config(d, centered);
+  lay_inv_rows(c, f.t, d, f.R);
+  f.x = c.take<double>(Tg * d.ds); f.u = c.take<double>(Tg * d.nu); f.a = c.take<double>(Tg * d.nv); f.time = c.take<double>(Tg);
+  for (int k = 0; k < 3; k++) f.Df[k] = c.take<double>(Tg * d.nv * d.nv);
+  for (int k = 0; k < 3; k++) f.Ds[k] = c.take<double>(Tg * d.nr * d.nv);
+  c.take<double>(CARVE_SPARE_DOUBLES);
+  f.t.fail = c.take<int>(f.R); f.failure = c.take<int>(Tg); f.dofmap = c.take<int>(2 * d.nv + 2);
+}
+
 // ------------------------------------------------------------------------------ cost derivatives
 // what cd_kernel writes; the Hessians only on request (null otherwise)
 struct CdOut { double *cr, *cx, *cu, *cxx, *cuu, *cxu; };

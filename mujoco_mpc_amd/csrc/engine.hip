@@ -13,6 +13,10 @@
 //                   rollout kernel's phases from that row's own state, control and time (mjpc_hip_step_batch)
 //   fd_assemble_kernel / fd_difference_kernel  (transition_fd.h)  mjpc_hip_transition_fd: the perturbed table around the nominal
 //                   knots, and the A / B / C / D entries from the stepped rows
+//   inv_kernel     (rollout_inv_cached / _direct / _spill.hip, inverse.h)  one workgroup per ROW of a state / acceleration table: one inverse-
+//                   dynamics evaluation behind the rollout kernel's pre-solve phases, no solver (mjpc_hip_inverse_batch)
+//   ifd_assemble_kernel / ifd_difference_kernel  (inverse_fd.h)  mjpc_hip_inverse_fd: the perturbed table around the nominal
+//                   configurations, and the six blocks df/d(q, v, a), ds/d(q, v, a) from the evaluated rows
 //   ukf_sigma_kernel / ukf_mean_kernel / ukf_cov_kernel  (estimator.h)  mjpc_hip_unscented_moments: the sigma-point table around a mean
 //                   state, and the weighted means, difference table and covariance blocks of the stepped rows
 //   cd_kernel / gd_backward_kernel  (cost_derivatives.h)  mjpc_hip_cost_derivatives / mjpc_hip_trajectory_gradient: the cost derivatives of
@@ -37,6 +41,7 @@
 #include "philox.h"
 #include "gradient.h"
 #include "transition_fd.h"
+#include "inverse_fd.h"
 #include "estimator.h"
 #include "cost_derivatives.h"
 #include "riccati.h"
@@ -62,6 +67,14 @@ typedef void (*StepLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_
   extern "C" void mjpc_launch_step_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, double *, double *, int *, const int *);
 MJPC_STEP_DECL(cached) MJPC_STEP_DECL(direct) MJPC_STEP_DECL(spill)
 #undef MJPC_STEP_DECL
+// the inverse-dynamics kernels (rollout_inv_*.hip, inv_tu.h): opaque here as well
+typedef void (*InvLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *state_tab, const double *ctrl_tab,
+                            const double *time_tab, const double *qacc_tab, int discrete, double *qfrc_inverse_out, double *qfrc_constraint_out,
+                            double *residual_out, int *failure_out, const int *late_tab);
+#define MJPC_INV_DECL(tu) extern "C" const void *mjpc_pick_inv_##tu(int nv); \
+  extern "C" void mjpc_launch_inv_##tu(const void *, int, size_t, hipStream_t, const KParams *, const double *, const double *, const double *, const double *, int, double *, double *, double *, int *, const int *);
+MJPC_INV_DECL(cached) MJPC_INV_DECL(direct) MJPC_INV_DECL(spill)
+#undef MJPC_INV_DECL
 // the feedback-policy rollout kernels (rollout_fb_*.hip, feedback_tu.h): opaque here as well
 typedef void (*FbLaunchFn)(const void *fn, int n, size_t lds_bytes, hipStream_t stream, const KParams *K, const double *xbar, const double *ubar,
                            const double *kbar, const double *Kbar, const double *alpha, const double *scale);
@@ -152,6 +165,35 @@ extern "C" __global__ void __launch_bounds__(FD_TILE * FD_TILE) fd_difference_ke
   }
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
     int w = wave_or_i(fd_failure(a, t, (int)threadIdx.x, 64));
+    if (threadIdx.x == 0) a.failure[t] = w;
+  }
+}
+
+// mjpc_hip_inverse_fd, table assembly: one wave per table row, its lanes walk the row's ds + nu + 1 + nv elements
+extern "C" __global__ void __launch_bounds__(256) ifd_assemble_kernel(const InvFdArgs a, unsigned rows) {
+  const size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= rows) return;
+  const int n = ifd_row_elements(a);
+  for (int i = threadIdx.x & 63; i < n; i += 64) ifd_assemble(a, g, i);
+}
+
+// mjpc_hip_inverse_fd, differences: block (x, y, z) owns the FD_TILE x FD_TILE tile of configuration z's combined matrix
+// [DfDq DfDv DfDa; DsDq DsDv DsDa] at output rows y * FD_TILE, columns x * FD_TILE, turned in LDS as in fd_difference_kernel
+extern "C" __global__ void __launch_bounds__(FD_TILE * FD_TILE) ifd_difference_kernel(const InvFdArgs a) {
+  __shared__ double tile[FD_TILE][FD_TILE + 1];
+  const int t = blockIdx.z, o0 = blockIdx.y * FD_TILE, c0 = blockIdx.x * FD_TILE;
+  const int no = a.nv + a.nr, nc = 3 * a.nv;
+  {
+    const int oi = threadIdx.x % FD_TILE, ci = threadIdx.x / FD_TILE, o = o0 + oi, c = c0 + ci;
+    if (o < no && c < nc && ifd_dest(a, t, o, c)) tile[oi][ci] = ifd_entry(a, t, o, c);
+  }
+  __syncthreads();
+  {
+    const int ci = threadIdx.x % FD_TILE, oi = threadIdx.x / FD_TILE, o = o0 + oi, c = c0 + ci;
+    if (o < no && c < nc) { double *d = ifd_dest(a, t, o, c); if (d) *d = tile[oi][ci]; }
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
+    int w = wave_or_i(ifd_failure(a, t, (int)threadIdx.x, 64));
     if (threadIdx.x == 0) a.failure[t] = w;
   }
 }
@@ -419,6 +461,8 @@ struct MjpcHipEngine {
   bool cost_rows_ok = false;   // cost_rows_tile of the current task
   // one-step kernel (mjpc_hip_step_batch / mjpc_hip_transition_fd): picked at the first call, in the full-capacity rollout's flavour
   const void *step_kernel = nullptr; StepLaunchFn step_launch = nullptr;
+  // inverse-dynamics kernel (mjpc_hip_inverse_batch / mjpc_hip_inverse_fd): picked at the first call, same flavour
+  const void *inv_kernel = nullptr; InvLaunchFn inv_launch = nullptr;
   // feedback rollout kernel (mjpc_hip_plan_feedback): picked at the first call, in the full-capacity rollout's flavour
   const void *fb_kernel = nullptr; FbLaunchFn fb_launch = nullptr;
   hipEvent_t ev_fb[2] = {nullptr, nullptr}; int fb_resampled = 0; double fb_resample_us = 0;
@@ -1116,6 +1160,115 @@ int mjpc_hip_transition_fd(MjpcHipEngine *e, int T, const double *x, const doubl
     if (nr * nd) HIPCHK(hipMemcpyAsync(C + t0 * nr * nd, a.C, sizeof(double) * Tg * nr * nd, hipMemcpyDeviceToHost, e->stream));
     if (Tw && nr * nu) HIPCHK(hipMemcpyAsync(D + t0 * nr * nu, a.D, sizeof(double) * Tw * nr * nu, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(failure + t0, a.failure, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ batched inverse dynamics, FD derivatives
+// common front of mjpc_hip_inverse_batch / mjpc_hip_inverse_fd: the refusal of the discrete form for the dense implicit integrators (before
+// anything is touched), step_prepare's checks, inputs and parameters, and the inverse kernel of the engine's flavour
+static int inverse_prepare(MjpcHipEngine *e, const char *who, const double *mocap, const double *userdata, int discrete, KParams *Kout) {
+  if (discrete && e->K.M.int_dense) {
+    set_error(std::string(who) + ": discrete != 0 is not built for models with a dense implicit integrator (mjINT_IMPLICIT, implicitfast with fluid forces): "
+              "the integrator's matrix needs the velocity derivative of the bias forces; use discrete = 0");
+    return -1;
+  }
+  // (step_prepare also picks the step kernel of the flavour and sets its LDS attribute at the engine's first one-step call: an inverse call
+  // never launches it, the coupling only loads that kernel's code object early; its checks, staged inputs and parameters are what is wanted)
+  int rc = step_prepare(e, who, mocap, userdata, Kout);
+  if (rc != 0) return rc;
+  if (!e->inv_kernel) {
+    const void *k = e->spill ? mjpc_pick_inv_spill(e->nv) : e->cached ? mjpc_pick_inv_cached(e->nv) : mjpc_pick_inv_direct(e->nv);
+    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
+    e->inv_kernel = k;
+    e->inv_launch = e->spill ? mjpc_launch_inv_spill : e->cached ? mjpc_launch_inv_cached : mjpc_launch_inv_direct;
+  }
+  return 0;
+}
+
+// rows [0, rows) of the tables through the inverse kernel, at most max_local workgroups per launch (stream-ordered, as step_rows)
+static void inverse_rows(MjpcHipEngine *e, const KParams &K, size_t rows, const InvTab &t, int discrete) {
+  const int *late = e->pm.late_blocks ? e->at<int>(B_IB) + e->pm.late_i0 : nullptr;
+  for (size_t r0 = 0; r0 < rows; r0 += (size_t)e->max_local) {
+    const int nl = (int)(rows - r0 < (size_t)e->max_local ? rows - r0 : (size_t)e->max_local);
+    e->inv_launch(e->inv_kernel, nl, e->lds_bytes, e->stream, &K, t.state + r0 * e->ds, t.ctrl + r0 * e->nu, t.time + r0, t.qacc + r0 * e->nv, discrete,
+                  t.qfrc + r0 * e->nv, t.qfrc_constraint + r0 * e->nv, t.residual + r0 * e->nr, t.fail + r0, late);
+  }
+}
+
+int mjpc_hip_inverse_batch(MjpcHipEngine *e, int n, const double *states, const double *ctrl, const double *qacc, const double *time, const double *mocap,
+                           const double *userdata, int discrete, double *qfrc_inverse, double *qfrc_constraint, double *residual, int *failure) {
+  if (!e) { set_error("mjpc_hip_inverse_batch: invalid argument"); return -1; }
+  if (n < 1) { set_error("mjpc_hip_inverse_batch: n < 1"); return -1; }
+  if (!states || !time || !qacc || (e->nu > 0 && !ctrl) || !qfrc_inverse || !failure) { set_error("mjpc_hip_inverse_batch: null input"); return -1; }
+  KParams K;
+  discrete = discrete ? 1 : 0;
+  int rc = inverse_prepare(e, "mjpc_hip_inverse_batch", mocap, userdata, discrete, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv;
+  for (size_t p0 = 0; p0 < (size_t)n; p0 += STEP_PASS_ROWS) {
+    const size_t R = (size_t)n - p0 < STEP_PASS_ROWS ? (size_t)n - p0 : STEP_PASS_ROWS;
+    InvTab t;
+    PLACE(B_FD, t, e->dims(), R);
+    HIPCHK(hipMemcpyAsync(t.state, states + p0 * ds, sizeof(double) * R * ds, hipMemcpyHostToDevice, e->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(t.ctrl, ctrl + p0 * nu, sizeof(double) * R * nu, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(t.time, time + p0, sizeof(double) * R, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(t.qacc, qacc + p0 * nv, sizeof(double) * R * nv, hipMemcpyHostToDevice, e->stream));
+    inverse_rows(e, K, R, t, discrete);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(qfrc_inverse + p0 * nv, t.qfrc, sizeof(double) * R * nv, hipMemcpyDeviceToHost, e->stream));
+    if (qfrc_constraint) HIPCHK(hipMemcpyAsync(qfrc_constraint + p0 * nv, t.qfrc_constraint, sizeof(double) * R * nv, hipMemcpyDeviceToHost, e->stream));
+    if (nr && residual) HIPCHK(hipMemcpyAsync(residual + p0 * nr, t.residual, sizeof(double) * R * nr, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(failure + p0, t.fail, sizeof(int) * R, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  return 0;
+}
+
+int mjpc_hip_inverse_fd(MjpcHipEngine *e, int T, const double *states, const double *ctrl, const double *qacc, const double *time, const double *mocap,
+                        const double *userdata, int discrete, double eps, int centered, double *DfDq, double *DfDv, double *DfDa, double *DsDq,
+                        double *DsDv, double *DsDa, int *failure) {
+  if (!e) { set_error("mjpc_hip_inverse_fd: invalid argument"); return -1; }
+  if (T < 1) { set_error("mjpc_hip_inverse_fd: T < 1"); return -1; }
+  if (!(eps > 0)) { set_error("mjpc_hip_inverse_fd: eps <= 0"); return -1; }
+  if (!states || !time || !qacc || (e->nu > 0 && !ctrl) || !failure) { set_error("mjpc_hip_inverse_fd: null input"); return -1; }
+  KParams K;
+  discrete = discrete ? 1 : 0; centered = centered ? 1 : 0;
+  int rc = inverse_prepare(e, "mjpc_hip_inverse_fd", mocap, userdata, discrete, &K);
+  if (rc != 0) return rc;
+  const size_t ds = e->ds, nu = e->nu, nr = e->nr, nv = e->nv;
+  const std::vector<int> dofmap = fd_dofmap(e);
+  const size_t E = inv_fd_rows_per_config(e->dims(), centered), Tg_max = STEP_PASS_ROWS / E < 1 ? 1 : STEP_PASS_ROWS / E;
+  double *const Df[3] = {DfDq, DfDv, DfDa}, *const Ds[3] = {DsDq, DsDv, DsDa};
+  for (size_t t0 = 0; t0 < (size_t)T; t0 += Tg_max) {
+    const size_t Tg = (size_t)T - t0 < Tg_max ? (size_t)T - t0 : Tg_max;
+    InvFdLay L;
+    PLACE(B_FD, L, e->dims(), Tg, centered);
+    HIPCHK(hipMemcpyAsync(L.x, states + t0 * ds, sizeof(double) * Tg * ds, hipMemcpyHostToDevice, e->stream));
+    if (nu) HIPCHK(hipMemcpyAsync(L.u, ctrl + t0 * nu, sizeof(double) * Tg * nu, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(L.a, qacc + t0 * nv, sizeof(double) * Tg * nv, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(L.time, time + t0, sizeof(double) * Tg, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(L.dofmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+    InvFdArgs a;
+    a.x = L.x; a.u = L.u; a.a = L.a; a.time = L.time; a.dofmap = L.dofmap;
+    a.T = (int)Tg; a.nq = e->nq; a.nv = e->nv; a.na = e->na; a.nu = e->nu; a.nr = e->nr; a.centered = centered;
+    a.eps = eps; a.cs = cos(0.5 * eps); a.sn = sin(0.5 * eps);
+    a.state_tab = L.t.state; a.ctrl_tab = L.t.ctrl; a.time_tab = L.t.time; a.qacc_tab = L.t.qacc; a.qfrc = L.t.qfrc; a.residual = L.t.residual; a.fail = L.t.fail;
+    // a block the caller does not want is not computed
+    a.DfDq = Df[0] ? L.Df[0] : nullptr; a.DfDv = Df[1] ? L.Df[1] : nullptr; a.DfDa = Df[2] ? L.Df[2] : nullptr;
+    a.DsDq = Ds[0] && nr ? L.Ds[0] : nullptr; a.DsDv = Ds[1] && nr ? L.Ds[1] : nullptr; a.DsDa = Ds[2] && nr ? L.Ds[2] : nullptr;
+    a.failure = L.failure;
+    hipLaunchKernelGGL(ifd_assemble_kernel, dim3((unsigned)((L.R + 3) / 4)), dim3(256), 0, e->stream, a, (unsigned)L.R);
+    inverse_rows(e, K, L.R, L.t, discrete);
+    hipLaunchKernelGGL(ifd_difference_kernel, dim3((unsigned)((3 * nv + FD_TILE - 1) / FD_TILE), (unsigned)((nv + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tg),
+                       dim3(FD_TILE * FD_TILE), 0, e->stream, a);
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < 3; k++) {
+      if (Df[k]) HIPCHK(hipMemcpyAsync(Df[k] + t0 * nv * nv, L.Df[k], sizeof(double) * Tg * nv * nv, hipMemcpyDeviceToHost, e->stream));
+      if (Ds[k] && nr) HIPCHK(hipMemcpyAsync(Ds[k] + t0 * nr * nv, L.Ds[k], sizeof(double) * Tg * nr * nv, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(failure + t0, L.failure, sizeof(int) * Tg, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   return 0;

@@ -944,6 +944,73 @@ bool ModelDerivatives::Compute(MjpcHipEngine* engine, const double* x, const dou
   return true;
 }
 
+// ------------------------------------------------------------------ InverseDerivatives
+void InverseDerivatives::Allocate(int ds, int nq, int nv, int nu, int nr, int T) {
+  dim_state = ds; dim_q = nq; dim_v = nv; dim_action = nu; dim_sensor = nr;
+  for (std::vector<double>* b : {&DfDq, &DfDv, &DfDa}) b->resize((size_t)T * nv * nv);
+  for (std::vector<double>* b : {&DsDq, &DsDv, &DsDa}) b->resize((size_t)T * nr * nv);
+  failure.resize(T);
+  row_stage.assign(nr, kStageAcc);
+}
+
+void InverseDerivatives::Reset(int T) {
+  if ((size_t)T > failure.size()) { std::vector<int> keep = row_stage; Allocate(dim_state, dim_q, dim_v, dim_action, dim_sensor, T); row_stage = keep; }
+  const size_t nv = dim_v, nr = dim_sensor;
+  for (std::vector<double>* b : {&DfDq, &DfDv, &DfDa}) std::fill(b->begin(), b->begin() + (size_t)T * nv * nv, 0.0);
+  for (std::vector<double>* b : {&DsDq, &DsDv, &DsDa}) std::fill(b->begin(), b->begin() + (size_t)T * nr * nv, 0.0);
+  std::fill(failure.begin(), failure.begin() + T, 0);
+}
+
+void InverseDerivatives::SetRowStages(const int* stage) { row_stage.assign(stage, stage + dim_sensor); }
+
+bool InverseDerivatives::RowStagesFromTable(const MjpcHipTask* task, int* stage) {
+  if (!task || task->task_id != MJPC_TASK_TABLE || task->num_int < 3 || !task->int_data) return false;
+  const int* d = task->int_data;
+  const int nblock = d[1], nterm = d[2];
+  if (nblock < 0 || nterm < 0 || task->num_int < 3 + 6 * nblock + 4 * nterm) return false;
+  const int *B = d + 3, *Tm = B + 6 * nblock;
+  for (int i = 0; i < task->num_residual; i++) stage[i] = kStagePos;
+  for (int b = 0; b < nblock; b++, B += 6) {
+    int st = kStagePos;
+    for (int j = B[4]; j < B[4] + B[5] && j < nterm; j++) {
+      const int kind = Tm[4 * j];
+      const int ks = (kind >= MJPC_TBL_QACC || kind == MJPC_TBL_ACTUATOR_FORCE) ? kStageAcc
+                     : (kind == MJPC_TBL_QVEL || kind == MJPC_TBL_SUBTREE_LINVEL || kind == MJPC_TBL_LINVEL || kind == MJPC_TBL_ANGVEL) ? kStageVel : kStagePos;
+      if (ks > st) st = ks;
+    }
+    for (int i = B[1]; i < B[1] + B[2] && i < task->num_residual; i++) if (i >= 0) stage[i] = st;
+  }
+  return true;
+}
+
+bool InverseDerivatives::Compute(MjpcHipEngine* engine, const double* x, const double* u, const double* a, const double* h, int T, double tol, int mode,
+                                 int discrete, const double* mocap, const double* userdata) {
+  if (T < 1) { Fatal("InverseDerivatives: T < 1"); return false; }
+  if (dim_state < 1) { Fatal("InverseDerivatives: not allocated"); return false; }
+  const size_t ds = dim_state, nq = dim_q, nv = dim_v, nr = dim_sensor;
+  Reset(T);
+  // the window's rows with the ends as the reference evaluates them: zero velocity and acceleration at 0, zero acceleration at T - 1
+  gx_.assign(x, x + (size_t)T * ds); ga_.assign(a, a + (size_t)T * nv);
+  std::fill(gx_.begin() + nq, gx_.begin() + nq + nv, 0.0);
+  std::fill(ga_.begin(), ga_.begin() + nv, 0.0);
+  std::fill(ga_.begin() + (size_t)(T - 1) * nv, ga_.begin() + (size_t)T * nv, 0.0);
+  if (mjpc_hip_inverse_fd(engine, T, gx_.data(), u, ga_.data(), h, mocap, userdata, discrete, tol, mode, DfDq.data(), DfDv.data(), DfDa.data(),
+                          nr ? DsDq.data() : nullptr, nr ? DsDv.data() : nullptr, nr ? DsDa.data() : nullptr, failure.data()) != 0) return false;
+  auto zero_block = [&](std::vector<double>& b, size_t t, size_t rows) { std::fill(b.begin() + t * rows * nv, b.begin() + (t + 1) * rows * nv, 0.0); };
+  auto zero_rows = [&](std::vector<double>& b, size_t t, int from_stage) {
+    for (size_t i = 0; i < nr; i++) if (row_stage[i] >= from_stage) std::fill(b.begin() + (t * nr + i) * nv, b.begin() + (t * nr + i + 1) * nv, 0.0);
+  };
+  // the last configuration first: a window of one configuration is a first one
+  if (T > 1) {
+    const size_t t = (size_t)T - 1;
+    zero_block(DfDq, t, nv); zero_block(DfDv, t, nv); zero_block(DfDa, t, nv); zero_block(DsDa, t, nr);
+    zero_rows(DsDq, t, kStageAcc); zero_rows(DsDv, t, kStageAcc);
+  }
+  zero_block(DfDq, 0, nv); zero_block(DfDv, 0, nv); zero_block(DfDa, 0, nv); zero_block(DsDv, 0, nr); zero_block(DsDa, 0, nr);
+  zero_rows(DsDq, 0, kStageVel);
+  return true;
+}
+
 // ------------------------------------------------------------------ CostDerivatives
 void CostDerivatives::Allocate(int nd, int nu, int nr, int T) {
   dim_state_derivative = nd; dim_action = nu; dim_residual = nr; horizon = T;
@@ -3121,6 +3188,32 @@ void mjpc_ilqg_policy_action(int nq, int nv, int na, int nu, int njnt, const int
   p.feedback_gain.assign(feedback_gain, feedback_gain + H * nu * nd);
   p.feedback_scaling = feedback_scaling;
   p.Action(action, state, time);
+}
+
+// ---- InverseDerivatives
+void* mjpc_id_create(int dim_state, int nq, int nv, int nu, int nr, int T) { auto* d = new mjpc_hip::InverseDerivatives(); d->Allocate(dim_state, nq, nv, nu, nr, T); d->Reset(T); return d; }
+void mjpc_id_destroy(void* id) { delete (mjpc_hip::InverseDerivatives*)id; }
+void mjpc_id_set_row_stages(void* id, const int* stage) { ((mjpc_hip::InverseDerivatives*)id)->SetRowStages(stage); }
+int mjpc_id_row_stages_from_table(void* id, const MjpcHipTask* task) {
+  auto* d = (mjpc_hip::InverseDerivatives*)id;
+  if (!task || task->num_residual != d->dim_sensor) return -1;
+  std::vector<int> st(d->dim_sensor + 1);
+  if (!mjpc_hip::InverseDerivatives::RowStagesFromTable(task, st.data())) return -1;
+  d->SetRowStages(st.data());
+  return 0;
+}
+void mjpc_id_row_stages(void* id, int* stage) { auto* d = (mjpc_hip::InverseDerivatives*)id; std::copy(d->row_stage.begin(), d->row_stage.end(), stage); }
+int mjpc_id_compute(void* id, MjpcHipEngine* engine, const double* x, const double* u, const double* a, const double* h, int T, double tol, int mode,
+                    int discrete, const double* mocap, const double* userdata) {
+  return ((mjpc_hip::InverseDerivatives*)id)->Compute(engine, x, u, a, h, T, tol, mode, discrete, mocap, userdata) ? 0 : -1;
+}
+void mjpc_id_blocks(void* id, int T, double* DfDq, double* DfDv, double* DfDa, double* DsDq, double* DsDv, double* DsDa, int* failure) {
+  auto* d = (mjpc_hip::InverseDerivatives*)id;
+  const size_t nf = (size_t)T * d->dim_v * d->dim_v, ns = (size_t)T * d->dim_sensor * d->dim_v;
+  double* out[6] = {DfDq, DfDv, DfDa, DsDq, DsDv, DsDa};
+  const std::vector<double>* src[6] = {&d->DfDq, &d->DfDv, &d->DfDa, &d->DsDq, &d->DsDv, &d->DsDa};
+  for (int k = 0; k < 6; k++) if (out[k]) std::copy(src[k]->begin(), src[k]->begin() + (k < 3 ? nf : ns), out[k]);
+  if (failure) std::copy(d->failure.begin(), d->failure.begin() + T, failure);
 }
 
 // ---- ModelDerivatives

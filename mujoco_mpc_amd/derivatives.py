@@ -8,8 +8,9 @@ current cost table.  gradient_compute: the gradient planner's backward recursion
 HipBackend.trajectory_gradient runs on the device behind the two.  What iLQG, the gradient planner and iLQS linearise around; the gradient
 planner itself is cplanner.GradientPlanner.  ILQGBackwardPass, boxqp and ilqg_policy_action are iLQG's backward pass (Riccati recursion, box-constrained
 control solve, regularisation loop) and policy, on the host and on the device (HipBackend.ilqg_backward_pass / trajectory_ilqg); iLQG's feedback rollouts
-and line search, and iLQS, are not part of this package.  No CPU fallback: the step evaluations and the cost derivatives
-are the engine's kernels.
+and line search, and iLQS, are not part of this package.  InverseDerivatives: the six Jacobians of the inverse dynamics along a window (one
+mjpc_hip_inverse_fd call), what the reference's direct optimiser and batch estimator linearise around; the optimiser itself is not part
+of this package.  No CPU fallback: the step and inverse evaluations and the cost derivatives are the engine's kernels.
 """
 from __future__ import annotations
 
@@ -37,6 +38,14 @@ def _lib():
         lib.mjpc_md_interpolate.argtypes = [C.c_void_p]; lib.mjpc_md_interpolate.restype = None
         lib.mjpc_md_indices.argtypes = [C.c_void_p, _ip, _ip, _ip]; lib.mjpc_md_indices.restype = None
         lib.mjpc_md_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip]; lib.mjpc_md_blocks.restype = None
+        lib.mjpc_id_create.restype = C.c_void_p
+        lib.mjpc_id_create.argtypes = [C.c_int] * 6
+        lib.mjpc_id_destroy.argtypes = [C.c_void_p]; lib.mjpc_id_destroy.restype = None
+        lib.mjpc_id_set_row_stages.argtypes = [C.c_void_p, _ip]; lib.mjpc_id_set_row_stages.restype = None
+        lib.mjpc_id_row_stages_from_table.argtypes = [C.c_void_p, C.POINTER(capi.MjpcHipTask)]
+        lib.mjpc_id_row_stages.argtypes = [C.c_void_p, _ip]; lib.mjpc_id_row_stages.restype = None
+        lib.mjpc_id_compute.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]
+        lib.mjpc_id_blocks.argtypes = [C.c_void_p, C.c_int] + [_dp] * 6 + [_ip]; lib.mjpc_id_blocks.restype = None
         lib.mjpc_cd_create.restype = C.c_void_p
         lib.mjpc_cd_create.argtypes = [C.c_int] * 4
         lib.mjpc_cd_destroy.argtypes = [C.c_void_p]; lib.mjpc_cd_destroy.restype = None
@@ -115,6 +124,60 @@ class CostDerivatives:
         nd, nu, nr = self.nd, self.nu, self.nr
         o = dict(cr=np.zeros((T, nr)), cx=np.zeros((T, nd)), cu=np.zeros((T, nu)), cxx=np.zeros((T, nd, nd)), cuu=np.zeros((T, nu, nu)), cxu=np.zeros((T, nd, nu)))
         self.lib.mjpc_cd_blocks(self.h, T, *[_ptr(o[k]) for k in ("cr", "cx", "cu", "cxx", "cuu", "cxu")])
+        return o
+
+
+class InverseDerivatives:
+    """DfDq, DfDv, DfDa [T, nv, nv] and DsDq, DsDv, DsDa [T, nr, nv] of the inverse dynamics along a window of T configurations
+    (mjpc_hip::InverseDerivatives; Direct::InverseDynamicsDerivatives of the reference): one mjpc_hip_inverse_fd call, then the window's
+    ends as the reference keeps them.  At t = 0 (evaluated at zero velocity and acceleration) only the position-stage rows of DsDq, at
+    t = T - 1 (zero acceleration) only DsDq and DsDv without their acceleration-stage rows; every other block there is zero.  The row
+    stages (0 position, 1 velocity, 2 acceleration) come from the task's residual table; without a table every row counts as
+    acceleration stage until set_row_stages."""
+
+    def __init__(self, model: dict, task: dict, T=2):
+        nq, nv, na = model["nq"], model["nv"], model["na"]
+        self.ds, self.nq, self.nv, self.nu, self.nr = nq + nv + na, nq, nv, model["nu"], task["num_residual"]
+        self.T = int(T)
+        self.lib = _lib()
+        self.h = C.c_void_p(self.lib.mjpc_id_create(self.ds, nq, nv, self.nu, self.nr, self.T))
+        self._cm = capi.CModel(model, task)
+        self.lib.mjpc_id_row_stages_from_table(self.h, C.byref(self._cm.c_task))      # -1: not a table, the rows stay acceleration stage
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mjpc_id_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def row_stages(self):
+        st = np.zeros(max(self.nr, 1), np.int32)
+        self.lib.mjpc_id_row_stages(self.h, st.ctypes.data_as(_ip))
+        return st[:self.nr]
+
+    def set_row_stages(self, stage):
+        st = np.ascontiguousarray(stage, dtype=np.int32).reshape(self.nr)
+        self.lib.mjpc_id_set_row_stages(self.h, (st if st.size else np.zeros(1, np.int32)).ctypes.data_as(_ip))
+
+    def compute(self, backend: HipBackend, x, u, a, h, tol=1e-6, mode=0, discrete=True, mocap=None, userdata=None):
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, self.nu); a = np.ascontiguousarray(a, dtype=np.float64).reshape(T, self.nv)
+        h = np.ascontiguousarray(h, dtype=np.float64).reshape(T)
+        mo, ud, pmo, pud = backend._shared(mocap, userdata)
+        rc = self.lib.mjpc_id_compute(self.h, backend.h, _ptr(x), _ptr(u), _ptr(a), _ptr(h), T, float(tol), int(mode), int(bool(discrete)), pmo, pud)
+        cplanner._check()
+        if rc != 0:
+            raise RuntimeError("InverseDerivatives.compute failed: " + self.lib.mjpc_hip_last_error().decode())
+        self.T = max(self.T, T)
+        nv, nr = self.nv, self.nr
+        names = ("DfDq", "DfDv", "DfDa", "DsDq", "DsDv", "DsDa")
+        o = {k: np.zeros((T, nv if i < 3 else nr, nv)) for i, k in enumerate(names)}
+        o["failure"] = np.zeros(T, np.int32)
+        self.lib.mjpc_id_blocks(self.h, T, *[_ptr(o[k]) for k in names], o["failure"].ctypes.data_as(_ip))
         return o
 
 

@@ -195,6 +195,48 @@ class HipBackend:
             raise RuntimeError("mjpc_hip_transition_fd failed: " + self.lib.mjpc_hip_last_error().decode())
         return o
 
+    def inverse_batch(self, states, ctrl, qacc, time, mocap=None, userdata=None, discrete=False, fill=0.0):
+        """One inverse-dynamics evaluation at each of n configurations (mjpc_hip_inverse_batch): states [n, nq+nv+na], ctrl [n, nu],
+        qacc [n, nv], time [n] -> dict(qfrc_inverse [n, nv], qfrc_constraint [n, nv], residual [n, nr] with the late rows at the given
+        acceleration, failure [n] MJPC_WARN_* bits).  discrete: qacc is a step's (v' - v) / timestep.  A refused call (discrete on a
+        model with a dense implicit integrator) raises and writes nothing: the outputs would have kept `fill`."""
+        ds, _, nu, nr = self._dims()
+        nv = self.model["nv"]
+        x = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, ds); n = x.shape[0]
+        u = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(n, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(n)
+        a = np.ascontiguousarray(qacc, dtype=np.float64).reshape(n, nv)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(qfrc_inverse=np.full((n, nv), float(fill)), qfrc_constraint=np.full((n, nv), float(fill)), residual=np.full((n, nr), float(fill)),
+                 failure=np.zeros(n, np.int32))
+        dp = capi.c_double_p
+        ptr = lambda v: (v if v.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_inverse_batch(self.h, n, ptr(x), ptr(u), ptr(a), ptr(t), pmo, pud, int(bool(discrete)), ptr(o["qfrc_inverse"]),
+                                             ptr(o["qfrc_constraint"]), ptr(o["residual"]), o["failure"].ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_inverse_batch failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
+    def inverse_fd(self, x, u, qacc, time, mocap=None, userdata=None, discrete=False, eps=1e-6, centered=False, want=(1,) * 6, fill=0.0):
+        """Finite-difference derivatives of the inverse dynamics at T configurations (mjpc_hip_inverse_fd): dict(DfDq, DfDv, DfDa
+        [T, nv, nv], DsDq, DsDv, DsDa [T, nr, nv], failure [T]), entry [i][j] = d out_i / d in_j.  want: which of the six blocks are
+        asked for, in that order (the others are not computed and come back as None)."""
+        ds, _, nu, nr = self._dims()
+        nv = self.model["nv"]
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, ds); T = x.shape[0]
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(T, nu); t = np.ascontiguousarray(time, dtype=np.float64).reshape(T)
+        a = np.ascontiguousarray(qacc, dtype=np.float64).reshape(T, nv)
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        names = ["DfDq", "DfDv", "DfDa", "DsDq", "DsDv", "DsDa"]
+        o = {k: (np.full((T, nv if i < 3 else nr, nv), float(fill)) if want[i] else None) for i, k in enumerate(names)}
+        o["failure"] = np.zeros(T, np.int32)
+        dp = capi.c_double_p
+        ptr = lambda v: None if v is None else (v if v.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_inverse_fd(self.h, T, ptr(x), ptr(u), ptr(a), ptr(t), pmo, pud, int(bool(discrete)), float(eps), int(bool(centered)),
+                                          *[ptr(o[k]) for k in names], o["failure"].ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_inverse_fd failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
     def unscented_moments(self, state, factor, sigma_step, weights, ctrl, time, noise_process, noise_sensor, sensor_first_row=0, num_sensor=None,
                           mocap=None, userdata=None, sigma_next=True):
         """The device half of an unscented filter update (mjpc_hip_unscented_moments): the 2nd+1 sigma points around `state` from the lower

@@ -615,6 +615,83 @@ int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const dou
                              const double *mocap, const double *userdata, double eps, int centered, const MjpcHipRiccatiSettings *s,
                              double *regularization, double *regularization_rate, double *k, double *K, double *Vx, double *Vxx, double *Qx,
                              double *Qu, double *Qxx, double *Qxu, double *Quu, double *dV, int *status, int *failure);
+/* ---- The direct optimiser's window cost: gradient and band Hessian (mjpc/direct/direct.cc:683-1480, 1945-2106) -----------------------
+ * A window is T >= 3 configurations of nv dofs; ntotal = nv T, nband = 3 nv.  Its cost is
+ *   sum_t sum_i w_ti Norm_i(s_ti - y_ti)  +  sum_{0 < t < T-1} 0.5 (f_t - tau_t)' diag(w_f) (f_t - tau_t)
+ * over the sensors i (runs of rows of the engine's residual, starting at sensor_first_row, as for mjpc_hip_unscented_moments) and the
+ * inverse-dynamics force f, with v_t = differentiatePos(q_{t-1}, q_t) / h and a_t = (v_{t+1} - v_t) / h, so that configuration t's
+ * terms depend on q_{t-1}, q_t, q_{t+1} alone and the Gauss-Newton Hessian is banded.
+ *   w_ti = time_weight / noise_sensor[i] / sensor_dim[i] / T, time_weight = 1 / h^2 / h^4 for a position / velocity / acceleration stage
+ *     sensor under time_scaling_sensor (else 1); times first_step_position_sensors at t = 0, times (last_step_position_sensors ||
+ *     last_step_velocity_sensors) at t = T - 1; a sensor whose sensor_mask[t][i] is 0 is left out
+ *   w_f[j] = h^4 / noise_process[j] / nv / (T - 2) (1 in place of h^4 without time_scaling_force)
+ *   at t = 0 the residual of every sensor that is not position stage is zero; at t = T - 1 a position (velocity) stage sensor's
+ *     residual stays under last_step_position_sensors (last_step_velocity_sensors), every other is zero
+ * sensor_stage: 0 position, 1 velocity, 2 acceleration.  sensor_norm / sensor_norm_parameter [num_sensor][2]: the cost table's norm
+ * types and {p, q}.
+ *
+ * mjpc_hip_direct_assemble: the algebra alone, on the caller's arrays.
+ *   in   residual_sensor [T][ns] = prediction - measurement, residual_force [T][nv] (rows 0 and T - 1 are not read), before any
+ *        zeroing; the six blocks of mjpc_hip_inverse_fd, [T][nv][nv] and [T][nr][nv], as that call returns them: the ends' rules of
+ *        mjpc_hip::InverseDerivatives (t = 0 keeps the position-stage rows of DsDq alone; t = T - 1 keeps DsDq and DsDv without their
+ *        acceleration-stage rows) are applied here, to what is read; dvdq0, dvdq1 [T][nv][nv] = dv_t/dq_{t-1}, dv_t/dq_t (index 0 is
+ *        not read)
+ *   out  cost [3] = {cost, cost_sensor, cost_force}; gradient [ntotal]; hessian_band [ntotal][nband], MuJoCo's lower band (row R
+ *        holds columns R - nband + 1 .. R, the diagonal at column nband - 1, leading zeros in front of column 0)
+ *   optional (NULL: not copied)  block_sensor [T][ns][nband], block_force [T][nv][nband]: configuration t's Jacobian, column c standing
+ *        for global column nv (t - 1) + c (t = 0: columns nv .. 2 nv alone; t = T - 1: the first 2 nv; what a configuration does
+ *        not have is zero); norm_gradient_sensor [T][ns], norm_gradient_force [T][nv] (the latter weighted, as the reference's);
+ *        residual_sensor_out [T][ns], residual_force_out [T][nv]: the residuals behind the zeroing rules
+ * One owner per output entry; an entry's sensor part is summed over ascending t and within t over ascending sensor, its force part
+ * over ascending t, the total is sensor + force, by the summation rule of mjpc_hip_cost_derivatives (`/` and sqrt correctly rounded):
+ * no atomics, two calls give the same bits, mjpc_hip::DirectCost::AssembleHost gives the same bits.  The engine lends its device and
+ * stream only (nv, nr are the caller's).  Blocking.  Errors, before anything is touched: a plan in flight, T < 3, nv < 1, null inputs,
+ * settings->struct_size, num_sensor < 0, a sensor dimension < 1, dimensions that do not sum to num_sensor_rows, sensor rows outside
+ * [0, nr), a stage outside 0 .. 2, a noise value <= 0, timestep <= 0. */
+typedef struct MjpcHipDirectSettings {
+  int struct_size;                        /* sizeof(MjpcHipDirectSettings) */
+  int num_sensor, sensor_first_row, num_sensor_rows;
+  const int *sensor_dim, *sensor_stage, *sensor_norm;     /* [num_sensor] */
+  const double *sensor_norm_parameter;    /* [num_sensor][2] */
+  const double *noise_sensor;             /* [num_sensor] */
+  const double *noise_process;            /* [nv] */
+  const int *sensor_mask;                 /* [T][num_sensor]; NULL: every sensor on */
+  int sensor_flag, force_flag, time_scaling_sensor, time_scaling_force;
+  int first_step_position_sensors, last_step_position_sensors, last_step_velocity_sensors;
+  double timestep;                        /* h */
+} MjpcHipDirectSettings;
+/* mjpc_hip_direct_cost: the cost alone of nwin >= 1 candidate windows in one call (a line search is one launch of the inverse kernel over
+ * nwin T rows): q [nwin][T][nq], act [nwin][T][na], ctrl [nwin][T][nu] per window; time [T], sensor_measurement [T][ns],
+ * force_measurement [T][nv], the mask, mocap and userdata are shared.  On the device: the windows' rows (v_t = differentiatePos(q_{t-1},
+ * q_t) / h, a_t = (v_{t+1} - v_t) / h, a quaternion dof's velocity the body-frame rotation vector in the feedback rollouts' spelling; v_0
+ * = a_0 = a_{T-1} = 0) written into the inverse kernel's table, the existing inverse kernel, the residuals, norms and one reduction per
+ * window.  cost [nwin][3] = {cost, cost_sensor, cost_force}; optional (NULL: not copied) velocity, acceleration [nwin][T][nv],
+ * sensor_prediction [nwin][T][ns], force_prediction [nwin][T][nv], failure [nwin][T] (the evaluation's MJPC_WARN_* bits: they do not stop
+ * the call).  settings->timestep is h.
+ *
+ * mjpc_hip_direct_cost_derivatives: one window, everything on the device with nothing downloaded in between: the window's rows and the
+ * velocity blocks dv_t/dq_{t-1}, dv_t/dq_t (-1/h, 1/h on plain coordinates, the 3 x 3 blocks of the quaternion difference over h on ball
+ * and free-rotation dofs, with the reference's swapped argument order), mjpc_hip_inverse_fd's table, evaluations and differences, the
+ * residuals of the base evaluations, and the algebra of mjpc_hip_direct_assemble on the blocks where they lie.  Required: cost [3],
+ * gradient, hessian_band; every other output is optional.  failure [T].  The costs are the bits mjpc_hip_direct_cost gives for the
+ * same window.
+ * Errors of both, before anything is touched: those of mjpc_hip_direct_assemble, nwin < 1, fd_eps <= 0, discrete != 0 on an int_dense
+ * model (as mjpc_hip_inverse_fd), a window beyond one pass of the inverse tables, a plan in flight. */
+int mjpc_hip_direct_cost(MjpcHipEngine *e, int nwin, int T, const MjpcHipDirectSettings *s, int discrete, const double *q, const double *act,
+                         const double *ctrl, const double *time, const double *sensor_measurement, const double *force_measurement,
+                         const double *mocap, const double *userdata, double *cost, double *velocity, double *acceleration,
+                         double *sensor_prediction, double *force_prediction, int *failure);
+int mjpc_hip_direct_cost_derivatives(MjpcHipEngine *e, int T, const MjpcHipDirectSettings *s, double fd_eps, int centered, int discrete,
+                                     const double *q, const double *act, const double *ctrl, const double *time, const double *sensor_measurement,
+                                     const double *force_measurement, const double *mocap, const double *userdata, double *cost, double *gradient,
+                                     double *hessian_band, double *block_sensor, double *block_force, double *norm_gradient_sensor,
+                                     double *norm_gradient_force, double *residual_sensor, double *residual_force, double *DfDq, double *DfDv,
+                                     double *DfDa, double *DsDq, double *DsDv, double *DsDa, double *dvdq0, double *dvdq1, int *failure);
+int mjpc_hip_direct_assemble(MjpcHipEngine *e, int T, int nv, int nr, const MjpcHipDirectSettings *s, const double *residual_sensor,
+                             const double *residual_force, const double *DfDq, const double *DfDv, const double *DfDa, const double *DsDq,
+                             const double *DsDv, const double *DsDa, const double *dvdq0, const double *dvdq1, double *cost, double *gradient,
+                             double *hessian_band, double *block_sensor, double *block_force, double *norm_gradient_sensor,
+                             double *norm_gradient_force, double *residual_sensor_out, double *residual_force_out);
 /* ---- Rollouts under a feedback policy (iLQG's ActionRollouts / FeedbackRollouts, mjpc/planners/ilqg/planner.cc:618-712) ------------
  * Candidate i of the batch applies at step t < H-1, with x_t its own state at that step,
  *   u = clamp( (ubar[t] + action_step[i] * kbar[t]) + feedback_scaling[i] * ( Kbar[t] * StateDiff(xbar[t], x_t) ), ctrlrange )

@@ -414,6 +414,65 @@ class InverseDerivatives {
   std::vector<double> gx_, ga_;
 };
 
+// mjpc/direct/direct.cc:683-1480, 1945-2106 (Direct::Cost with gradient and Hessian, from BlockSensor / BlockForce to TotalHessian): the
+// cost of a window of T >= 3 configurations, its gradient [nv T] and its Gauss-Newton Hessian in MuJoCo's lower band [nv T][3 nv],
+// from the residuals, the six blocks of InverseDerivatives and the velocity blocks dv_t/dq_{t-1}, dv_t/dq_t.  The formulas, the layout
+// and the order of every sum are those of mjpc_hip_direct_assemble (include/mjpc_hip.h).  Assemble runs them on the device;
+// AssembleHost is the same algebra on the host by the same summation rule (this library is compiled without contraction) and gives
+// the device's bits, as Gradient and iLQGBackwardPass give theirs'.  The sensors are runs of rows of the engine's residual.
+// Cost and CostDerivatives evaluate the window it owns on the device (mjpc_hip_direct_cost, mjpc_hip_direct_cost_derivatives).
+// Not here yet: the band solve and the optimiser's loop.
+class DirectCost {
+ public:
+  enum { kStagePos = 0, kStageVel = 1, kStageAcc = 2 };
+  struct Settings {            // direct.h's defaults
+    bool sensor_flag = true, force_flag = true, time_scaling_sensor = true, time_scaling_force = true;
+    bool first_step_position_sensors = true, last_step_position_sensors = false, last_step_velocity_sensors = false;
+  } settings;
+  double timestep = 0.0;
+
+  void Allocate(int nv, int nr, int T);                // noise_process = 1, no sensors, no mask
+  // num_sensor sensors of dim[i] rows each, the first at residual row first_row; stage [num_sensor] of kStage*, norm [num_sensor] the cost
+  // table's norm types, norm_parameter [num_sensor][2] = {p, q}, noise [num_sensor].  Clears the mask
+  void SetSensors(int first_row, int num_sensor, const int* dim, const int* stage, const int* norm, const double* norm_parameter, const double* noise);
+  void SetProcessNoise(const double* noise);           // [nv]
+  void SetMask(const int* mask, int T);                // [T][num_sensor]; null: every sensor on
+  // residual_sensor [T][ns], residual_force [T][nv], DfD* [T][nv][nv], DsD* [T][nr][nv], dvdq0, dvdq1 [T][nv][nv].  false after a
+  // refusal (Assemble: mjpc_hip_last_error; AssembleHost refuses what the engine refuses, through the planner's error handler)
+  bool Assemble(MjpcHipEngine* engine, int T, const double* residual_sensor, const double* residual_force, const double* DfDq, const double* DfDv,
+                const double* DfDa, const double* DsDq, const double* DsDv, const double* DsDa, const double* dvdq0, const double* dvdq1);
+  bool AssembleHost(int T, const double* residual_sensor, const double* residual_force, const double* DfDq, const double* DfDv, const double* DfDa,
+                    const double* DsDq, const double* DsDv, const double* DsDa, const double* dvdq0, const double* dvdq1);
+
+  // The window (Direct's configuration, act, ctrl, times, sensor_measurement, force_measurement) for Cost and CostDerivatives: T
+  // configurations of the engine's model; act / ctrl / measurements null: zeros.  sensor_measurement [T][ns], force_measurement [T][nv]
+  void SetWindow(int T, int nq, int na, int nu, const double* q, const double* act, const double* ctrl, const double* time,
+                 const double* sensor_measurement, const double* force_measurement);
+  double fd_tolerance = 1.0e-6;                        // finite-difference eps
+  int fd_mode = 0, discrete = 1;                       // flg_centered, mjENBL_INVDISCRETE
+  // the cost alone of nwin candidate windows q_windows [nwin][T][nq] (null: the window itself) in ONE mjpc_hip_direct_cost call, the
+  // window's act, ctrl and measurements shared; costs [nwin][3].  false after an engine error (mjpc_hip_last_error)
+  bool Cost(MjpcHipEngine* engine, const double* q_windows, int nwin, const double* mocap = nullptr, const double* userdata = nullptr);
+  // cost, gradient, band Hessian and blocks of the window in ONE mjpc_hip_direct_cost_derivatives call, nothing downloaded in between
+  bool CostDerivatives(MjpcHipEngine* engine, const double* mocap = nullptr, const double* userdata = nullptr);
+  std::vector<double> configuration, act, ctrl, times, sensor_measurement, force_measurement;
+  std::vector<double> costs;                           // [nwin][3] of the last Cost
+  std::vector<int> failure;                            // [nwin][T] of the last Cost, [T] of the last CostDerivatives
+  int window_length = 0, dim_q = 0, dim_act = 0, dim_action = 0;
+
+  double cost[3] = {0.0, 0.0, 0.0};                    // cost, cost_sensor, cost_force
+  std::vector<double> gradient, hessian_band;          // [nv T], [nv T][3 nv]
+  std::vector<double> block_sensor, block_force;       // [T][ns][3 nv], [T][nv][3 nv]
+  std::vector<double> norm_gradient_sensor, norm_gradient_force, residual_sensor, residual_force;      // [T][ns], [T][nv]
+  std::vector<int> sensor_dim, sensor_stage, sensor_norm, sensor_mask;
+  std::vector<double> sensor_norm_parameter, noise_sensor, noise_process;
+  int dim_v = 0, dim_residual = 0, sensor_first_row = 0, num_sensor_rows = 0;
+
+ private:
+  void Size(int T);
+  MjpcHipDirectSettings View(int T) const;
+};
+
 // mjpc/planners/cost_derivatives.{h,cc}: derivatives of the cost along a trajectory from the residual and its Jacobians.  The
 // reference's third thread-pool fan-out (one task per knot) is ONE mjpc_hip_cost_derivatives call; the cost table and risk are the
 // engine's current task, so Compute takes no norms / weights / parameters.  crr is not materialised (a dense type's Hessian is

@@ -7,6 +7,7 @@
  *   mjpc_cem_* / mjpc_robust_* / mjpc_sg_* -> CrossEntropyPlanner / RobustPlanner / SampleGradientPlanner
  *   mjpc_md_*       -> mjpc::ModelDerivatives                 (mjpc/planners/model_derivatives.h:30-70)
  *   mjpc_id_*       -> mjpc::Direct::InverseDynamicsDerivatives (mjpc/direct/direct.cc:1641-1830)
+ *   mjpc_dc_*       -> mjpc::Direct::Cost with gradient and band Hessian, the algebra on given blocks (mjpc/direct/direct.cc:683-1480, 1945-2106)
  *   mjpc_cd_* / mjpc_gd_* -> mjpc::CostDerivatives, mjpc::Gradient (mjpc/planners/cost_derivatives.h, planners/gradient/gradient.h)
  *   mjpc_ilqg_* / mjpc_ilqs_* -> mjpc::iLQGPlanner, mjpc::iLQSPlanner (mjpc/planners/ilqg/planner.h, planners/ilqs/planner.h)
  * Handles are opaque; errors go through the installed handler (default: print + abort, like mju_error).
@@ -153,6 +154,33 @@ int mjpc_id_compute(void *id, MjpcHipEngine *engine, const double *x, const doub
                     int discrete, const double *mocap, const double *userdata);
 /* the first T blocks out of the object; any pointer may be NULL */
 void mjpc_id_blocks(void *id, int T, double *DfDq, double *DfDv, double *DfDa, double *DsDq, double *DsDv, double *DsDa, int *failure);
+
+/* DirectCost (mjpc/direct/direct.cc:683-1480, 1945-2106, Direct::Cost with gradient and Hessian): the window's cost, gradient and band
+ * Hessian from the residuals, the six blocks of mjpc_id_* and the velocity blocks.  set_settings: flags [7] = sensor_flag, force_flag,
+ * time_scaling_sensor, time_scaling_force, first_step_position_sensors, last_step_position_sensors, last_step_velocity_sensors.
+ * assemble: on the device through mjpc_hip_direct_assemble, or with engine == NULL on the host (DirectCost::AssembleHost, the same
+ * bits); 0 = ok, -1 = refused (mjpc_hip_last_error / the planner's error handler).  outputs: any pointer may be NULL. */
+void *mjpc_dc_create(int nv, int nr, int T);
+void mjpc_dc_destroy(void *dc);
+void mjpc_dc_set_sensors(void *dc, int first_row, int num_sensor, const int *dim, const int *stage, const int *norm, const double *norm_parameter,
+                         const double *noise);
+void mjpc_dc_set_process_noise(void *dc, const double *noise);
+void mjpc_dc_set_mask(void *dc, const int *mask, int T);
+void mjpc_dc_set_settings(void *dc, const int *flags, double timestep);
+int mjpc_dc_assemble(void *dc, MjpcHipEngine *engine, int T, const double *residual_sensor, const double *residual_force, const double *DfDq,
+                     const double *DfDv, const double *DfDa, const double *DsDq, const double *DsDv, const double *DsDa, const double *dvdq0,
+                     const double *dvdq1);
+/* the window the object owns, and its evaluation on the device: cost = DirectCost::Cost (nwin candidate windows in one
+ * mjpc_hip_direct_cost call; q_windows NULL: the window itself; costs [nwin][3], failure [nwin][T]), cost_derivatives =
+ * DirectCost::CostDerivatives (one mjpc_hip_direct_cost_derivatives call; the results through mjpc_dc_outputs, failure [T]) */
+void mjpc_dc_set_window(void *dc, int T, int nq, int na, int nu, const double *q, const double *act, const double *ctrl, const double *time,
+                        const double *sensor_measurement, const double *force_measurement);
+void mjpc_dc_set_fd(void *dc, double tolerance, int mode, int discrete);
+int mjpc_dc_cost(void *dc, MjpcHipEngine *engine, const double *q_windows, int nwin, const double *mocap, const double *userdata, double *costs,
+                 int *failure);
+int mjpc_dc_cost_derivatives(void *dc, MjpcHipEngine *engine, const double *mocap, const double *userdata, int *failure);
+void mjpc_dc_outputs(void *dc, double *cost, double *gradient, double *hessian_band, double *block_sensor, double *block_force,
+                     double *norm_gradient_sensor, double *norm_gradient_force, double *residual_sensor, double *residual_force);
 
 /* CostDerivatives (mjpc/planners/cost_derivatives.h): create = Allocate + Reset; compute on the caller's engine under its current task.
  * 0 = ok, -1 = engine error (mjpc_hip_last_error). */

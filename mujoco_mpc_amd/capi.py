@@ -248,6 +248,47 @@ def riccati_settings(regularization_type=0, action_limits_on=1, max_regularizati
     return s
 
 
+class MjpcHipDirectSettings(C.Structure):
+    """include/mjpc_hip.h: the sensors, noises and settings of the direct optimiser's window cost"""
+    _fields_ = [("struct_size", C.c_int), ("num_sensor", C.c_int), ("sensor_first_row", C.c_int), ("num_sensor_rows", C.c_int),
+                ("sensor_dim", c_int_p), ("sensor_stage", c_int_p), ("sensor_norm", c_int_p), ("sensor_norm_parameter", c_double_p),
+                ("noise_sensor", c_double_p), ("noise_process", c_double_p), ("sensor_mask", c_int_p),
+                ("sensor_flag", C.c_int), ("force_flag", C.c_int), ("time_scaling_sensor", C.c_int), ("time_scaling_force", C.c_int),
+                ("first_step_position_sensors", C.c_int), ("last_step_position_sensors", C.c_int), ("last_step_velocity_sensors", C.c_int),
+                ("timestep", C.c_double)]
+
+
+def direct_settings(sensor_dim, sensor_stage, sensor_norm, sensor_norm_parameter, noise_sensor, noise_process, timestep, sensor_first_row=0,
+                    sensor_mask=None, sensor_flag=True, force_flag=True, time_scaling_sensor=True, time_scaling_force=True,
+                    first_step_position_sensors=True, last_step_position_sensors=False, last_step_velocity_sensors=False):
+    """MjpcHipDirectSettings over contiguous copies of the arrays (kept alive on the struct).  sensor_norm_parameter [num_sensor, 2] = {p, q};
+    sensor_mask [T, num_sensor] or None (every sensor on).  The defaults of the flags are the reference's (direct/direct.h)."""
+    keep = []
+
+    def ints(x):
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.int32).ravel()); keep.append(a)
+        return (a if a.size else np.zeros(1, np.int32)).ctypes.data_as(c_int_p)
+
+    def dbls(x):
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel()); keep.append(a)
+        return (a if a.size else np.zeros(1)).ctypes.data_as(c_double_p)
+    s = MjpcHipDirectSettings()
+    s.struct_size = C.sizeof(MjpcHipDirectSettings)
+    dim = np.asarray(sensor_dim, dtype=np.int64).ravel()
+    s.num_sensor = int(dim.size); s.sensor_first_row = int(sensor_first_row); s.num_sensor_rows = int(dim.sum())
+    s.sensor_dim = ints(sensor_dim); s.sensor_stage = ints(sensor_stage); s.sensor_norm = ints(sensor_norm)
+    s.sensor_norm_parameter = dbls(sensor_norm_parameter); s.noise_sensor = dbls(noise_sensor); s.noise_process = dbls(noise_process)
+    if sensor_mask is not None:
+        s.sensor_mask = ints(sensor_mask)
+    s.sensor_flag = int(bool(sensor_flag)); s.force_flag = int(bool(force_flag))
+    s.time_scaling_sensor = int(bool(time_scaling_sensor)); s.time_scaling_force = int(bool(time_scaling_force))
+    s.first_step_position_sensors = int(bool(first_step_position_sensors)); s.last_step_position_sensors = int(bool(last_step_position_sensors))
+    s.last_step_velocity_sensors = int(bool(last_step_velocity_sensors))
+    s.timestep = float(timestep)
+    s._keep = keep
+    return s
+
+
 class MjpcHipFeedbackPolicy(C.Structure):
     """include/mjpc_hip.h: the feedback policy of mjpc_hip_plan_feedback (iLQG's ActionRollouts / FeedbackRollouts)"""
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("T", C.c_int), ("representation", C.c_int),
@@ -319,6 +360,10 @@ def load_engine():
     lib.mjpc_hip_trajectory_ilqg.argtypes = ([C.c_void_p, C.c_int] + [c_double_p] * 6 + [C.c_double, C.c_int, C.POINTER(MjpcHipRiccatiSettings)]
                                              + [c_double_p] * 12 + [c_int_p, c_int_p])
     lib.mjpc_hip_riccati_layout_bytes.argtypes = [C.c_int, C.c_int, c_int_p]
+    lib.mjpc_hip_direct_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MjpcHipDirectSettings), C.c_int] + [c_double_p] * 13 + [c_int_p]
+    lib.mjpc_hip_direct_cost_derivatives.argtypes = ([C.c_void_p, C.c_int, C.POINTER(MjpcHipDirectSettings), C.c_double, C.c_int, C.c_int] + [c_double_p] * 25
+                                                     + [c_int_p])
+    lib.mjpc_hip_direct_assemble.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.POINTER(MjpcHipDirectSettings)] + [c_double_p] * 19
     lib.mjpc_hip_get_knots.argtypes = [C.c_void_p, c_double_p]
     lib.mjpc_hip_get_frame.argtypes = [C.c_void_p] + [c_double_p] * 5
     lib.mjpc_hip_kernel_time.argtypes = [C.c_void_p, c_double_p, c_double_p]
@@ -381,7 +426,7 @@ EXPORTED_SYMBOLS = [
     "mjpc_hip_plan_mixed_async", "mjpc_hip_plan_mixed", "mjpc_hip_noise_history_reset", "mjpc_hip_sample_gradient",
     "mjpc_hip_plan_feedback_async", "mjpc_hip_plan_feedback", "mjpc_hip_feedback_resample_time_us", "mjpc_hip_sizeof_feedback_policy",
     "mjpc_hip_step_batch", "mjpc_hip_transition_fd", "mjpc_hip_inverse_batch", "mjpc_hip_inverse_fd", "mjpc_hip_unscented_moments", "mjpc_hip_linearize_step", "mjpc_hip_cost_derivatives", "mjpc_hip_trajectory_gradient",
-    "mjpc_hip_ilqg_backward_pass", "mjpc_hip_trajectory_ilqg", "mjpc_hip_riccati_layout_bytes",
+    "mjpc_hip_ilqg_backward_pass", "mjpc_hip_trajectory_ilqg", "mjpc_hip_riccati_layout_bytes", "mjpc_hip_direct_assemble", "mjpc_hip_direct_cost", "mjpc_hip_direct_cost_derivatives",
     "mjpc_hip_multi_create", "mjpc_hip_multi_destroy", "mjpc_hip_multi_set_task", "mjpc_hip_multi_plan", "mjpc_hip_multi_get_candidate",
     "mjpc_hip_multi_get_knots", "mjpc_hip_multi_get_traces", "mjpc_hip_multi_num_devices", "mjpc_hip_multi_engine",
 ]

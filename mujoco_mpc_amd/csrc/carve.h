@@ -161,6 +161,69 @@ static inline void lay(Carve &c, IlqgLay &l, const Dims &d, size_t T, int center
   lay_fd_ints(c, l.fd, d, T);
 }
 
+// ------------------------------------------------------------------------------ the direct optimiser's window cost (direct_cost.h)
+// the sensors' description and the mask, uploaded as they are; the ints behind the doubles, two to a double
+struct DcSpec { double *prm, *noise_sensor, *noise_process; int *dim, *first, *stage, *norm, *row_sensor, *mask; };
+static inline void lay(Carve &c, DcSpec &s, size_t T, size_t nv, size_t ns, size_t num_sensor) {
+  s.prm = c.take<double>(2 * num_sensor); s.noise_sensor = c.take<double>(num_sensor); s.noise_process = c.take<double>(nv);
+  s.dim = c.take<int>(num_sensor); s.first = c.take<int>(num_sensor); s.stage = c.take<int>(num_sensor); s.norm = c.take<int>(num_sensor);
+  s.row_sensor = c.take<int>(ns); s.mask = c.take<int>(T * num_sensor);
+  c.align_to<double>();
+}
+// what the dc_* kernels write: per configuration the residuals, norm gradients and Hessian parts, weights and values; the blocks J and
+// N J [T][ns + nv][3 nv]; the band, the gradient and the three costs
+struct DcWork { double *res_s, *ng_s, *hd_s, *hs_s, *w_s, *wy_s, *res_f, *ng_f, *y_f, *Js, *Jf, *NJs, *NJf, *band, *gradient, *cost; };
+static inline void lay(Carve &c, DcWork &w, size_t T, size_t nv, size_t ns, size_t num_sensor) {
+  w.res_s = c.take<double>(T * ns); w.ng_s = c.take<double>(T * ns); w.hd_s = c.take<double>(T * ns);
+  w.hs_s = c.take<double>(2 * T * num_sensor); w.w_s = c.take<double>(T * num_sensor); w.wy_s = c.take<double>(T * num_sensor);
+  w.res_f = c.take<double>(T * nv); w.ng_f = c.take<double>(T * nv); w.y_f = c.take<double>(T);
+  w.Js = c.take<double>(T * ns * 3 * nv); w.Jf = c.take<double>(T * nv * 3 * nv); w.NJs = c.take<double>(T * ns * 3 * nv); w.NJf = c.take<double>(T * nv * 3 * nv);
+  w.band = c.take<double>(T * nv * 3 * nv); w.gradient = c.take<double>(T * nv); w.cost = c.take<double>(3);
+}
+// mjpc_hip_direct_assemble: the caller's arrays (residuals, the six inverse blocks in the order DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, the two
+// velocity blocks), the sensors, the kernels' own
+struct DcLay { double *rs, *rf, *Df[3], *Ds[3], *V0, *V1; DcSpec spec; DcWork work; };
+static inline void lay(Carve &c, DcLay &l, size_t T, size_t nv, size_t nr, size_t ns, size_t num_sensor) {
+  l.rs = c.take<double>(T * ns); l.rf = c.take<double>(T * nv);
+  for (int k = 0; k < 3; k++) l.Df[k] = c.take<double>(T * nv * nv);
+  for (int k = 0; k < 3; k++) l.Ds[k] = c.take<double>(T * nr * nv);
+  l.V0 = c.take<double>(T * nv * nv); l.V1 = c.take<double>(T * nv * nv);
+  lay(c, l.spec, T, nv, ns, num_sensor);
+  lay(c, l.work, T, nv, ns, num_sensor);
+  c.take<double>(CARVE_SPARE_DOUBLES);
+}
+
+// mjpc_hip_direct_cost: nwin windows of T configurations through the inverse kernel's table (R = nwin T rows), value only: the work
+// arrays of every window but no blocks
+struct DcCostLay { InvTab t; double *q, *act, *ctrl, *time, *y_s, *y_f, *rs, *rf; int *dofmap; DcSpec spec; DcWork work; };
+static inline void lay(Carve &c, DcCostLay &l, const Dims &d, size_t W, size_t T, size_t ns, size_t num_sensor) {
+  const size_t R = W * T;
+  lay_inv_rows(c, l.t, d, R);
+  l.q = c.take<double>(R * d.nq); l.act = c.take<double>(R * d.na); l.ctrl = c.take<double>(R * d.nu); l.time = c.take<double>(T);
+  l.y_s = c.take<double>(T * ns); l.y_f = c.take<double>(T * d.nv); l.rs = c.take<double>(R * ns); l.rf = c.take<double>(R * d.nv);
+  lay(c, l.spec, T, d.nv, ns, num_sensor);
+  DcWork &w = l.work;
+  w = DcWork();
+  w.res_s = c.take<double>(R * ns); w.ng_s = c.take<double>(R * ns); w.hd_s = c.take<double>(R * ns);
+  w.hs_s = c.take<double>(2 * R * num_sensor); w.w_s = c.take<double>(R * num_sensor); w.wy_s = c.take<double>(R * num_sensor);
+  w.res_f = c.take<double>(R * d.nv); w.ng_f = c.take<double>(R * d.nv); w.y_f = c.take<double>(R); w.cost = c.take<double>(3 * W);
+  c.take<double>(CARVE_SPARE_DOUBLES);
+  l.t.fail = c.take<int>(R); l.dofmap = c.take<int>(2 * d.nv + 2);
+}
+// mjpc_hip_direct_cost_derivatives: one pass of mjpc_hip_inverse_fd over the window (its nominal rows are written on the device), the
+// window's inputs and measurements, the residuals, the velocity blocks, the sensors, the algebra's work arrays
+struct DcDerivLay { InvFdLay fd; double *q, *act, *ctrl, *time, *y_s, *y_f, *rs, *rf, *V0, *V1; DcSpec spec; DcWork work; };
+static inline void lay(Carve &c, DcDerivLay &l, const Dims &d, size_t T, int centered, size_t ns, size_t num_sensor) {
+  lay(c, l.fd, d, T, centered);
+  c.align_to<double>();
+  l.q = c.take<double>(T * d.nq); l.act = c.take<double>(T * d.na); l.ctrl = c.take<double>(T * d.nu); l.time = c.take<double>(T);
+  l.y_s = c.take<double>(T * ns); l.y_f = c.take<double>(T * d.nv); l.rs = c.take<double>(T * ns); l.rf = c.take<double>(T * d.nv);
+  l.V0 = c.take<double>(T * d.nv * d.nv); l.V1 = c.take<double>(T * d.nv * d.nv);
+  lay(c, l.spec, T, d.nv, ns, num_sensor);
+  lay(c, l.work, T, d.nv, ns, num_sensor);
+  c.take<double>(CARVE_SPARE_DOUBLES);
+}
+
 // ------------------------------------------------------------------------------ unscented moments, ns sensor rows, R = 2 nd + 1 points
 // the block that goes up in one copy; dofmap, qmap: ints, two to a double
 struct UkfIn { double *x, *L, *u, *noise_process, *noise_sensor; int *dofmap, *qmap; };

@@ -44,6 +44,7 @@
 #include "inverse_fd.h"
 #include "estimator.h"
 #include "cost_derivatives.h"
+#include "direct_cost.h"
 #include "riccati.h"
 #include "feedback_resample.h"
 #include "host.h"
@@ -295,6 +296,74 @@ extern "C" __global__ void __launch_bounds__(CD_TILE * CD_TILE) cd_kernel(const 
     fs += ni;
   }
   if (dst) *dst = cd_risk_entry(a, acc, L.gv[CD_TILE + ii], L.gv[jj], s);
+}
+
+// mjpc_hip_direct_cost / _derivatives, the window's rows: one wave per row (w, t), its lanes walk the row's ds + nu + 1 + nv elements
+extern "C" __global__ void __launch_bounds__(256) dc_window_kernel(const DcWinArgs a, unsigned rows) {
+  const size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= rows) return;
+  const int n = a.nq + a.nv + a.na + a.nu + 1 + a.nv;
+  for (int i = threadIdx.x & 63; i < n; i += 64) dc_window_row(a, g, i);
+}
+
+// mjpc_hip_direct_cost_derivatives, velocity blocks: one thread per entry of [T][nv][nv]
+extern "C" __global__ void __launch_bounds__(DC_THREADS) dc_vblock_kernel(const DcWinArgs a, size_t n) {
+  const size_t e = (size_t)blockIdx.x * DC_THREADS + threadIdx.x;
+  if (e < n) dc_velocity_block(a, e);
+}
+
+// mjpc_hip_direct_cost / _derivatives, residuals: one thread per entry of [nwin T][ns + nv]
+extern "C" __global__ void __launch_bounds__(DC_THREADS) dc_residual_kernel(const DcResArgs a, size_t n) {
+  const size_t e = (size_t)blockIdx.x * DC_THREADS + threadIdx.x;
+  if (e < n) dc_residual(a, e);
+}
+
+// mjpc_hip_direct_assemble, norms: block t owns configuration t; its threads walk the sensors, then the dofs of the force term
+extern "C" __global__ void __launch_bounds__(64) dc_norm_kernel(const DcArgs a0) {
+  const DcArgs a = dc_window(a0, (int)blockIdx.y);          // (a value call's windows in y; one window otherwise)
+  const int t = blockIdx.x;
+  for (int i = threadIdx.x; i < a.num_sensor; i += 64) dc_norm_sensor(a, t, i);
+  for (int i = threadIdx.x; i < a.nv; i += 64) dc_norm_force(a, t, i);
+  if (threadIdx.x == 0) a.y_f[t] = dc_force_value(a, t);
+}
+
+// mjpc_hip_direct_assemble, totals: one workgroup per window; thread 0 sums the sensors' weighted norms, thread 1 the force terms
+extern "C" __global__ void __launch_bounds__(64) dc_cost_kernel(const DcArgs a0) {
+  const DcArgs a = dc_window(a0, (int)blockIdx.x);          // one workgroup per window
+  __shared__ double part[2];
+  if (threadIdx.x < 2) part[threadIdx.x] = dc_cost_part(a, (int)threadIdx.x);
+  __syncthreads();
+  if (threadIdx.x == 0) { a.cost[0] = add_rn(part[0], part[1]); a.cost[1] = part[0]; a.cost[2] = part[1]; }
+}
+
+// mjpc_hip_direct_assemble, chain rule: block (x, y, z) owns the DC_TILE x DC_TILE tile of configuration x's block [ns + nv][3 nv] at
+// rows y * DC_TILE, columns z * DC_TILE (the configuration in x: T is unbounded); the contraction over the dofs goes through LDS in
+// chunks of DC_TILE (direct_cost.h)
+extern "C" __global__ void __launch_bounds__(DC_TILE * DC_TILE) dc_block_kernel(const DcArgs a) {
+  __shared__ double dc_sm[DC_TILE_DOUBLES];
+  const DcTiles L = dc_tiles(dc_sm);
+  const int t = blockIdx.x, o0 = blockIdx.y * DC_TILE, c0 = blockIdx.z * DC_TILE, tid = threadIdx.x;
+  double p1 = 0, p2 = 0;
+  for (int k0 = 0; k0 < a.nv; k0 += DC_TILE) {
+    dc_block_stage(a, t, o0, c0, k0, tid, L);
+    __syncthreads();
+    dc_block_accum(a, k0, tid, L, p1, p2);
+    __syncthreads();
+  }
+  dc_block_store(a, t, o0, c0, tid, p1, p2);
+}
+
+// mjpc_hip_direct_assemble, norm Hessian times block: one thread per entry of [T][ns + nv][3 nv], the lanes along a row
+extern "C" __global__ void __launch_bounds__(DC_THREADS) dc_nj_kernel(const DcArgs a, size_t n) {
+  const size_t e = (size_t)blockIdx.x * DC_THREADS + threadIdx.x;
+  if (e < n) dc_nj(a, e);
+}
+
+// mjpc_hip_direct_assemble, gradient and band Hessian: one thread per entry of [ntotal][3 nv + 1], the lanes along a band row (the
+// reads of N J run along its rows, the block's own entry is a broadcast)
+extern "C" __global__ void __launch_bounds__(DC_THREADS) dc_entry_kernel(const DcArgs a, size_t n) {
+  const size_t e = (size_t)blockIdx.x * DC_THREADS + threadIdx.x;
+  if (e < n) dc_entry(a, e);
 }
 
 // mjpc_hip_trajectory_gradient, backward recursion: one workgroup, one lane per column of [A | B]; Vx_t and Qu_{t-1} pass through LDS
@@ -1582,6 +1651,244 @@ int mjpc_hip_trajectory_ilqg(MjpcHipEngine *e, int T, const double *x, const dou
   // failure[] travels behind the block; rc_run zeroes the block alone, so this copy may be queued first
   HIPCHK(hipMemcpyAsync(L.out.failure, f.failure, sizeof(int) * Tz, hipMemcpyDeviceToDevice, e->stream));
   return rc_run(e, g, L.out, Tz, L.scratch, regularization, regularization_rate, k, K, Vx, Vxx, Qx, Qu, Qxx, Qxu, Quu, dV, status, failure);
+}
+
+// ------------------------------------------------------------------------------ the direct optimiser's window cost
+// the settings' checks (every refusal of the header, before anything is touched) and the sensors' row tables
+static int dc_check(const char *w, int T, int nv, int nr, const MjpcHipDirectSettings *s, std::vector<int> &first, std::vector<int> &row_sensor) {
+  const std::string who = w;
+  if (!s || s->struct_size != (int)sizeof(MjpcHipDirectSettings)) { set_error(who + ": MjpcHipDirectSettings.struct_size does not match this library"); return -1; }
+  if (T < 3) { set_error(who + ": T < 3"); return -1; }
+  if (nv < 1) { set_error(who + ": nv < 1"); return -1; }
+  if (s->num_sensor < 0 || s->num_sensor_rows < 0) { set_error(who + ": num_sensor < 0"); return -1; }
+  if (!(s->timestep > 0)) { set_error(who + ": timestep <= 0"); return -1; }
+  if (!s->noise_process || (s->num_sensor && (!s->sensor_dim || !s->sensor_stage || !s->sensor_norm || !s->sensor_norm_parameter || !s->noise_sensor))) {
+    set_error(who + ": null input"); return -1; }
+  if (s->sensor_first_row < 0 || (long long)s->sensor_first_row + s->num_sensor_rows > nr) { set_error(who + ": the sensor rows lie outside the residual"); return -1; }
+  first.assign(s->num_sensor, 0); row_sensor.assign(s->num_sensor_rows, 0);
+  long long rows = 0;
+  for (int i = 0; i < s->num_sensor; i++) {
+    if (s->sensor_dim[i] < 1) { set_error(who + ": a sensor dimension < 1"); return -1; }
+    if (s->sensor_stage[i] < 0 || s->sensor_stage[i] > 2) { set_error(who + ": a sensor stage outside 0 .. 2"); return -1; }
+    if (!(s->noise_sensor[i] > 0)) { set_error(who + ": a sensor noise value <= 0"); return -1; }
+    first[i] = (int)rows;
+    for (int r = 0; r < s->sensor_dim[i] && rows + r < s->num_sensor_rows; r++) row_sensor[rows + r] = i;
+    rows += s->sensor_dim[i];
+  }
+  if (rows != s->num_sensor_rows) { set_error(who + ": the sensor dimensions do not sum to num_sensor_rows"); return -1; }
+  for (int i = 0; i < nv; i++) if (!(s->noise_process[i] > 0)) { set_error(who + ": a process noise value <= 0"); return -1; }
+  return 0;
+}
+
+// the sensors go up; the kernels' arguments over the layout
+static int dc_upload_spec(MjpcHipEngine *e, const DcSpec &d, const DcWork &w, int T, int nv, int nr, const MjpcHipDirectSettings *s, const std::vector<int> &first,
+                          const std::vector<int> &row_sensor, DcArgs *out) {
+  const size_t m = s->num_sensor, ns = s->num_sensor_rows;
+  auto upd = [&](double *dst, const double *src, size_t n) { return n ? hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  auto upi = [&](int *dst, const int *src, size_t n) { return n ? hipMemcpyAsync(dst, src, sizeof(int) * n, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  HIPCHK(upd(d.prm, s->sensor_norm_parameter, 2 * m)); HIPCHK(upd(d.noise_sensor, s->noise_sensor, m)); HIPCHK(upd(d.noise_process, s->noise_process, nv));
+  HIPCHK(upi(d.dim, s->sensor_dim, m)); HIPCHK(upi(d.first, first.data(), m)); HIPCHK(upi(d.stage, s->sensor_stage, m)); HIPCHK(upi(d.norm, s->sensor_norm, m));
+  HIPCHK(upi(d.row_sensor, row_sensor.data(), ns));
+  if (s->sensor_mask) HIPCHK(upi(d.mask, s->sensor_mask, (size_t)T * m));
+  DcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.T = T; a.nv = nv; a.nr = nr; a.ns = (int)ns; a.row0 = s->sensor_first_row; a.num_sensor = (int)m;
+  a.dim = d.dim; a.first = d.first; a.stage = d.stage; a.norm = d.norm; a.row_sensor = d.row_sensor;
+  a.prm = d.prm; a.noise_sensor = d.noise_sensor; a.noise_process = d.noise_process; a.mask = s->sensor_mask ? d.mask : nullptr;
+  a.sensor_flag = s->sensor_flag ? 1 : 0; a.force_flag = s->force_flag ? 1 : 0; a.time_scaling_sensor = s->time_scaling_sensor ? 1 : 0;
+  a.time_scaling_force = s->time_scaling_force ? 1 : 0; a.first_pos = s->first_step_position_sensors ? 1 : 0;
+  a.last_pos = s->last_step_position_sensors ? 1 : 0; a.last_vel = s->last_step_velocity_sensors ? 1 : 0; a.h = s->timestep;
+  a.res_s = w.res_s; a.ng_s = w.ng_s; a.hd_s = w.hd_s; a.hs_s = w.hs_s; a.w_s = w.w_s; a.wy_s = w.wy_s; a.res_f = w.res_f; a.ng_f = w.ng_f; a.y_f = w.y_f;
+  a.Js = w.Js; a.Jf = w.Jf; a.NJs = w.NJs; a.NJf = w.NJf; a.gradient = w.gradient; a.band = w.band; a.cost = w.cost;
+  *out = a;
+  return 0;
+}
+
+// norms, totals, chain rule, N J, gradient and band: five launches in stream order, nothing in between
+static void dc_launch(MjpcHipEngine *e, const DcArgs &a) {
+  const size_t T = a.T, no = (size_t)a.ns + a.nv, nb = 3 * (size_t)a.nv;
+  const size_t n_nj = T * no * nb, n_entry = T * a.nv * (nb + 1);
+  hipLaunchKernelGGL(dc_norm_kernel, dim3((unsigned)T, 1), dim3(64), 0, e->stream, a);
+  hipLaunchKernelGGL(dc_cost_kernel, dim3(1), dim3(64), 0, e->stream, a);
+  hipLaunchKernelGGL(dc_block_kernel, dim3((unsigned)T, (unsigned)((no + DC_TILE - 1) / DC_TILE), (unsigned)((nb + DC_TILE - 1) / DC_TILE)), dim3(DC_TILE * DC_TILE), 0,
+                     e->stream, a);
+  hipLaunchKernelGGL(dc_nj_kernel, dim3((unsigned)((n_nj + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, e->stream, a, n_nj);
+  hipLaunchKernelGGL(dc_entry_kernel, dim3((unsigned)((n_entry + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, e->stream, a, n_entry);
+}
+
+int mjpc_hip_direct_assemble(MjpcHipEngine *e, int T, int nv, int nr, const MjpcHipDirectSettings *s, const double *residual_sensor, const double *residual_force,
+                             const double *DfDq, const double *DfDv, const double *DfDa, const double *DsDq, const double *DsDv, const double *DsDa,
+                             const double *dvdq0, const double *dvdq1, double *cost, double *gradient, double *hessian_band, double *block_sensor,
+                             double *block_force, double *norm_gradient_sensor, double *norm_gradient_force, double *residual_sensor_out, double *residual_force_out) {
+  const char *who = "mjpc_hip_direct_assemble";
+  if (!e) { set_error(std::string(who) + ": invalid argument"); return -1; }
+  if (e->pending) { set_error(std::string(who) + ": a plan step is in flight (call mjpc_hip_plan_fetch first)"); return -1; }
+  std::vector<int> first, row_sensor;
+  if (dc_check(who, T, nv, nr, s, first, row_sensor) != 0) return -1;
+  const size_t Tz = T, n = nv, ns = s->num_sensor_rows, nb = 3 * n;
+  if (nr < 0 || (ns && (!residual_sensor || !DsDq || !DsDv || !DsDa)) || !residual_force || !DfDq || !DfDv || !DfDa || !dvdq0 || !dvdq1 || !cost || !gradient ||
+      !hessian_band) { set_error(std::string(who) + ": null input"); return -1; }
+  // the grids: one block per DC_THREADS entries, the chain rule's tiles in y and z
+  if ((Tz * (ns + n) * nb + DC_THREADS - 1) / DC_THREADS > 0x7fffffffull || (Tz * n * (nb + 1) + DC_THREADS - 1) / DC_THREADS > 0x7fffffffull ||
+      (ns + n + DC_TILE - 1) / DC_TILE > 65535 || (nb + DC_TILE - 1) / DC_TILE > 65535) {
+    set_error(std::string(who) + ": the window is too large for one launch"); return -1; }
+  HIPCHK(hipSetDevice(e->device));
+  DcLay L;
+  PLACE(B_FD, L, Tz, n, (size_t)nr, ns, (size_t)s->num_sensor);
+  auto up = [&](double *dst, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  HIPCHK(up(L.rs, residual_sensor, Tz * ns)); HIPCHK(up(L.rf, residual_force, Tz * n));
+  const double *Df[3] = {DfDq, DfDv, DfDa}, *Ds[3] = {DsDq, DsDv, DsDa};
+  for (int k = 0; k < 3; k++) { HIPCHK(up(L.Df[k], Df[k], Tz * n * n)); if (ns) HIPCHK(up(L.Ds[k], Ds[k], Tz * (size_t)nr * n)); }
+  HIPCHK(up(L.V0, dvdq0, Tz * n * n)); HIPCHK(up(L.V1, dvdq1, Tz * n * n));
+  DcArgs a;
+  int rc = dc_upload_spec(e, L.spec, L.work, T, nv, nr, s, first, row_sensor, &a);
+  if (rc != 0) return rc;
+  a.rs = L.rs; a.rf = L.rf; a.V0 = L.V0; a.V1 = L.V1;
+  for (int k = 0; k < 3; k++) { a.Df[k] = L.Df[k]; a.Ds[k] = L.Ds[k]; }
+  dc_launch(e, a);
+  HIPCHK(hipGetLastError());
+  auto down = [&](double *dst, const double *src, size_t cnt) { return dst && cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
+  const DcWork &w = L.work;
+  HIPCHK(down(cost, w.cost, 3)); HIPCHK(down(gradient, w.gradient, Tz * n)); HIPCHK(down(hessian_band, w.band, Tz * n * nb));
+  HIPCHK(down(block_sensor, w.Js, Tz * ns * nb)); HIPCHK(down(block_force, w.Jf, Tz * n * nb));
+  HIPCHK(down(norm_gradient_sensor, w.ng_s, Tz * ns)); HIPCHK(down(norm_gradient_force, w.ng_f, Tz * n));
+  HIPCHK(down(residual_sensor_out, w.res_s, Tz * ns)); HIPCHK(down(residual_force_out, w.res_f, Tz * n));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+// common front of the two window calls: the refusals, in the header's order, before anything is touched
+static int dc_window_check(MjpcHipEngine *e, const char *w, int nwin, int T, const MjpcHipDirectSettings *s, const double *q, const double *act, const double *ctrl,
+                           const double *time, const double *y_s, const double *y_f, std::vector<int> &first, std::vector<int> &row_sensor) {
+  const std::string who = w;
+  if (nwin < 1) { set_error(who + ": nwin < 1"); return -1; }
+  if (dc_check(w, T, e->nv, e->nr, s, first, row_sensor) != 0) return -1;
+  if (!q || !time || (e->na > 0 && !act) || (e->nu > 0 && !ctrl) || (s->num_sensor_rows && !y_s) || !y_f) { set_error(who + ": null input"); return -1; }
+  if ((size_t)nwin * T > STEP_PASS_ROWS) { set_error(who + ": nwin * T too large for one pass of the inverse tables"); return -1; }
+  return 0;
+}
+
+static DcWinArgs dc_win_args(const MjpcHipEngine *e, int nwin, int T, double h, const double *q, const double *act, const double *ctrl, const double *time,
+                             const int *dofmap, double *x, double *u, double *a, double *tm, double *V0, double *V1) {
+  DcWinArgs w;
+  w.q = q; w.act = act; w.ctrl = ctrl; w.time = time; w.dofmap = dofmap; w.nwin = nwin; w.T = T; w.nq = e->nq; w.nv = e->nv; w.na = e->na; w.nu = e->nu; w.h = h;
+  w.x = x; w.u = u; w.a = a; w.tm = tm; w.V0 = V0; w.V1 = V1;
+  return w;
+}
+
+int mjpc_hip_direct_cost(MjpcHipEngine *e, int nwin, int T, const MjpcHipDirectSettings *s, int discrete, const double *q, const double *act, const double *ctrl,
+                         const double *time, const double *sensor_measurement, const double *force_measurement, const double *mocap, const double *userdata,
+                         double *cost, double *velocity, double *acceleration, double *sensor_prediction, double *force_prediction, int *failure) {
+  const char *who = "mjpc_hip_direct_cost";
+  if (!e) { set_error(std::string(who) + ": invalid argument"); return -1; }
+  std::vector<int> first, row_sensor;
+  if (dc_window_check(e, who, nwin, T, s, q, act, ctrl, time, sensor_measurement, force_measurement, first, row_sensor) != 0) return -1;
+  if (!cost) { set_error(std::string(who) + ": null input"); return -1; }
+  KParams K;
+  discrete = discrete ? 1 : 0;
+  int rc = inverse_prepare(e, who, mocap, userdata, discrete, &K);
+  if (rc != 0) return rc;
+  const size_t Tz = T, W = nwin, R = W * Tz, nq = e->nq, nv = e->nv, na = e->na, nu = e->nu, nr = e->nr, ds = e->ds, ns = s->num_sensor_rows, m = s->num_sensor;
+  const std::vector<int> dofmap = fd_dofmap(e);
+  DcCostLay L;
+  PLACE(B_FD, L, e->dims(), W, Tz, ns, m);
+  auto up = [&](double *dst, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  HIPCHK(up(L.q, q, R * nq)); HIPCHK(up(L.act, act, R * na)); HIPCHK(up(L.ctrl, ctrl, R * nu)); HIPCHK(up(L.time, time, Tz));
+  HIPCHK(up(L.y_s, sensor_measurement, Tz * ns)); HIPCHK(up(L.y_f, force_measurement, Tz * nv));
+  HIPCHK(hipMemcpyAsync(L.dofmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+  DcArgs a;
+  rc = dc_upload_spec(e, L.spec, L.work, T, (int)nv, (int)nr, s, first, row_sensor, &a);
+  if (rc != 0) return rc;
+  a.rs = L.rs; a.rf = L.rf;
+  const DcWinArgs w = dc_win_args(e, nwin, T, s->timestep, L.q, L.act, L.ctrl, L.time, L.dofmap, L.t.state, L.t.ctrl, L.t.qacc, L.t.time, nullptr, nullptr);
+  hipLaunchKernelGGL(dc_window_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, e->stream, w, (unsigned)R);
+  inverse_rows(e, K, R, L.t, discrete);
+  DcResArgs r;
+  r.residual = L.t.residual; r.qfrc = L.t.qfrc; r.y_s = L.y_s; r.y_f = L.y_f; r.T = T; r.nv = (int)nv; r.nr = (int)nr; r.ns = (int)ns; r.row0 = s->sensor_first_row; r.E = 1;
+  r.rs = L.rs; r.rf = L.rf;
+  const size_t n_res = R * (ns + nv);
+  hipLaunchKernelGGL(dc_residual_kernel, dim3((unsigned)((n_res + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, e->stream, r, n_res);
+  hipLaunchKernelGGL(dc_norm_kernel, dim3((unsigned)Tz, (unsigned)W), dim3(64), 0, e->stream, a);
+  hipLaunchKernelGGL(dc_cost_kernel, dim3((unsigned)W), dim3(64), 0, e->stream, a);
+  HIPCHK(hipGetLastError());
+  auto down = [&](double *dst, const double *src, size_t cnt) { return dst && cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
+  HIPCHK(down(cost, L.work.cost, 3 * W));
+  if (velocity) HIPCHK(hipMemcpy2DAsync(velocity, sizeof(double) * nv, L.t.state + nq, sizeof(double) * ds, sizeof(double) * nv, R, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(down(acceleration, L.t.qacc, R * nv)); HIPCHK(down(force_prediction, L.t.qfrc, R * nv));
+  if (sensor_prediction && ns) HIPCHK(hipMemcpy2DAsync(sensor_prediction, sizeof(double) * ns, L.t.residual + s->sensor_first_row, sizeof(double) * nr, sizeof(double) * ns, R,
+                                                       hipMemcpyDeviceToHost, e->stream));
+  if (failure) HIPCHK(hipMemcpyAsync(failure, L.t.fail, sizeof(int) * R, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int mjpc_hip_direct_cost_derivatives(MjpcHipEngine *e, int T, const MjpcHipDirectSettings *s, double fd_eps, int centered, int discrete, const double *q,
+                                     const double *act, const double *ctrl, const double *time, const double *sensor_measurement, const double *force_measurement,
+                                     const double *mocap, const double *userdata, double *cost, double *gradient, double *hessian_band, double *block_sensor,
+                                     double *block_force, double *norm_gradient_sensor, double *norm_gradient_force, double *residual_sensor, double *residual_force,
+                                     double *DfDq, double *DfDv, double *DfDa, double *DsDq, double *DsDv, double *DsDa, double *dvdq0, double *dvdq1, int *failure) {
+  const char *who = "mjpc_hip_direct_cost_derivatives";
+  if (!e) { set_error(std::string(who) + ": invalid argument"); return -1; }
+  if (!(fd_eps > 0)) { set_error(std::string(who) + ": fd_eps <= 0"); return -1; }
+  std::vector<int> first, row_sensor;
+  if (dc_window_check(e, who, 1, T, s, q, act, ctrl, time, sensor_measurement, force_measurement, first, row_sensor) != 0) return -1;
+  if (!cost || !gradient || !hessian_band) { set_error(std::string(who) + ": null input"); return -1; }
+  centered = centered ? 1 : 0; discrete = discrete ? 1 : 0;
+  const size_t E = inv_fd_rows_per_config(e->dims(), centered);
+  if ((size_t)T * E > STEP_PASS_ROWS) { set_error(std::string(who) + ": T too large for one pass of the inverse tables (" + std::to_string(STEP_PASS_ROWS / E) + " configurations for this model)"); return -1; }
+  KParams K;
+  int rc = inverse_prepare(e, who, mocap, userdata, discrete, &K);
+  if (rc != 0) return rc;
+  const size_t Tz = T, nq = e->nq, nv = e->nv, na = e->na, nu = e->nu, nr = e->nr, ns = s->num_sensor_rows, m = s->num_sensor, nb = 3 * nv;
+  const std::vector<int> dofmap = fd_dofmap(e);
+  DcDerivLay L;
+  PLACE(B_FD, L, e->dims(), Tz, centered, ns, m);
+  auto up = [&](double *dst, const double *src, size_t cnt) { return cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyHostToDevice, e->stream) : hipSuccess; };
+  HIPCHK(up(L.q, q, Tz * nq)); HIPCHK(up(L.act, act, Tz * na)); HIPCHK(up(L.ctrl, ctrl, Tz * nu)); HIPCHK(up(L.time, time, Tz));
+  HIPCHK(up(L.y_s, sensor_measurement, Tz * ns)); HIPCHK(up(L.y_f, force_measurement, Tz * nv));
+  HIPCHK(hipMemcpyAsync(L.fd.dofmap, dofmap.data(), sizeof(int) * (2 * nv + 2), hipMemcpyHostToDevice, e->stream));
+  DcArgs a;
+  rc = dc_upload_spec(e, L.spec, L.work, T, (int)nv, (int)nr, s, first, row_sensor, &a);
+  if (rc != 0) return rc;
+  // the window's nominal rows where ifd_assemble reads them, and the velocity blocks
+  const DcWinArgs w = dc_win_args(e, 1, T, s->timestep, L.q, L.act, L.ctrl, L.time, L.fd.dofmap, L.fd.x, L.fd.u, L.fd.a, L.fd.time, L.V0, L.V1);
+  hipLaunchKernelGGL(dc_window_kernel, dim3((unsigned)((Tz + 3) / 4)), dim3(256), 0, e->stream, w, (unsigned)Tz);
+  const size_t n_vb = Tz * nv * nv;
+  hipLaunchKernelGGL(dc_vblock_kernel, dim3((unsigned)((n_vb + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, e->stream, w, n_vb);
+  // mjpc_hip_inverse_fd's table, evaluations and differences, all six blocks
+  InvFdArgs f;
+  f.x = L.fd.x; f.u = L.fd.u; f.a = L.fd.a; f.time = L.fd.time; f.dofmap = L.fd.dofmap;
+  f.T = T; f.nq = e->nq; f.nv = e->nv; f.na = e->na; f.nu = e->nu; f.nr = e->nr; f.centered = centered;
+  f.eps = fd_eps; f.cs = cos(0.5 * fd_eps); f.sn = sin(0.5 * fd_eps);
+  f.state_tab = L.fd.t.state; f.ctrl_tab = L.fd.t.ctrl; f.time_tab = L.fd.t.time; f.qacc_tab = L.fd.t.qacc; f.qfrc = L.fd.t.qfrc; f.residual = L.fd.t.residual; f.fail = L.fd.t.fail;
+  f.DfDq = L.fd.Df[0]; f.DfDv = L.fd.Df[1]; f.DfDa = L.fd.Df[2]; f.DsDq = nr ? L.fd.Ds[0] : nullptr; f.DsDv = nr ? L.fd.Ds[1] : nullptr; f.DsDa = nr ? L.fd.Ds[2] : nullptr;
+  f.failure = L.fd.failure;
+  hipLaunchKernelGGL(ifd_assemble_kernel, dim3((unsigned)((L.fd.R + 3) / 4)), dim3(256), 0, e->stream, f, (unsigned)L.fd.R);
+  inverse_rows(e, K, L.fd.R, L.fd.t, discrete);
+  hipLaunchKernelGGL(ifd_difference_kernel, dim3((unsigned)((3 * nv + FD_TILE - 1) / FD_TILE), (unsigned)((nv + nr + FD_TILE - 1) / FD_TILE), (unsigned)Tz),
+                     dim3(FD_TILE * FD_TILE), 0, e->stream, f);
+  // residuals of the base evaluations, then the algebra on the blocks where they lie
+  DcResArgs r;
+  r.residual = L.fd.t.residual; r.qfrc = L.fd.t.qfrc; r.y_s = L.y_s; r.y_f = L.y_f; r.T = T; r.nv = (int)nv; r.nr = (int)nr; r.ns = (int)ns; r.row0 = s->sensor_first_row;
+  r.E = (int)E; r.rs = L.rs; r.rf = L.rf;
+  const size_t n_res = Tz * (ns + nv);
+  hipLaunchKernelGGL(dc_residual_kernel, dim3((unsigned)((n_res + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, e->stream, r, n_res);
+  a.rs = L.rs; a.rf = L.rf; a.V0 = L.V0; a.V1 = L.V1;
+  for (int k = 0; k < 3; k++) { a.Df[k] = L.fd.Df[k]; a.Ds[k] = L.fd.Ds[k]; }
+  dc_launch(e, a);
+  HIPCHK(hipGetLastError());
+  auto down = [&](double *dst, const double *src, size_t cnt) { return dst && cnt ? hipMemcpyAsync(dst, src, sizeof(double) * cnt, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
+  const DcWork &k = L.work;
+  HIPCHK(down(cost, k.cost, 3)); HIPCHK(down(gradient, k.gradient, Tz * nv)); HIPCHK(down(hessian_band, k.band, Tz * nv * nb));
+  HIPCHK(down(block_sensor, k.Js, Tz * ns * nb)); HIPCHK(down(block_force, k.Jf, Tz * nv * nb));
+  HIPCHK(down(norm_gradient_sensor, k.ng_s, Tz * ns)); HIPCHK(down(norm_gradient_force, k.ng_f, Tz * nv));
+  HIPCHK(down(residual_sensor, k.res_s, Tz * ns)); HIPCHK(down(residual_force, k.res_f, Tz * nv));
+  double *const Dfo[3] = {DfDq, DfDv, DfDa}, *const Dso[3] = {DsDq, DsDv, DsDa};
+  for (int i = 0; i < 3; i++) { HIPCHK(down(Dfo[i], L.fd.Df[i], Tz * nv * nv)); HIPCHK(down(Dso[i], L.fd.Ds[i], Tz * nr * nv)); }
+  HIPCHK(down(dvdq0, L.V0, Tz * nv * nv)); HIPCHK(down(dvdq1, L.V1, Tz * nv * nv));
+  if (failure) HIPCHK(hipMemcpyAsync(failure, L.fd.failure, sizeof(int) * Tz, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
 }
 
 int mjpc_hip_get_frame(MjpcHipEngine *e, double *xpos, double *xmat, double *site_xpos, double *subtree_com, double *subtree_linvel) {

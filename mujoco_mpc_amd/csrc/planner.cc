@@ -3278,3 +3278,334 @@ void mjpc_robust_last(void* p, int* out, double* scores, double* noisy_returns) 
 void* mjpc_robust_delegate(void* p) { return &((mjpc_hip::RobustPlanner*)p)->delegate; }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ DirectCost
+// The norms are the device's own functions (csrc/cost_derivatives.h: norm_grad_hess, norm_hess_entry), compiled for the host in a
+// translation unit of their own (direct_norms.cc) the way the 1-lane emulation compiles them; everything around them is restated below.
+namespace mjpc_hip {
+namespace device_norms {
+double norm_grad_hess(double* g, double* hd, double* hs, const double* x, const double* prm, int n, int type);
+double norm_hess_entry(int type, const double* x, const double* g, const double* hs, int i, int j);
+int norm_dense(int type);
+}  // namespace device_norms
+
+void DirectCost::Allocate(int nv, int nr, int T) {
+  dim_v = nv; dim_residual = nr;
+  noise_process.assign(nv, 1.0);
+  SetSensors(0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+  Size(T);
+}
+
+void DirectCost::SetSensors(int first_row, int num_sensor, const int* dim, const int* stage, const int* norm, const double* norm_parameter, const double* noise) {
+  sensor_first_row = first_row;
+  sensor_dim.assign(dim, dim + num_sensor); sensor_stage.assign(stage, stage + num_sensor); sensor_norm.assign(norm, norm + num_sensor);
+  sensor_norm_parameter.assign(norm_parameter, norm_parameter + 2 * num_sensor); noise_sensor.assign(noise, noise + num_sensor);
+  num_sensor_rows = std::accumulate(sensor_dim.begin(), sensor_dim.end(), 0);
+  sensor_mask.clear();
+}
+
+void DirectCost::SetProcessNoise(const double* noise) { noise_process.assign(noise, noise + dim_v); }
+
+void DirectCost::SetMask(const int* mask, int T) {
+  if (mask) sensor_mask.assign(mask, mask + (size_t)T * sensor_dim.size()); else sensor_mask.clear();
+}
+
+void DirectCost::Size(int T) {
+  const size_t Tz = T > 0 ? T : 0, nv = dim_v, ns = num_sensor_rows, nb = 3 * nv;
+  gradient.assign(Tz * nv, 0.0); hessian_band.assign(Tz * nv * nb, 0.0);
+  block_sensor.assign(Tz * ns * nb, 0.0); block_force.assign(Tz * nv * nb, 0.0);
+  norm_gradient_sensor.assign(Tz * ns, 0.0); residual_sensor.assign(Tz * ns, 0.0);
+  norm_gradient_force.assign(Tz * nv, 0.0); residual_force.assign(Tz * nv, 0.0);
+  cost[0] = cost[1] = cost[2] = 0.0;
+}
+
+MjpcHipDirectSettings DirectCost::View(int T) const {
+  MjpcHipDirectSettings s;
+  std::memset(&s, 0, sizeof(s));
+  s.struct_size = (int)sizeof(s);
+  s.num_sensor = (int)sensor_dim.size(); s.sensor_first_row = sensor_first_row; s.num_sensor_rows = num_sensor_rows;
+  s.sensor_dim = sensor_dim.data(); s.sensor_stage = sensor_stage.data(); s.sensor_norm = sensor_norm.data();
+  s.sensor_norm_parameter = sensor_norm_parameter.data(); s.noise_sensor = noise_sensor.data(); s.noise_process = noise_process.data();
+  s.sensor_mask = sensor_mask.empty() ? nullptr : sensor_mask.data();          // (the callers have checked that it covers T)
+  s.sensor_flag = settings.sensor_flag; s.force_flag = settings.force_flag; s.time_scaling_sensor = settings.time_scaling_sensor;
+  s.time_scaling_force = settings.time_scaling_force; s.first_step_position_sensors = settings.first_step_position_sensors;
+  s.last_step_position_sensors = settings.last_step_position_sensors; s.last_step_velocity_sensors = settings.last_step_velocity_sensors;
+  s.timestep = timestep;
+  return s;
+}
+
+void DirectCost::SetWindow(int T, int nq, int na, int nu, const double* q, const double* a, const double* u, const double* time, const double* ys,
+                           const double* yf) {
+  window_length = T; dim_q = nq; dim_act = na; dim_action = nu;
+  const size_t Tz = T > 0 ? T : 0;
+  auto set = [](std::vector<double>& v, const double* src, size_t n) { if (src) v.assign(src, src + n); else v.assign(n, 0.0); };
+  set(configuration, q, Tz * nq); set(act, a, Tz * na); set(ctrl, u, Tz * nu); set(times, time, Tz);
+  set(sensor_measurement, ys, Tz * num_sensor_rows); set(force_measurement, yf, Tz * dim_v);
+}
+
+// a mask that does not cover the window is an error, not "every sensor on"
+static bool MaskCovers(const std::vector<int>& mask, size_t T, size_t m) { return mask.empty() || mask.size() >= T * m; }
+
+bool DirectCost::Cost(MjpcHipEngine* engine, const double* q_windows, int nwin, const double* mocap, const double* userdata) {
+  const int T = window_length;
+  if (!MaskCovers(sensor_mask, T, sensor_dim.size())) { Fatal("DirectCost: the mask holds fewer than T configurations"); return false; }
+  if (!q_windows) { q_windows = configuration.data(); nwin = 1; }
+  if (nwin < 1) { Fatal("DirectCost: nwin < 1"); return false; }
+  const MjpcHipDirectSettings s = View(T);
+  // act and ctrl are the window's for every candidate
+  std::vector<double> a((size_t)nwin * act.size()), u((size_t)nwin * ctrl.size());
+  for (int w = 0; w < nwin; w++) { std::copy(act.begin(), act.end(), a.begin() + w * act.size()); std::copy(ctrl.begin(), ctrl.end(), u.begin() + w * ctrl.size()); }
+  costs.assign((size_t)3 * nwin, 0.0); failure.assign((size_t)nwin * (T > 0 ? T : 0), 0);
+  const bool ok = mjpc_hip_direct_cost(engine, nwin, T, &s, discrete, q_windows, a.data(), u.data(), times.data(), sensor_measurement.data(),
+                                       force_measurement.data(), mocap, userdata, costs.data(), nullptr, nullptr, nullptr, nullptr, failure.data()) == 0;
+  if (ok) std::copy(costs.begin(), costs.begin() + 3, cost);
+  return ok;
+}
+
+bool DirectCost::CostDerivatives(MjpcHipEngine* engine, const double* mocap, const double* userdata) {
+  const int T = window_length;
+  if (!MaskCovers(sensor_mask, T, sensor_dim.size())) { Fatal("DirectCost: the mask holds fewer than T configurations"); return false; }
+  Size(T);
+  failure.assign(T > 0 ? T : 0, 0);
+  const MjpcHipDirectSettings s = View(T);
+  auto p = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
+  return mjpc_hip_direct_cost_derivatives(engine, T, &s, fd_tolerance, fd_mode, discrete, configuration.data(), act.data(), ctrl.data(), times.data(),
+                                          sensor_measurement.data(), force_measurement.data(), mocap, userdata, cost, p(gradient), p(hessian_band),
+                                          p(block_sensor), p(block_force), p(norm_gradient_sensor), p(norm_gradient_force), p(residual_sensor),
+                                          p(residual_force), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, failure.data()) == 0;
+}
+
+bool DirectCost::Assemble(MjpcHipEngine* engine, int T, const double* rs, const double* rf, const double* DfDq, const double* DfDv, const double* DfDa,
+                          const double* DsDq, const double* DsDv, const double* DsDa, const double* dvdq0, const double* dvdq1) {
+  if (!MaskCovers(sensor_mask, T > 0 ? T : 0, sensor_dim.size())) { Fatal("DirectCost: the mask holds fewer than T configurations"); return false; }
+  Size(T);
+  const MjpcHipDirectSettings s = View(T);
+  auto p = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
+  return mjpc_hip_direct_assemble(engine, T, dim_v, dim_residual, &s, rs, rf, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, dvdq0, dvdq1, cost, p(gradient),
+                                  p(hessian_band), p(block_sensor), p(block_force), p(norm_gradient_sensor), p(norm_gradient_force), p(residual_sensor),
+                                  p(residual_force)) == 0;
+}
+
+// The order of mjpc_hip_direct_assemble (csrc/direct_cost.h), stage by stage over whole arrays: residuals, weights and norms; totals; the
+// blocks J_t; N_t J_t; every gradient and band entry as its own sum.  Every product and every add below is rounded on its own.
+bool DirectCost::AssembleHost(int T, const double* rs, const double* rf, const double* DfDq, const double* DfDv, const double* DfDa, const double* DsDq,
+                              const double* DsDv, const double* DsDa, const double* dvdq0, const double* dvdq1) {
+  const int nv = dim_v, nr = dim_residual, ns = num_sensor_rows, m = (int)sensor_dim.size(), nb = 3 * nv;
+  if (T < 3) { Fatal("DirectCost: T < 3"); return false; }
+  if (nv < 1) { Fatal("DirectCost: not allocated"); return false; }
+  if (!(timestep > 0)) { Fatal("DirectCost: timestep <= 0"); return false; }
+  if (sensor_first_row < 0 || sensor_first_row + ns > nr) { Fatal("DirectCost: the sensor rows lie outside the residual"); return false; }
+  if (!MaskCovers(sensor_mask, T, sensor_dim.size())) { Fatal("DirectCost: the mask holds fewer than T configurations"); return false; }
+  for (int i = 0; i < m; i++) {
+    if (sensor_dim[i] < 1) { Fatal("DirectCost: a sensor dimension < 1"); return false; }
+    if (sensor_stage[i] < 0 || sensor_stage[i] > 2) { Fatal("DirectCost: a sensor stage outside 0 .. 2"); return false; }
+    if (!(noise_sensor[i] > 0)) { Fatal("DirectCost: a sensor noise value <= 0"); return false; }
+  }
+  for (int i = 0; i < nv; i++) if (!(noise_process[i] > 0)) { Fatal("DirectCost: a process noise value <= 0"); return false; }
+  if ((ns && (!rs || !DsDq || !DsDv || !DsDa)) || !rf || !DfDq || !DfDv || !DfDa || !dvdq0 || !dvdq1) { Fatal("DirectCost: null input"); return false; }
+  Size(T);
+  const MjpcHipDirectSettings s = View(T);
+  const double h = timestep, h2 = h * h, h4 = h2 * h2, ih = 1.0 / h;
+  std::vector<int> first(m), owner(ns);
+  for (int i = 0, r = 0; i < m; r += sensor_dim[i], i++) { first[i] = r; for (int k = 0; k < sensor_dim[i]; k++) owner[r + k] = i; }
+  auto interior = [&](int t) { return t >= 1 && t <= T - 2; };
+  auto masked = [&](int t, int i) { return s.sensor_mask && !s.sensor_mask[(size_t)t * m + i]; };
+  std::vector<double> wf(nv);
+  for (int i = 0; i < nv; i++) wf[i] = (settings.time_scaling_force ? h4 : 1.0) / noise_process[i] / (double)nv / (double)(T - 2);
+
+  // residuals, weights, norms
+  std::vector<double> hd((size_t)T * ns), hs((size_t)2 * T * m), w((size_t)T * m), yf(T, 0.0);
+  double cs = 0.0, cf = 0.0;
+  for (int t = 0; t < T; t++) {
+    for (int i = 0; i < m; i++) {
+      const int st = sensor_stage[i], n = sensor_dim[i];
+      const bool keep = t == 0 ? st == kStagePos
+                               : (t == T - 1 ? (st == kStagePos && settings.last_step_position_sensors) || (st == kStageVel && settings.last_step_velocity_sensors) : true);
+      const size_t o = (size_t)t * ns + first[i], k = (size_t)t * m + i;
+      double* x = residual_sensor.data() + o;
+      for (int r = 0; r < n; r++) x[r] = keep ? rs[o + r] : 0.0;
+      const double* prm = sensor_norm_parameter.data() + 2 * i;
+      double y = device_norms::norm_grad_hess(norm_gradient_sensor.data() + o, hd.data() + o, hs.data() + 2 * k, x, prm, n, sensor_norm[i]);
+      // the values that need no more than sqrt, by the summation rule
+      double c = 0.0;
+      switch (sensor_norm[i]) {
+        case -1: y = x[0]; break;
+        case 0: for (int r = 0; r < n; r++) c = c + x[r] * x[r]; y = 0.5 * c; break;
+        case 2: for (int r = 0; r < n; r++) c = c + x[r] * x[r]; y = std::sqrt(c + prm[0] * prm[0]) + -prm[0]; break;
+        case 6: for (int r = 0; r < n; r++) c = c + (std::sqrt(x[r] * x[r] + prm[0] * prm[0]) + -prm[0]); y = c; break;
+        default: break;
+      }
+      double tw = 1.0;
+      if (settings.time_scaling_sensor) tw = st == kStageVel ? h2 : (st == kStageAcc ? h4 : 1.0);
+      double wi = tw / noise_sensor[i] / (double)n / (double)T;
+      if (t == 0) wi = wi * (settings.first_step_position_sensors ? 1.0 : 0.0);
+      if (t == T - 1) wi = wi * ((settings.last_step_position_sensors || settings.last_step_velocity_sensors) ? 1.0 : 0.0);
+      w[k] = wi;
+      if (settings.sensor_flag) cs = cs + (masked(t, i) ? 0.0 : wi * y);
+    }
+    for (int i = 0; i < nv; i++) {
+      const size_t o = (size_t)t * nv + i;
+      residual_force[o] = interior(t) ? rf[o] : 0.0;
+      norm_gradient_force[o] = interior(t) ? wf[i] * rf[o] : 0.0;
+    }
+    if (interior(t)) {
+      double c = 0.0;
+      for (int i = 0; i < nv; i++) { const double r = rf[(size_t)t * nv + i]; c = c + r * (wf[i] * r); }
+      yf[t] = 0.5 * c;
+    }
+  }
+  if (settings.force_flag) for (int t = 1; t <= T - 2; t++) cf = cf + yf[t];
+  cost[0] = cs + cf; cost[1] = cs; cost[2] = cf;
+
+  // the blocks: row o < ns a sensor row, else dof o - ns of the force; (base + P1) + P2
+  const double* Df[3] = {DfDq, DfDv, DfDa};
+  const double* Ds[3] = {DsDq, DsDv, DsDa};
+  auto D = [&](int t, int which, int o, int k) {
+    if (o < ns) {
+      const int st = sensor_stage[owner[o]];
+      const bool keep = t == 0 ? (which == 0 && st == kStagePos) : (t == T - 1 ? (which < 2 && st < kStageAcc) : true);
+      return keep ? Ds[which][((size_t)t * nr + sensor_first_row + o) * nv + k] : 0.0;
+    }
+    return interior(t) ? Df[which][((size_t)t * nv + (o - ns)) * nv + k] : 0.0;
+  };
+  auto J = [&](int t, int o, int c) -> double& {
+    return o < ns ? block_sensor[((size_t)t * ns + o) * nb + c] : block_force[((size_t)t * nv + (o - ns)) * nb + c];
+  };
+  for (int t = 0; t < T; t++)
+    for (int o = 0; o < ns + nv; o++)
+      for (int c = 0; c < nb; c++) {
+        const int g = c / nv, j = c % nv;
+        const bool hasV = t >= 1 && g < 2, hasA = interior(t);
+        double p1 = 0.0, p2 = 0.0;
+        if (hasV) {
+          const double* V = (g == 0 ? dvdq0 : dvdq1) + (size_t)t * nv * nv;
+          for (int k = 0; k < nv; k++) p1 = p1 + D(t, 1, o, k) * V[(size_t)k * nv + j];
+        }
+        if (hasA)
+          for (int k = 0; k < nv; k++) {
+            const size_t e = ((size_t)t * nv + k) * nv + j, e1 = e + (size_t)nv * nv;
+            const double A = g == 0 ? dvdq0[e] * -ih : (g == 1 ? (dvdq0[e1] + -dvdq1[e]) * ih : dvdq1[e1] * ih);
+            p2 = p2 + D(t, 2, o, k) * A;
+          }
+        J(t, o, c) = ((g == 1 ? D(t, 0, o, j) : 0.0) + p1) + p2;
+      }
+
+  // N J
+  std::vector<double> NJs((size_t)T * ns * nb), NJf((size_t)T * nv * nb);
+  for (int t = 0; t < T; t++) {
+    const size_t row = (size_t)t * ns;
+    for (int o = 0; o < ns; o++) {
+      const int i = owner[o], f = first[i], n = sensor_dim[i];
+      for (int c = 0; c < nb; c++) {
+        double v;
+        if (!device_norms::norm_dense(sensor_norm[i])) v = hd[row + o] * block_sensor[(row + o) * nb + c];
+        else {
+          v = 0.0;
+          for (int q = 0; q < n; q++)
+            v = v + device_norms::norm_hess_entry(sensor_norm[i], residual_sensor.data() + row + f, norm_gradient_sensor.data() + row + f,
+                                                  hs.data() + 2 * ((size_t)t * m + i), o - f, q) * block_sensor[(row + f + q) * nb + c];
+        }
+        NJs[(row + o) * nb + c] = v;
+      }
+    }
+    for (int o = 0; o < nv; o++)
+      for (int c = 0; c < nb; c++) { const size_t at = ((size_t)t * nv + o) * nb + c; NJf[at] = interior(t) ? wf[o] * block_force[at] : 0.0; }
+  }
+
+  // gradient and band: one sum per entry
+  auto col = [&](int t, int G) {
+    const int c = G - nv * (t - 1);
+    if (c < 0 || c >= nb) return -1;
+    if ((t == 0 && c / nv != 1) || (t == T - 1 && c / nv == 2)) return -1;
+    return c;
+  };
+  auto sensor_sum = [&](int t, int ca, const double* X, int cb, double acc) {
+    for (int i = 0; i < m; i++) {
+      if (masked(t, i)) continue;
+      const size_t row = (size_t)t * ns + first[i];
+      double sum = 0.0;
+      for (int r = 0; r < sensor_dim[i]; r++) sum = sum + block_sensor[(row + r) * nb + ca] * (X ? X[(row + r) * nb + cb] : norm_gradient_sensor[row + r]);
+      acc = acc + w[(size_t)t * m + i] * sum;
+    }
+    return acc;
+  };
+  auto force_sum = [&](int t, int ca, const double* X, int cb, double acc) {
+    const size_t row = (size_t)t * nv;
+    double sum = 0.0;
+    for (int r = 0; r < nv; r++) sum = sum + block_force[(row + r) * nb + ca] * (X ? X[(row + r) * nb + cb] : norm_gradient_force[row + r]);
+    return acc + sum;
+  };
+  for (int R = 0; R < nv * T; R++) {
+    const int lo = std::max(0, R / nv - 1), hi = std::min(T - 1, R / nv + 1);
+    for (int C = 0; C <= nb; C++) {
+      const int G = C == nb ? R : R - (nb - 1 - C);
+      double es = 0.0, ef = 0.0;
+      if (G >= 0)
+        for (int t = lo; t <= hi; t++) {
+          const int ca = col(t, R), cb = col(t, G);
+          if (ca < 0 || cb < 0) continue;
+          if (settings.sensor_flag) es = sensor_sum(t, ca, C == nb ? nullptr : NJs.data(), cb, es);
+          if (settings.force_flag && interior(t)) ef = force_sum(t, ca, C == nb ? nullptr : NJf.data(), cb, ef);
+        }
+      (C == nb ? gradient[R] : hessian_band[(size_t)R * nb + C]) = es + ef;
+    }
+  }
+  return true;
+}
+
+}  // namespace mjpc_hip
+
+// ---- DirectCost
+extern "C" {
+void* mjpc_dc_create(int nv, int nr, int T) { auto* d = new mjpc_hip::DirectCost(); d->Allocate(nv, nr, T); return d; }
+void mjpc_dc_destroy(void* dc) { delete (mjpc_hip::DirectCost*)dc; }
+void mjpc_dc_set_sensors(void* dc, int first_row, int num_sensor, const int* dim, const int* stage, const int* norm, const double* norm_parameter,
+                         const double* noise) {
+  ((mjpc_hip::DirectCost*)dc)->SetSensors(first_row, num_sensor, dim, stage, norm, norm_parameter, noise);
+}
+void mjpc_dc_set_process_noise(void* dc, const double* noise) { ((mjpc_hip::DirectCost*)dc)->SetProcessNoise(noise); }
+void mjpc_dc_set_mask(void* dc, const int* mask, int T) { ((mjpc_hip::DirectCost*)dc)->SetMask(mask, T); }
+void mjpc_dc_set_settings(void* dc, const int* flags, double timestep) {
+  auto* d = (mjpc_hip::DirectCost*)dc;
+  d->settings.sensor_flag = flags[0]; d->settings.force_flag = flags[1]; d->settings.time_scaling_sensor = flags[2]; d->settings.time_scaling_force = flags[3];
+  d->settings.first_step_position_sensors = flags[4]; d->settings.last_step_position_sensors = flags[5]; d->settings.last_step_velocity_sensors = flags[6];
+  d->timestep = timestep;
+}
+int mjpc_dc_assemble(void* dc, MjpcHipEngine* engine, int T, const double* residual_sensor, const double* residual_force, const double* DfDq,
+                     const double* DfDv, const double* DfDa, const double* DsDq, const double* DsDv, const double* DsDa, const double* dvdq0,
+                     const double* dvdq1) {
+  auto* d = (mjpc_hip::DirectCost*)dc;
+  const bool ok = engine ? d->Assemble(engine, T, residual_sensor, residual_force, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, dvdq0, dvdq1)
+                         : d->AssembleHost(T, residual_sensor, residual_force, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, dvdq0, dvdq1);
+  return ok ? 0 : -1;
+}
+void mjpc_dc_set_window(void* dc, int T, int nq, int na, int nu, const double* q, const double* act, const double* ctrl, const double* time,
+                        const double* sensor_measurement, const double* force_measurement) {
+  ((mjpc_hip::DirectCost*)dc)->SetWindow(T, nq, na, nu, q, act, ctrl, time, sensor_measurement, force_measurement);
+}
+void mjpc_dc_set_fd(void* dc, double tolerance, int mode, int discrete) {
+  auto* d = (mjpc_hip::DirectCost*)dc; d->fd_tolerance = tolerance; d->fd_mode = mode; d->discrete = discrete;
+}
+int mjpc_dc_cost(void* dc, MjpcHipEngine* engine, const double* q_windows, int nwin, const double* mocap, const double* userdata, double* costs, int* failure) {
+  auto* d = (mjpc_hip::DirectCost*)dc;
+  if (!d->Cost(engine, q_windows, nwin, mocap, userdata)) return -1;
+  if (costs) std::copy(d->costs.begin(), d->costs.end(), costs);
+  if (failure) std::copy(d->failure.begin(), d->failure.end(), failure);
+  return 0;
+}
+int mjpc_dc_cost_derivatives(void* dc, MjpcHipEngine* engine, const double* mocap, const double* userdata, int* failure) {
+  auto* d = (mjpc_hip::DirectCost*)dc;
+  if (!d->CostDerivatives(engine, mocap, userdata)) return -1;
+  if (failure) std::copy(d->failure.begin(), d->failure.end(), failure);
+  return 0;
+}
+void mjpc_dc_outputs(void* dc, double* cost, double* gradient, double* hessian_band, double* block_sensor, double* block_force,
+                     double* norm_gradient_sensor, double* norm_gradient_force, double* residual_sensor, double* residual_force) {
+  auto* d = (mjpc_hip::DirectCost*)dc;
+  if (cost) std::copy(d->cost, d->cost + 3, cost);
+  double* out[8] = {gradient, hessian_band, block_sensor, block_force, norm_gradient_sensor, norm_gradient_force, residual_sensor, residual_force};
+  const std::vector<double>* src[8] = {&d->gradient, &d->hessian_band, &d->block_sensor, &d->block_force, &d->norm_gradient_sensor,
+                                       &d->norm_gradient_force, &d->residual_sensor, &d->residual_force};
+  for (int k = 0; k < 8; k++) if (out[k]) std::copy(src[k]->begin(), src[k]->end(), out[k]);
+}
+}  // extern "C"

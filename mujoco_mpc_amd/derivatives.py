@@ -10,7 +10,8 @@ planner itself is cplanner.GradientPlanner.  ILQGBackwardPass, boxqp and ilqg_po
 control solve, regularisation loop) and policy, on the host and on the device (HipBackend.ilqg_backward_pass / trajectory_ilqg); iLQG's feedback rollouts
 and line search, and iLQS, are not part of this package.  InverseDerivatives: the six Jacobians of the inverse dynamics along a window (one
 mjpc_hip_inverse_fd call), what the reference's direct optimiser and batch estimator linearise around; the optimiser itself is not part
-of this package.  No CPU fallback: the step and inverse evaluations and the cost derivatives are the engine's kernels.
+of this package.  DirectCost: that optimiser's window cost, gradient and band Hessian from those blocks (mjpc_hip_direct_assemble, and
+the same algebra on the host).  No CPU fallback: the step and inverse evaluations and the cost derivatives are the engine's kernels.
 """
 from __future__ import annotations
 
@@ -46,6 +47,19 @@ def _lib():
         lib.mjpc_id_row_stages.argtypes = [C.c_void_p, _ip]; lib.mjpc_id_row_stages.restype = None
         lib.mjpc_id_compute.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]
         lib.mjpc_id_blocks.argtypes = [C.c_void_p, C.c_int] + [_dp] * 6 + [_ip]; lib.mjpc_id_blocks.restype = None
+        lib.mjpc_dc_create.restype = C.c_void_p
+        lib.mjpc_dc_create.argtypes = [C.c_int] * 3
+        lib.mjpc_dc_destroy.argtypes = [C.c_void_p]; lib.mjpc_dc_destroy.restype = None
+        lib.mjpc_dc_set_sensors.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip, _dp, _dp]; lib.mjpc_dc_set_sensors.restype = None
+        lib.mjpc_dc_set_process_noise.argtypes = [C.c_void_p, _dp]; lib.mjpc_dc_set_process_noise.restype = None
+        lib.mjpc_dc_set_mask.argtypes = [C.c_void_p, _ip, C.c_int]; lib.mjpc_dc_set_mask.restype = None
+        lib.mjpc_dc_set_settings.argtypes = [C.c_void_p, _ip, C.c_double]; lib.mjpc_dc_set_settings.restype = None
+        lib.mjpc_dc_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [_dp] * 10
+        lib.mjpc_dc_set_window.argtypes = [C.c_void_p] + [C.c_int] * 4 + [_dp] * 6; lib.mjpc_dc_set_window.restype = None
+        lib.mjpc_dc_set_fd.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]; lib.mjpc_dc_set_fd.restype = None
+        lib.mjpc_dc_cost.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_int, _dp, _dp, _dp, _ip]
+        lib.mjpc_dc_cost_derivatives.argtypes = [C.c_void_p, C.c_void_p, _dp, _dp, _ip]
+        lib.mjpc_dc_outputs.argtypes = [C.c_void_p] + [_dp] * 9; lib.mjpc_dc_outputs.restype = None
         lib.mjpc_cd_create.restype = C.c_void_p
         lib.mjpc_cd_create.argtypes = [C.c_int] * 4
         lib.mjpc_cd_destroy.argtypes = [C.c_void_p]; lib.mjpc_cd_destroy.restype = None
@@ -179,6 +193,121 @@ class InverseDerivatives:
         o["failure"] = np.zeros(T, np.int32)
         self.lib.mjpc_id_blocks(self.h, T, *[_ptr(o[k]) for k in names], o["failure"].ctypes.data_as(_ip))
         return o
+
+
+class DirectCost:
+    """The direct optimiser's window cost with its gradient [T nv] and Gauss-Newton Hessian in MuJoCo's lower band [T nv, 3 nv]
+    (mjpc_hip::DirectCost; Direct::Cost of the reference) from the window's residuals, the six blocks of InverseDerivatives and the velocity
+    blocks dv_t/dq_{t-1}, dv_t/dq_t.  assemble runs on the device (mjpc_hip_direct_assemble), assemble_host the same algebra on the host
+    with the same bits.  The sensors are runs of rows of the residual: sensor_dim, sensor_stage (0 position, 1 velocity, 2 acceleration),
+    sensor_norm (the cost table's norm types), sensor_norm_parameter [num_sensor, 2], noise_sensor; flags: the keywords of
+    capi.direct_settings.  set_window / cost / cost_derivatives: the window the object owns, evaluated on the device (mjpc_hip_direct_cost,
+    mjpc_hip_direct_cost_derivatives).  The band solve and the optimiser's loop are not part of this package."""
+
+    FLAGS = ("sensor_flag", "force_flag", "time_scaling_sensor", "time_scaling_force", "first_step_position_sensors", "last_step_position_sensors",
+             "last_step_velocity_sensors")
+
+    def __init__(self, nv, nr, timestep, sensor_dim, sensor_stage, sensor_norm, sensor_norm_parameter, noise_sensor, noise_process=None,
+                 sensor_first_row=0, sensor_mask=None, T=3, **flags):
+        self.nv, self.nr, self.T = int(nv), int(nr), int(T)
+        self.lib = _lib()
+        self.h = C.c_void_p(self.lib.mjpc_dc_create(self.nv, self.nr, self.T))
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int32).ravel())      # noqa: E731
+        f64 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())      # noqa: E731
+        dim, stage, norm, prm, noise = i32(sensor_dim), i32(sensor_stage), i32(sensor_norm), f64(sensor_norm_parameter), f64(noise_sensor)
+        self.num_sensor, self.ns = int(dim.size), int(dim.sum())
+        ip = lambda a: (a if a.size else np.zeros(1, np.int32)).ctypes.data_as(_ip)      # noqa: E731
+        self.lib.mjpc_dc_set_sensors(self.h, int(sensor_first_row), self.num_sensor, ip(dim), ip(stage), ip(norm), _ptr(prm), _ptr(noise))
+        if noise_process is not None:
+            self.lib.mjpc_dc_set_process_noise(self.h, _ptr(f64(noise_process).reshape(self.nv)))
+        if sensor_mask is not None:
+            mk = i32(sensor_mask)
+            self.lib.mjpc_dc_set_mask(self.h, ip(mk), mk.size // max(self.num_sensor, 1))
+        defaults = dict(zip(self.FLAGS, (1, 1, 1, 1, 1, 0, 0)))
+        unknown = set(flags) - set(defaults)
+        if unknown:
+            raise TypeError(f"DirectCost: unknown settings {sorted(unknown)}")
+        defaults.update({k: int(bool(v)) for k, v in flags.items()})
+        self.lib.mjpc_dc_set_settings(self.h, i32([defaults[k] for k in self.FLAGS]).ctypes.data_as(_ip), float(timestep))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.mjpc_dc_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, engine, residual_sensor, residual_force, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, dvdq0, dvdq1):
+        nv, nr, ns = self.nv, self.nr, self.ns
+        f64 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)      # noqa: E731
+        DfDq = f64(DfDq, -1, nv, nv); T = DfDq.shape[0]
+        ins = [f64(residual_sensor, T, ns), f64(residual_force, T, nv), DfDq, f64(DfDv, T, nv, nv), f64(DfDa, T, nv, nv), f64(DsDq, T, nr, nv),
+               f64(DsDv, T, nr, nv), f64(DsDa, T, nr, nv), f64(dvdq0, T, nv, nv), f64(dvdq1, T, nv, nv)]
+        rc = self.lib.mjpc_dc_assemble(self.h, engine, T, *[_ptr(a) for a in ins])
+        cplanner._check()
+        if rc != 0:
+            raise RuntimeError("DirectCost.assemble failed: " + self.lib.mjpc_hip_last_error().decode())
+        return self._outputs(T)
+
+    def _outputs(self, T):
+        nv, ns = self.nv, self.ns
+        o = dict(cost=np.zeros(3), gradient=np.zeros(T * nv), hessian_band=np.zeros((T * nv, 3 * nv)), block_sensor=np.zeros((T, ns, 3 * nv)),
+                 block_force=np.zeros((T, nv, 3 * nv)), norm_gradient_sensor=np.zeros((T, ns)), norm_gradient_force=np.zeros((T, nv)),
+                 residual_sensor=np.zeros((T, ns)), residual_force=np.zeros((T, nv)))
+        self.lib.mjpc_dc_outputs(self.h, *[_ptr(a) if a.size else None for a in o.values()])
+        return o
+
+    def set_window(self, model, q, act=None, ctrl=None, time=None, sensor_measurement=None, force_measurement=None, tol=1e-6, mode=0, discrete=True):
+        """the window the object owns: q [T, nq] and, where given, act [T, na], ctrl [T, nu], time [T], sensor_measurement [T, ns],
+        force_measurement [T, nv] (None: zeros); tol, mode, discrete: the finite differences of cost_derivatives and mjENBL_INVDISCRETE"""
+        nq, na, nu = model["nq"], model["na"], model["nu"]
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, nq); T = self.window_T = q.shape[0]
+        self.nq = nq
+        arr = lambda a, n: None if a is None or n == 0 else np.ascontiguousarray(a, dtype=np.float64).reshape(T, n)      # noqa: E731
+        ins = [q, arr(act, na), arr(ctrl, nu), arr(time, 1), arr(sensor_measurement, self.ns), arr(force_measurement, self.nv)]
+        self.lib.mjpc_dc_set_window(self.h, T, nq, na, nu, *[None if a is None else _ptr(a) for a in ins])
+        self.lib.mjpc_dc_set_fd(self.h, float(tol), int(mode), int(bool(discrete)))
+
+    def cost(self, backend: HipBackend, q_windows=None, mocap=None, userdata=None):
+        """DirectCost::Cost: the costs [nwin, 3] (cost, cost_sensor, cost_force) of candidate windows q_windows [nwin, T, nq] (None: the window
+        itself) in one device call, and failure [nwin, T]"""
+        T = self.window_T
+        qw = None if q_windows is None else np.ascontiguousarray(q_windows, dtype=np.float64).reshape(-1, T, self.nq)
+        W = 1 if qw is None else qw.shape[0]
+        costs = np.zeros((W, 3)); fail = np.zeros((W, T), np.int32)
+        mo, ud, pmo, pud = backend._shared(mocap, userdata)
+        rc = self.lib.mjpc_dc_cost(self.h, backend.h, None if qw is None else _ptr(qw), W, pmo, pud, _ptr(costs), fail.ctypes.data_as(_ip))
+        cplanner._check()
+        if rc != 0:
+            raise RuntimeError("DirectCost.cost failed: " + self.lib.mjpc_hip_last_error().decode())
+        return dict(cost=costs, failure=fail)
+
+    def cost_derivatives(self, backend: HipBackend, mocap=None, userdata=None):
+        """DirectCost::CostDerivatives: the window's cost, gradient, band Hessian and blocks in one device call -> the dict of assemble plus
+        failure [T]"""
+        T = self.window_T
+        fail = np.zeros(T, np.int32)
+        mo, ud, pmo, pud = backend._shared(mocap, userdata)
+        rc = self.lib.mjpc_dc_cost_derivatives(self.h, backend.h, pmo, pud, fail.ctypes.data_as(_ip))
+        cplanner._check()
+        if rc != 0:
+            raise RuntimeError("DirectCost.cost_derivatives failed: " + self.lib.mjpc_hip_last_error().decode())
+        o = self._outputs(T)
+        o["failure"] = fail
+        return o
+
+    def assemble(self, backend: HipBackend, *arrays):
+        """(residual_sensor [T, ns], residual_force [T, nv], DfDq, DfDv, DfDa [T, nv, nv], DsDq, DsDv, DsDa [T, nr, nv], dvdq0, dvdq1 [T, nv, nv])
+        -> dict(cost [3], gradient, hessian_band, block_sensor, block_force, norm_gradient_sensor, norm_gradient_force, residual_sensor,
+        residual_force), on the device"""
+        return self._run(backend.h, *arrays)
+
+    def assemble_host(self, *arrays):
+        """assemble on the host (no GPU), bit-equal to the device"""
+        return self._run(None, *arrays)
 
 
 class ModelDerivatives:

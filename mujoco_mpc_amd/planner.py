@@ -354,6 +354,79 @@ class HipBackend:
         o["status"] = st; o["regularization"] = float(reg[0]); o["regularization_rate"] = float(reg[1])
         return o
 
+    def _window(self, q, act, ctrl, time, sensor_measurement, force_measurement, settings):
+        nq, nv, na, nu = self.model["nq"], self.model["nv"], self.model["na"], self.model["nu"]
+        f64 = lambda a, *sh: np.ascontiguousarray(np.zeros(sh) if a is None else a, dtype=np.float64).reshape(*sh)      # noqa: E731
+        q = np.ascontiguousarray(q, dtype=np.float64); q = q.reshape((1,) + q.shape) if q.ndim == 2 else q
+        W, T = q.shape[0], q.shape[1]
+        tile = lambda a, n: np.ascontiguousarray(np.broadcast_to(np.zeros((1, T, n)) if a is None or n == 0 else f64(a, -1, T, n), (W, T, n)))      # noqa: E731
+        return W, T, [q.reshape(W, T, nq), tile(act, na), tile(ctrl, nu), f64(time, T), f64(sensor_measurement, T, settings.num_sensor_rows),
+                      f64(force_measurement, T, nv)]
+
+    def direct_cost(self, settings, q, act, ctrl, time, sensor_measurement, force_measurement, mocap=None, userdata=None, discrete=True, fill=0.0):
+        """The direct optimiser's cost of nwin candidate windows in one call (mjpc_hip_direct_cost): q [nwin, T, nq] (or [T, nq]); act, ctrl per
+        window or shared (None: zeros); time [T], sensor_measurement [T, ns], force_measurement [T, nv] shared.  -> dict(cost [nwin, 3] = cost,
+        cost_sensor, cost_force; velocity, acceleration, force_prediction [nwin, T, nv]; sensor_prediction [nwin, T, ns]; failure [nwin, T])."""
+        W, T, ins = self._window(q, act, ctrl, time, sensor_measurement, force_measurement, settings)
+        nv, ns = self.model["nv"], settings.num_sensor_rows
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(cost=np.full((W, 3), fill), velocity=np.full((W, T, nv), fill), acceleration=np.full((W, T, nv), fill),
+                 sensor_prediction=np.full((W, T, ns), fill), force_prediction=np.full((W, T, nv), fill))
+        fail = np.zeros((W, T), np.int32)
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(capi.c_double_p)      # noqa: E731
+        rc = self.lib.mjpc_hip_direct_cost(self.h, W, T, C.byref(settings), int(bool(discrete)), *[ptr(a) for a in ins], pmo, pud,
+                                           *[ptr(a) for a in o.values()], fail.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_direct_cost failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["failure"] = fail
+        return o
+
+    def direct_cost_derivatives(self, settings, q, act, ctrl, time, sensor_measurement, force_measurement, mocap=None, userdata=None, discrete=True,
+                                eps=1e-6, centered=False, fill=0.0):
+        """Cost, gradient and band Hessian of one window with everything on the device (mjpc_hip_direct_cost_derivatives): q [T, nq], act, ctrl,
+        time [T], measurements as direct_cost.  -> the dict of direct_assemble plus DfDq .. DsDa, dvdq0, dvdq1 [T, nv, nv], failure [T]."""
+        W, T, ins = self._window(q, act, ctrl, time, sensor_measurement, force_measurement, settings)
+        if W != 1:
+            raise ValueError("direct_cost_derivatives: one window")
+        nv, nr, ns = self.model["nv"], self.task["num_residual"], settings.num_sensor_rows
+        mo, ud, pmo, pud = self._shared(mocap, userdata)
+        o = dict(cost=np.full(3, fill), gradient=np.full(T * nv, fill), hessian_band=np.full((T * nv, 3 * nv), fill),
+                 block_sensor=np.full((T, ns, 3 * nv), fill), block_force=np.full((T, nv, 3 * nv), fill), norm_gradient_sensor=np.full((T, ns), fill),
+                 norm_gradient_force=np.full((T, nv), fill), residual_sensor=np.full((T, ns), fill), residual_force=np.full((T, nv), fill),
+                 DfDq=np.full((T, nv, nv), fill), DfDv=np.full((T, nv, nv), fill), DfDa=np.full((T, nv, nv), fill), DsDq=np.full((T, nr, nv), fill),
+                 DsDv=np.full((T, nr, nv), fill), DsDa=np.full((T, nr, nv), fill), dvdq0=np.full((T, nv, nv), fill), dvdq1=np.full((T, nv, nv), fill))
+        fail = np.zeros(T, np.int32)
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(capi.c_double_p)      # noqa: E731
+        rc = self.lib.mjpc_hip_direct_cost_derivatives(self.h, T, C.byref(settings), float(eps), int(bool(centered)), int(bool(discrete)),
+                                                       *[ptr(a) for a in ins], pmo, pud, *[ptr(a) for a in o.values()], fail.ctypes.data_as(capi.c_int_p))
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_direct_cost_derivatives failed: " + self.lib.mjpc_hip_last_error().decode())
+        o["failure"] = fail
+        return o
+
+    def direct_assemble(self, settings, residual_sensor, residual_force, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, dvdq0, dvdq1, fill=0.0):
+        """The direct optimiser's window cost, gradient and band Hessian from given arrays (mjpc_hip_direct_assemble): the chain rule over the six
+        inverse blocks DfD* [T, nv, nv], DsD* [T, nr, nv] and the velocity blocks dvdq0, dvdq1 [T, nv, nv], the norms of residual_sensor [T, ns] and
+        residual_force [T, nv], and the sums, on the device.  settings: capi.direct_settings(...).  nv, nr and T are the arrays' (they need not be
+        the engine's model's).  -> dict(cost [3] = cost, cost_sensor, cost_force; gradient [T nv]; hessian_band [T nv, 3 nv]; block_sensor
+        [T, ns, 3 nv]; block_force [T, nv, 3 nv]; norm_gradient_sensor; norm_gradient_force; residual_sensor; residual_force)."""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)      # noqa: E731
+        DfDq = f64(DfDq); T, nv = DfDq.shape[0], DfDq.shape[-1]
+        ns = settings.num_sensor_rows
+        DsDq = f64(DsDq).reshape(T, -1, nv); nr = DsDq.shape[1]
+        ins = [f64(residual_sensor).reshape(T, ns), f64(residual_force).reshape(T, nv), DfDq.reshape(T, nv, nv), f64(DfDv).reshape(T, nv, nv),
+               f64(DfDa).reshape(T, nv, nv), DsDq, f64(DsDv).reshape(T, nr, nv), f64(DsDa).reshape(T, nr, nv), f64(dvdq0).reshape(T, nv, nv),
+               f64(dvdq1).reshape(T, nv, nv)]
+        o = dict(cost=np.full(3, fill), gradient=np.full(T * nv, fill), hessian_band=np.full((T * nv, 3 * nv), fill),
+                 block_sensor=np.full((T, ns, 3 * nv), fill), block_force=np.full((T, nv, 3 * nv), fill), norm_gradient_sensor=np.full((T, ns), fill),
+                 norm_gradient_force=np.full((T, nv), fill), residual_sensor=np.full((T, ns), fill), residual_force=np.full((T, nv), fill))
+        dp = capi.c_double_p
+        ptr = lambda a: (a if a.size else np.zeros(1)).ctypes.data_as(dp)      # noqa: E731
+        rc = self.lib.mjpc_hip_direct_assemble(self.h, T, nv, nr, C.byref(settings), *[ptr(a) for a in ins], *[ptr(a) for a in o.values()])
+        if rc != 0:
+            raise RuntimeError("mjpc_hip_direct_assemble failed: " + self.lib.mjpc_hip_last_error().decode())
+        return o
+
     def trajectory_ilqg(self, x, u, time, residual, mocap=None, userdata=None, eps=1e-6, centered=False, regularization=1.0, regularization_rate=1.0,
                         settings=None, **kw):
         """One derivative iteration of iLQG on the device (mjpc_hip_trajectory_ilqg): transition_fd with the last knot terminal, cost derivatives

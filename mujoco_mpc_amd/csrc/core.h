@@ -239,21 +239,63 @@ DEV Rows out_rows(const KParams *K) {
   return R;
 }
 
-// candidate policy (planner.cc:313-339) + initial state (trajectory.cc:120-137)
+// ---- what every kernel family's init phase does (ph_init here, ph_init_step in transition.h, ph_init_feedback in feedback.h) ----
+// The families differ only in where state, time and knots come from; what is particular to one stays in its own phase, between
+// these helpers.
+// the workgroup's LDS copy of the model tables (everything after it reads them through c.M)
+DEV void init_model_cache(const KParams *K) {
+  double *mcd = lds_base() + K->L.mc_d; int *mci = (int *)(lds_base() + K->L.mc_i);
+  PFOR(e, K->cache_d) mcd[e] = K->dbase[e];
+  PFOR(e, K->cache_i) mci[e] = K->ibase[e];
+  SYNC();
+}
+// mocap poses, the initial state x[nq+nv+na] (trajectory.cc:120-137) with the first state row, and the arrays a step expects zeroed
+DEV void init_arrays(Ctx &c, const KParams *K, const Rows &R, const double *x) {
+  const DevModel &M = *c.M;
+  int nq = M.nq, nv = M.nv;
+  PFOR(i, M.nmocap) {
+    d_copy3(c.mocap_pos + 3 * i, K->mocap + 7 * i);
+    d_copy4(c.mocap_quat + 4 * i, K->mocap + 7 * i + 3);
+  }
+  PFOR(i, nq) { c.qpos[i] = x[i]; R.states[i] = x[i]; }
+  PFOR(i, nv) { c.qvel[i] = x[nq + i]; R.states[nq + i] = x[nq + i]; c.qacc_ws[i] = 0; }
+  if (M.na) PFOR(i, M.na) { C_ACT(c)[i] = x[nq + nv + i]; R.states[nq + nv + i] = x[nq + nv + i]; C_ACTDOT(c)[i] = 0; }
+  PFOR(e, nv * M.nvp) c.qM[e] = 0;
+  // (no qH in the layout of a one-column-group register solve.  qH's size is the distance to Linv: both are nv-sized blocks that
+  // never spill, laid out back to back in every layout, host.h make_layout)
+  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;
+#ifndef MJPC_LEAN_LDS      // (the dense tier has neither in LDS)
+  PFOR(e, M.nhpair + nv) c.hpair[e] = MI(hpair_i)[e] | (MI(hpair_j)[e] << 8);
+  PFOR(k, 6 * M.nbody) c.xfrc[k] = 0;
+#endif
+  PFOR(k, M.nu) c.ctrl[k] = 0;      // data->ctrl after Reset (planner.cc:124-130); only visible when H == 1
+}
+// lane 0: the first time row, the world body, the misc[] words and the profile stamp; then the context's clock
+DEV void init_world(Ctx &c, const Rows &R, double time) {
+  if (LANE == 0) {
+    R.times[0] = time;
+    for (int k = 0; k < 3; k++) { c.xpos[k] = 0; c.xipos[k] = 0; c.subtree_linvel[k] = 0; }
+    c.xquat[0] = 1; c.xquat[1] = 0; c.xquat[2] = 0; c.xquat[3] = 0;
+    for (int k = 0; k < 9; k++) { c.xmat[k] = (k % 4 == 0) ? 1.0 : 0.0; c.ximat[k] = c.xmat[k]; }
+    for (int k = 0; k < 6; k++) { c.cvel[k] = 0; c.cfrc[k] = 0; c.cacc[k] = (k >= 3) ? -c.M->gravity[k - 3] : 0.0; }
+    for (int k = 0; k < MISC_INTS; k++) c.misc[k] = 0;
+#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
+    for (int q = 0; q < NPROF; q++) c.prof[q] = 0;
+    c.prof[NPROF] = (long long)__builtin_amdgcn_s_memtime();
+#endif
+  }
+  c.time = time;
+}
+
+// candidate policy (planner.cc:313-339) + initial state
 DEV_NOINLINE void ph_init(KP Kc) {
   Ctx c;
   const KParams *K = kp_generic(Kc);
   ctx_init(c, K, lds_base());
-  // the workgroup's LDS copy of the model tables (everything below reads them through c.M)
-  {
-    double *mcd = lds_base() + K->L.mc_d; int *mci = (int *)(lds_base() + K->L.mc_i);
-    PFOR(e, K->cache_d) mcd[e] = K->dbase[e];
-    PFOR(e, K->cache_i) mci[e] = K->ibase[e];
-    SYNC();
-  }
+  init_model_cache(K);
   const DevModel &M = *c.M;
   Rows R = out_rows(K);
-  int nq = M.nq, nv = M.nv, nu = M.nu, P = K->P, r = cand_index();
+  int nu = M.nu, P = K->P, r = cand_index();
   int gi = K->offset + r;
 #ifndef MJPC_LEAN_LDS
   PFOR(p, P) c.knot_times[p] = K->knot_times[p];
@@ -273,37 +315,8 @@ DEV_NOINLINE void ph_init(KP Kc) {
     c.knot_values[e] = v;
     K->knots[(size_t)r * P * nu + e] = v;
   }
-  PFOR(i, M.nmocap) {
-    d_copy3(c.mocap_pos + 3 * i, K->mocap + 7 * i);
-    d_copy4(c.mocap_quat + 4 * i, K->mocap + 7 * i + 3);
-  }
-  PFOR(i, nq) { c.qpos[i] = K->state[i]; R.states[i] = K->state[i]; }
-  PFOR(i, nv) { c.qvel[i] = K->state[nq + i]; R.states[nq + i] = K->state[nq + i]; c.qacc_ws[i] = 0; }
-  if (M.na) PFOR(i, M.na) { C_ACT(c)[i] = K->state[nq + nv + i]; R.states[nq + nv + i] = K->state[nq + nv + i]; C_ACTDOT(c)[i] = 0; }
-  PFOR(e, nv * M.nvp) c.qM[e] = 0;
-  // (no qH in the layout of a one-column-group register solve.  qH's size is the distance to Linv: both are nv-sized blocks that
-  // never spill, laid out back to back in every layout, host.h make_layout)
-  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;
-#ifndef MJPC_LEAN_LDS
-  PFOR(e, M.nhpair + nv) c.hpair[e] = MI(hpair_i)[e] | (MI(hpair_j)[e] << 8);
-#endif
-#ifndef MJPC_LEAN_LDS
-  PFOR(k, 6 * M.nbody) c.xfrc[k] = 0;
-#endif
-  PFOR(k, nu) c.ctrl[k] = 0;      // data->ctrl after Reset (planner.cc:124-130); only visible when H == 1
-  if (LANE == 0) {
-    R.times[0] = K->time;
-    for (int k = 0; k < 3; k++) { c.xpos[k] = 0; c.xipos[k] = 0; c.subtree_linvel[k] = 0; }
-    c.xquat[0] = 1; c.xquat[1] = 0; c.xquat[2] = 0; c.xquat[3] = 0;
-    for (int k = 0; k < 9; k++) { c.xmat[k] = (k % 4 == 0) ? 1.0 : 0.0; c.ximat[k] = c.xmat[k]; }
-    for (int k = 0; k < 6; k++) { c.cvel[k] = 0; c.cfrc[k] = 0; c.cacc[k] = (k >= 3) ? -M.gravity[k - 3] : 0.0; }
-    for (int k = 0; k < MISC_INTS; k++) c.misc[k] = 0;
-#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
-    for (int q = 0; q < NPROF; q++) c.prof[q] = 0;
-    c.prof[NPROF] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-  }
-  c.time = K->time;
+  init_arrays(c, K, R, K->state);
+  init_world(c, R, K->time);
   ctx_close(c);
 }
 
@@ -839,8 +852,34 @@ DEV_NOINLINE void ph_resume(KP Kc) {
 }
 
 // ======================================================================================
-// the whole rollout of the workgroup's candidate  (trajectory.cc:100-210 + 312-326)
+// the step skeleton every kernel family runs (rollout here, transition.h, inverse.h, feedback.h).  Wave roles: the owner (r0, wave
+// 0) has the serial chain of a step, the side wave (r1, the last) what runs beside it, the waves between are helpers.  Barrier
+// order of a step: head (owner alone) | pre-solve window | solve window | integration (owner alone); a family puts its own head
+// before and its own phases behind these windows, and a workgroup barrier closes each.
 // ======================================================================================
+// contacts and constraint rows on the owner, smooth dynamics on the side wave, inertia and contact-free rows on the two helpers
+// (their hand-offs inside the window are flags, ph_constraints).  Without helper waves the side wave does the inertia itself
+template <int NVT>
+DEV void presolve_window(KP Kc, int t, bool r0, bool r1) {
+  if (r0) ph_constraints(Kc, t);
+  if (r1) ph_smooth<NVT>(Kc, t);
+#if MJPC_HELPER
+  if (ROLEH && WAVE_ID() == 1) ph_inertia<NVT>(Kc, t);
+  if (ROLEH && WAVE_ID() == MJPC_WAVES - 2) ph_noncontact(Kc, t);
+#endif
+}
+// the owner's and the helpers' part of the solve window: the Newton solve (and noslip pass) with the helpers in its job loops.
+// What the side wave does under its shadow (residual and cost, the integrator's factor) is each family's own: threading the
+// rollouts' cost sum through a shared helper changed the kernel entry functions, which hold the per-step loop
+template <int NVT>
+DEV void solve_window(KP Kc, int t, int last, bool r0) {
+  if (r0) { ph_solve<NVT>(Kc, last, t); if (Kc->M.noslip_iterations > 0) ph_noslip<NVT>(Kc, last); }
+#if MJPC_HELPER
+  if (ROLEH) ph_solve_helper<NVT>(Kc, t);
+#endif
+}
+
+// the whole rollout of the workgroup's candidate  (trajectory.cc:100-210 + 312-326)
 template <int NVT>
 DEV void rollout(KP Kc) {
   int H = Kc->H;
@@ -871,17 +910,9 @@ DEV void rollout(KP Kc) {
     if (r0) ph_head<NVT>(Kc, t, last);
     XBAR(); RPROF(2);
     if (uniform_i(misc[MISC_BAD_STATE])) { failure = 1; break; }
-    if (r0) ph_constraints(Kc, t);
-    if (r1) ph_smooth<NVT>(Kc, t);
-#if MJPC_HELPER
-    if (ROLEH && WAVE_ID() == 1) ph_inertia<NVT>(Kc, t);
-    if (ROLEH && WAVE_ID() == MJPC_WAVES - 2) ph_noncontact(Kc, t);
-#endif
+    presolve_window<NVT>(Kc, t, r0, r1);
     XBAR(); RPROF(3);
-    if (r0) { ph_solve<NVT>(Kc, last, t); if (Kc->M.noslip_iterations > 0) ph_noslip<NVT>(Kc, last); }
-#if MJPC_HELPER
-    if (ROLEH) ph_solve_helper<NVT>(Kc, t);
-#endif
+    solve_window<NVT>(Kc, t, last, r0);
     if (r1) {
       CostOut o = ph_residual_cost(Kc, t, last); total += o.cost;
       if (!last) ph_prefactor<NVT>(Kc);

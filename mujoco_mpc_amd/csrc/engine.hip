@@ -590,6 +590,54 @@ static hipError_t reserve_knots(MjpcHipEngine *e, int P) {
   return rc;
 }
 
+// a copy of the engine's parameters for a launch that is no sampling plan: no spline policy, no noise, no candidate table, no force
+// noise, full capacity.  The caller sets what is its own: P, H, N, offset, nlocal, time (and state / frame where it has none)
+static KParams bare_params(const MjpcHipEngine *e) {
+  KParams K = e->K;
+  K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0; K.interp = 0; K.use_device_noise = 0; K.nominal_index = 0;
+  K.xfrc_std = 0; K.xfrc_rate = 0; K.retry = 0; K.tier = 0;
+  return K;
+}
+
+// a kernel family's kernel of the engine's flavour (that of the full-capacity rollout kernel, pick_flavour; same compile-time dof
+// count), looked up at the family's first call: its dynamic-LDS attribute is set, kernel and launcher are remembered
+typedef const void *(*PickFn)(int nv);
+template <class LaunchFn>
+static int family_kernel(MjpcHipEngine *e, const void **kernel, LaunchFn *launch, const PickFn (&pick)[3], const LaunchFn (&launchers)[3]) {
+  if (*kernel) return 0;
+  const int f = e->spill ? 2 : e->cached ? 1 : 0;
+  const void *k = pick[f](e->nv);
+  HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
+  *kernel = k; *launch = launchers[f];
+  return 0;
+}
+#define FAMILY_KERNEL(e, fam) family_kernel(e, &(e)->fam##_kernel, &(e)->fam##_launch, {mjpc_pick_##fam##_direct, mjpc_pick_##fam##_cached, mjpc_pick_##fam##_spill}, \
+                                            {mjpc_launch_##fam##_direct, mjpc_launch_##fam##_cached, mjpc_launch_##fam##_spill})
+
+// doubles of the packed result of nl candidates (pack_kernel): winner and its return, returns and failure words, then the winner's
+// rows (the knot row alone for a summary-only engine; a plan without knots, P = 0, has an empty one)
+static size_t pack_doubles(const MjpcHipEngine *e, int nl, int H, int P) {
+  size_t n = 2 + 2 * (size_t)nl;
+  for (int k = 0; k < (e->summary_only ? 1 : NROWS); k++) n += row_doubles(e, k, H, P);
+  return n;
+}
+
+// what follows the rollouts of any plan (ev[2] recorded): the winner, its rows packed and on their way to pinned memory, and the
+// plan marked in flight for mjpc_hip_plan_fetch
+static int plan_tail(MjpcHipEngine *e, int nl, int H, int P, int offset, size_t need_pack) {
+  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
+  HIPCHK(hipEventRecord(e->ev[3], e->stream));
+  PackArgs pa{e->at<int>(B_WINNER), e->at(B_WINNER_VAL), e->at(B_RETURNS), e->at<int>(B_FAILURE), e->at(B_KNOTS + 1), e->at(B_KNOTS + 2), e->at(B_KNOTS + 3),
+              e->at(B_KNOTS + 4), e->at(B_KNOTS + 5), e->at(B_KNOTS + 6), e->at(B_KNOTS), nl, H, P, e->ds, e->nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->at(B_PACK)};
+  e->last_summary = e->summary_only;
+  hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
+  HIPCHK(hipMemcpyAsync(e->at(H_PACK), e->at(B_PACK), sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipGetLastError());
+  e->last_H = H; e->last_P = P; e->last_nlocal = nl; e->last_offset = offset; e->pending = 1;
+  return 0;
+}
+
 // n doubles of the caller's (zeros when src is null) through the pinned staging block at offset `at` into device buffer b, stream-ordered
 static hipError_t stage(MjpcHipEngine *e, size_t at, const double *src, size_t n, int b) {
   double *h = e->at(H_SMALL) + at;
@@ -813,8 +861,7 @@ static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int fir
   // the buffers that grow with the plan (a repeated plan allocates nothing); the packed result: pack_kernel
   const size_t need = (size_t)nl * P * nu;
   const bool table = in->candidate_knots || mixed;
-  size_t need_pack = 2 + 2 * (size_t)nl;
-  for (int k = 0; k < (e->summary_only ? 1 : NROWS); k++) need_pack += row_doubles(e, k, H, P);
+  const size_t need_pack = pack_doubles(e, nl, H, P);
   HIPCHK(e->buf[B_EPS].reserve(sizeof(double) * (need + 1)));
   HIPCHK(reserve_knots(e, P));
   if (table) HIPCHK(e->buf[B_CAND].reserve(sizeof(double) * (need + 1)));
@@ -876,16 +923,7 @@ static int plan_async_impl(MjpcHipEngine *e, const MjpcHipPlanInput *in, int fir
   K.retry = 0;
   e->last_dense = dense;
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
-  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
-  HIPCHK(hipEventRecord(e->ev[3], e->stream));
-  PackArgs pa{e->at<int>(B_WINNER), e->at(B_WINNER_VAL), e->at(B_RETURNS), e->at<int>(B_FAILURE), e->at(B_KNOTS + 1), e->at(B_KNOTS + 2), e->at(B_KNOTS + 3),
-              e->at(B_KNOTS + 4), e->at(B_KNOTS + 5), e->at(B_KNOTS + 6), e->at(B_KNOTS), nl, H, P, e->ds, nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->at(B_PACK)};
-  e->last_summary = e->summary_only;
-  hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
-  HIPCHK(hipMemcpyAsync(e->at(H_PACK), e->at(B_PACK), sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipGetLastError());
-  e->last_H = H; e->last_P = P; e->last_nlocal = nl; e->last_offset = in->candidate_offset; e->pending = 1;
-  return 0;
+  return plan_tail(e, nl, H, P, in->candidate_offset, need_pack);
 }
 
 int mjpc_hip_plan_async(MjpcHipEngine *e, const MjpcHipPlanInput *in) { return plan_async_impl(e, in, -1); }
@@ -970,18 +1008,12 @@ int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, c
   }
   if (nd > FB_DX_CAPACITY(nv)) return bad("2 nv + na exceeds the state-difference scratch of the kernel");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->fb_kernel) {
-    const void *k = e->spill ? mjpc_pick_fb_spill(e->nv) : e->cached ? mjpc_pick_fb_cached(e->nv) : mjpc_pick_fb_direct(e->nv);
-    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
-    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&e->ev_fb[i]));
-    e->fb_kernel = k;
-    e->fb_launch = e->spill ? mjpc_launch_fb_spill : e->cached ? mjpc_launch_fb_cached : mjpc_launch_fb_direct;
-  }
+  if (!e->fb_kernel) for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&e->ev_fb[i]));      // (the resampling's two, with the family's first call)
+  if (int rc = FAMILY_KERNEL(e, fb)) return rc;
   // the call's device block (FbLay, carve.h)
   const size_t Tz = (size_t)T;
   const bool timed = p->mode == MJPC_FEEDBACK_TIME;
-  size_t need_pack = 2 + 2 * (size_t)nl;
-  for (int k = 1; k < (e->summary_only ? 1 : NROWS); k++) need_pack += row_doubles(e, k, H, 0);
+  const size_t need_pack = pack_doubles(e, nl, H, 0);
   FbLay L;
   PLACE(B_FBP, L, e->dims(), Tz, H, nl, timed);
   HIPCHK(reserve_knots(e, 1));
@@ -1017,26 +1049,13 @@ int mjpc_hip_plan_feedback_async(MjpcHipEngine *e, const MjpcHipPlanInput *in, c
     xbar = ra.xbar; ubar = ra.ubar; kbar = d_impr ? ra.kbar : nullptr; Kbar = ra.Kbar;
   }
   if (!p->use_feedback) xbar = nullptr;
-  // a copy of the engine's parameters: no spline, no noise, no candidate table, no force noise, full capacity
-  KParams K = e->K;
-  K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
-  K.time = in->time; K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0;
-  K.P = 0; K.interp = 0; K.H = H; K.N = in->num_trajectory; K.offset = in->candidate_offset; K.nlocal = nl; K.use_device_noise = 0; K.nominal_index = 0;
-  K.xfrc_std = 0; K.xfrc_rate = 0; K.retry = 0; K.tier = 0;
+  KParams K = bare_params(e);
+  K.time = in->time; K.P = 0; K.H = H; K.N = in->num_trajectory; K.offset = in->candidate_offset; K.nlocal = nl;
   HIPCHK(hipEventRecord(e->ev[1], e->stream));
   e->fb_launch(e->fb_kernel, nl, e->lds_bytes, e->stream, &K, xbar, ubar, kbar, Kbar, L.alpha, L.scale);
   e->last_dense = 0;
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
-  hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, e->stream, e->at(B_RETURNS), nl, e->at<int>(B_WINNER), e->at(B_WINNER_VAL));
-  HIPCHK(hipEventRecord(e->ev[3], e->stream));
-  PackArgs pa{e->at<int>(B_WINNER), e->at(B_WINNER_VAL), e->at(B_RETURNS), e->at<int>(B_FAILURE), e->at(B_KNOTS + 1), e->at(B_KNOTS + 2), e->at(B_KNOTS + 3),
-              e->at(B_KNOTS + 4), e->at(B_KNOTS + 5), e->at(B_KNOTS + 6), e->at(B_KNOTS), nl, H, 0, ds, nu, e->nr, e->ntr, e->summary_only ? 0 : 1, e->at(B_PACK)};
-  e->last_summary = e->summary_only;
-  hipLaunchKernelGGL(pack_kernel, dim3(8), dim3(256), 0, e->stream, pa);
-  HIPCHK(hipMemcpyAsync(e->at(H_PACK), e->at(B_PACK), sizeof(double) * need_pack, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipGetLastError());
-  e->last_H = H; e->last_P = 0; e->last_nlocal = nl; e->last_offset = in->candidate_offset; e->pending = 1;
-  return 0;
+  return plan_tail(e, nl, H, 0, in->candidate_offset, need_pack);
 }
 
 int mjpc_hip_plan_feedback(MjpcHipEngine *e, const MjpcHipPlanInput *in, const MjpcHipFeedbackPolicy *p, MjpcHipPlanOutput *out) {
@@ -1092,24 +1111,15 @@ static int step_prepare(MjpcHipEngine *e, const char *who, const double *mocap, 
   if (e->max_horizon < 2) { set_error(std::string(who) + ": the engine was created with max_horizon < 2 (a step records two state rows)"); return -1; }
   if (e->nmocap > 0 && !mocap) { set_error(std::string(who) + ": null input"); return -1; }
   HIPCHK(hipSetDevice(e->device));
-  if (!e->step_kernel) {
-    // the flavour of the full-capacity rollout kernel (pick_flavour), same compile-time dof count
-    const void *k = e->spill ? mjpc_pick_step_spill(e->nv) : e->cached ? mjpc_pick_step_cached(e->nv) : mjpc_pick_step_direct(e->nv);
-    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
-    e->step_kernel = k;
-    e->step_launch = e->spill ? mjpc_launch_step_spill : e->cached ? mjpc_launch_step_cached : mjpc_launch_step_direct;
-  }
+  if (int rc = FAMILY_KERNEL(e, step)) return rc;
   HIPCHK(reserve_knots(e, 1));
   if (e->nmocap) HIPCHK(stage(e, e->hs.mocap, mocap, 7 * e->nmocap, B_MOCAP));
   if (e->nuserdata) HIPCHK(stage(e, e->hs.userdata, userdata, e->nuserdata, B_USERDATA));
-  // a copy of the engine's parameters: a step has no plan state, no noise and no candidate table, one knot (its control), two
-  // state rows per workgroup
-  KParams K = e->K;
-  K.state = nullptr; K.noise_eps = nullptr; K.noise_sel = nullptr; K.noise_std = nullptr; K.cand_knots = nullptr;
+  // a step has no plan state either, one knot (its control) and two state rows per workgroup
+  KParams K = bare_params(e);
+  K.state = nullptr;
   K.frame = nullptr;                       // (the kinematic frame of the last plan stays what it was)
-  K.time = 0; K.sigma0 = 0; K.sigma1 = 0; K.seed = 0; K.stream = 0;
-  K.P = 1; K.interp = 0; K.H = 2; K.N = e->max_local; K.offset = 0; K.nlocal = 0; K.use_device_noise = 0; K.nominal_index = 0;
-  K.xfrc_std = 0; K.xfrc_rate = 0;
+  K.time = 0; K.P = 1; K.H = 2; K.N = e->max_local; K.offset = 0; K.nlocal = 0;
   *Kout = K;
   // the row buffers are about to be overwritten: the last plan's candidates are no longer there to be fetched
   e->last_nlocal = 0;
@@ -1247,13 +1257,7 @@ static int inverse_prepare(MjpcHipEngine *e, const char *who, const double *moca
   // never launches it, the coupling only loads that kernel's code object early; its checks, staged inputs and parameters are what is wanted)
   int rc = step_prepare(e, who, mocap, userdata, Kout);
   if (rc != 0) return rc;
-  if (!e->inv_kernel) {
-    const void *k = e->spill ? mjpc_pick_inv_spill(e->nv) : e->cached ? mjpc_pick_inv_cached(e->nv) : mjpc_pick_inv_direct(e->nv);
-    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes));
-    e->inv_kernel = k;
-    e->inv_launch = e->spill ? mjpc_launch_inv_spill : e->cached ? mjpc_launch_inv_cached : mjpc_launch_inv_direct;
-  }
-  return 0;
+  return FAMILY_KERNEL(e, inv);
 }
 
 // rows [0, rows) of the tables through the inverse kernel, at most max_local workgroups per launch (stream-ordered, as step_rows)

@@ -7,7 +7,7 @@
 //
 // Included by the rollout_fb_*.hip translation units only (never by rollout_tu.inc or core.h: the open-loop kernels do not change).
 // ph_init_feedback is ph_init without a spline policy, ph_head_feedback<NVT> is ph_head with the policy block replaced; every other
-// phase is core.h's own, in the wave roles and barrier order of rollout<NVT>.  Full capacity only: no dense tier, no checkpoint.
+// phase is core.h's own, on core.h's step skeleton.  Full capacity only: no dense tier, no checkpoint.
 //
 // Bit rule: the arithmetic is that of the host's iLQGPolicy::Action / StateDiff (planner.cc) - each row of Kbar * dx starts
 // at 0.0 and takes ascending index with one rounded product and one rounded add, alpha * kbar is one product and one add (mju_addScl),
@@ -51,45 +51,15 @@ DEV void fb_quat_diff(double *res, const double *qa, const double *qb) {
   for (int k = 0; k < 3; k++) res[k] = mul_rn(ax[k], speed);
 }
 
-// sibling of ph_init: the same LDS model-cache copy, zeroing and initial state; no knots are read and no knot rows written
+// the engine's state and time; no knots are read and no knot rows written
 DEV_NOINLINE void ph_init_feedback(FP Fc) {
   Ctx c;
   const KParams *K = &fp_generic(Fc)->K;
   ctx_init(c, K, lds_base());
-  {
-    double *mcd = lds_base() + K->L.mc_d; int *mci = (int *)(lds_base() + K->L.mc_i);
-    PFOR(e, K->cache_d) mcd[e] = K->dbase[e];
-    PFOR(e, K->cache_i) mci[e] = K->ibase[e];
-    SYNC();
-  }
-  const DevModel &M = *c.M;
+  init_model_cache(K);
   Rows R = out_rows(K);
-  int nq = M.nq, nv = M.nv, nu = M.nu;
-  PFOR(i, M.nmocap) {
-    d_copy3(c.mocap_pos + 3 * i, K->mocap + 7 * i);
-    d_copy4(c.mocap_quat + 4 * i, K->mocap + 7 * i + 3);
-  }
-  PFOR(i, nq) { c.qpos[i] = K->state[i]; R.states[i] = K->state[i]; }
-  PFOR(i, nv) { c.qvel[i] = K->state[nq + i]; R.states[nq + i] = K->state[nq + i]; c.qacc_ws[i] = 0; }
-  if (M.na) PFOR(i, M.na) { C_ACT(c)[i] = K->state[nq + nv + i]; R.states[nq + nv + i] = K->state[nq + nv + i]; C_ACTDOT(c)[i] = 0; }
-  PFOR(e, nv * M.nvp) c.qM[e] = 0;
-  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;
-  PFOR(e, M.nhpair + nv) c.hpair[e] = MI(hpair_i)[e] | (MI(hpair_j)[e] << 8);
-  PFOR(k, 6 * M.nbody) c.xfrc[k] = 0;
-  PFOR(k, nu) c.ctrl[k] = 0;
-  if (LANE == 0) {
-    R.times[0] = K->time;
-    for (int k = 0; k < 3; k++) { c.xpos[k] = 0; c.xipos[k] = 0; c.subtree_linvel[k] = 0; }
-    c.xquat[0] = 1; c.xquat[1] = 0; c.xquat[2] = 0; c.xquat[3] = 0;
-    for (int k = 0; k < 9; k++) { c.xmat[k] = (k % 4 == 0) ? 1.0 : 0.0; c.ximat[k] = c.xmat[k]; }
-    for (int k = 0; k < 6; k++) { c.cvel[k] = 0; c.cfrc[k] = 0; c.cacc[k] = (k >= 3) ? -M.gravity[k - 3] : 0.0; }
-    for (int k = 0; k < MISC_INTS; k++) c.misc[k] = 0;
-#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
-    for (int q = 0; q < NPROF; q++) c.prof[q] = 0;
-    c.prof[NPROF] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-  }
-  c.time = K->time;
+  init_arrays(c, K, R, K->state);
+  init_world(c, R, K->time);
   ctx_close(c);
 }
 
@@ -171,17 +141,9 @@ DEV void rollout_feedback(FP Fc) {
     if (r0) ph_head_feedback<NVT>(Fc, t, last);
     XBAR();
     if (uniform_i(misc[MISC_BAD_STATE])) { failure = 1; break; }
-    if (r0) ph_constraints(Kc, t);
-    if (r1) ph_smooth<NVT>(Kc, t);
-#if MJPC_HELPER
-    if (ROLEH && WAVE_ID() == 1) ph_inertia<NVT>(Kc, t);
-    if (ROLEH && WAVE_ID() == MJPC_WAVES - 2) ph_noncontact(Kc, t);
-#endif
+    presolve_window<NVT>(Kc, t, r0, r1);
     XBAR();
-    if (r0) { ph_solve<NVT>(Kc, last, t); if (Kc->M.noslip_iterations > 0) ph_noslip<NVT>(Kc, last); }
-#if MJPC_HELPER
-    if (ROLEH) ph_solve_helper<NVT>(Kc, t);
-#endif
+    solve_window<NVT>(Kc, t, last, r0);
     if (r1) {
       CostOut o = ph_residual_cost(Kc, t, last); total += o.cost;
       if (!last) ph_prefactor<NVT>(Kc);

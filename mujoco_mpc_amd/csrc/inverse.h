@@ -4,10 +4,9 @@
 // (mjpc/direct/direct.cc:1545-1576: mj_inverse at every configuration of a window; :1717-1756: mjd_inverseFD = 1 + 3 nv of them).
 //
 // Included by the rollout_inv_*.hip translation units only.  A sibling of transition.h: the same init, head and pre-solve window
-// (ph_constraints, ph_smooth, ph_inertia, ph_noncontact in their waves), the same barriers, and then NO solver: behind the window
-// the owner wave evaluates the force law of the step's constraint rows at jar = J a - aref once (ph_inverse), the side wave the
-// residual; the late rows then read the given acceleration and the inverse efc_force.  No ph_solve, ph_noslip, ph_prefactor or
-// ph_integrate, and the helper waves never enter ph_solve_helper: its loops wait for job words only solve_constraints posts.
+// (core.h's step skeleton), and then NO solver: behind the window the owner wave evaluates the force law of the step's
+// constraint rows at jar = J a - aref once (ph_inverse), the side wave the residual; the late rows then read the given
+// acceleration and the inverse efc_force.  No ph_solve, ph_noslip, ph_prefactor or ph_integrate, and the helper waves never enter ph_solve_helper: its loops wait for job words only solve_constraints posts.
 //
 //   qfrc_constraint = J^T f(J a - aref)                                  constraint_update<DIMT, true>(c, 0, jar), solver.h
 //   qfrc_inverse    = M a + qfrc_bias - qfrc_passive - qfrc_constraint   (MuJoCo's meaning: actuator forces are not subtracted)
@@ -172,19 +171,10 @@ DEV_NOINLINE void ph_inverse(IP Ic) {
   ctx_close(c);
 }
 
-// side wave, after the last barrier: the residual row, the warning bits and the diagnostics (the forces went out in ph_inverse)
+// side wave, after the last barrier: the row's tail alone (the forces went out in ph_inverse)
 DEV_NOINLINE void ph_finish_inverse(IP Ic, int failure, int have_residual) {
   Ctx c; ctx_open(c, (KP)Ic, 1);
-  const StepParams *S = sp_generic((SP)Ic);
-  const KParams *K = c.K;
-  const int r = cand_index(), nr = c.M->task.num_residual;
-  if (have_residual) PFOR(i, nr) S->residual_out[(size_t)r * nr + i] = c.residual[i];
-  if (LANE == 0) {
-    int w = failure ? (c.warning ? c.warning : 1) : 0;
-    S->failure_out[r] = w;
-    K->failure[r] = w;
-    if (K->diag) { K->diag[4 * r] = 0; K->diag[4 * r + 1] = c.misc[MISC_MAX_NCON]; K->diag[4 * r + 2] = c.misc[MISC_MAX_NEFC]; K->diag[4 * r + 3] = c.warning; }
-  }
+  finish_row(c, sp_generic((SP)Ic), failure, have_residual, false);
 }
 
 // transition<NVT> without its solve, prefactor and integration
@@ -202,12 +192,7 @@ DEV void inverse(IP Ic) {
     if (r0) ph_head<NVT>(Kc, t, last);
     XBAR();
     if (uniform_i(misc[MISC_BAD_STATE])) { failure = 1; break; }
-    if (r0) ph_constraints(Kc, t);
-    if (r1) ph_smooth<NVT>(Kc, t);
-#if MJPC_HELPER
-    if (ROLEH && WAVE_ID() == 1) ph_inertia<NVT>(Kc, t);
-    if (ROLEH && WAVE_ID() == MJPC_WAVES - 2) ph_noncontact(Kc, t);
-#endif
+    presolve_window<NVT>(Kc, t, r0, r1);
     XBAR();
     // (the helper waves go straight to the next barrier: no job loop)
     if (r0) ph_inverse<NVT>(Ic);

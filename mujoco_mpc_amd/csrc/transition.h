@@ -4,7 +4,7 @@
 // mjd_transitionFD per knot = 1 + (2nv+na+nu) independent steps); a rollout starts every candidate from the same K->state.
 //
 // Included by the rollout_step_*.hip translation units only (never by rollout_tu.inc or core.h: the rollout kernels do not
-// change).  The phases are core.h's own, in the wave roles and barrier order of rollout<NVT> for t = 0, last = 0; with H = 2 and
+// change).  The phases are core.h's own, on core.h's step skeleton for t = 0, last = 0; with H = 2 and
 // P = 1 in the kernel parameters they record into candidate rows [r][2][...] of the engine's row buffers exactly as the first step
 // of a two-step plan does, so a step is bit for bit the first step of mjpc_hip_plan(N = 1, H = 2, P = 1, candidate_knots = ctrl).
 #pragma once
@@ -29,21 +29,16 @@ typedef const __attribute__((address_space(4))) StepParams *SP;
 DEV const StepParams *sp_generic(SP s) { return (const StepParams *)kp_generic((KP)s); }
 #include "late_rows.h"
 
-// sibling of ph_init: the same LDS model-cache copy and zeroing; state, time and the one-knot policy come from row r of the tables
+// state, time and the one-knot policy come from row r of the tables
 DEV_NOINLINE void ph_init_step(SP Sc) {
   Ctx c;
   const StepParams *S = sp_generic(Sc);
   const KParams *K = &S->K;
   ctx_init(c, K, lds_base());
-  {
-    double *mcd = lds_base() + K->L.mc_d; int *mci = (int *)(lds_base() + K->L.mc_i);
-    PFOR(e, K->cache_d) mcd[e] = K->dbase[e];
-    PFOR(e, K->cache_i) mci[e] = K->ibase[e];
-    SYNC();
-  }
+  init_model_cache(K);
   const DevModel &M = *c.M;
   Rows R = out_rows(K);
-  int nq = M.nq, nv = M.nv, nu = M.nu, r = cand_index();
+  int nu = M.nu, r = cand_index();
   const double *x = S->state_tab + (size_t)r * R.ds;
   if (LANE == 0) c.knot_times[0] = 0.0;          // P = 1: spline_sample returns the knot's value at any time
   PFOR(k, nu) {
@@ -51,56 +46,39 @@ DEV_NOINLINE void ph_init_step(SP Sc) {
     c.knot_values[k] = v;
     K->knots[(size_t)r * nu + k] = v;
   }
-  PFOR(i, M.nmocap) {
-    d_copy3(c.mocap_pos + 3 * i, K->mocap + 7 * i);
-    d_copy4(c.mocap_quat + 4 * i, K->mocap + 7 * i + 3);
-  }
-  PFOR(i, nq) { c.qpos[i] = x[i]; R.states[i] = x[i]; }
-  PFOR(i, nv) { c.qvel[i] = x[nq + i]; R.states[nq + i] = x[nq + i]; c.qacc_ws[i] = 0; }
-  if (M.na) PFOR(i, M.na) { C_ACT(c)[i] = x[nq + nv + i]; R.states[nq + nv + i] = x[nq + nv + i]; C_ACTDOT(c)[i] = 0; }
-  PFOR(e, nv * M.nvp) c.qM[e] = 0;
-  if (K->L.Linv - K->L.qH >= nv * M.nvp) PFOR(e, nv * M.nvp) c.qH[e] = 0;
-  PFOR(e, M.nhpair + nv) c.hpair[e] = MI(hpair_i)[e] | (MI(hpair_j)[e] << 8);
-  PFOR(k, 6 * M.nbody) c.xfrc[k] = 0;
-  PFOR(k, nu) c.ctrl[k] = 0;
+  init_arrays(c, K, R, x);
   // a step that stops before its residual (bad state) reports NaN there, not what an earlier launch left
   PFOR(i, R.nr) S->residual_out[(size_t)r * R.nr + i] = __builtin_nan("");
-  double time = S->time_tab[r];
-  if (LANE == 0) {
-    R.times[0] = time;
-    for (int k = 0; k < 3; k++) { c.xpos[k] = 0; c.xipos[k] = 0; c.subtree_linvel[k] = 0; }
-    c.xquat[0] = 1; c.xquat[1] = 0; c.xquat[2] = 0; c.xquat[3] = 0;
-    for (int k = 0; k < 9; k++) { c.xmat[k] = (k % 4 == 0) ? 1.0 : 0.0; c.ximat[k] = c.xmat[k]; }
-    for (int k = 0; k < 6; k++) { c.cvel[k] = 0; c.cfrc[k] = 0; c.cacc[k] = (k >= 3) ? -M.gravity[k - 3] : 0.0; }
-    for (int k = 0; k < MISC_INTS; k++) c.misc[k] = 0;
-#if defined(MJPC_PROFILE) && !defined(MJPC_EMU)
-    for (int q = 0; q < NPROF; q++) c.prof[q] = 0;
-    c.prof[NPROF] = (long long)__builtin_amdgcn_s_memtime();
-#endif
-  }
-  c.time = time;
+  init_world(c, R, S->time_tab[r]);
   ctx_close(c);
 }
 
-// side wave, after the last barrier: the state in LDS (the integrated one, or the input when the step stopped before integration),
-// the residual row of the step, the warning bits and the diagnostics
-DEV_NOINLINE void ph_finish_step(SP Sc, int failure, int have_residual) {
-  Ctx c; ctx_open(c, (KP)Sc, 1);
-  const StepParams *S = sp_generic(Sc);
+// what ends a one-row evaluation (ph_finish_step here, ph_finish_inverse in inverse.h): the residual row, the warning bits to the
+// caller's table and the engine's own, and the diagnostics (an evaluation without a solve reports 0 iterations)
+DEV void finish_row(Ctx &c, const StepParams *S, int failure, int have_residual, bool solved) {
   const KParams *K = c.K;
-  const DevModel &M = *c.M;
-  int r = cand_index(), nq = M.nq, nv = M.nv, ds = nq + nv + M.na, nr = M.task.num_residual;
-  double *y = S->next_state + (size_t)r * ds;
-  PFOR(i, nq) y[i] = c.qpos[i];
-  PFOR(i, nv) y[nq + i] = c.qvel[i];
-  if (M.na) PFOR(i, M.na) y[nq + nv + i] = C_ACT(c)[i];
+  const int r = cand_index(), nr = c.M->task.num_residual;
   if (have_residual) PFOR(i, nr) S->residual_out[(size_t)r * nr + i] = c.residual[i];
   if (LANE == 0) {
     int w = failure ? (c.warning ? c.warning : 1) : 0;
     S->failure_out[r] = w;
     K->failure[r] = w;
-    if (K->diag) { K->diag[4 * r] = c.misc[MISC_SUM_ITER]; K->diag[4 * r + 1] = c.misc[MISC_MAX_NCON]; K->diag[4 * r + 2] = c.misc[MISC_MAX_NEFC]; K->diag[4 * r + 3] = c.warning; }
+    if (K->diag) { K->diag[4 * r] = solved ? c.misc[MISC_SUM_ITER] : 0; K->diag[4 * r + 1] = c.misc[MISC_MAX_NCON]; K->diag[4 * r + 2] = c.misc[MISC_MAX_NEFC]; K->diag[4 * r + 3] = c.warning; }
   }
+}
+
+// side wave, after the last barrier: the state in LDS (the integrated one, or the input when the step stopped before integration),
+// then the row's tail
+DEV_NOINLINE void ph_finish_step(SP Sc, int failure, int have_residual) {
+  Ctx c; ctx_open(c, (KP)Sc, 1);
+  const StepParams *S = sp_generic(Sc);
+  const DevModel &M = *c.M;
+  int r = cand_index(), nq = M.nq, nv = M.nv, ds = nq + nv + M.na;
+  double *y = S->next_state + (size_t)r * ds;
+  PFOR(i, nq) y[i] = c.qpos[i];
+  PFOR(i, nv) y[nq + i] = c.qvel[i];
+  if (M.na) PFOR(i, M.na) y[nq + nv + i] = C_ACT(c)[i];
+  finish_row(c, S, failure, have_residual, true);
 }
 
 // the body of rollout<NVT> for t = 0, last = 0, once: no terminal forward, no checkpoint / retry, no return
@@ -117,17 +95,9 @@ DEV void transition(SP Sc) {
     if (r0) ph_head<NVT>(Kc, t, last);
     XBAR();
     if (uniform_i(misc[MISC_BAD_STATE])) { failure = 1; break; }
-    if (r0) ph_constraints(Kc, t);
-    if (r1) ph_smooth<NVT>(Kc, t);
-#if MJPC_HELPER
-    if (ROLEH && WAVE_ID() == 1) ph_inertia<NVT>(Kc, t);
-    if (ROLEH && WAVE_ID() == MJPC_WAVES - 2) ph_noncontact(Kc, t);
-#endif
+    presolve_window<NVT>(Kc, t, r0, r1);
     XBAR();
-    if (r0) { ph_solve<NVT>(Kc, last, t); if (Kc->M.noslip_iterations > 0) ph_noslip<NVT>(Kc, last); }
-#if MJPC_HELPER
-    if (ROLEH) ph_solve_helper<NVT>(Kc, t);
-#endif
+    solve_window<NVT>(Kc, t, last, r0);
     if (r1) {
       ph_residual_cost(Kc, t, last);
       ph_prefactor<NVT>(Kc);
